@@ -51,6 +51,24 @@ def make_reads(n_reads, seed):
     return [lut[c].tobytes().decode() for c in codes]
 
 
+DUMP_ROWS = 32768                      # chunks written by --dump-outputs: 32768 x (250 + 16) x 4 bytes = 35 MB, under its 64 MB cap
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, sig, dur):
+    """--dump-outputs: what the timed path handed its caller in the last step (predict_chunks -> signal fp32 [B, 250] pA,
+    dur int32 [B, 16]) as <out_dir>/signal.npy and dur.npy, both float32 (the dwell counts are small integers: exact).  Every row
+    when B <= DUMP_ROWS, else the same DUMP_ROWS rows, in ascending order, drawn with numpy's default_rng(DUMP_SEED): for a
+    given workload two builds write the same chunks, so their files compare element for element."""
+    B = int(sig.shape[0])
+    rows = None if B <= DUMP_ROWS else np.sort(np.random.default_rng(DUMP_SEED).choice(B, DUMP_ROWS, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in (("signal", sig), ("dur", dur)):
+        if rows is not None:
+            t = t.index_select(0, torch.from_numpy(rows).to(t.device))
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.float().cpu().numpy())
+
+
 def pmc_counters(mode, chunks_per_launch, root=None):
     """From the newest committed PMC passes (tools/pmc_run.sh -> profiles/*/pmc_summary.json), for the decoder kernel:
     HBM bytes per launch = (2 x FETCH_SIZE + WRITE_SIZE) KB -- FETCH_SIZE reports half of a wide coalesced read on
@@ -943,7 +961,12 @@ def main():
                     help="seconds after the timed region by which the line is written, whatever the secondary legs are doing")
     ap.add_argument("--mode", default="f16x3", choices=["f32", "f16x3", "f16"],
                     help="decoder arithmetic: f32-input MFMA, or split-f16 (3 f16 MFMA products, fp32 accumulate)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/signal.npy and DIR/dur.npy (float32; a fixed "
+                         f"sample of {DUMP_ROWS} chunks when there are more; rank 0's shard with --gpus > 1)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.rccl_selftest_child:
         return rccl_selftest_child()
     if a.rccl_selftest_only:                 # the self-test alone (this process stays off the GPU): proves the bring-up code on whatever is there
@@ -1049,6 +1072,8 @@ def main():
     eng.set_profiling(False)
     dec_ms, dec_launches, dec_chunks = eng.kernel_ms()
     live = eng.stats()
+    if a.dump_outputs and rank == 0:                       # before any later leg writes into sig / dur
+        dump_outputs(a.dump_outputs, sig, dur)
     el = host.max(el)
     ranks_seen = host.size()
     per_rank = [float(x) for x in host.gather(B * a.steps / own)]

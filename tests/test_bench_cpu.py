@@ -240,6 +240,39 @@ def test_mismatched_world_size_is_refused():
     assert p.returncode != 0 and "WORLD_SIZE=2" in p.stderr
 
 
+def test_steps_below_one_are_refused():
+    p = _run("--steps", "0")
+    assert p.returncode != 0 and "--steps" in p.stderr
+
+
+def test_dump_outputs_writes_every_chunk_or_the_same_sample(tmp_path):
+    """--dump-outputs: float32 .npy files of the caller's arrays; every row of a small batch, and above DUMP_ROWS chunks the same
+    ascending sample of whole rows on every call, within the 64 MB cap."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    sig = torch.randn(7, 250)
+    dur = torch.randint(0, 40, (7, 16), dtype=torch.int32)
+    bench.dump_outputs(str(tmp_path / "small"), sig, dur)
+    s, d = np.load(tmp_path / "small" / "signal.npy"), np.load(tmp_path / "small" / "dur.npy")
+    assert s.dtype == d.dtype == np.float32 and np.array_equal(s, sig.numpy()) and np.array_equal(d, dur.numpy())
+
+    B = bench.DUMP_ROWS + 5000
+    sig = torch.arange(B, dtype=torch.float32)[:, None].expand(B, 250).contiguous()      # row i holds i: the file says which rows
+    dur = torch.arange(B, dtype=torch.int32)[:, None].expand(B, 16).contiguous()
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), sig, dur)
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64 * 10**6
+    s, d = np.load(tmp_path / "a" / "signal.npy"), np.load(tmp_path / "a" / "dur.npy")
+    assert s.dtype == d.dtype == np.float32 and s.shape == (bench.DUMP_ROWS, 250) and d.shape == (bench.DUMP_ROWS, 16)
+    rows = s[:, 0]
+    assert (s == rows[:, None]).all() and (d == rows[:, None]).all()                 # whole rows, signal and dur of the same chunks
+    assert np.all(np.diff(rows) > 0) and rows[-1] < B
+    for name in ("signal.npy", "dur.npy"):
+        assert np.array_equal(np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name))
+
+
 _SHARDED_WORKER = r"""
 import json, os, sys
 sys.path.insert(0, sys.argv[1])

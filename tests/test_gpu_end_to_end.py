@@ -227,6 +227,26 @@ def test_bench_contract_line():
     assert cb["parity"]["dwell_indices_equal"] and cb["parity"]["signal_mae_pa"] < cb["parity"]["tolerance_mae_pa"]
 
 
+def test_bench_steps_and_dumped_outputs(tmp_path):
+    """--steps K is K timed launches (one launch per step at this size), ms_per_step their time, and --dump-outputs holds exactly
+    what the hot path returns for the bench's seeded inputs (every chunk: 60 reads are below the sample size)."""
+    sys.path.insert(0, ROOT)
+    import bench
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--reads", "60",
+                        "--no-cpu-baseline", "--dump-outputs", str(tmp_path)], cwd=ROOT, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
+    assert d["steps"] == 3 and d["roofline"]["launches"] == 3 and d["ms_per_step"] > 0
+    sd, cfg = S.load_checkpoint(os.path.join(GOLDEN, "synthetic_k9.ckpt"))
+    bases, nv, _ = S.encode_reads(bench.make_reads(60, 1234), cfg["seq_kmer"])
+    eng = S.Engine(sd, cfg, device=0, mode="f16x3")
+    out = eng.predict_chunks(torch.from_numpy(bases).cuda(), torch.from_numpy(nv).cuda(), S.PredictParams(seed=42))
+    sig, dur = np.load(tmp_path / "signal.npy"), np.load(tmp_path / "dur.npy")
+    assert sig.dtype == dur.dtype == np.float32 and sig.shape == (bases.shape[0], 250)
+    assert np.array_equal(sig, out["signal"].cpu().numpy()) and np.array_equal(dur, out["dur"].cpu().numpy().astype(np.float32))
+    eng.close()
+
+
 def test_rna_profile_streaming_equals_reference_flow(tmp_path):
     """rna-004: dwell 4000/130 = 30.8 samples per base (16 k-mers overflow the 250-sample chunk: crop path), signals
     reversed per read (signal_io.py:140-141) -- on the GPU in the streaming path, on the host in the reference flow."""

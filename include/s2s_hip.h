@@ -41,6 +41,10 @@ extern "C" {
 #define S2S_MODE_F16 3      /* REDUCED PRECISION, outside the 1e-4 pA bound: decoder operands rounded to f16 once (the
                              * precision class of the reference's own fp16-autocast GPU path, inference.py:404), one MFMA
                              * product per product; the frontend stays F16X3, so dwell indices remain bit-exact */
+/*   S2S_MODE_GENERIC  any model size within the limits below, exact fp32 (the parity contract of S2S_MODE_F32): a layer-wise
+ *                   pipeline of its own kernels (csrc/s2s_generic.h) over slices of the launch's chunks, the f32-input MFMA for every
+ *                   matrix product, an exact softmax with its own row maximum.  Same Philox counters as the tuned instances. */
+#define S2S_MODE_GENERIC 4
 
 #define S2S_T_ENC 16         /* config.yaml:18 max_dna_len    */
 #define S2S_T_DEC 250        /* config.yaml:19 max_signal_len */
@@ -49,21 +53,28 @@ extern "C" {
 #define S2S_HEADS 8          /* config.yaml:28,30             */
 
 /* Model hyper-parameters that change the predict arithmetic (config.yaml:17-31; the keys
- * Encoder/Decoder.__init__ read, modules.py:22-63, 97-131).  Only the shipped architecture
- * family is supported: dmodel 64, dff 256, 8 heads, 16 k-mers in, 250 samples out; the layer
- * counts and the k-mer size are free. */
+ * Encoder/Decoder.__init__ read, modules.py:22-63, 97-131).  Every mode: 16 k-mers in, 250 samples
+ * out (the chunk geometry of the export kernels and the host framing), seq_kmer 1..16, encoder and
+ * decoder layers 1..4, pre_layers 0..4.  Sizes:
+ *   tuned modes (F32, F16X3, F16): the shipped architecture family only -- dmodel 64, dff 256,
+ *                   8 heads in encoder and decoder;
+ *   S2S_MODE_GENERIC: dmodel a multiple of 16 in 16..512, dff a multiple of 8 in 8..2048, encoder and
+ *                   decoder heads each 1..16 and a divisor of dmodel (head_dim = dmodel / heads).
+ * A refused configuration is S2S_ERR_ARG from s2s_create (the message names the key) and
+ * s2s_blob_floats returns 0 for it. */
 typedef struct s2s_config {
     int32_t seq_kmer;          /* 9 (dna-r10*, rna-004*) or 6 (dna-r9*), utils.py:257-260 */
     int32_t max_dna_len;       /* must be 16  */
     int32_t max_signal_len;    /* must be 250 */
-    int32_t dmodel;            /* must be 64  */
-    int32_t dff;               /* must be 256 */
-    int32_t n_heads;           /* must be 8 (encoder_heads == decoder_heads) */
+    int32_t dmodel;            /* tuned: 64;  generic: 16..512, a multiple of 16 */
+    int32_t dff;               /* tuned: 256; generic: 8..2048, a multiple of 8 */
+    int32_t n_heads;           /* encoder heads; tuned: 8; generic: 1..16, divides dmodel */
     int32_t encoder_layers;    /* 1..4 */
     int32_t decoder_layers;    /* 1..4 */
     int32_t pre_layers;        /* 0..4 */
     float scaling_max_value;   /* 165.0, model.py:221 */
     int32_t compute_mode;      /* arithmetic of the decoder FFT blocks: one of the S2S_MODE_* values */
+    int32_t decoder_heads;     /* 0 = n_heads; tuned: 0 or n_heads; generic: 1..16, divides dmodel */
 } s2s_config;
 
 /* Per-call scalars: the attributes predict_step reads from the LightningModule
@@ -79,7 +90,7 @@ typedef struct s2s_params {
     uint64_t seed;             /* key of the counter-based Philox4x32-10 generator */
 } s2s_params;
 
-/* Optional stage outputs for parity tests (all nullable, device). */
+/* Optional stage outputs for parity tests (all nullable, device).  [64] below is [dmodel] for a generic handle. */
 typedef struct s2s_debug {
     float* emb_out;            /* [B][16][64]  Encoder.forward 2nd result (modules.py:72-77) */
     float* enc_out;            /* [B][16][64]  Encoder.forward 1st result (modules.py:80-89) */
@@ -97,7 +108,8 @@ typedef struct s2s_debug {
 
 typedef struct s2s_handle s2s_handle;
 
-/* Number of fp32 values the weight blob must hold for `cfg`, and the order:
+/* Number of fp32 values the weight blob must hold for `cfg` (0 for a refused configuration), and the order, written for the
+ * tuned sizes -- for S2S_MODE_GENERIC read every 64 as dmodel and every 256 as dff:
  *   encoders.position_enc[16*64]; src_emb.weight[64][5k], .bias[64];
  *   pre_net_stack.i.weight[64][64], .bias[64]                               (i < pre_layers)
  *   per encoder layer: LAYER (below)
@@ -108,7 +120,12 @@ typedef struct s2s_handle s2s_handle;
  * LAYER = slf_attn.{w_qs,w_ks,w_vs}.{weight[64][64],bias[64]}, slf_attn.fc.{weight,bias},
  *         slf_attn.layer_norm.{weight,bias}[64], pos_ffn.w_1.{weight[256][64],bias[256]},
  *         pos_ffn.w_2.{weight[64][256],bias[64]}, pos_ffn.layer_norm.{weight,bias}[64]
- * i.e. the reference state_dict (SURVEY.md section 8 a-W) in its native [out][in] layouts. */
+ * i.e. the reference state_dict (SURVEY.md section 8 a-W) in its native [out][in] layouts.
+ *
+ * A generic handle runs a launch in slices of at most S2S_GENERIC_WORKSPACE_BYTES / (4 * per-chunk floats) chunks, per-chunk
+ * floats = 16 dmodel + 250 dmodel + 250 max(3 dmodel, dff) + 16 + 250 (each buffer is then rounded up to a multiple of
+ * 64 floats); the workspace grows on demand (the first launch of a larger batch synchronises the stream) and is reused. */
+#define S2S_GENERIC_WORKSPACE_BYTES (512u << 20)
 size_t s2s_blob_floats(const s2s_config* cfg);
 
 /* Replaces seq2squiggle.load_from_checkpoint + .to(device) (inference.py:386-399): takes the
@@ -326,7 +343,8 @@ int s2s_get_attention_path(const s2s_handle* h, int32_t* path, double* calibrati
  *   [2] ... of them redone on the safe path (0 in S2S_MODE_F32, which has no fast path),
  *   [3] shader-clock cycles (s_memtime) and [4] 100 MHz ticks (s_memrealtime) of one thread per workgroup over the whole
  *       kernel, summed over [5] workgroups: [3] / [4] / 10 is the clock in GHz the SIMDs really ran at,
- *   [6] chunks launched on the exact attention path (s2s_set_attention_path), [7..9] reserved (0). */
+ *   [6] chunks launched on the exact attention path (s2s_set_attention_path), [7..9] reserved (0).
+ * A generic handle counts [0] and [1] (with its decoder head count), and has no redo, clock or exact-path counts ([2..6] 0). */
 int s2s_stats_read(s2s_handle* h, uint64_t* out10);
 
 /* Diagnostic builds (-DS2S_DIAG, never the shipped library): per wave of a workgroup (8 rows) 48 per-phase shader-cycle sums

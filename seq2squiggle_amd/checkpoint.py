@@ -79,12 +79,22 @@ def state_dict_to_blob(sd: Dict[str, torch.Tensor], cfg: dict) -> np.ndarray:
     return np.concatenate([sd[n].detach().float().cpu().numpy().ravel() for n in blob_names(cfg)]).astype(np.float32)
 
 
-MODES = {"f32": 0, "f16x3": 1, "f16": 3}     # f16: reduced precision (see include/s2s_hip.h)
+MODES = {"f32": 0, "f16x3": 1, "f16": 3, "generic": 4}     # f16: reduced precision; generic: any size (see include/s2s_hip.h)
+TUNED_MODES = ("f32", "f16x3", "f16")
+TUNED_SIZES = {"dmodel": 64, "dff": 256, "encoder_heads": 8, "decoder_heads": 8}
+
+
+def is_tuned_family(cfg: dict) -> bool:
+    """Does `cfg` have the sizes the tuned instances (f32, f16x3, f16) are written for?  Other sizes run on "generic"."""
+    return all(int(cfg[k]) == v for k, v in TUNED_SIZES.items())
+
+
+def default_mode(cfg: dict) -> str:
+    """The instance a checkpoint runs on when none is asked for: "f16x3" for the tuned sizes, "generic" otherwise."""
+    return "f16x3" if is_tuned_family(cfg) else "generic"
 
 
 def config_to_c(cfg: dict, mode: str = "f16x3") -> S2SConfig:
-    if cfg["encoder_heads"] != cfg["decoder_heads"]:
-        raise ValueError("encoder_heads != decoder_heads is not supported")
     if mode not in MODES:
         raise ValueError(f"mode must be one of {sorted(MODES)}")
     if cfg.get("allowed_chars", "_ACGT") != "_ACGT":
@@ -93,4 +103,5 @@ def config_to_c(cfg: dict, mode: str = "f16x3") -> S2SConfig:
                      max_signal_len=int(cfg["max_signal_len"]), dmodel=int(cfg["dmodel"]), dff=int(cfg["dff"]),
                      n_heads=int(cfg["encoder_heads"]), encoder_layers=int(cfg["encoder_layers"]),
                      decoder_layers=int(cfg["decoder_layers"]), pre_layers=int(cfg["pre_layers"]),
-                     scaling_max_value=float(cfg["scaling_max_value"]), compute_mode=MODES[mode])
+                     scaling_max_value=float(cfg["scaling_max_value"]), compute_mode=MODES[mode],
+                     decoder_heads=int(cfg["decoder_heads"]))

@@ -10,6 +10,7 @@
 // plus s2s_export_* for the per-read zero-strip / int16 conversion and s2s_svb_* for the containers' signal codecs.
 #include "s2s_device.h"
 #include "s2s_device_h.h"
+#include "s2s_generic.h"
 #include "../../include/s2s_hip.h"
 
 #include <cctype>
@@ -850,6 +851,17 @@ struct s2s_handle {
     double calib_redo_rate = -1.0;          // share of the calibration launch's softmax runs that overflowed the fast path (-1: not calibrated)
     std::vector<EventPair> events;
     std::string err;
+    // S2S_MODE_GENERIC (s2s_generic.h): blob offsets into d_arena, and the slice workspace (grown on demand, s2s_predict_*)
+    struct Generic {
+        int d = 0, dff = 0, h_enc = 0, h_dec = 0;
+        long long pe_enc = 0, pe_dec = 0, emb_wt = 0, emb_b = 0, out_w = 0, out_b = 0, w0cat = 0, b0cat = 0;
+        long long pre_w[S2S_MAX_LAYERS] = {}, pre_b[S2S_MAX_LAYERS] = {};
+        GenLayer enc[S2S_MAX_LAYERS] = {}, dec[S2S_MAX_LAYERS] = {};
+        GenHeads heads = {};
+        int slice_max = 0;            // chunks per slice (S2S_GENERIC_WORKSPACE_BYTES)
+        float* ws = nullptr;
+        int ws_chunks = 0;            // slice capacity of ws
+    } gen;
 };
 
 namespace {
@@ -887,9 +899,25 @@ struct DeviceGuard {
 size_t layer_floats() { return 4 * (64 * 64 + 64) + 2 * 64 + (256 * 64 + 256) + (64 * 256 + 64) + 2 * 64; }
 size_t mlp_floats() { return 64 * 64 + 64 + 64 + 1; }
 
+const char* check_cfg_generic(const s2s_config* c) {
+    if (c->max_dna_len != S2S_T_ENC) return "max_dna_len must be 16";
+    if (c->max_signal_len != S2S_T_DEC) return "max_signal_len must be 250";
+    if (c->dmodel < 16 || c->dmodel > 512 || c->dmodel % 16) return "dmodel must be a multiple of 16 in 16..512 (S2S_MODE_GENERIC)";
+    if (c->dff < 8 || c->dff > 2048 || c->dff % 8) return "dff must be a multiple of 8 in 8..2048 (S2S_MODE_GENERIC)";
+    if (c->n_heads < 1 || c->n_heads > 16 || c->dmodel % c->n_heads)
+        return "n_heads (encoder heads) must be 1..16 and divide dmodel (S2S_MODE_GENERIC)";
+    if (c->decoder_heads < 0 || c->decoder_heads > 16 || (c->decoder_heads && c->dmodel % c->decoder_heads))
+        return "decoder_heads must be 0 (= n_heads) or 1..16 and divide dmodel (S2S_MODE_GENERIC)";
+    if (c->encoder_layers < 1 || c->encoder_layers > S2S_MAX_LAYERS) return "encoder_layers must be 1..4";
+    if (c->decoder_layers < 1 || c->decoder_layers > S2S_MAX_LAYERS) return "decoder_layers must be 1..4";
+    if (c->pre_layers < 0 || c->pre_layers > S2S_MAX_LAYERS) return "pre_layers must be 0..4";
+    return nullptr;
+}
+
 const char* check_cfg(const s2s_config* c) {
     if (!c) return "config is NULL";
     if (c->seq_kmer < 1 || c->seq_kmer > 16) return "seq_kmer must be 1..16";
+    if (c->compute_mode == S2S_MODE_GENERIC) return check_cfg_generic(c);
     if (c->max_dna_len != S2S_T_ENC) return "max_dna_len must be 16";
     if (c->max_signal_len != S2S_T_DEC) return "max_signal_len must be 250";
     if (c->dmodel != S2S_DMODEL) return "dmodel must be 64";
@@ -900,7 +928,18 @@ const char* check_cfg(const s2s_config* c) {
     if (c->pre_layers < 0 || c->pre_layers > S2S_MAX_LAYERS) return "pre_layers must be 0..4";
     if (c->compute_mode != S2S_MODE_F32 && c->compute_mode != S2S_MODE_F16X3 && c->compute_mode != S2S_MODE_F16)
         return "compute_mode must be S2S_MODE_F32, S2S_MODE_F16X3 or S2S_MODE_F16";
+    if (c->decoder_heads != 0 && c->decoder_heads != c->n_heads) return "decoder_heads must be 0 or equal to n_heads (8)";
     return nullptr;
+}
+
+int cfg_dec_heads(const s2s_config* c) { return c->decoder_heads ? c->decoder_heads : c->n_heads; }
+
+size_t generic_layer_floats(size_t d, size_t f) { return 4 * (d * d + d) + 2 * d + (f * d + f) + (d * f + d) + 2 * d; }
+
+// fp32 floats of one chunk in the generic workspace: XE [16][d], SIG [16], XD [250][d], SE [250], BIG [250][max(3d, dff)]
+size_t generic_chunk_floats(const s2s_config* c) {
+    const size_t d = c->dmodel, big = 3 * d > (size_t)c->dff ? 3 * d : (size_t)c->dff;
+    return 16 * d + 16 + 250 * d + 250 + 250 * big;
 }
 
 // Arena builder: every piece starts on a 16-byte boundary (float4 loads).
@@ -1100,6 +1139,57 @@ MlpOff pack_mlp(Arena& A, const float*& p) {
     return m;
 }
 
+// S2S_MODE_GENERIC: the blob in its native [out][in] layouts (the GEMM reads nn.Linear weights as they are), except src_emb.weight
+// transposed to [5k][d] (a one-hot column is one contiguous row) and the three q/k/v projections and the three heads' first
+// layers each concatenated into one [3d][d] matrix with its [3d] bias.
+void pack_generic(Arena& A, s2s_handle::Generic& G, const s2s_config* cfg, const float* p) {
+    const int d = cfg->dmodel, f = cfg->dff, k = cfg->seq_kmer;
+    const size_t dd = (size_t)d * d;
+    G.d = d; G.dff = f; G.h_enc = cfg->n_heads; G.h_dec = cfg_dec_heads(cfg);
+    G.pe_enc = A.put(take(p, 16 * (size_t)d), 16 * (size_t)d);
+    {
+        const float* w = take(p, (size_t)d * 5 * k);
+        std::vector<float> wt((size_t)5 * k * d);
+        for (int o = 0; o < d; ++o)
+            for (int i = 0; i < 5 * k; ++i) wt[(size_t)i * d + o] = w[(size_t)o * 5 * k + i];
+        G.emb_wt = A.put(wt.data(), wt.size());
+        G.emb_b = A.put(take(p, d), d);
+    }
+    for (int i = 0; i < cfg->pre_layers; ++i) { G.pre_w[i] = A.put(take(p, dd), dd); G.pre_b[i] = A.put(take(p, d), d); }
+    auto layer = [&](GenLayer& L) {
+        std::vector<float> w(3 * dd), b(3 * (size_t)d);
+        for (int j = 0; j < 3; ++j) {                        // w_qs, w_ks, w_vs: weight then bias each
+            std::memcpy(w.data() + j * dd, take(p, dd), dd * sizeof(float));
+            std::memcpy(b.data() + (size_t)j * d, take(p, d), d * sizeof(float));
+        }
+        L.wqkv = A.put(w.data(), w.size()); L.bqkv = A.put(b.data(), b.size());
+        L.wfc = A.put(take(p, dd), dd); L.bfc = A.put(take(p, d), d);
+        L.ln1g = A.put(take(p, d), d); L.ln1b = A.put(take(p, d), d);
+        L.w1 = A.put(take(p, (size_t)f * d), (size_t)f * d); L.b1 = A.put(take(p, f), f);
+        L.w2 = A.put(take(p, (size_t)d * f), (size_t)d * f); L.b2 = A.put(take(p, d), d);
+        L.ln2g = A.put(take(p, d), d); L.ln2b = A.put(take(p, d), d);
+    };
+    for (int l = 0; l < cfg->encoder_layers; ++l) layer(G.enc[l]);
+    {   // noise_sampler.stdv_layer, duration_sampler.conc_layer, .rate_layer: 0.weight [d][d], 0.bias [d], 3.weight [d], 3.bias [1]
+        std::vector<float> w(3 * dd), b(3 * (size_t)d);
+        std::vector<float> w3[3], b3[3];
+        for (int j = 0; j < 3; ++j) {
+            std::memcpy(w.data() + j * dd, take(p, dd), dd * sizeof(float));
+            std::memcpy(b.data() + (size_t)j * d, take(p, d), d * sizeof(float));
+            const float* x = take(p, d); w3[j].assign(x, x + d);
+            const float* y = take(p, 1); b3[j].assign(y, y + 1);
+        }
+        G.w0cat = A.put(w.data(), w.size()); G.b0cat = A.put(b.data(), b.size());
+        for (int j = 0; j < 3; ++j) { G.heads.w3[j] = A.put(w3[j].data(), d); G.heads.b3[j] = A.put(b3[j].data(), 1); }
+    }
+    G.pe_dec = A.put(take(p, 250 * (size_t)d), 250 * (size_t)d);
+    for (int l = 0; l < cfg->decoder_layers; ++l) layer(G.dec[l]);
+    G.out_w = A.put(take(p, d), d);
+    G.out_b = A.put(take(p, 1), 1);
+    G.slice_max = (int)(S2S_GENERIC_WORKSPACE_BYTES / (4 * generic_chunk_floats(cfg)));
+    if (G.slice_max < 1) G.slice_max = 1;
+}
+
 ParamsDev to_dev(const s2s_params* p) {
     ParamsDev d;
     d.dwell_mean = p->dwell_mean; d.dwell_std = p->dwell_std; d.noise_std = p->noise_std;
@@ -1111,10 +1201,120 @@ ParamsDev to_dev(const s2s_params* p) {
 
 }  // namespace
 
+// ---- S2S_MODE_GENERIC (s2s_generic.h): the launch in slices of at most gen.slice_max chunks, each slice stage by stage.
+namespace {
+template <int EPI>
+void gen_gemm(hipStream_t st, const float* A, int lda, const float* W, const float* bias, float* C, int ldc, const float* R, int M, int N, int K) {
+    const dim3 grid((M + GEN_BM - 1) / GEN_BM, (N + GEN_BN - 1) / GEN_BN);
+    hipLaunchKernelGGL(gen_gemm_kernel<EPI>, grid, dim3(256), 0, st, A, lda, W, K, bias, C, ldc, R, ldc, M, N, K);
+}
+
+// one FFTBlock (layers.py:116-142) on the rows X [n*T][d]; BIG [n*T][max(3d, dff)] holds QKV (O replaces Q), then the FFN hidden
+void gen_fft_block(hipStream_t st, const float* W, const GenLayer& L, float* X, float* BIG, int n, int T, int d, int dff, int H) {
+    const int M = n * T, hd = d / H;
+    gen_gemm<0>(st, X, d, W + L.wqkv, W + L.bqkv, BIG, 3 * d, nullptr, M, 3 * d, d);
+    const size_t stage = gen_attn_lds_bytes(T, hd, true);
+    if (stage <= GEN_ATTN_STAGE_BYTES)
+        hipLaunchKernelGGL(gen_attention_kernel<true>, dim3(n * H), dim3(256), stage, st, BIG, d, H, T);
+    else
+        hipLaunchKernelGGL(gen_attention_kernel<false>, dim3(n * H), dim3(256), gen_attn_lds_bytes(T, hd, false), st, BIG, d, H, T);
+    gen_gemm<2>(st, BIG, 3 * d, W + L.wfc, W + L.bfc, X, d, X, M, d, d);
+    hipLaunchKernelGGL(gen_layernorm_kernel, dim3((M + 3) / 4), dim3(256), 0, st, X, W + L.ln1g, W + L.ln1b, (long long)M, d);
+    gen_gemm<1>(st, X, d, W + L.w1, W + L.b1, BIG, dff, nullptr, M, dff, d);
+    gen_gemm<2>(st, BIG, dff, W + L.w2, W + L.b2, X, d, X, M, d, dff);
+    hipLaunchKernelGGL(gen_layernorm_kernel, dim3((M + 3) / 4), dim3(256), 0, st, X, W + L.ln2g, W + L.ln2b, (long long)M, d);
+}
+
+size_t up64(size_t n) { return (n + 63) & ~(size_t)63; }
+}  // namespace
+
+static int predict_generic(s2s_handle* h, hipStream_t st, const uint8_t* bases, const int64_t* chunk_start, const uint8_t* n_valid,
+                           int64_t first_global_chunk, int32_t B, const ParamsDev& P, const float* inject_g, const float* inject_zdw,
+                           const float* inject_z01, float* out_signal, int32_t* out_dur, const DebugDev& D) {
+    s2s_handle::Generic& G = h->gen;
+    const int d = G.d, dff = G.dff, k = h->cfg.seq_kmer, nb = S2S_T_ENC + k - 1;
+    const size_t big_w = (size_t)(3 * d > dff ? 3 * d : dff);
+    const int want = B < G.slice_max ? B : G.slice_max;
+    if (want > G.ws_chunks) {                 // grows outside of the steady state only
+        HIP_TRY(h, hipStreamSynchronize(st));
+        if (G.ws) (void)hipFree(G.ws);
+        G.ws = nullptr; G.ws_chunks = 0;
+        const size_t n = want;
+        const size_t floats = up64(n * 16 * d) + up64(n * 16) + up64(n * 250 * d) + up64(n * 250) + up64(n * 250 * big_w);
+        HIP_TRY(h, hipMalloc(&G.ws, floats * sizeof(float)));
+        G.ws_chunks = want;
+    }
+    const size_t S = G.ws_chunks;
+    float* XE = G.ws;
+    float* SIG = XE + up64(S * 16 * d);
+    float* XD = SIG + up64(S * 16);
+    float* SE = XD + up64(S * 250 * d);
+    float* BIG = SE + up64(S * 250);
+    const float* W = h->d_arena;
+    EventPair ev{};
+    if (h->profiling) {
+        HIP_TRY(h, hipEventCreate(&ev.a));
+        HIP_TRY(h, hipEventCreate(&ev.b));
+        HIP_TRY(h, hipEventRecord(ev.a, st));
+    }
+    for (int64_t s = 0; s < B; s += S) {
+        const int n = (int)((B - s < (int64_t)S) ? (B - s) : (int64_t)S);
+        const int Me = n * 16, Md = n * 250;
+        const long long fc = (long long)(first_global_chunk + s);
+        DebugDev Ds = D;                      // the caller's arrays, offset to the slice
+        auto off = [&](float* p, size_t per) { return p ? p + (size_t)s * per : nullptr; };
+        Ds.sigma = off(D.sigma, 16); Ds.conc = off(D.conc, 16); Ds.rate = off(D.rate, 16); Ds.g = off(D.g, 16);
+        Ds.y_scaled = off(D.y_scaled, 250); Ds.z01 = off(D.z01, 250);
+        // encoder input: src_emb + pre-net (modules.py:70-77), or the caller's rows (s2s_debug.emb_in)
+        if (D.emb_in) {
+            HIP_TRY(h, hipMemcpyAsync(XE, D.emb_in + (size_t)s * 16 * d, (size_t)Me * d * sizeof(float), hipMemcpyDeviceToDevice, st));
+        } else {
+            const uint8_t* tb = chunk_start ? bases : bases + (size_t)s * nb;
+            const long long* tcs = reinterpret_cast<const long long*>(chunk_start ? chunk_start + s : nullptr);
+            const long long tot = (long long)Me * d;
+            hipLaunchKernelGGL(gen_embed_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, W + G.emb_wt, W + G.emb_b, k, d, tb, tcs,
+                               n_valid + s, n, XE);
+            float* cur = XE;
+            for (int i = 0; i < h->cfg.pre_layers; ++i) {
+                float* nxt = cur == XE ? BIG : XE;
+                gen_gemm<1>(st, cur, d, W + G.pre_w[i], W + G.pre_b[i], nxt, d, nullptr, Me, d, d);
+                cur = nxt;
+            }
+            if (cur != XE) HIP_TRY(h, hipMemcpyAsync(XE, cur, (size_t)Me * d * sizeof(float), hipMemcpyDeviceToDevice, st));
+        }
+        if (D.emb_out)
+            HIP_TRY(h, hipMemcpyAsync(D.emb_out + (size_t)s * 16 * d, XE, (size_t)Me * d * sizeof(float), hipMemcpyDeviceToDevice, st));
+        // heads (modules.py:182-195, 267-278): the three first layers as one GEMM, then the dwell source; + position_enc
+        gen_gemm<1>(st, XE, d, W + G.w0cat, W + G.b0cat, BIG, 3 * d, nullptr, Me, P.duration_sampling ? 3 * d : d, d);
+        hipLaunchKernelGGL(gen_dwell_kernel, dim3((Me + 3) / 4), dim3(256), 0, st, W, G.heads, G.pe_enc, d, n, BIG, XE, SIG, fc, P,
+                           inject_g ? inject_g + s * 16 : nullptr, inject_zdw ? inject_zdw + s * 16 : nullptr, out_dur + s * 16, Ds);
+        for (int l = 0; l < h->cfg.encoder_layers; ++l) gen_fft_block(st, W, G.enc[l], XE, BIG, n, 16, d, dff, G.h_enc);
+        if (D.enc_out)
+            HIP_TRY(h, hipMemcpyAsync(D.enc_out + (size_t)s * 16 * d, XE, (size_t)Me * d * sizeof(float), hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(gen_lenreg_kernel, dim3((Md + 3) / 4), dim3(256), 0, st, W, G.pe_dec, d, n, XE, SIG, out_dur + s * 16, XD, SE,
+                           D.dec_in ? D.dec_in + (size_t)s * 250 * d : nullptr);
+        for (int l = 0; l < h->cfg.decoder_layers; ++l) gen_fft_block(st, W, G.dec[l], XD, BIG, n, 250, d, dff, G.h_dec);
+        hipLaunchKernelGGL(gen_emit_kernel, dim3((Md + 3) / 4), dim3(256), 0, st, W, G.out_w, G.out_b, h->cfg.scaling_max_value, d, n, XD, SE,
+                           fc, P, inject_z01 ? inject_z01 + (size_t)s * 250 : nullptr, out_signal + (size_t)s * 250, Ds);
+    }
+    if (h->profiling) {
+        HIP_TRY(h, hipEventRecord(ev.b, st));
+        ev.chunks = B;
+        h->events.push_back(ev);
+    }
+    HIP_TRY(h, hipGetLastError());
+    return S2S_OK;
+}
+
 extern "C" {
 
 size_t s2s_blob_floats(const s2s_config* c) {
     if (check_cfg(c)) return 0;
+    if (c->compute_mode == S2S_MODE_GENERIC) {
+        const size_t d = c->dmodel, f = c->dff;
+        return 16 * d + d * 5 * c->seq_kmer + d + (size_t)c->pre_layers * (d * d + d) +
+               (size_t)(c->encoder_layers + c->decoder_layers) * generic_layer_floats(d, f) + 3 * (d * d + d + d + 1) + 250 * d + d + 1;
+    }
     return (size_t)16 * 64 + (size_t)64 * 5 * c->seq_kmer + 64 + (size_t)c->pre_layers * (4096 + 64) +
            (size_t)(c->encoder_layers + c->decoder_layers) * layer_floats() + 3 * mlp_floats() + (size_t)250 * 64 + 64 + 1;
 }
@@ -1128,7 +1328,7 @@ static int predict_impl(s2s_handle* h, void* stream_, const uint8_t* bases, cons
 // every head on the exact path (s2s_device_h.h: the online softmax as its own kernel instance).  A fixed input, so the same weights always get the same
 // answer, on any device.  The export scratch inside the slab holds the launch's buffers.
 static int calibrate_attention(s2s_handle* h) {
-    if (h->cfg.compute_mode == S2S_MODE_F32) return S2S_OK;
+    if (h->cfg.compute_mode == S2S_MODE_F32 || h->cfg.compute_mode == S2S_MODE_GENERIC) return S2S_OK;
     const int B = 512, nb = S2S_T_ENC + h->cfg.seq_kmer - 1;
     std::vector<uint8_t> host((size_t)B * nb + B);
     uint32_t x = 0x9E3779B9u;
@@ -1203,6 +1403,9 @@ int s2s_create(const s2s_config* cfg, const void* blob, size_t blob_bytes, int d
     Arena A;
     ModelDev& M = h->model;
     std::memset(&M, 0, sizeof M);
+    if (cfg->compute_mode == S2S_MODE_GENERIC) {
+        pack_generic(A, h->gen, cfg, static_cast<const float*>(blob));
+    } else {
     M.k = k; M.enc_layers = cfg->encoder_layers; M.dec_layers = cfg->decoder_layers; M.pre_layers = cfg->pre_layers;
     M.scale = cfg->scaling_max_value;
     const float* p = static_cast<const float*>(blob);
@@ -1229,6 +1432,7 @@ int s2s_create(const s2s_config* cfg, const void* blob, size_t blob_bytes, int d
     for (int l = 0; l < cfg->decoder_layers; ++l) M.dec[l] = pack_layer(A, p);
     M.out_w = A.put(take(p, 64), 64);
     M.out_b = A.put(take(p, 1), 1);
+    }
     while (A.v.size() % 4) A.v.push_back(0.0f);
     h->arena_floats = A.v.size();
 
@@ -1274,6 +1478,10 @@ int s2s_create(const s2s_config* cfg, const void* blob, size_t blob_bytes, int d
     for (const auto& k : dyn_lds)
         if ((e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.bytes)) != hipSuccess)
             return bail(e, "hipFuncSetAttribute(dynamic LDS)");
+    if (cfg->compute_mode == S2S_MODE_GENERIC &&
+        (e = hipFuncSetAttribute(reinterpret_cast<const void*>(gen_attention_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 GEN_ATTN_STAGE_BYTES)) != hipSuccess)
+        return bail(e, "hipFuncSetAttribute(generic attention LDS)");
 #if defined(S2S_DIAG) || defined(S2S_TILEHIST)
     if ((e = hipMalloc(&h->d_diag, 8 * 48 * sizeof(unsigned long long))) != hipSuccess) return bail(e, "hipMalloc(diag)");
     if ((e = hipMemset(h->d_diag, 0, 8 * 48 * sizeof(unsigned long long))) != hipSuccess) return bail(e, "hipMemset(diag)");
@@ -1319,6 +1527,7 @@ void s2s_destroy(s2s_handle* h) {
     free_scratch(h, h->ws_counts);
     free_scratch(h, h->ws_offs);
     free_scratch(h, h->ws_svb);
+    if (h->gen.ws) (void)hipFree(h->gen.ws);
     if (h->slab) (void)hipFree(h->slab);
     if (h->d_diag) (void)hipFree(h->d_diag);
     delete h;
@@ -1350,6 +1559,9 @@ static int predict_impl(s2s_handle* h, void* stream_, const uint8_t* bases, cons
     D.diag = h->d_diag;
     D.stats = h->d_stats;
     h->stat_chunks += B;
+    if (h->cfg.compute_mode == S2S_MODE_GENERIC)
+        return predict_generic(h, stream, bases, chunk_start, n_valid, first_global_chunk, B, P, inject_g, inject_zdw, inject_z01,
+                               out_signal, out_dur, D);
     const int nb = S2S_T_ENC + h->cfg.seq_kmer - 1;
     for (int64_t s = 0; s < B; s += h->tile) {
         const int n = (int)((B - s < h->tile) ? (B - s) : h->tile);
@@ -1522,7 +1734,9 @@ int s2s_stats_read(s2s_handle* h, uint64_t* out10) {
     HIP_TRY(h, hipMemcpy(raw, h->d_stats, sizeof raw, hipMemcpyDeviceToHost));
     HIP_TRY(h, hipMemset(h->d_stats, 0, sizeof raw));
     out10[0] = (uint64_t)h->stat_chunks;
-    out10[1] = (uint64_t)h->stat_chunks * DEC_WAVES * S2S_HEADS * (uint64_t)h->cfg.decoder_layers;
+    out10[1] = h->cfg.compute_mode == S2S_MODE_GENERIC
+                   ? (uint64_t)h->stat_chunks * (uint64_t)cfg_dec_heads(&h->cfg) * (uint64_t)h->cfg.decoder_layers
+                   : (uint64_t)h->stat_chunks * DEC_WAVES * S2S_HEADS * (uint64_t)h->cfg.decoder_layers;
     out10[2] = raw[S2S_STAT_REDO];
     out10[3] = raw[S2S_STAT_CYCLES]; out10[4] = raw[S2S_STAT_TICKS]; out10[5] = raw[S2S_STAT_WGS];
     out10[6] = (uint64_t)h->stat_exact_chunks; out10[7] = 0; out10[8] = 0; out10[9] = 0;

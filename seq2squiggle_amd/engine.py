@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .checkpoint import config_to_c, load_checkpoint, state_dict_to_blob
+from .checkpoint import TUNED_MODES, TUNED_SIZES, config_to_c, default_mode, is_tuned_family, load_checkpoint, state_dict_to_blob
 
 T_ENC, T_DEC = 16, 250
 
@@ -44,15 +44,24 @@ class Engine:
     """Weights resident on one GPU + the predict / export entry points."""
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], config: dict, device: Optional[int] = None,
-                 mode: str = "f16x3"):
+                 mode: Optional[str] = None):
+        """mode: "f16x3", "f32", "f16" (the tuned instances, shipped sizes only) or "generic" (any size within the limits of
+        include/s2s_hip.h); None picks "f16x3" for the shipped sizes and "generic" otherwise."""
         self._h = None
+        if mode is None:
+            mode = default_mode(config)
+        elif mode in TUNED_MODES and not is_tuned_family(config):
+            sizes = ", ".join(f"{k} {config[k]}" for k in TUNED_SIZES)
+            raise ValueError(f"mode {mode!r} runs only dmodel 64, dff 256, 8 encoder / decoder heads; this checkpoint has {sizes}: "
+                             "use mode 'generic'")
         L = _lib.lib()                       # raises when the HIP extension is missing
         if not torch.cuda.is_available():
             raise RuntimeError("seq2squiggle_amd needs a ROCm GPU (gfx950); there is no CPU fallback")
         self.device_index = torch.cuda.current_device() if device is None else int(device)
         self.device = torch.device("cuda", self.device_index)
         self.config = dict(config)
-        self._pe_dec_host = state_dict["decoders.position_enc"].detach().float().reshape(1, T_DEC, 64).clone()
+        self.dmodel = int(config["dmodel"])
+        self._pe_dec_host = state_dict["decoders.position_enc"].detach().float().reshape(1, T_DEC, self.dmodel).clone()
         self._pe_dec = None
         self.k = int(config["seq_kmer"])
         self.mode = mode
@@ -73,12 +82,12 @@ class Engine:
             self.set_profiling(True)
 
     @classmethod
-    def from_checkpoint(cls, path: str, device: Optional[int] = None, mode: str = "f16x3") -> "Engine":
+    def from_checkpoint(cls, path: str, device: Optional[int] = None, mode: Optional[str] = None) -> "Engine":
         sd, cfg = load_checkpoint(path)
         return cls(sd, cfg, device, mode)
 
     def decoder_position_enc(self) -> torch.Tensor:
-        """decoders.position_enc [1,250,64] on the engine's device (the stand-alone Decoder operator adds it, modules.py:136)."""
+        """decoders.position_enc [1,250,dmodel] on the engine's device (the stand-alone Decoder operator adds it, modules.py:136)."""
         if self._pe_dec is None:
             self._pe_dec = self._pe_dec_host.to(self.device)
         return self._pe_dec
@@ -114,7 +123,7 @@ class Engine:
                        dec_in: Optional[torch.Tensor] = None):
         """bases uint8 [B, 16+k-1] and n_valid uint8 [B] on the engine's device ->
         dict(signal fp32 [B,250] pA, dur int32 [B,16] [, debug stage tensors]).
-        emb_in [B,16,64] / dec_in [B,250,64] (float32): stage inputs taken from these tensors instead of being computed from the
+        emb_in [B,16,dmodel] / dec_in [B,250,dmodel] (float32): stage inputs taken from these tensors instead of being computed from the
         bases -- the stand-alone sub-module operators of seq2squiggle_amd.modules (s2s_debug.emb_in / dec_in)."""
         B = int(bases.shape[0])
         nb = T_ENC + self.k - 1
@@ -123,8 +132,8 @@ class Engine:
         if n_valid.dtype != torch.uint8 or n_valid.shape != (B,) or not n_valid.is_contiguous():
             raise ValueError("n_valid must be contiguous uint8 [B]")
         for name, t, shape in (("inject_g", inject_g, (B, T_ENC)), ("inject_zdw", inject_zdw, (B, T_ENC)),
-                               ("inject_z01", inject_z01, (B, T_DEC)), ("emb_in", emb_in, (B, T_ENC, 64)),
-                               ("dec_in", dec_in, (B, T_DEC, 64))):
+                               ("inject_z01", inject_z01, (B, T_DEC)), ("emb_in", emb_in, (B, T_ENC, self.dmodel)),
+                               ("dec_in", dec_in, (B, T_DEC, self.dmodel))):
             if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous()
                                   or t.device != self.device):
                 raise ValueError(f"{name} must be contiguous float32 {shape} on {self.device}")
@@ -140,7 +149,7 @@ class Engine:
         dbg = None
         if debug:
             f = dict(dtype=torch.float32, device=self.device)
-            out.update(emb_out=torch.zeros(B, 16, 64, **f), enc_out=torch.zeros(B, 16, 64, **f),
+            out.update(emb_out=torch.zeros(B, 16, self.dmodel, **f), enc_out=torch.zeros(B, 16, self.dmodel, **f),
                        sigma=torch.zeros(B, 16, **f), conc=torch.zeros(B, 16, **f), rate=torch.zeros(B, 16, **f),
                        g=torch.zeros(B, 16, **f), y_scaled=torch.zeros(B, T_DEC, **f), z01=torch.zeros(B, T_DEC, **f))
             dbg = _lib.S2SDebug(*[out[n].data_ptr() for n in ("emb_out", "enc_out", "sigma", "conc", "rate", "g",

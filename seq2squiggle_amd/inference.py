@@ -3,7 +3,7 @@ inference_run 270-427) with the Lightning Trainer replaced by a plain loop over 
 Weight download (inference.py:85-221) needs the network and is out of scope: pass --model."""
 import logging
 import os
-from typing import Iterable, Iterator, Tuple
+from typing import Iterable, Iterator, Optional, Tuple
 
 import numpy as np
 import torch
@@ -415,7 +415,7 @@ def inference_run(config: dict, saved_weights: str, fasta: str, read_input: bool
                   duration_sampling: bool, distr: str, predict_batch_size: int, export_every_n_samples: int,
                   sample_rate: int, bps: int, digitisation: int, range_val: float, offset_mean: float, offset_std: float,
                   median_before_mean: float, median_before_std: float, min_noise: float, min_duration: float,
-                  min_read_len: int, preserve_read_ids: bool, seed: int, mode: str = "f16x3", streaming: bool = True,
+                  min_read_len: int, preserve_read_ids: bool, seed: int, mode: Optional[str] = None, streaming: bool = True,
                   attention_path: str = "auto"):
     """Same 30 parameters as the reference (inference.py:270-301) plus `mode` (decoder arithmetic), `streaming`
     (True: run_streaming; False: the reference's predict_step / export_and_clear_results flow, batch by batch) and

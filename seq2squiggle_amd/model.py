@@ -49,7 +49,7 @@ class seq2squiggle:
     def __init__(self, *, config: dict, save_valid_plots: bool = True, out_writer=None, dwell_mean: float = 9.0,
                  dwell_std: float = 0.0, noise_std: float = -1, noise_sampling: bool = False,
                  duration_sampling: bool = False, export_every_n_samples: int = 2000000, min_noise: float = 0.5,
-                 min_duration: int = 1, state_dict=None, device: Optional[int] = None, mode: str = "f16x3",
+                 min_duration: int = 1, state_dict=None, device: Optional[int] = None, mode: Optional[str] = None,
                  seed: int = 0, first_global_chunk: int = 0):
         if state_dict is None:
             raise ValueError("the predict-only model needs trained weights: use load_from_checkpoint()")
@@ -70,6 +70,9 @@ class seq2squiggle:
         self.seed = seed
         self.chunks_done = int(first_global_chunk)      # global chunk index: keys the device RNG counters
         self.engine = Engine(state_dict, config, device=device, mode=mode)
+        logging.getLogger("seq2squiggle").info(
+            f"predict instance: {self.engine.mode} (dmodel {config['dmodel']}, dff {config['dff']}, "
+            f"heads {config['encoder_heads']} / {config['decoder_heads']})")
         self.device = self.engine.device
 
     @classmethod

@@ -44,7 +44,7 @@ def _f32(x: torch.Tensor, eng: Engine, shape) -> torch.Tensor:
 
 
 class Encoder:
-    """modules.py:22-89.  forward(src_seq [B,16,5k] or [B,16,k,5] one-hot) -> (enc_out, emb_out), each [B,16,64]."""
+    """modules.py:22-89.  forward(src_seq [B,16,5k] or [B,16,k,5] one-hot) -> (enc_out, emb_out), each [B,16,dmodel]."""
 
     def __init__(self, ctx: _Context):
         self._ctx = ctx
@@ -71,8 +71,8 @@ class NoiseSampler:
         ctx = self._ctx
         if ctx.out is not None and _same(x, ctx.out["emb_out"]):
             return ctx.out["sigma"].unsqueeze(-1)
-        eng = ctx.engine                                                         # stand-alone: any emb_out [B,16,64]
-        x = _f32(x, eng, (x.shape[0], 16, 64))
+        eng = ctx.engine                                                         # stand-alone: any emb_out [B,16,dmodel]
+        x = _f32(x, eng, (x.shape[0], 16, eng.dmodel))
         out = eng.predict_chunks(*_dummy_bases(eng, x.shape[0]), ctx.params, debug=True, emb_in=x, **ctx.inject)
         return out["sigma"].unsqueeze(-1)
 
@@ -80,7 +80,7 @@ class NoiseSampler:
 
 
 class LengthRegulator:
-    """modules.py:344-441.  forward(emb_out, x, noise_std_prediction, ...) -> (out [B,250,64], dur_float [B,16], dist,
+    """modules.py:344-441.  forward(emb_out, x, noise_std_prediction, ...) -> (out [B,250,dmodel], dur_float [B,16], dist,
     noise_ext [B,250,1], None).  The dwell source is the one the context's PredictParams select (the keyword arguments of
     the reference call are checked against them); `out` is assembled here from enc_out and the kernel's dwell counts -- the
     kernel itself never materialises it -- and `dist` is the Gamma of the kernel's conc / rate."""
@@ -103,9 +103,9 @@ class LengthRegulator:
         chained = o is not None and _same(emb_out, o["emb_out"])
         if not chained:                              # stand-alone: the dwell source on the caller's emb_out (one launch), then pure indexing
             eng = ctx.engine
-            e = _f32(emb_out, eng, (emb_out.shape[0], 16, 64))
+            e = _f32(emb_out, eng, (emb_out.shape[0], 16, eng.dmodel))
             o = eng.predict_chunks(*_dummy_bases(eng, e.shape[0]), p, debug=True, emb_in=e, **ctx.inject)
-        x_src = o["enc_out"] if chained and _same(x, o["enc_out"]) else _f32(x, ctx.engine, (o["dur"].shape[0], 16, 64))
+        x_src = o["enc_out"] if chained and _same(x, o["enc_out"]) else _f32(x, ctx.engine, (o["dur"].shape[0], 16, ctx.engine.dmodel))
         sig = noise_std_prediction
         sig_src = (o["sigma"] if chained and _same(sig, o["sigma"].unsqueeze(-1))
                    else _f32(sig.reshape(sig.shape[0], 16), ctx.engine, (o["dur"].shape[0], 16)))
@@ -115,7 +115,7 @@ class LengthRegulator:
         idx = (cum.unsqueeze(1) <= t).sum(-1)                                   # [B,250]: 16 = past the last dwell
         live = (idx < 16).unsqueeze(-1)
         row = idx.clamp(max=15)
-        out = torch.where(live, x_src.gather(1, row.unsqueeze(-1).expand(-1, -1, 64)), torch.zeros((), device=dur.device))
+        out = torch.where(live, x_src.gather(1, row.unsqueeze(-1).expand(-1, -1, x_src.shape[-1])), torch.zeros((), device=dur.device))
         noise_ext = torch.where(live, sig_src.gather(1, row).unsqueeze(-1), torch.zeros((), device=dur.device))
         dist = torch.distributions.Gamma(o["conc"], o["rate"]) if p.duration_sampling else None
         ctx.lr_out = out if chained and x_src is o["enc_out"] else None
@@ -125,7 +125,7 @@ class LengthRegulator:
 
 
 class Decoder:
-    """modules.py:97-142.  forward(enc_seq [B,250,64]) -> [B,250,1] (scaled units, after the ReLU)."""
+    """modules.py:97-142.  forward(enc_seq [B,250,dmodel]) -> [B,250,1] (scaled units, after the ReLU)."""
 
     def __init__(self, ctx: _Context):
         self._ctx = ctx
@@ -136,8 +136,8 @@ class Decoder:
         ctx = self._ctx
         if ctx.out is not None and _same(enc_seq, getattr(ctx, "lr_out", None)):
             return ctx.out["y_scaled"].unsqueeze(-1)
-        eng = ctx.engine                                                         # stand-alone: any [B,250,64]; position_enc is added
-        x = _f32(enc_seq, eng, (enc_seq.shape[0], 250, 64)) + eng.decoder_position_enc()   # inside the operator (modules.py:136)
+        eng = ctx.engine                                                         # stand-alone: any [B,250,dmodel]; position_enc is added
+        x = _f32(enc_seq, eng, (enc_seq.shape[0], 250, eng.dmodel)) + eng.decoder_position_enc()   # inside the operator (modules.py:136)
         params = PredictParams(**{**ctx.params.__dict__, "noise_std": 0.0})
         out = eng.predict_chunks(*_dummy_bases(eng, x.shape[0]), params, debug=True, dec_in=x.contiguous())
         return out["y_scaled"].unsqueeze(-1)

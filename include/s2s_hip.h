@@ -45,6 +45,16 @@ extern "C" {
  *                   pipeline of its own kernels (csrc/s2s_generic.h) over slices of the launch's chunks, the f32-input MFMA for every
  *                   matrix product, an exact softmax with its own row maximum.  Same Philox counters as the tuned instances. */
 #define S2S_MODE_GENERIC 4
+/*   S2S_MODE_GENERIC_F16  REDUCED PRECISION, outside the 1e-4 pA bound, opt-in (never chosen by default): every size
+ *                   S2S_MODE_GENERIC accepts, at the precision class of the reference's 16-mixed GPU path (inference.py:403-404).
+ *                   Embedding, pre-net, encoder FFT blocks, the noise and duration heads, dwell and the length regulator are
+ *                   S2S_MODE_GENERIC's exact fp32 code (emb_out, enc_out, sigma, conc, rate, g and the dwell indices are bit-equal to
+ *                   it); in the decoder FFT blocks every matrix product (QKV, fc, w_1, w_2, Q.K^T, P.V) takes its operands rounded to
+ *                   f16 once and accumulates in fp32 (v_mfma_f32_16x16x32_f16, csrc/s2s_generic_h.h), with fp32 bias, ReLU, residual
+ *                   and LayerNorm, an fp32 softmax with its exact row maximum, P rounded to f16 after the normalisation;
+ *                   out_linear, scale, noise and clamp stay fp32.  Range: a decoder activation or weight of magnitude >= 65,504
+ *                   becomes inf in f16 -- the limit of the reference's own 16-mixed run. */
+#define S2S_MODE_GENERIC_F16 5
 
 #define S2S_T_ENC 16         /* config.yaml:18 max_dna_len    */
 #define S2S_T_DEC 250        /* config.yaml:19 max_signal_len */
@@ -58,8 +68,8 @@ extern "C" {
  * decoder layers 1..4, pre_layers 0..4.  Sizes:
  *   tuned modes (F32, F16X3, F16): the shipped architecture family only -- dmodel 64, dff 256,
  *                   8 heads in encoder and decoder;
- *   S2S_MODE_GENERIC: dmodel a multiple of 16 in 16..512, dff a multiple of 8 in 8..2048, encoder and
- *                   decoder heads each 1..16 and a divisor of dmodel (head_dim = dmodel / heads).
+ *   S2S_MODE_GENERIC and S2S_MODE_GENERIC_F16: dmodel a multiple of 16 in 16..512, dff a multiple of 8 in
+ *                   8..2048, encoder and decoder heads each 1..16 and a divisor of dmodel (head_dim = dmodel / heads).
  * A refused configuration is S2S_ERR_ARG from s2s_create (the message names the key) and
  * s2s_blob_floats returns 0 for it. */
 typedef struct s2s_config {
@@ -109,7 +119,7 @@ typedef struct s2s_debug {
 typedef struct s2s_handle s2s_handle;
 
 /* Number of fp32 values the weight blob must hold for `cfg` (0 for a refused configuration), and the order, written for the
- * tuned sizes -- for S2S_MODE_GENERIC read every 64 as dmodel and every 256 as dff:
+ * tuned sizes -- for S2S_MODE_GENERIC and S2S_MODE_GENERIC_F16 (the same blob) read every 64 as dmodel and every 256 as dff:
  *   encoders.position_enc[16*64]; src_emb.weight[64][5k], .bias[64];
  *   pre_net_stack.i.weight[64][64], .bias[64]                               (i < pre_layers)
  *   per encoder layer: LAYER (below)

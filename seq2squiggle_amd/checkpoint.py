@@ -79,7 +79,8 @@ def state_dict_to_blob(sd: Dict[str, torch.Tensor], cfg: dict) -> np.ndarray:
     return np.concatenate([sd[n].detach().float().cpu().numpy().ravel() for n in blob_names(cfg)]).astype(np.float32)
 
 
-MODES = {"f32": 0, "f16x3": 1, "f16": 3, "generic": 4}     # f16: reduced precision; generic: any size (see include/s2s_hip.h)
+# f16: reduced precision; generic: any size; generic-f16: any size, reduced precision, opt-in only (see include/s2s_hip.h)
+MODES = {"f32": 0, "f16x3": 1, "f16": 3, "generic": 4, "generic-f16": 5}
 TUNED_MODES = ("f32", "f16x3", "f16")
 TUNED_SIZES = {"dmodel": 64, "dff": 256, "encoder_heads": 8, "decoder_heads": 8}
 

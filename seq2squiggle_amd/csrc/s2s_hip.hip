@@ -11,6 +11,7 @@
 #include "s2s_device.h"
 #include "s2s_device_h.h"
 #include "s2s_generic.h"
+#include "s2s_generic_h.h"
 #include "../../include/s2s_hip.h"
 
 #include <cctype>
@@ -851,13 +852,17 @@ struct s2s_handle {
     double calib_redo_rate = -1.0;          // share of the calibration launch's softmax runs that overflowed the fast path (-1: not calibrated)
     std::vector<EventPair> events;
     std::string err;
-    // S2S_MODE_GENERIC (s2s_generic.h): blob offsets into d_arena, and the slice workspace (grown on demand, s2s_predict_*)
+    // S2S_MODE_GENERIC / _GENERIC_F16 (s2s_generic.h, s2s_generic_h.h): blob offsets into d_arena, and the slice workspace (grown on
+    // demand, s2s_predict_*)
     struct Generic {
         int d = 0, dff = 0, h_enc = 0, h_dec = 0;
+        bool f16 = false;             // S2S_MODE_GENERIC_F16: the decoder FFT blocks on f16 operands (dech)
         long long pe_enc = 0, pe_dec = 0, emb_wt = 0, emb_b = 0, out_w = 0, out_b = 0, w0cat = 0, b0cat = 0;
         long long pre_w[S2S_MAX_LAYERS] = {}, pre_b[S2S_MAX_LAYERS] = {};
         GenLayer enc[S2S_MAX_LAYERS] = {}, dec[S2S_MAX_LAYERS] = {};
+        GenLayerH dech[S2S_MAX_LAYERS] = {};
         GenHeads heads = {};
+        int ld_d = 0, ld_f = 0;       // row pitch (halves) of the f16 weights with K = dmodel / dff
         int slice_max = 0;            // chunks per slice (S2S_GENERIC_WORKSPACE_BYTES)
         float* ws = nullptr;
         int ws_chunks = 0;            // slice capacity of ws
@@ -899,6 +904,8 @@ struct DeviceGuard {
 size_t layer_floats() { return 4 * (64 * 64 + 64) + 2 * 64 + (256 * 64 + 256) + (64 * 256 + 64) + 2 * 64; }
 size_t mlp_floats() { return 64 * 64 + 64 + 64 + 1; }
 
+bool mode_generic(int m) { return m == S2S_MODE_GENERIC || m == S2S_MODE_GENERIC_F16; }
+
 const char* check_cfg_generic(const s2s_config* c) {
     if (c->max_dna_len != S2S_T_ENC) return "max_dna_len must be 16";
     if (c->max_signal_len != S2S_T_DEC) return "max_signal_len must be 250";
@@ -917,7 +924,7 @@ const char* check_cfg_generic(const s2s_config* c) {
 const char* check_cfg(const s2s_config* c) {
     if (!c) return "config is NULL";
     if (c->seq_kmer < 1 || c->seq_kmer > 16) return "seq_kmer must be 1..16";
-    if (c->compute_mode == S2S_MODE_GENERIC) return check_cfg_generic(c);
+    if (mode_generic(c->compute_mode)) return check_cfg_generic(c);
     if (c->max_dna_len != S2S_T_ENC) return "max_dna_len must be 16";
     if (c->max_signal_len != S2S_T_DEC) return "max_signal_len must be 250";
     if (c->dmodel != S2S_DMODEL) return "dmodel must be 64";
@@ -1184,6 +1191,26 @@ void pack_generic(Arena& A, s2s_handle::Generic& G, const s2s_config* cfg, const
     }
     G.pe_dec = A.put(take(p, 250 * (size_t)d), 250 * (size_t)d);
     for (int l = 0; l < cfg->decoder_layers; ++l) layer(G.dec[l]);
+    G.f16 = cfg->compute_mode == S2S_MODE_GENERIC_F16;
+    if (G.f16) {   // the decoder's four weight matrices once more, rounded to f16, rows zero-padded to K rounded up to 32 (gen_gemm_h_kernel)
+        G.ld_d = (d + 31) & ~31;
+        G.ld_f = (f + 31) & ~31;
+        auto put_h = [&](long long off, int rows, int K, int ldw) {
+            const SplitF16 h = split_f16(A.v.data() + off, (size_t)rows * K);
+            std::vector<_Float16> t((size_t)rows * ldw, (_Float16)0.0f);
+            for (int r = 0; r < rows; ++r) std::memcpy(t.data() + (size_t)r * ldw, h.hi.data() + (size_t)r * K, K * sizeof(_Float16));
+            std::vector<float> raw(t.size() / 2);
+            std::memcpy(raw.data(), t.data(), t.size() * sizeof(_Float16));
+            return (long long)A.put(raw.data(), raw.size());
+        };
+        for (int l = 0; l < cfg->decoder_layers; ++l) {
+            const GenLayer& L = G.dec[l];
+            G.dech[l].wqkv = put_h(L.wqkv, 3 * d, d, G.ld_d);
+            G.dech[l].wfc = put_h(L.wfc, d, d, G.ld_d);
+            G.dech[l].w1 = put_h(L.w1, f, d, G.ld_d);
+            G.dech[l].w2 = put_h(L.w2, d, f, G.ld_f);
+        }
+    }
     G.out_w = A.put(take(p, d), d);
     G.out_b = A.put(take(p, 1), 1);
     G.slice_max = (int)(S2S_GENERIC_WORKSPACE_BYTES / (4 * generic_chunk_floats(cfg)));
@@ -1222,6 +1249,28 @@ void gen_fft_block(hipStream_t st, const float* W, const GenLayer& L, float* X, 
     hipLaunchKernelGGL(gen_layernorm_kernel, dim3((M + 3) / 4), dim3(256), 0, st, X, W + L.ln1g, W + L.ln1b, (long long)M, d);
     gen_gemm<1>(st, X, d, W + L.w1, W + L.b1, BIG, dff, nullptr, M, dff, d);
     gen_gemm<2>(st, BIG, dff, W + L.w2, W + L.b2, X, d, X, M, d, dff);
+    hipLaunchKernelGGL(gen_layernorm_kernel, dim3((M + 3) / 4), dim3(256), 0, st, X, W + L.ln2g, W + L.ln2b, (long long)M, d);
+}
+
+// S2S_MODE_GENERIC_F16's decoder FFTBlock: gen_fft_block with the matrix products on f16 operands (s2s_generic_h.h); the
+// LayerNorms, the biases, ReLU and the residuals stay fp32.  T = 250.
+template <int EPI>
+void gen_gemm_h(hipStream_t st, const float* A, int lda, const float* Wh, int ldw, const float* bias, float* C, int ldc, const float* R, int M, int N,
+                int K) {
+    const dim3 grid((M + GEN_BM - 1) / GEN_BM, (N + GEN_BN - 1) / GEN_BN);
+    hipLaunchKernelGGL(gen_gemm_h_kernel<EPI>, grid, dim3(256), 0, st, A, lda, reinterpret_cast<const _Float16*>(Wh), ldw, bias, C, ldc, R, ldc,
+                       M, N, K);
+}
+
+void gen_fft_block_h(hipStream_t st, const float* W, const GenLayer& L, const GenLayerH& LH, int ld_d, int ld_f, float* X, float* BIG, int n,
+                     int d, int dff, int H) {
+    const int M = n * GEN_T_DEC;
+    gen_gemm_h<0>(st, X, d, W + LH.wqkv, ld_d, W + L.bqkv, BIG, 3 * d, nullptr, M, 3 * d, d);
+    hipLaunchKernelGGL(gen_attention_h_kernel, dim3(n * H), dim3(1024), 0, st, BIG, d, H);
+    gen_gemm_h<2>(st, BIG, 3 * d, W + LH.wfc, ld_d, W + L.bfc, X, d, X, M, d, d);
+    hipLaunchKernelGGL(gen_layernorm_kernel, dim3((M + 3) / 4), dim3(256), 0, st, X, W + L.ln1g, W + L.ln1b, (long long)M, d);
+    gen_gemm_h<1>(st, X, d, W + LH.w1, ld_d, W + L.b1, BIG, dff, nullptr, M, dff, d);
+    gen_gemm_h<2>(st, BIG, dff, W + LH.w2, ld_f, W + L.b2, X, d, X, M, d, dff);
     hipLaunchKernelGGL(gen_layernorm_kernel, dim3((M + 3) / 4), dim3(256), 0, st, X, W + L.ln2g, W + L.ln2b, (long long)M, d);
 }
 
@@ -1293,7 +1342,12 @@ static int predict_generic(s2s_handle* h, hipStream_t st, const uint8_t* bases, 
             HIP_TRY(h, hipMemcpyAsync(D.enc_out + (size_t)s * 16 * d, XE, (size_t)Me * d * sizeof(float), hipMemcpyDeviceToDevice, st));
         hipLaunchKernelGGL(gen_lenreg_kernel, dim3((Md + 3) / 4), dim3(256), 0, st, W, G.pe_dec, d, n, XE, SIG, out_dur + s * 16, XD, SE,
                            D.dec_in ? D.dec_in + (size_t)s * 250 * d : nullptr);
-        for (int l = 0; l < h->cfg.decoder_layers; ++l) gen_fft_block(st, W, G.dec[l], XD, BIG, n, 250, d, dff, G.h_dec);
+        for (int l = 0; l < h->cfg.decoder_layers; ++l) {
+            if (G.f16)
+                gen_fft_block_h(st, W, G.dec[l], G.dech[l], G.ld_d, G.ld_f, XD, BIG, n, d, dff, G.h_dec);
+            else
+                gen_fft_block(st, W, G.dec[l], XD, BIG, n, 250, d, dff, G.h_dec);
+        }
         hipLaunchKernelGGL(gen_emit_kernel, dim3((Md + 3) / 4), dim3(256), 0, st, W, G.out_w, G.out_b, h->cfg.scaling_max_value, d, n, XD, SE,
                            fc, P, inject_z01 ? inject_z01 + (size_t)s * 250 : nullptr, out_signal + (size_t)s * 250, Ds);
     }
@@ -1310,7 +1364,7 @@ extern "C" {
 
 size_t s2s_blob_floats(const s2s_config* c) {
     if (check_cfg(c)) return 0;
-    if (c->compute_mode == S2S_MODE_GENERIC) {
+    if (mode_generic(c->compute_mode)) {
         const size_t d = c->dmodel, f = c->dff;
         return 16 * d + d * 5 * c->seq_kmer + d + (size_t)c->pre_layers * (d * d + d) +
                (size_t)(c->encoder_layers + c->decoder_layers) * generic_layer_floats(d, f) + 3 * (d * d + d + d + 1) + 250 * d + d + 1;
@@ -1328,7 +1382,7 @@ static int predict_impl(s2s_handle* h, void* stream_, const uint8_t* bases, cons
 // every head on the exact path (s2s_device_h.h: the online softmax as its own kernel instance).  A fixed input, so the same weights always get the same
 // answer, on any device.  The export scratch inside the slab holds the launch's buffers.
 static int calibrate_attention(s2s_handle* h) {
-    if (h->cfg.compute_mode == S2S_MODE_F32 || h->cfg.compute_mode == S2S_MODE_GENERIC) return S2S_OK;
+    if (h->cfg.compute_mode == S2S_MODE_F32 || mode_generic(h->cfg.compute_mode)) return S2S_OK;
     const int B = 512, nb = S2S_T_ENC + h->cfg.seq_kmer - 1;
     std::vector<uint8_t> host((size_t)B * nb + B);
     uint32_t x = 0x9E3779B9u;
@@ -1403,7 +1457,7 @@ int s2s_create(const s2s_config* cfg, const void* blob, size_t blob_bytes, int d
     Arena A;
     ModelDev& M = h->model;
     std::memset(&M, 0, sizeof M);
-    if (cfg->compute_mode == S2S_MODE_GENERIC) {
+    if (mode_generic(cfg->compute_mode)) {
         pack_generic(A, h->gen, cfg, static_cast<const float*>(blob));
     } else {
     M.k = k; M.enc_layers = cfg->encoder_layers; M.dec_layers = cfg->decoder_layers; M.pre_layers = cfg->pre_layers;
@@ -1478,7 +1532,7 @@ int s2s_create(const s2s_config* cfg, const void* blob, size_t blob_bytes, int d
     for (const auto& k : dyn_lds)
         if ((e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.bytes)) != hipSuccess)
             return bail(e, "hipFuncSetAttribute(dynamic LDS)");
-    if (cfg->compute_mode == S2S_MODE_GENERIC &&
+    if (mode_generic(cfg->compute_mode) &&
         (e = hipFuncSetAttribute(reinterpret_cast<const void*>(gen_attention_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                  GEN_ATTN_STAGE_BYTES)) != hipSuccess)
         return bail(e, "hipFuncSetAttribute(generic attention LDS)");
@@ -1559,7 +1613,7 @@ static int predict_impl(s2s_handle* h, void* stream_, const uint8_t* bases, cons
     D.diag = h->d_diag;
     D.stats = h->d_stats;
     h->stat_chunks += B;
-    if (h->cfg.compute_mode == S2S_MODE_GENERIC)
+    if (mode_generic(h->cfg.compute_mode))
         return predict_generic(h, stream, bases, chunk_start, n_valid, first_global_chunk, B, P, inject_g, inject_zdw, inject_z01,
                                out_signal, out_dur, D);
     const int nb = S2S_T_ENC + h->cfg.seq_kmer - 1;
@@ -1734,7 +1788,7 @@ int s2s_stats_read(s2s_handle* h, uint64_t* out10) {
     HIP_TRY(h, hipMemcpy(raw, h->d_stats, sizeof raw, hipMemcpyDeviceToHost));
     HIP_TRY(h, hipMemset(h->d_stats, 0, sizeof raw));
     out10[0] = (uint64_t)h->stat_chunks;
-    out10[1] = h->cfg.compute_mode == S2S_MODE_GENERIC
+    out10[1] = mode_generic(h->cfg.compute_mode)
                    ? (uint64_t)h->stat_chunks * (uint64_t)cfg_dec_heads(&h->cfg) * (uint64_t)h->cfg.decoder_layers
                    : (uint64_t)h->stat_chunks * DEC_WAVES * S2S_HEADS * (uint64_t)h->cfg.decoder_layers;
     out10[2] = raw[S2S_STAT_REDO];

@@ -45,15 +45,16 @@ class Engine:
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], config: dict, device: Optional[int] = None,
                  mode: Optional[str] = None):
-        """mode: "f16x3", "f32", "f16" (the tuned instances, shipped sizes only) or "generic" (any size within the limits of
-        include/s2s_hip.h); None picks "f16x3" for the shipped sizes and "generic" otherwise."""
+        """mode: "f16x3", "f32", "f16" (the tuned instances, shipped sizes only), "generic" (any size within the limits of
+        include/s2s_hip.h) or "generic-f16" (the same sizes, the decoder's matrix products on f16 operands: reduced precision, never
+        picked by default); None picks "f16x3" for the shipped sizes and "generic" otherwise."""
         self._h = None
         if mode is None:
             mode = default_mode(config)
         elif mode in TUNED_MODES and not is_tuned_family(config):
             sizes = ", ".join(f"{k} {config[k]}" for k in TUNED_SIZES)
             raise ValueError(f"mode {mode!r} runs only dmodel 64, dff 256, 8 encoder / decoder heads; this checkpoint has {sizes}: "
-                             "use mode 'generic'")
+                             "use mode 'generic'" + (" (exact fp32) or 'generic-f16' (reduced precision)" if mode == "f16" else ""))
         L = _lib.lib()                       # raises when the HIP extension is missing
         if not torch.cuda.is_available():
             raise RuntimeError("seq2squiggle_amd needs a ROCm GPU (gfx950); there is no CPU fallback")

@@ -2,7 +2,7 @@
 """Throughput of the size-generic instance (GPU box): chunks/s of predict_chunks in mode "generic" for the shipped size
 (tests/golden/synthetic_k9.ckpt) and every size case of tests/_sized_models.py, next to the tuned "f32" instance at the default size, with
 the built-in samplers.  One JSON line per case; the device clock is read with amd-smi where available (read-only).
-    python tools/generic_rate.py [chunks]"""
+    python tools/generic_rate.py [chunks] [tag:mode ...]     (default: every case below)"""
 import json, os, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -47,6 +47,7 @@ def rate(tag, mode):
 
 
 print(json.dumps({"device": torch.cuda.get_device_name(0), "clock_before": clock()}))
-for tag, mode in (("k9", "f32"), ("k9", "generic"), ("d32", "generic"), ("d128", "generic"), ("d512", "generic")):
+CASES = [("k9", "f32")] + [(t, m) for t in ("k9", "d32", "d128", "d512") for m in ("generic", "generic-f16")]
+for tag, mode in ([tuple(a.split(":", 1)) for a in sys.argv[2:]] or CASES):
     print(json.dumps(rate(tag, mode)), flush=True)
 print(json.dumps({"clock_after": clock()}))

@@ -55,6 +55,16 @@ extern "C" {
  *                   out_linear, scale, noise and clamp stay fp32.  Range: a decoder activation or weight of magnitude >= 65,504
  *                   becomes inf in f16 -- the limit of the reference's own 16-mixed run. */
 #define S2S_MODE_GENERIC_F16 5
+/*   S2S_MODE_GENERIC_GEOMETRY  S2S_MODE_GENERIC (every size it accepts, exact fp32, the same parity bound) with the chunk geometry
+ *                   a property of the handle: max_dna_len 1..S2S_GEOMETRY_MAX_DNA_LEN k-mers in and max_signal_len
+ *                   1..S2S_GEOMETRY_MAX_SIGNAL_LEN samples out per chunk, the checkpoint's own.  At 16 / 250 it runs
+ *                   S2S_MODE_GENERIC's kernels on S2S_MODE_GENERIC's numbers; beyond 256 samples the decoder attention is an
+ *                   MFMA kernel of its own (csrc/s2s_generic.h, gen_attention_long_kernel).  Every [16] and [250] of this header
+ *                   reads as [max_dna_len] and [max_signal_len] for such a handle.  Reduced precision at other geometries (a
+ *                   S2S_MODE_GENERIC_F16 counterpart) does not exist yet. */
+#define S2S_MODE_GENERIC_GEOMETRY 6
+#define S2S_GEOMETRY_MAX_DNA_LEN 64
+#define S2S_GEOMETRY_MAX_SIGNAL_LEN 1024
 
 #define S2S_T_ENC 16         /* config.yaml:18 max_dna_len    */
 #define S2S_T_DEC 250        /* config.yaml:19 max_signal_len */
@@ -63,19 +73,19 @@ extern "C" {
 #define S2S_HEADS 8          /* config.yaml:28,30             */
 
 /* Model hyper-parameters that change the predict arithmetic (config.yaml:17-31; the keys
- * Encoder/Decoder.__init__ read, modules.py:22-63, 97-131).  Every mode: 16 k-mers in, 250 samples
- * out (the chunk geometry of the export kernels and the host framing), seq_kmer 1..16, encoder and
- * decoder layers 1..4, pre_layers 0..4.  Sizes:
+ * Encoder/Decoder.__init__ read, modules.py:22-63, 97-131).  Every mode but S2S_MODE_GENERIC_GEOMETRY: 16 k-mers in,
+ * 250 samples out (the chunk geometry of the export kernels and the host framing); S2S_MODE_GENERIC_GEOMETRY: max_dna_len
+ * 1..64, max_signal_len 1..1024.  Every mode: seq_kmer 1..16, encoder and decoder layers 1..4, pre_layers 0..4.  Sizes:
  *   tuned modes (F32, F16X3, F16): the shipped architecture family only -- dmodel 64, dff 256,
  *                   8 heads in encoder and decoder;
- *   S2S_MODE_GENERIC and S2S_MODE_GENERIC_F16: dmodel a multiple of 16 in 16..512, dff a multiple of 8 in
+ *   S2S_MODE_GENERIC, S2S_MODE_GENERIC_F16 and S2S_MODE_GENERIC_GEOMETRY: dmodel a multiple of 16 in 16..512, dff a multiple of 8 in
  *                   8..2048, encoder and decoder heads each 1..16 and a divisor of dmodel (head_dim = dmodel / heads).
  * A refused configuration is S2S_ERR_ARG from s2s_create (the message names the key) and
  * s2s_blob_floats returns 0 for it. */
 typedef struct s2s_config {
     int32_t seq_kmer;          /* 9 (dna-r10*, rna-004*) or 6 (dna-r9*), utils.py:257-260 */
-    int32_t max_dna_len;       /* must be 16  */
-    int32_t max_signal_len;    /* must be 250 */
+    int32_t max_dna_len;       /* must be 16;  S2S_MODE_GENERIC_GEOMETRY: 1..64   */
+    int32_t max_signal_len;    /* must be 250; S2S_MODE_GENERIC_GEOMETRY: 1..1024 */
     int32_t dmodel;            /* tuned: 64;  generic: 16..512, a multiple of 16 */
     int32_t dff;               /* tuned: 256; generic: 8..2048, a multiple of 8 */
     int32_t n_heads;           /* encoder heads; tuned: 8; generic: 1..16, divides dmodel */
@@ -100,7 +110,8 @@ typedef struct s2s_params {
     uint64_t seed;             /* key of the counter-based Philox4x32-10 generator */
 } s2s_params;
 
-/* Optional stage outputs for parity tests (all nullable, device).  [64] below is [dmodel] for a generic handle. */
+/* Optional stage outputs for parity tests (all nullable, device).  [64] below is [dmodel] for a generic handle; [16] and [250]
+ * are [max_dna_len] and [max_signal_len] for a S2S_MODE_GENERIC_GEOMETRY handle. */
 typedef struct s2s_debug {
     float* emb_out;            /* [B][16][64]  Encoder.forward 2nd result (modules.py:72-77) */
     float* enc_out;            /* [B][16][64]  Encoder.forward 1st result (modules.py:80-89) */
@@ -119,7 +130,8 @@ typedef struct s2s_debug {
 typedef struct s2s_handle s2s_handle;
 
 /* Number of fp32 values the weight blob must hold for `cfg` (0 for a refused configuration), and the order, written for the
- * tuned sizes -- for S2S_MODE_GENERIC and S2S_MODE_GENERIC_F16 (the same blob) read every 64 as dmodel and every 256 as dff:
+ * tuned sizes -- for S2S_MODE_GENERIC, S2S_MODE_GENERIC_F16 and S2S_MODE_GENERIC_GEOMETRY (the same blob) read every 64 as dmodel
+ * and every 256 as dff, and for S2S_MODE_GENERIC_GEOMETRY 16 as max_dna_len and 250 as max_signal_len in the position tables:
  *   encoders.position_enc[16*64]; src_emb.weight[64][5k], .bias[64];
  *   pre_net_stack.i.weight[64][64], .bias[64]                               (i < pre_layers)
  *   per encoder layer: LAYER (below)
@@ -133,7 +145,8 @@ typedef struct s2s_handle s2s_handle;
  * i.e. the reference state_dict (SURVEY.md section 8 a-W) in its native [out][in] layouts.
  *
  * A generic handle runs a launch in slices of at most S2S_GENERIC_WORKSPACE_BYTES / (4 * per-chunk floats) chunks, per-chunk
- * floats = 16 dmodel + 250 dmodel + 250 max(3 dmodel, dff) + 16 + 250 (each buffer is then rounded up to a multiple of
+ * floats = te dmodel + ts dmodel + max(te, ts) max(3 dmodel, dff) + te + ts, te / ts = max_dna_len / max_signal_len (16 / 250
+ * outside S2S_MODE_GENERIC_GEOMETRY; each buffer is then rounded up to a multiple of
  * 64 floats); the workspace grows on demand (the first launch of a larger batch synchronises the stream) and is reused. */
 #define S2S_GENERIC_WORKSPACE_BYTES (512u << 20)
 size_t s2s_blob_floats(const s2s_config* cfg);
@@ -189,6 +202,7 @@ int s2s_predict_packed(s2s_handle* h, void* stream, const uint8_t* read_bytes, c
  *  out_dac      nullable device int16 [capacity]: round_half_even(pa*digitisation/range - offset)
  *               wrapped to int16; reversed per read when rna != 0 (signal_io.py:140-141);
  *  capacity     size of out_pa/out_dac in samples (B*250 always suffices).
+ * Rows are 250 samples, max_signal_len for a S2S_MODE_GENERIC_GEOMETRY handle.
  */
 int s2s_export_reads(s2s_handle* h, void* stream, const float* signal, int32_t B,
                      const int32_t* read_first, int32_t R, int64_t* out_offsets, float* out_pa,

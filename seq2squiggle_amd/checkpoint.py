@@ -79,10 +79,17 @@ def state_dict_to_blob(sd: Dict[str, torch.Tensor], cfg: dict) -> np.ndarray:
     return np.concatenate([sd[n].detach().float().cpu().numpy().ravel() for n in blob_names(cfg)]).astype(np.float32)
 
 
-# f16: reduced precision; generic: any size; generic-f16: any size, reduced precision, opt-in only (see include/s2s_hip.h)
-MODES = {"f32": 0, "f16x3": 1, "f16": 3, "generic": 4, "generic-f16": 5}
+# f16: reduced precision; generic: any size; generic-f16: any size, reduced precision, opt-in only; generic-geometry: any size at any
+# chunk geometry (max_dna_len / max_signal_len), exact fp32 (see include/s2s_hip.h)
+MODES = {"f32": 0, "f16x3": 1, "f16": 3, "generic": 4, "generic-f16": 5, "generic-geometry": 6}
 TUNED_MODES = ("f32", "f16x3", "f16")
 TUNED_SIZES = {"dmodel": 64, "dff": 256, "encoder_heads": 8, "decoder_heads": 8}
+DEFAULT_GEOMETRY = {"max_dna_len": 16, "max_signal_len": 250}     # the only chunk geometry of every mode but generic-geometry
+
+
+def is_default_geometry(cfg: dict) -> bool:
+    """Does `cfg` chunk reads as 16 k-mers -> 250 samples?  Other geometries run on "generic-geometry" only."""
+    return all(int(cfg[k]) == v for k, v in DEFAULT_GEOMETRY.items())
 
 
 def is_tuned_family(cfg: dict) -> bool:
@@ -91,7 +98,10 @@ def is_tuned_family(cfg: dict) -> bool:
 
 
 def default_mode(cfg: dict) -> str:
-    """The instance a checkpoint runs on when none is asked for: "f16x3" for the tuned sizes, "generic" otherwise."""
+    """The instance a checkpoint runs on when none is asked for: "generic-geometry" at any chunk geometry but 16 / 250, else
+    "f16x3" for the tuned sizes and "generic" for the others."""
+    if not is_default_geometry(cfg):
+        return "generic-geometry"
     return "f16x3" if is_tuned_family(cfg) else "generic"
 
 

@@ -5,7 +5,8 @@ Reference: split_sequence (utils.py:350-356) = extract_kmers (334-339) + add_rem
 (dataloader.py:358-398).  The reference materialises fp16 one-hot [C,16,k,5]; the device path
 takes the raw bases instead: chunk c is read[16c : 16c+15+k] plus the number of real k-mers in
 it (k-mers past the read's end are the all-"_" pad k-mer, which is NOT a window over padded
-bases, so it cannot be expressed by padding the bytes alone).
+bases, so it cannot be expressed by padding the bytes alone).  16 is the config's max_dna_len: every
+function takes it as `t_enc` (default 16; a "generic-geometry" checkpoint chunks at its own).
 """
 from typing import Iterable, List, Sequence, Tuple
 
@@ -14,16 +15,17 @@ import numpy as np
 T_ENC = 16
 
 
-def n_chunks(read_len: int, k: int) -> int:
+def n_chunks(read_len: int, k: int, t_enc: int = T_ENC) -> int:
     n_kmer = read_len - k + 1
-    return 0 if n_kmer <= 0 else -(-n_kmer // T_ENC)
+    return 0 if n_kmer <= 0 else -(-n_kmer // t_enc)
 
 
-def encode_read(seq: str, k: int) -> Tuple[np.ndarray, np.ndarray]:
-    """-> (bases uint8 [C, 16+k-1] ASCII, n_valid uint8 [C]).  A read shorter than k gives C == 0
+def encode_read(seq: str, k: int, t_enc: int = T_ENC) -> Tuple[np.ndarray, np.ndarray]:
+    """-> (bases uint8 [C, t_enc+k-1] ASCII, n_valid uint8 [C]).  A read shorter than k gives C == 0
     (the reference skips it, dataloader.py:393-398)."""
+    T_ENC = t_enc
     nb = T_ENC + k - 1
-    C = n_chunks(len(seq), k)
+    C = n_chunks(len(seq), k, T_ENC)
     if C == 0:
         return np.zeros((0, nb), np.uint8), np.zeros((0,), np.uint8)
     raw = np.frombuffer(seq.encode("latin-1"), dtype=np.uint8)
@@ -35,16 +37,16 @@ def encode_read(seq: str, k: int) -> Tuple[np.ndarray, np.ndarray]:
     return buf[idx], nv
 
 
-def encode_reads(seqs: Sequence[str], k: int):
+def encode_reads(seqs: Sequence[str], k: int, t_enc: int = T_ENC):
     """Encode many reads -> (bases [C_total, nb], n_valid [C_total], read_first int32 [R+1]).
     Reads that yield no chunk keep an empty range."""
     parts, nvs, first = [], [], [0]
     for s in seqs:
-        b, nv = encode_read(s, k)
+        b, nv = encode_read(s, k, t_enc)
         parts.append(b)
         nvs.append(nv)
         first.append(first[-1] + b.shape[0])
-    nb = T_ENC + k - 1
+    nb = t_enc + k - 1
     bases = np.concatenate(parts, 0) if parts else np.zeros((0, nb), np.uint8)
     n_valid = np.concatenate(nvs, 0) if nvs else np.zeros((0,), np.uint8)
     return bases, n_valid, np.asarray(first, dtype=np.int32)
@@ -71,10 +73,12 @@ def codes_to_bases(codes: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
     return bases, n_valid
 
 
-def pack_reads(seqs: Sequence[str], k: int):
+def pack_reads(seqs: Sequence[str], k: int, t_enc: int = T_ENC):
     """Flat form for device-side chunking: -> (flat uint8 bytes with every read padded by "_" to 16*C + k - 1,
     chunk_start int64 [C_total] into flat, n_valid uint8 [C_total], read_first int32 [R+1]).  Chunk b is
-    flat[chunk_start[b] : chunk_start[b] + 16 + k - 1]: one gather on the GPU replaces the per-read window copies."""
+    flat[chunk_start[b] : chunk_start[b] + 16 + k - 1]: one gather on the GPU replaces the per-read window copies.
+    (16 = t_enc.)"""
+    T_ENC = t_enc
     lens = np.fromiter((len(s) for s in seqs), dtype=np.int64, count=len(seqs))
     n_kmer = np.maximum(lens - k + 1, 0)
     C = -(-n_kmer // T_ENC)

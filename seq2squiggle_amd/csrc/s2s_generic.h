@@ -8,16 +8,18 @@
 //   gen_gemm_kernel<EPI>   Y = X W^T + b [ReLU | + residual] on v_mfma_f32_16x16x4_f32                 (pre-net, QKV, fc, FFN, heads)
 //   gen_layernorm_kernel   nn.LayerNorm(dmodel, eps 1e-5) per row, one wave per row                   (layers.py:86, 112)
 //   gen_attention_kernel   one workgroup per (chunk, head): exact fp32 softmax with its row maximum    (layers.py:19-41, 64-88)
+//   gen_attention_long_kernel  the same for more than 256 keys, on v_mfma_f32_16x16x4_f32: one workgroup per (chunk, head, 64 queries)
 //   gen_dwell_kernel       Linear(d,1) + Softplus of the three heads, the dwell source, + position_enc (modules.py:197-225, 275-278, 396-438, 80)
 //   gen_lenreg_kernel      length regulator gather + decoder positions                                (modules.py:344-392, 136)
 //   gen_emit_kernel        out_linear + ReLU, x scale, noise, clamp                                   (modules.py:140-141, model.py:221-240)
 // The random draws use the tuned instances' Philox counters (s2s_device.h), so a default-size checkpoint gets the same dwell
-// stream and noise under either instance.
+// stream and noise under either instance.  The chunk geometry is a run-time argument of every kernel here: te k-mers in (max_dna_len)
+// and ts samples out (max_signal_len) per chunk -- 16 / 250 for S2S_MODE_GENERIC, the checkpoint's own for
+// S2S_MODE_GENERIC_GEOMETRY.
 #pragma once
 #include "s2s_device.h"
 
-#define GEN_T_ENC 16
-#define GEN_T_DEC 250
+#define GEN_T_DEC 250          // the decoder length of S2S_MODE_GENERIC_F16's attention (s2s_generic_h.h)
 
 // fp32 blob offsets of one FFT block (host: pack_generic); wqkv is [3d][d] (w_qs | w_ks | w_vs rows), bqkv [3d]
 struct GenLayer { long long wqkv, bqkv, wfc, bfc, ln1g, ln1b, w1, b1, w2, b2, ln2g, ln2b; };
@@ -41,13 +43,13 @@ __device__ __forceinline__ int gen_base_code(unsigned char ch) {       // utils.
 //      (row, feature); emb_wt is W_emb^T [5k][d].  chunk_start (nullable): packed reads, chunk b at bases + chunk_start[b].
 __global__ void __launch_bounds__(256) gen_embed_kernel(const float* __restrict__ emb_wt, const float* __restrict__ emb_b, int k, int d,
                                                         const uint8_t* __restrict__ bases, const long long* __restrict__ chunk_start,
-                                                        const uint8_t* __restrict__ n_valid, int S, float* __restrict__ X) {
+                                                        const uint8_t* __restrict__ n_valid, int S, int te, float* __restrict__ X) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long long)S * GEN_T_ENC * d) return;
+    if (i >= (long long)S * te * d) return;
     const int f = (int)(i % d);
     const long long row = i / d;
-    const int b = (int)(row / GEN_T_ENC), c = (int)(row % GEN_T_ENC);
-    const uint8_t* bp = chunk_start ? bases + chunk_start[b] : bases + (long long)b * (GEN_T_ENC + k - 1);
+    const int b = (int)(row / te), c = (int)(row % te);
+    const uint8_t* bp = chunk_start ? bases + chunk_start[b] : bases + (long long)b * (te + k - 1);
     const bool pad = c >= n_valid[b];                                       // pad k-mer = "_" * k (utils.py:342-347)
     float x = emb_b[f];
     for (int j = 0; j < k; ++j) {
@@ -244,6 +246,104 @@ __global__ void __launch_bounds__(256) gen_attention_kernel(float* __restrict__ 
     }
 }
 
+// ---- scaled dot-product attention of one (chunk, head) over more than 256 keys (the decoder of S2S_MODE_GENERIC_GEOMETRY at
+//      max_signal_len > 256; gen_attention_kernel holds one query's scores as one register per key and lane, at most 256 keys),
+//      on v_mfma_f32_16x16x4_f32: exact fp32 products, fp32 accumulation.  One workgroup per (chunk, head, 64 queries), wave w
+//      owning queries 16w .. 16w + 15 of the tile; no LDS -- K and V are read through the L1 / L2, which the four waves share.
+//      Keys go 16 at a time, in two passes:
+//        1. S^T = K Q^T / temperature (A = 16 keys x 4 head dims, B = 4 head dims x the wave's 16 queries), each query's exact
+//           row maximum;
+//        2. S^T again, p = exp(s - max), the row sum, and O^T += V^T P^T: lane (g, c) holds the scores of keys 4g + r of query c
+//           in accumulator register r, so step r of the product takes register r as its B operand as it stands (its k-index g is
+//           key 4g + r) and reads V in that key order as the A operand; then O = O^T^T / sum.
+//      A two-pass softmax, as torch.softmax computes it: p is exp(s - max) with the exact row maximum and O is never rescaled;
+//      the price is the score product done twice (an online softmax would rescale O once per new maximum, one more rounding
+//      each time, against the exact-fp32 parity bound).  NT output tiles of 16 head dims, 16 NT >= hd (NT 1 | 8 | 32 for
+//      hd <= 16 | 128 | 512); for NT = 1 the wave's four Q fragments stay in registers.  O overwrites Q in place,
+//      as in gen_attention_kernel: query q's row is read only by the wave that owns it, and written after its last read.
+template <int NT>
+__global__ void __launch_bounds__(256) gen_attention_long_kernel(float* __restrict__ QKV, int d, int H, int T) {
+    constexpr int QF = NT == 1 ? 4 : 0;                        // Q fragments held in registers (hd <= 16)
+    const int nqt = (T + 63) / 64;
+    const int b = blockIdx.x / (H * nqt), h = (blockIdx.x / nqt) % H, qt = blockIdx.x % nqt;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int g = lane >> 4, c = lane & 15;
+    const int hd = d / H, ld = 3 * d;
+    const int q0 = qt * 64 + wave * 16;
+    if (q0 >= T) return;                                       // (no barriers below)
+    float* base = QKV + (long long)b * T * ld + h * hd;
+    const int q = q0 + c;                                      // this lane's query: B-operand and output column c
+    const bool qin = q < T;
+    const float* qrow = base + (long long)(qin ? q : T - 1) * ld;
+    const float temp = sqrtf((float)hd);                       // temperature d_k ** 0.5 (layers.py:58)
+    // Loads stay inside the chunk's rows and the head's columns by clamping the index; what a clamped load brings in is multiplied
+    // by zero (a Q element past hd) or lands in an output row that is not stored (a V column past hd), and a key past T gets p = 0.
+    float qf[QF > 0 ? QF : 1];
+#pragma unroll
+    for (int i = 0; i < QF; ++i) qf[i] = 4 * i + g < hd ? qrow[min(4 * i + g, hd - 1)] : 0.0f;
+    auto scores = [&](int j0) {                                // lane (g, c), register r: key j0 + 4g + r, query c (unscaled)
+        const float* krow = base + (long long)min(j0 + c, T - 1) * ld + d;   // A-operand row c: key j0 + c
+        f32x4 s = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (QF > 0) {
+#pragma unroll
+            for (int i = 0; i < QF; ++i)
+                if (4 * i < hd) s = MFMA4(krow[min(4 * i + g, hd - 1)], qf[i], s);
+        } else {
+            for (int e0 = 0; e0 < hd; e0 += 4) {
+                const int e = min(e0 + g, hd - 1);
+                const float qv = qrow[e];
+                s = MFMA4(krow[e], e0 + g < hd ? qv : 0.0f, s);
+            }
+        }
+        return s;
+    };
+    float mx = -__builtin_inff();
+    for (int j0 = 0; j0 < T; j0 += 16) {
+        const f32x4 s = scores(j0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if (j0 + 4 * g + r < T) mx = fmaxf(mx, s[r] / temp);
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));                    // the four lanes of query c: c, c + 16, c + 32, c + 48
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    f32x4 acc[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    float sum = 0.0f;
+    const int nt = (hd + 15) / 16;
+    for (int j0 = 0; j0 < T; j0 += 16) {
+        const f32x4 s = scores(j0);
+        float p[4];
+        const float* vrow[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int key = j0 + 4 * g + r;
+            p[r] = key < T ? expf(s[r] / temp - mx) : 0.0f;
+            sum += p[r];
+            vrow[r] = base + (long long)min(key, T - 1) * ld + 2 * d;
+        }
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            if (t < nt) {
+                const int e = min(16 * t + c, hd - 1);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) acc[t] = MFMA4(vrow[r][e], p[r], acc[t]);
+            }
+        }
+    }
+    sum += __shfl_xor(sum, 16, 64);
+    sum += __shfl_xor(sum, 32, 64);
+    if (!qin) return;
+    float* orow = base + (long long)q * ld;
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int e = 16 * t + 4 * g + r;                  // acc[t][r] of lane (g, c) = O[query c][16t + 4g + r]
+            if (e < hd) orow[e] = acc[t][r] / sum;
+        }
+}
+
 // ---- the three heads' second layer (Linear(d,1) + Softplus, modules.py:182-195, 267-278) on the ReLU'd hidden rows
 //      hid [row][3d] (noise | conc | rate), the dwell source (modules.py:396-438) and, on the same rows, + position_enc for the
 //      encoder (modules.py:80).  One wave per encoder row (chunk b, position c).
@@ -251,12 +351,12 @@ struct GenHeads { long long w3[3], b3[3]; };
 __global__ void __launch_bounds__(256) gen_dwell_kernel(const float* __restrict__ W, GenHeads hw, long long pe_enc, int d, int S,
                                                         const float* __restrict__ hid, float* __restrict__ X, float* __restrict__ sigma_out,
                                                         long long first_chunk, ParamsDev P, const float* __restrict__ inj_g,
-                                                        const float* __restrict__ inj_zdw, int* __restrict__ out_dur, DebugDev dbg) {
+                                                        const float* __restrict__ inj_zdw, int* __restrict__ out_dur, DebugDev dbg, int te) {
     const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
-    if (row >= (long long)S * GEN_T_ENC) return;
-    const int c = (int)(row % GEN_T_ENC);
-    const unsigned long long chunk = (unsigned long long)(first_chunk + row / GEN_T_ENC);
+    if (row >= (long long)S * te) return;
+    const int c = (int)(row % te);
+    const unsigned long long chunk = (unsigned long long)(first_chunk + row / te);
     float hv[3] = {0.0f, 1.0f, 1.0f};
     const int nh = P.duration_sampling ? 3 : 1;
     for (int q = 0; q < nh; ++q) {
@@ -268,7 +368,7 @@ __global__ void __launch_bounds__(256) gen_dwell_kernel(const float* __restrict_
     const float* pe = W + pe_enc + (long long)c * d;
     for (int f = lane; f < d; f += 64) xr[f] += pe[f];
     if (lane != 0) return;
-    const long long drow = row;                               // (the caller's [B][16] arrays come offset to the slice)
+    const long long drow = row;                               // (the caller's [B][te] arrays come offset to the slice)
     const float sg = hv[0];
     sigma_out[row] = sg;
     if (dbg.sigma) dbg.sigma[drow] = sg;
@@ -303,33 +403,33 @@ __global__ void __launch_bounds__(256) gen_dwell_kernel(const float* __restrict_
 }
 
 // ---- length regulator (modules.py:344-392) as a gather: decoder row t copies encoder row i(t) = #{j : cum[j] <= t}, zero past
-//      cum[15], + position_enc (modules.py:136); sigma_ext likewise.  dec_in (nullable): the rows come from memory instead (the
+//      cum[te - 1], + position_enc (modules.py:136); sigma_ext likewise.  dec_in (nullable): the rows come from memory instead (the
 //      stand-alone Decoder operator; it adds position_enc itself).  One thread per (row, feature group of 64).
 __global__ void __launch_bounds__(256) gen_lenreg_kernel(const float* __restrict__ W, long long pe_dec, int d, int S,
                                                          const float* __restrict__ Xe, const float* __restrict__ sigma,
                                                          const int* __restrict__ dur, float* __restrict__ Xd, float* __restrict__ sig_ext,
-                                                         const float* __restrict__ dec_in) {
+                                                         const float* __restrict__ dec_in, int te, int ts) {
     const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
-    if (row >= (long long)S * GEN_T_DEC) return;
-    const long long b = row / GEN_T_DEC;
-    const int t = (int)(row % GEN_T_DEC);
+    if (row >= (long long)S * ts) return;
+    const long long b = row / ts;
+    const int t = (int)(row % ts);
     float* xo = Xd + row * d;
     if (dec_in) {
         for (int f = lane; f < d; f += 64) xo[f] = dec_in[row * d + f];
         return;
     }
     int idx = 0, run = 0;
-    for (int j = 0; j < GEN_T_ENC; ++j) {                     // a dwell past the crop at 250 (modules.py:386) acts like 251
-        const int dj = dur[b * GEN_T_ENC + j];
-        run += dj < GEN_T_DEC + 1 ? dj : GEN_T_DEC + 1;
+    for (int j = 0; j < te; ++j) {                            // a dwell past the crop at ts (modules.py:386) acts like ts + 1
+        const int dj = dur[b * te + j];
+        run += dj < ts + 1 ? dj : ts + 1;
         idx += run <= t ? 1 : 0;
     }
-    const bool live = idx < GEN_T_ENC;
-    const float* er = Xe + (b * GEN_T_ENC + (live ? idx : 0)) * d;
+    const bool live = idx < te;
+    const float* er = Xe + (b * te + (live ? idx : 0)) * d;
     const float* pe = W + pe_dec + (long long)t * d;
     for (int f = lane; f < d; f += 64) xo[f] = (live ? er[f] : 0.0f) + pe[f];
-    if (lane == 0) sig_ext[row] = live ? sigma[b * GEN_T_ENC + idx] : 0.0f;
+    if (lane == 0) sig_ext[row] = live ? sigma[b * te + idx] : 0.0f;
 }
 
 // ---- out_linear + ReLU (modules.py:140-141), x scale (model.py:221), noise where != 0 (model.py:224-238), clamp (model.py:240).
@@ -337,12 +437,12 @@ __global__ void __launch_bounds__(256) gen_lenreg_kernel(const float* __restrict
 __global__ void __launch_bounds__(256) gen_emit_kernel(const float* __restrict__ W, long long out_w, long long out_b, float scale, int d, int S,
                                                        const float* __restrict__ Xd, const float* __restrict__ sig_ext,
                                                        long long first_chunk, ParamsDev P, const float* __restrict__ inj_z01,
-                                                       float* __restrict__ out_signal, DebugDev dbg) {
+                                                       float* __restrict__ out_signal, DebugDev dbg, int ts) {
     const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
-    if (row >= (long long)S * GEN_T_DEC) return;
-    const int t = (int)(row % GEN_T_DEC);
-    const unsigned long long chunk = (unsigned long long)(first_chunk + row / GEN_T_DEC);
+    if (row >= (long long)S * ts) return;
+    const int t = (int)(row % ts);
+    const unsigned long long chunk = (unsigned long long)(first_chunk + row / ts);
     float part = 0.0f;
     for (int f = lane; f < d; f += 64) part += Xd[row * d + f] * W[out_w + f];
     const float ys = relu1(gen_wave_sum(part) + W[out_b]);

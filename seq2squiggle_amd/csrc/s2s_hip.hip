@@ -611,12 +611,15 @@ __global__ __launch_bounds__(DEC_WAVES * 64, DEC_WPS) void s2s_fused_kernel(
 }
 
 // ================================================================================ export
-// per-chunk count of non-zero samples (model.py:286 strips by value)
-__global__ __launch_bounds__(256) void s2s_count_kernel(const float* __restrict__ signal, int B, int* __restrict__ counts) {
+// per-chunk count of non-zero samples (model.py:286 strips by value).  The export kernels take rows of TD samples: the tuned
+// instance TD = S2S_T_DEC, and TD = 0 for the row length `ts` of a S2S_MODE_GENERIC_GEOMETRY handle at another max_signal_len.
+template <int TD>
+__global__ __launch_bounds__(256) void s2s_count_kernel(const float* __restrict__ signal, int B, int* __restrict__ counts, int ts) {
+    const int T = TD ? TD : ts;
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (b >= B) return;
     int n = 0;
-    for (int t = lane; t < S2S_T_DEC; t += 64) n += signal[(size_t)b * S2S_T_DEC + t] != 0.0f;
+    for (int t = lane; t < T; t += 64) n += signal[(size_t)b * T + t] != 0.0f;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
     if (lane == 0) counts[b] = n;
@@ -669,10 +672,12 @@ __global__ __launch_bounds__(256) void s2s_read_offsets_kernel(const long long* 
     if (r <= R) out_offsets[r] = offs[read_first[r]];
 }
 
+template <int TD>
 __global__ __launch_bounds__(256) void s2s_compact_kernel(const float* __restrict__ signal, int B, const long long* __restrict__ offs,
                                                           const int* __restrict__ read_first, int R, float* __restrict__ out_pa,
                                                           short* __restrict__ out_dac, long long capacity, float dig, float range,
-                                                          float offset, int rna) {
+                                                          float offset, int rna, int ts) {
+    const int T = TD ? TD : ts;
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (b >= B) return;
     long long pos = offs[b];
@@ -683,9 +688,9 @@ __global__ __launch_bounds__(256) void s2s_compact_kernel(const float* __restric
         r_lo = offs[read_first[lo]];
         r_hi = offs[read_first[lo + 1]];
     }
-    for (int t0 = 0; t0 < S2S_T_DEC; t0 += 64) {
+    for (int t0 = 0; t0 < T; t0 += 64) {
         const int t = t0 + lane;
-        const float v = (t < S2S_T_DEC) ? signal[(size_t)b * S2S_T_DEC + t] : 0.0f;
+        const float v = (t < T) ? signal[(size_t)b * T + t] : 0.0f;
         const bool keep = v != 0.0f;
         const unsigned long long mask = __ballot(keep);
         const long long dst = pos + __popcll(mask & ((1ull << lane) - 1ull));
@@ -856,6 +861,7 @@ struct s2s_handle {
     // demand, s2s_predict_*)
     struct Generic {
         int d = 0, dff = 0, h_enc = 0, h_dec = 0;
+        int te = 16, ts = 250;        // chunk geometry: max_dna_len, max_signal_len (the checkpoint's in S2S_MODE_GENERIC_GEOMETRY)
         bool f16 = false;             // S2S_MODE_GENERIC_F16: the decoder FFT blocks on f16 operands (dech)
         long long pe_enc = 0, pe_dec = 0, emb_wt = 0, emb_b = 0, out_w = 0, out_b = 0, w0cat = 0, b0cat = 0;
         long long pre_w[S2S_MAX_LAYERS] = {}, pre_b[S2S_MAX_LAYERS] = {};
@@ -904,11 +910,18 @@ struct DeviceGuard {
 size_t layer_floats() { return 4 * (64 * 64 + 64) + 2 * 64 + (256 * 64 + 256) + (64 * 256 + 64) + 2 * 64; }
 size_t mlp_floats() { return 64 * 64 + 64 + 64 + 1; }
 
-bool mode_generic(int m) { return m == S2S_MODE_GENERIC || m == S2S_MODE_GENERIC_F16; }
+bool mode_generic(int m) { return m == S2S_MODE_GENERIC || m == S2S_MODE_GENERIC_F16 || m == S2S_MODE_GENERIC_GEOMETRY; }
 
 const char* check_cfg_generic(const s2s_config* c) {
-    if (c->max_dna_len != S2S_T_ENC) return "max_dna_len must be 16";
-    if (c->max_signal_len != S2S_T_DEC) return "max_signal_len must be 250";
+    if (c->compute_mode == S2S_MODE_GENERIC_GEOMETRY) {
+        if (c->max_dna_len < 1 || c->max_dna_len > S2S_GEOMETRY_MAX_DNA_LEN)
+            return "max_dna_len must be 1..64 (S2S_MODE_GENERIC_GEOMETRY)";
+        if (c->max_signal_len < 1 || c->max_signal_len > S2S_GEOMETRY_MAX_SIGNAL_LEN)
+            return "max_signal_len must be 1..1024 (S2S_MODE_GENERIC_GEOMETRY)";
+    } else {
+        if (c->max_dna_len != S2S_T_ENC) return "max_dna_len must be 16";
+        if (c->max_signal_len != S2S_T_DEC) return "max_signal_len must be 250";
+    }
     if (c->dmodel < 16 || c->dmodel > 512 || c->dmodel % 16) return "dmodel must be a multiple of 16 in 16..512 (S2S_MODE_GENERIC)";
     if (c->dff < 8 || c->dff > 2048 || c->dff % 8) return "dff must be a multiple of 8 in 8..2048 (S2S_MODE_GENERIC)";
     if (c->n_heads < 1 || c->n_heads > 16 || c->dmodel % c->n_heads)
@@ -943,10 +956,12 @@ int cfg_dec_heads(const s2s_config* c) { return c->decoder_heads ? c->decoder_he
 
 size_t generic_layer_floats(size_t d, size_t f) { return 4 * (d * d + d) + 2 * d + (f * d + f) + (d * f + d) + 2 * d; }
 
-// fp32 floats of one chunk in the generic workspace: XE [16][d], SIG [16], XD [250][d], SE [250], BIG [250][max(3d, dff)]
+// fp32 floats of one chunk in the generic workspace: XE [te][d], SIG [te], XD [ts][d], SE [ts], BIG [max(te, ts)][max(3d, dff)]
+// (te / ts = max_dna_len / max_signal_len: 16 / 250 outside S2S_MODE_GENERIC_GEOMETRY)
 size_t generic_chunk_floats(const s2s_config* c) {
     const size_t d = c->dmodel, big = 3 * d > (size_t)c->dff ? 3 * d : (size_t)c->dff;
-    return 16 * d + 16 + 250 * d + 250 + 250 * big;
+    const size_t te = c->max_dna_len, ts = c->max_signal_len, tb = te > ts ? te : ts;
+    return te * d + te + ts * d + ts + tb * big;
 }
 
 // Arena builder: every piece starts on a 16-byte boundary (float4 loads).
@@ -1153,7 +1168,8 @@ void pack_generic(Arena& A, s2s_handle::Generic& G, const s2s_config* cfg, const
     const int d = cfg->dmodel, f = cfg->dff, k = cfg->seq_kmer;
     const size_t dd = (size_t)d * d;
     G.d = d; G.dff = f; G.h_enc = cfg->n_heads; G.h_dec = cfg_dec_heads(cfg);
-    G.pe_enc = A.put(take(p, 16 * (size_t)d), 16 * (size_t)d);
+    G.te = cfg->max_dna_len; G.ts = cfg->max_signal_len;
+    G.pe_enc = A.put(take(p, G.te * (size_t)d), G.te * (size_t)d);
     {
         const float* w = take(p, (size_t)d * 5 * k);
         std::vector<float> wt((size_t)5 * k * d);
@@ -1189,7 +1205,7 @@ void pack_generic(Arena& A, s2s_handle::Generic& G, const s2s_config* cfg, const
         G.w0cat = A.put(w.data(), w.size()); G.b0cat = A.put(b.data(), b.size());
         for (int j = 0; j < 3; ++j) { G.heads.w3[j] = A.put(w3[j].data(), d); G.heads.b3[j] = A.put(b3[j].data(), 1); }
     }
-    G.pe_dec = A.put(take(p, 250 * (size_t)d), 250 * (size_t)d);
+    G.pe_dec = A.put(take(p, G.ts * (size_t)d), G.ts * (size_t)d);
     for (int l = 0; l < cfg->decoder_layers; ++l) layer(G.dec[l]);
     G.f16 = cfg->compute_mode == S2S_MODE_GENERIC_F16;
     if (G.f16) {   // the decoder's four weight matrices once more, rounded to f16, rows zero-padded to K rounded up to 32 (gen_gemm_h_kernel)
@@ -1241,7 +1257,15 @@ void gen_fft_block(hipStream_t st, const float* W, const GenLayer& L, float* X, 
     const int M = n * T, hd = d / H;
     gen_gemm<0>(st, X, d, W + L.wqkv, W + L.bqkv, BIG, 3 * d, nullptr, M, 3 * d, d);
     const size_t stage = gen_attn_lds_bytes(T, hd, true);
-    if (stage <= GEN_ATTN_STAGE_BYTES)
+    if (T > 256) {                            // (S2S_MODE_GENERIC_GEOMETRY's decoder beyond 256 samples)
+        const dim3 grid((unsigned)n * H * ((T + 63) / 64));
+        if (hd <= 16)
+            hipLaunchKernelGGL(gen_attention_long_kernel<1>, grid, dim3(256), 0, st, BIG, d, H, T);
+        else if (hd <= 128)
+            hipLaunchKernelGGL(gen_attention_long_kernel<8>, grid, dim3(256), 0, st, BIG, d, H, T);
+        else
+            hipLaunchKernelGGL(gen_attention_long_kernel<32>, grid, dim3(256), 0, st, BIG, d, H, T);
+    } else if (stage <= GEN_ATTN_STAGE_BYTES)
         hipLaunchKernelGGL(gen_attention_kernel<true>, dim3(n * H), dim3(256), stage, st, BIG, d, H, T);
     else
         hipLaunchKernelGGL(gen_attention_kernel<false>, dim3(n * H), dim3(256), gen_attn_lds_bytes(T, hd, false), st, BIG, d, H, T);
@@ -1281,24 +1305,24 @@ static int predict_generic(s2s_handle* h, hipStream_t st, const uint8_t* bases, 
                            int64_t first_global_chunk, int32_t B, const ParamsDev& P, const float* inject_g, const float* inject_zdw,
                            const float* inject_z01, float* out_signal, int32_t* out_dur, const DebugDev& D) {
     s2s_handle::Generic& G = h->gen;
-    const int d = G.d, dff = G.dff, k = h->cfg.seq_kmer, nb = S2S_T_ENC + k - 1;
-    const size_t big_w = (size_t)(3 * d > dff ? 3 * d : dff);
+    const int d = G.d, dff = G.dff, k = h->cfg.seq_kmer, te = G.te, ts = G.ts, nb = te + k - 1;
+    const size_t big_w = (size_t)(3 * d > dff ? 3 * d : dff), tb = te > ts ? te : ts;
     const int want = B < G.slice_max ? B : G.slice_max;
     if (want > G.ws_chunks) {                 // grows outside of the steady state only
         HIP_TRY(h, hipStreamSynchronize(st));
         if (G.ws) (void)hipFree(G.ws);
         G.ws = nullptr; G.ws_chunks = 0;
         const size_t n = want;
-        const size_t floats = up64(n * 16 * d) + up64(n * 16) + up64(n * 250 * d) + up64(n * 250) + up64(n * 250 * big_w);
+        const size_t floats = up64(n * te * d) + up64(n * te) + up64(n * ts * d) + up64(n * ts) + up64(n * tb * big_w);
         HIP_TRY(h, hipMalloc(&G.ws, floats * sizeof(float)));
         G.ws_chunks = want;
     }
     const size_t S = G.ws_chunks;
     float* XE = G.ws;
-    float* SIG = XE + up64(S * 16 * d);
-    float* XD = SIG + up64(S * 16);
-    float* SE = XD + up64(S * 250 * d);
-    float* BIG = SE + up64(S * 250);
+    float* SIG = XE + up64(S * te * d);
+    float* XD = SIG + up64(S * te);
+    float* SE = XD + up64(S * ts * d);
+    float* BIG = SE + up64(S * ts);
     const float* W = h->d_arena;
     EventPair ev{};
     if (h->profiling) {
@@ -1308,21 +1332,21 @@ static int predict_generic(s2s_handle* h, hipStream_t st, const uint8_t* bases, 
     }
     for (int64_t s = 0; s < B; s += S) {
         const int n = (int)((B - s < (int64_t)S) ? (B - s) : (int64_t)S);
-        const int Me = n * 16, Md = n * 250;
+        const int Me = n * te, Md = n * ts;
         const long long fc = (long long)(first_global_chunk + s);
         DebugDev Ds = D;                      // the caller's arrays, offset to the slice
         auto off = [&](float* p, size_t per) { return p ? p + (size_t)s * per : nullptr; };
-        Ds.sigma = off(D.sigma, 16); Ds.conc = off(D.conc, 16); Ds.rate = off(D.rate, 16); Ds.g = off(D.g, 16);
-        Ds.y_scaled = off(D.y_scaled, 250); Ds.z01 = off(D.z01, 250);
+        Ds.sigma = off(D.sigma, te); Ds.conc = off(D.conc, te); Ds.rate = off(D.rate, te); Ds.g = off(D.g, te);
+        Ds.y_scaled = off(D.y_scaled, ts); Ds.z01 = off(D.z01, ts);
         // encoder input: src_emb + pre-net (modules.py:70-77), or the caller's rows (s2s_debug.emb_in)
         if (D.emb_in) {
-            HIP_TRY(h, hipMemcpyAsync(XE, D.emb_in + (size_t)s * 16 * d, (size_t)Me * d * sizeof(float), hipMemcpyDeviceToDevice, st));
+            HIP_TRY(h, hipMemcpyAsync(XE, D.emb_in + (size_t)s * te * d, (size_t)Me * d * sizeof(float), hipMemcpyDeviceToDevice, st));
         } else {
             const uint8_t* tb = chunk_start ? bases : bases + (size_t)s * nb;
             const long long* tcs = reinterpret_cast<const long long*>(chunk_start ? chunk_start + s : nullptr);
             const long long tot = (long long)Me * d;
             hipLaunchKernelGGL(gen_embed_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, W + G.emb_wt, W + G.emb_b, k, d, tb, tcs,
-                               n_valid + s, n, XE);
+                               n_valid + s, n, te, XE);
             float* cur = XE;
             for (int i = 0; i < h->cfg.pre_layers; ++i) {
                 float* nxt = cur == XE ? BIG : XE;
@@ -1332,24 +1356,24 @@ static int predict_generic(s2s_handle* h, hipStream_t st, const uint8_t* bases, 
             if (cur != XE) HIP_TRY(h, hipMemcpyAsync(XE, cur, (size_t)Me * d * sizeof(float), hipMemcpyDeviceToDevice, st));
         }
         if (D.emb_out)
-            HIP_TRY(h, hipMemcpyAsync(D.emb_out + (size_t)s * 16 * d, XE, (size_t)Me * d * sizeof(float), hipMemcpyDeviceToDevice, st));
+            HIP_TRY(h, hipMemcpyAsync(D.emb_out + (size_t)s * te * d, XE, (size_t)Me * d * sizeof(float), hipMemcpyDeviceToDevice, st));
         // heads (modules.py:182-195, 267-278): the three first layers as one GEMM, then the dwell source; + position_enc
         gen_gemm<1>(st, XE, d, W + G.w0cat, W + G.b0cat, BIG, 3 * d, nullptr, Me, P.duration_sampling ? 3 * d : d, d);
         hipLaunchKernelGGL(gen_dwell_kernel, dim3((Me + 3) / 4), dim3(256), 0, st, W, G.heads, G.pe_enc, d, n, BIG, XE, SIG, fc, P,
-                           inject_g ? inject_g + s * 16 : nullptr, inject_zdw ? inject_zdw + s * 16 : nullptr, out_dur + s * 16, Ds);
-        for (int l = 0; l < h->cfg.encoder_layers; ++l) gen_fft_block(st, W, G.enc[l], XE, BIG, n, 16, d, dff, G.h_enc);
+                           inject_g ? inject_g + s * te : nullptr, inject_zdw ? inject_zdw + s * te : nullptr, out_dur + s * te, Ds, te);
+        for (int l = 0; l < h->cfg.encoder_layers; ++l) gen_fft_block(st, W, G.enc[l], XE, BIG, n, te, d, dff, G.h_enc);
         if (D.enc_out)
-            HIP_TRY(h, hipMemcpyAsync(D.enc_out + (size_t)s * 16 * d, XE, (size_t)Me * d * sizeof(float), hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL(gen_lenreg_kernel, dim3((Md + 3) / 4), dim3(256), 0, st, W, G.pe_dec, d, n, XE, SIG, out_dur + s * 16, XD, SE,
-                           D.dec_in ? D.dec_in + (size_t)s * 250 * d : nullptr);
+            HIP_TRY(h, hipMemcpyAsync(D.enc_out + (size_t)s * te * d, XE, (size_t)Me * d * sizeof(float), hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(gen_lenreg_kernel, dim3((Md + 3) / 4), dim3(256), 0, st, W, G.pe_dec, d, n, XE, SIG, out_dur + s * te, XD, SE,
+                           D.dec_in ? D.dec_in + (size_t)s * ts * d : nullptr, te, ts);
         for (int l = 0; l < h->cfg.decoder_layers; ++l) {
             if (G.f16)
                 gen_fft_block_h(st, W, G.dec[l], G.dech[l], G.ld_d, G.ld_f, XD, BIG, n, d, dff, G.h_dec);
             else
-                gen_fft_block(st, W, G.dec[l], XD, BIG, n, 250, d, dff, G.h_dec);
+                gen_fft_block(st, W, G.dec[l], XD, BIG, n, ts, d, dff, G.h_dec);
         }
         hipLaunchKernelGGL(gen_emit_kernel, dim3((Md + 3) / 4), dim3(256), 0, st, W, G.out_w, G.out_b, h->cfg.scaling_max_value, d, n, XD, SE,
-                           fc, P, inject_z01 ? inject_z01 + (size_t)s * 250 : nullptr, out_signal + (size_t)s * 250, Ds);
+                           fc, P, inject_z01 ? inject_z01 + (size_t)s * ts : nullptr, out_signal + (size_t)s * ts, Ds, ts);
     }
     if (h->profiling) {
         HIP_TRY(h, hipEventRecord(ev.b, st));
@@ -1366,8 +1390,9 @@ size_t s2s_blob_floats(const s2s_config* c) {
     if (check_cfg(c)) return 0;
     if (mode_generic(c->compute_mode)) {
         const size_t d = c->dmodel, f = c->dff;
-        return 16 * d + d * 5 * c->seq_kmer + d + (size_t)c->pre_layers * (d * d + d) +
-               (size_t)(c->encoder_layers + c->decoder_layers) * generic_layer_floats(d, f) + 3 * (d * d + d + d + 1) + 250 * d + d + 1;
+        const size_t te = c->max_dna_len, ts = c->max_signal_len;     // 16 / 250 outside S2S_MODE_GENERIC_GEOMETRY
+        return te * d + d * 5 * c->seq_kmer + d + (size_t)c->pre_layers * (d * d + d) +
+               (size_t)(c->encoder_layers + c->decoder_layers) * generic_layer_floats(d, f) + 3 * (d * d + d + d + 1) + ts * d + d + 1;
     }
     return (size_t)16 * 64 + (size_t)64 * 5 * c->seq_kmer + 64 + (size_t)c->pre_layers * (4096 + 64) +
            (size_t)(c->encoder_layers + c->decoder_layers) * layer_floats() + 3 * mlp_floats() + (size_t)250 * 64 + 64 + 1;
@@ -1687,14 +1712,18 @@ int s2s_export_reads(s2s_handle* h, void* stream_, const float* signal, int32_t 
         HIP_TRY(h, hipMalloc(&h->ws_offs, (size_t)cap * sizeof(long long)));
         h->ws_export_cap = cap;
     }
-    if (B > 0) hipLaunchKernelGGL(s2s_count_kernel, dim3((B + 3) / 4), dim3(256), 0, stream, signal, B, h->ws_counts);
+    const int ts = h->cfg.max_signal_len;    // S2S_T_DEC except for a S2S_MODE_GENERIC_GEOMETRY handle
+    const bool tuned_rows = ts == S2S_T_DEC;
+    if (B > 0)
+        hipLaunchKernelGGL(tuned_rows ? s2s_count_kernel<S2S_T_DEC> : s2s_count_kernel<0>, dim3((B + 3) / 4), dim3(256), 0, stream, signal, B,
+                           h->ws_counts, ts);
     hipLaunchKernelGGL(s2s_scan_kernel, dim3(1), dim3(1024), 0, stream, h->ws_counts, B, h->ws_offs);
     hipLaunchKernelGGL(s2s_read_offsets_kernel, dim3((R + 256) / 256), dim3(256), 0, stream, h->ws_offs, read_first, R,
                        reinterpret_cast<long long*>(out_offsets));
     if (B > 0 && (out_pa || out_dac))
-        hipLaunchKernelGGL(s2s_compact_kernel, dim3((B + 3) / 4), dim3(256), 0, stream, signal, B, h->ws_offs, read_first, R,
-                           out_pa, reinterpret_cast<short*>(out_dac), (long long)capacity, digitisation, range, offset_mean,
-                           rna);
+        hipLaunchKernelGGL(tuned_rows ? s2s_compact_kernel<S2S_T_DEC> : s2s_compact_kernel<0>, dim3((B + 3) / 4), dim3(256), 0, stream,
+                           signal, B, h->ws_offs, read_first, R, out_pa, reinterpret_cast<short*>(out_dac), (long long)capacity,
+                           digitisation, range, offset_mean, rna, ts);
     HIP_TRY(h, hipGetLastError());
     return S2S_OK;
 }

@@ -13,9 +13,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from .checkpoint import TUNED_MODES, TUNED_SIZES, config_to_c, default_mode, is_tuned_family, load_checkpoint, state_dict_to_blob
+from .checkpoint import (DEFAULT_GEOMETRY, TUNED_MODES, TUNED_SIZES, config_to_c, default_mode, is_default_geometry, is_tuned_family,
+                         load_checkpoint, state_dict_to_blob)
 
-T_ENC, T_DEC = 16, 250
+T_ENC, T_DEC = 16, 250          # the chunk geometry of every mode but "generic-geometry" (Engine.t_enc / t_dec: the engine's own)
 
 
 @dataclass
@@ -46,11 +47,17 @@ class Engine:
     def __init__(self, state_dict: Dict[str, torch.Tensor], config: dict, device: Optional[int] = None,
                  mode: Optional[str] = None):
         """mode: "f16x3", "f32", "f16" (the tuned instances, shipped sizes only), "generic" (any size within the limits of
-        include/s2s_hip.h) or "generic-f16" (the same sizes, the decoder's matrix products on f16 operands: reduced precision, never
-        picked by default); None picks "f16x3" for the shipped sizes and "generic" otherwise."""
+        include/s2s_hip.h), "generic-f16" (the same sizes, the decoder's matrix products on f16 operands: reduced precision, never
+        picked by default) or "generic-geometry" (the sizes of "generic" at any max_dna_len 1-64 / max_signal_len 1-1024, exact
+        fp32); None picks "generic-geometry" for a chunk geometry other than 16 / 250, else "f16x3" for the shipped sizes and
+        "generic" otherwise."""
         self._h = None
         if mode is None:
             mode = default_mode(config)
+        elif mode != "generic-geometry" and not is_default_geometry(config):
+            geo = ", ".join(f"{k} {config[k]}" for k in DEFAULT_GEOMETRY)
+            raise ValueError(f"mode {mode!r} runs only max_dna_len 16 / max_signal_len 250; this checkpoint has {geo}: "
+                             "use mode 'generic-geometry'")
         elif mode in TUNED_MODES and not is_tuned_family(config):
             sizes = ", ".join(f"{k} {config[k]}" for k in TUNED_SIZES)
             raise ValueError(f"mode {mode!r} runs only dmodel 64, dff 256, 8 encoder / decoder heads; this checkpoint has {sizes}: "
@@ -62,7 +69,8 @@ class Engine:
         self.device = torch.device("cuda", self.device_index)
         self.config = dict(config)
         self.dmodel = int(config["dmodel"])
-        self._pe_dec_host = state_dict["decoders.position_enc"].detach().float().reshape(1, T_DEC, self.dmodel).clone()
+        self.t_enc, self.t_dec = int(config["max_dna_len"]), int(config["max_signal_len"])     # k-mers in, samples out per chunk
+        self._pe_dec_host = state_dict["decoders.position_enc"].detach().float().reshape(1, self.t_dec, self.dmodel).clone()
         self._pe_dec = None
         self.k = int(config["seq_kmer"])
         self.mode = mode
@@ -88,7 +96,7 @@ class Engine:
         return cls(sd, cfg, device, mode)
 
     def decoder_position_enc(self) -> torch.Tensor:
-        """decoders.position_enc [1,250,dmodel] on the engine's device (the stand-alone Decoder operator adds it, modules.py:136)."""
+        """decoders.position_enc [1,t_dec,dmodel] on the engine's device (the stand-alone Decoder operator adds it, modules.py:136)."""
         if self._pe_dec is None:
             self._pe_dec = self._pe_dec_host.to(self.device)
         return self._pe_dec
@@ -125,8 +133,10 @@ class Engine:
         """bases uint8 [B, 16+k-1] and n_valid uint8 [B] on the engine's device ->
         dict(signal fp32 [B,250] pA, dur int32 [B,16] [, debug stage tensors]).
         emb_in [B,16,dmodel] / dec_in [B,250,dmodel] (float32): stage inputs taken from these tensors instead of being computed from the
-        bases -- the stand-alone sub-module operators of seq2squiggle_amd.modules (s2s_debug.emb_in / dec_in)."""
+        bases -- the stand-alone sub-module operators of seq2squiggle_amd.modules (s2s_debug.emb_in / dec_in).
+        Every 16 above is the engine's t_enc (max_dna_len) and every 250 its t_dec (max_signal_len)."""
         B = int(bases.shape[0])
+        T_ENC, T_DEC = self.t_enc, self.t_dec
         nb = T_ENC + self.k - 1
         if bases.dtype != torch.uint8 or bases.dim() != 2 or bases.shape[1] != nb or not bases.is_contiguous():
             raise ValueError(f"bases must be contiguous uint8 [B, {nb}]")
@@ -150,9 +160,9 @@ class Engine:
         dbg = None
         if debug:
             f = dict(dtype=torch.float32, device=self.device)
-            out.update(emb_out=torch.zeros(B, 16, self.dmodel, **f), enc_out=torch.zeros(B, 16, self.dmodel, **f),
-                       sigma=torch.zeros(B, 16, **f), conc=torch.zeros(B, 16, **f), rate=torch.zeros(B, 16, **f),
-                       g=torch.zeros(B, 16, **f), y_scaled=torch.zeros(B, T_DEC, **f), z01=torch.zeros(B, T_DEC, **f))
+            out.update(emb_out=torch.zeros(B, T_ENC, self.dmodel, **f), enc_out=torch.zeros(B, T_ENC, self.dmodel, **f),
+                       sigma=torch.zeros(B, T_ENC, **f), conc=torch.zeros(B, T_ENC, **f), rate=torch.zeros(B, T_ENC, **f),
+                       g=torch.zeros(B, T_ENC, **f), y_scaled=torch.zeros(B, T_DEC, **f), z01=torch.zeros(B, T_DEC, **f))
             dbg = _lib.S2SDebug(*[out[n].data_ptr() for n in ("emb_out", "enc_out", "sigma", "conc", "rate", "g",
                                                               "y_scaled", "z01")])
         if emb_in is not None or dec_in is not None:
@@ -170,8 +180,9 @@ class Engine:
     def predict_packed(self, read_bytes: torch.Tensor, chunk_start: torch.Tensor, n_valid: torch.Tensor,
                        params: PredictParams, first_global_chunk: int = 0):
         """Chunks addressed inside a packed read buffer (chunker.pack_reads): read_bytes uint8 [N], chunk_start int64
-        [B], n_valid uint8 [B], all on the engine's device -> dict(signal [B,250], dur [B,16])."""
+        [B], n_valid uint8 [B], all on the engine's device -> dict(signal [B,t_dec], dur [B,t_enc])."""
         B = int(chunk_start.shape[0])
+        T_ENC, T_DEC = self.t_enc, self.t_dec
         for name, t, dt in (("read_bytes", read_bytes, torch.uint8), ("chunk_start", chunk_start, torch.int64),
                             ("n_valid", n_valid, torch.uint8)):
             if t.dtype != dt or not t.is_contiguous() or t.device != self.device or t.dim() != 1:
@@ -194,10 +205,11 @@ class Engine:
         """Per-read zero-strip (model.py:284-286) and optional int16 conversion (signal_io.py:134-141) on
         the GPU.  signal [B,250]; read_first int32 [R+1] -> dict(offsets int64 [R+1], pa, dac).  out_offsets / out_dac: write
         there instead of into fresh tensors (int64 [R+1] / int16 [>= B*250], e.g. two views of one buffer that then leaves the
-        device as a single copy)."""
+        device as a single copy).  Every 250 is the engine's t_dec."""
         B, R = int(signal.shape[0]), int(read_first.shape[0]) - 1
-        if signal.dtype != torch.float32 or not signal.is_contiguous() or signal.shape[1] != T_DEC:
-            raise ValueError("signal must be contiguous float32 [B,250]")
+        T_DEC = self.t_dec
+        if signal.dtype != torch.float32 or not signal.is_contiguous() or signal.dim() != 2 or signal.shape[1] != T_DEC:
+            raise ValueError(f"signal must be contiguous float32 [B,{T_DEC}]")
         if read_first.dtype != torch.int32 or not read_first.is_contiguous() or read_first.dim() != 1 or R < 0:
             raise ValueError("read_first must be contiguous int32 [R+1]")
         if signal.device != self.device or read_first.device != self.device:

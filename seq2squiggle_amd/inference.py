@@ -8,6 +8,7 @@ from typing import Iterable, Iterator, Optional, Tuple
 import numpy as np
 import torch
 
+from .checkpoint import load_checkpoint
 from .chunker import encode_read, n_chunks as _n_chunks, pack_reads
 from .model import seq2squiggle
 from .parallel import local_device, rank_output_path, rank_world, shard_reads
@@ -122,12 +123,13 @@ def check_model(model: object, config: dict) -> None:
                        f"file ({value})")
 
 
-def iter_batches(reads: Iterable[Tuple[str, str]], k: int, batch_size: int, device) -> Iterator[tuple]:
+def iter_batches(reads: Iterable[Tuple[str, str]], k: int, batch_size: int, device, t_enc: int = 16) -> Iterator[tuple]:
     """(read_ids, bases, n_valid) batches of up to batch_size chunks in read order: the job of load_fasta +
-    DataLoader (dataloader.py:401-453, 141-149).  Reads shorter than k yield nothing (dataloader.py:393-398)."""
+    DataLoader (dataloader.py:401-453, 141-149).  Reads shorter than k yield nothing (dataloader.py:393-398).
+    t_enc: k-mers per chunk (the checkpoint's max_dna_len)."""
     ids, parts, nvs, n = [], [], [], 0
     for seq, name in reads:
-        b, nv = encode_read(seq, k)
+        b, nv = encode_read(seq, k, t_enc)
         s = 0
         while s < b.shape[0]:
             take = min(batch_size - n, b.shape[0] - s)
@@ -210,7 +212,7 @@ def _copy_streams(dev):
     return streams
 
 
-def super_batches(reads: Iterable[Tuple[str, str]], k: int, max_chunks: int):
+def super_batches(reads: Iterable[Tuple[str, str]], k: int, max_chunks: int, t_enc: int = 16):
     """Whole reads grouped into super-batches of about max_chunks chunks (reads too short for one chunk are dropped).  The first
     groups are short (1/8, 1/4, 1/2 of max_chunks): the GPU starts as soon as a few reads exist, and the host, which prepares a
     chunk faster than the GPU predicts one, is ahead from then on.  When the iterable says how many reads are left
@@ -227,7 +229,7 @@ def super_batches(reads: Iterable[Tuple[str, str]], k: int, max_chunks: int):
     group, n = [], 0
     reads = iter(reads)
     for seq, name in reads:
-        c = _n_chunks(len(seq), k)
+        c = _n_chunks(len(seq), k, t_enc)
         if c == 0:
             logger.debug(f"Skipped read {name}.")
             continue
@@ -265,6 +267,7 @@ def run_streaming(model, reads: Iterable[Tuple[str, str]], writer, profile_dict:
         if trace is not None:
             trace.append((ev, time.perf_counter()))
     k = model.config["seq_kmer"]
+    t_enc, t_dec = model.engine.t_enc, model.engine.t_dec     # the checkpoint's chunk geometry
     dev = model.device
     rna = profile_name.startswith("rna")
     total = 0
@@ -285,15 +288,15 @@ def run_streaming(model, reads: Iterable[Tuple[str, str]], writer, profile_dict:
     def launch(group):
         nonlocal total, n_launched
         mark("pack")
-        flat, chunk_start, n_valid, read_first = pack_reads([s for s, _ in group], k)
+        flat, chunk_start, n_valid, read_first = pack_reads([s for s, _ in group], k, t_enc)
         B = int(read_first[-1])
         if B == 0:
             return None
         arrays = [flat, chunk_start, n_valid, read_first]
         if gpu_rows:
             # candidate rows of the signal codec from the chunk counts (the stripped lengths are not known here): read r may
-            # need up to ceil(250 * chunks / row_samples) rows; those it turns out not to need come back empty
-            n_rows = -(-(np.diff(read_first).astype(np.int64) * 250) // gpu_rows[1])
+            # need up to ceil(t_dec * chunks / row_samples) rows; those it turns out not to need come back empty
+            n_rows = -(-(np.diff(read_first).astype(np.int64) * t_dec) // gpu_rows[1])
             row_read = np.repeat(np.arange(len(group), dtype=np.int32), n_rows)
             row_index = (np.arange(int(n_rows.sum())) - np.repeat(np.cumsum(n_rows) - n_rows, n_rows)).astype(np.int32)
             arrays += [row_read, row_index]
@@ -315,7 +318,7 @@ def run_streaming(model, reads: Iterable[Tuple[str, str]], writer, profile_dict:
         # wave fits on a CU while the predict kernel holds its whole register file: it would wait for the NEXT super-batch's
         # kernel to end; a large copy goes through the DMA engines beside it.  The whole capacity is copied (its size is known
         # without a sync: 16 MB of int16 / 17 MB of coded signal per 32 k chunks) into pinned memory.
-        cap = B * 250
+        cap = B * t_dec
         if gpu_rows:
             N = int(row_read.shape[0])
             blob_cap = model.engine.svb_capacity(cap, N, gpu_rows[0])
@@ -388,7 +391,7 @@ def run_streaming(model, reads: Iterable[Tuple[str, str]], writer, profile_dict:
     n_reads = 0
     try:
         mark("first read wanted")
-        for group in super_batches(reads, k, max_chunks):
+        for group in super_batches(reads, k, max_chunks, t_enc):
             job = launch(group)
             if inflight is not None:
                 collect(inflight)
@@ -442,6 +445,9 @@ def inference_run(config: dict, saved_weights: str, fasta: str, read_input: bool
     if world > 1 and not seed:
         raise ValueError("multi-process runs need one seed for all ranks: pass an explicit --seed, or let the CLI share a "
                          "fresh one (parallel.shared_seed) before calling inference_run")
+    # chunks per read are counted at the checkpoint's max_dna_len (the model is built from its hyper_parameters, not from `config`);
+    # a sharded run needs them before the engine exists
+    t_enc = int(load_checkpoint(str(saved_weights))[1]["max_dna_len"]) if world > 1 else 16
     # belt and braces for a user's own torchrun (all devices visible): whatever allocates without naming a device -- a pinned buffer's
     # primary-context search, a library call -- lands on this rank's GPU.  Children of `predict --gpus N` see one device only.
     if torch.cuda.is_available():              # (without a GPU the engine's constructor is what raises, with its own message)
@@ -468,9 +474,9 @@ def inference_run(config: dict, saved_weights: str, fasta: str, read_input: bool
             picked = {}
 
             def shard_of(lens):
-                lo, hi, picked["first"] = shard_reads(lens, config["seq_kmer"], world)[rank]
+                lo, hi, picked["first"] = shard_reads(lens, config["seq_kmer"], world, t_enc)[rank]
                 picked["lo"] = lo
-                picked["records_before"] = sum(1 for L in lens[:lo] if _n_chunks(int(L), config["seq_kmer"]) > 0)
+                picked["records_before"] = sum(1 for L in lens[:lo] if _n_chunks(int(L), config["seq_kmer"], t_enc) > 0)
                 return lo, hi
             reads, lens = sample_read_shard(genome_seqs, genome_lens, n, r, c, seed, distr, profile, min_read_len, shard_of)
             first_chunk, first_read = picked["first"], picked["records_before"]
@@ -479,10 +485,10 @@ def inference_run(config: dict, saved_weights: str, fasta: str, read_input: bool
             reads, total_l = get_reads(fasta, read_input, n, r, c, config, distr, seed, profile, min_read_len, lazy=world == 1)
             if world > 1:                  # read mode: every rank parses the same file, then keeps its contiguous share
                 reads = list(reads)
-                lo, hi, first_chunk = shard_reads([len(s) for s, _ in reads], config["seq_kmer"], world)[rank]
+                lo, hi, first_chunk = shard_reads([len(s) for s, _ in reads], config["seq_kmer"], world, t_enc)[rank]
                 # records written before this shard: reads too short for one chunk produce none (dataloader.py:393-398), so they
                 # must not advance the shard writer's read numbering / record draws either
-                first_read = sum(1 for s_, _ in reads[:lo] if _n_chunks(len(s_), config["seq_kmer"]) > 0)
+                first_read = sum(1 for s_, _ in reads[:lo] if _n_chunks(len(s_), config["seq_kmer"], t_enc) > 0)
                 reads = reads[lo:hi]
                 logger.info(f"rank {rank}/{world}: reads {lo}..{hi}, first global chunk {first_chunk}")
     finally:
@@ -507,12 +513,12 @@ def inference_run(config: dict, saved_weights: str, fasta: str, read_input: bool
     if streaming and hasattr(writer, "dac_records"):
         n_chunks = run_streaming(load_model, reads, writer, profile_dict, profile, trace=_TRACE)
     else:
-        for batch in iter_batches(reads, config["seq_kmer"], predict_batch_size, load_model.device):
+        for batch in iter_batches(reads, config["seq_kmer"], predict_batch_size, load_model.device, load_model.engine.t_enc):
             load_model.predict_step(batch)
             n_chunks += len(batch[0])
         load_model.on_predict_epoch_end()
     torch.cuda.synchronize(load_model.device)
-    logger.info(f"Predicted {n_chunks} chunks ({n_chunks * 250} padded samples).")
+    logger.info(f"Predicted {n_chunks} chunks ({n_chunks * load_model.engine.t_dec} padded samples).")
     # how THESE weights behaved on THIS input (s2s_stats_read; the read resets the counters): the redo share of the fast softmax
     # path depends on the reads as well as on the checkpoint, and the calibration launch only saw 512 pseudo-random chunks
     eng = load_model.engine

@@ -72,7 +72,8 @@ class seq2squiggle:
         self.engine = Engine(state_dict, config, device=device, mode=mode)
         logging.getLogger("seq2squiggle").info(
             f"predict instance: {self.engine.mode} (dmodel {config['dmodel']}, dff {config['dff']}, "
-            f"heads {config['encoder_heads']} / {config['decoder_heads']})")
+            f"heads {config['encoder_heads']} / {config['decoder_heads']}"
+            + (f", max_dna_len {self.engine.t_enc} / max_signal_len {self.engine.t_dec})" if self.engine.mode == "generic-geometry" else ")"))
         self.device = self.engine.device
 
     @classmethod

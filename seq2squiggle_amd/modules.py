@@ -8,6 +8,7 @@ fed what the previous stage returned -- the way `predict_step` chains them (mode
 operators: the test instance of the kernel takes a stage's input from memory (s2s_debug.emb_in: the heads, the dwell source
 and the encoder blocks on a caller's emb_out; s2s_debug.dec_in: the decoder blocks and output projection on a caller's
 [B,250,64]), one launch per call, and the length regulator's expansion is index arithmetic on the caller's tensors.
+Every 16 and 250 below is the engine's t_enc and t_dec (max_dna_len, max_signal_len of its checkpoint).
 """
 from typing import Optional
 
@@ -32,9 +33,9 @@ def _same(a: torch.Tensor, b: Optional[torch.Tensor]) -> bool:
 
 
 def _dummy_bases(eng: Engine, B: int):
-    nb = 16 + eng.k - 1
+    nb = eng.t_enc + eng.k - 1
     return (torch.full((B, nb), ord("A"), dtype=torch.uint8, device=eng.device),
-            torch.full((B,), 16, dtype=torch.uint8, device=eng.device))
+            torch.full((B,), eng.t_enc, dtype=torch.uint8, device=eng.device))
 
 
 def _f32(x: torch.Tensor, eng: Engine, shape) -> torch.Tensor:
@@ -53,7 +54,7 @@ class Encoder:
         if return_attns or mask is not None:
             raise NotImplementedError("attention maps / masks are not part of the predict path (model.py:199)")
         ctx, eng = self._ctx, self._ctx.engine
-        onehot = src_seq.reshape(src_seq.shape[0], 16, eng.k, 5)
+        onehot = src_seq.reshape(src_seq.shape[0], eng.t_enc, eng.k, 5)
         bases, n_valid = onehot_to_bases(onehot.to(eng.device))
         ctx.out = eng.predict_chunks(bases.contiguous(), n_valid.contiguous(), ctx.params, debug=True, **ctx.inject)
         return ctx.out["enc_out"], ctx.out["emb_out"]
@@ -72,7 +73,7 @@ class NoiseSampler:
         if ctx.out is not None and _same(x, ctx.out["emb_out"]):
             return ctx.out["sigma"].unsqueeze(-1)
         eng = ctx.engine                                                         # stand-alone: any emb_out [B,16,dmodel]
-        x = _f32(x, eng, (x.shape[0], 16, eng.dmodel))
+        x = _f32(x, eng, (x.shape[0], eng.t_enc, eng.dmodel))
         out = eng.predict_chunks(*_dummy_bases(eng, x.shape[0]), ctx.params, debug=True, emb_in=x, **ctx.inject)
         return out["sigma"].unsqueeze(-1)
 
@@ -93,28 +94,29 @@ class LengthRegulator:
                 duration_sampling: Optional[bool] = None, min_length: Optional[float] = None):
         ctx = self._ctx
         o, p = ctx.out, ctx.params
+        te, ts = ctx.engine.t_enc, ctx.engine.t_dec
         if target is not None or alpha != 1.0:
             raise NotImplementedError("teacher-forced durations / alpha belong to training (modules.py:399-411)")
         for name, given, have in (("dwell_mean", dwell_mean, p.dwell_mean), ("dwell_std", dwell_std, p.dwell_std),
                                   ("duration_sampling", duration_sampling, p.duration_sampling),
-                                  ("min_length", min_length, p.min_duration), ("max_length", max_length, 250)):
+                                  ("min_length", min_length, p.min_duration), ("max_length", max_length, ts)):
             if given is not None and float(given) != float(have):
                 raise ValueError(f"LengthRegulator: {name}={given} differs from the context's PredictParams ({have})")
         chained = o is not None and _same(emb_out, o["emb_out"])
         if not chained:                              # stand-alone: the dwell source on the caller's emb_out (one launch), then pure indexing
             eng = ctx.engine
-            e = _f32(emb_out, eng, (emb_out.shape[0], 16, eng.dmodel))
+            e = _f32(emb_out, eng, (emb_out.shape[0], te, eng.dmodel))
             o = eng.predict_chunks(*_dummy_bases(eng, e.shape[0]), p, debug=True, emb_in=e, **ctx.inject)
-        x_src = o["enc_out"] if chained and _same(x, o["enc_out"]) else _f32(x, ctx.engine, (o["dur"].shape[0], 16, ctx.engine.dmodel))
+        x_src = o["enc_out"] if chained and _same(x, o["enc_out"]) else _f32(x, ctx.engine, (o["dur"].shape[0], te, ctx.engine.dmodel))
         sig = noise_std_prediction
         sig_src = (o["sigma"] if chained and _same(sig, o["sigma"].unsqueeze(-1))
-                   else _f32(sig.reshape(sig.shape[0], 16), ctx.engine, (o["dur"].shape[0], 16)))
+                   else _f32(sig.reshape(sig.shape[0], te), ctx.engine, (o["dur"].shape[0], te)))
         dur = o["dur"].long()
         cum = dur.cumsum(1)                                                     # modules.py:368
-        t = torch.arange(250, device=dur.device).view(1, 250, 1)
-        idx = (cum.unsqueeze(1) <= t).sum(-1)                                   # [B,250]: 16 = past the last dwell
-        live = (idx < 16).unsqueeze(-1)
-        row = idx.clamp(max=15)
+        t = torch.arange(ts, device=dur.device).view(1, ts, 1)
+        idx = (cum.unsqueeze(1) <= t).sum(-1)                                   # [B,ts]: te = past the last dwell
+        live = (idx < te).unsqueeze(-1)
+        row = idx.clamp(max=te - 1)
         out = torch.where(live, x_src.gather(1, row.unsqueeze(-1).expand(-1, -1, x_src.shape[-1])), torch.zeros((), device=dur.device))
         noise_ext = torch.where(live, sig_src.gather(1, row).unsqueeze(-1), torch.zeros((), device=dur.device))
         dist = torch.distributions.Gamma(o["conc"], o["rate"]) if p.duration_sampling else None
@@ -137,7 +139,7 @@ class Decoder:
         if ctx.out is not None and _same(enc_seq, getattr(ctx, "lr_out", None)):
             return ctx.out["y_scaled"].unsqueeze(-1)
         eng = ctx.engine                                                         # stand-alone: any [B,250,dmodel]; position_enc is added
-        x = _f32(enc_seq, eng, (enc_seq.shape[0], 250, eng.dmodel)) + eng.decoder_position_enc()   # inside the operator (modules.py:136)
+        x = _f32(enc_seq, eng, (enc_seq.shape[0], eng.t_dec, eng.dmodel)) + eng.decoder_position_enc()   # inside the operator (modules.py:136)
         params = PredictParams(**{**ctx.params.__dict__, "noise_std": 0.0})
         out = eng.predict_chunks(*_dummy_bases(eng, x.shape[0]), params, debug=True, dec_in=x.contiguous())
         return out["y_scaled"].unsqueeze(-1)

@@ -23,10 +23,10 @@ def local_device() -> int:
     return _ld()
 
 
-def shard_reads(read_lens: Sequence[int], k: int, world: int) -> List[Tuple[int, int, int]]:
+def shard_reads(read_lens: Sequence[int], k: int, world: int, t_enc: int = 16) -> List[Tuple[int, int, int]]:
     """-> per rank (first_read, end_read, first_global_chunk): contiguous read ranges whose chunk counts are as
-    equal as a prefix split allows."""
-    chunks = np.array([n_chunks(int(L), k) for L in read_lens], dtype=np.int64)
+    equal as a prefix split allows.  t_enc: k-mers per chunk (the checkpoint's max_dna_len)."""
+    chunks = np.array([n_chunks(int(L), k, t_enc) for L in read_lens], dtype=np.int64)
     cum = np.concatenate([[0], np.cumsum(chunks)])
     total = int(cum[-1])
     bounds = [0]

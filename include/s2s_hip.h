@@ -60,9 +60,21 @@ extern "C" {
  *                   1..S2S_GEOMETRY_MAX_SIGNAL_LEN samples out per chunk, the checkpoint's own.  At 16 / 250 it runs
  *                   S2S_MODE_GENERIC's kernels on S2S_MODE_GENERIC's numbers; beyond 256 samples the decoder attention is an
  *                   MFMA kernel of its own (csrc/s2s_generic.h, gen_attention_long_kernel).  Every [16] and [250] of this header
- *                   reads as [max_dna_len] and [max_signal_len] for such a handle.  Reduced precision at other geometries (a
- *                   S2S_MODE_GENERIC_F16 counterpart) does not exist yet. */
+ *                   reads as [max_dna_len] and [max_signal_len] for such a handle.  Its reduced-precision counterpart is
+ *                   S2S_MODE_GENERIC_GEOMETRY_F16. */
 #define S2S_MODE_GENERIC_GEOMETRY 6
+/*   S2S_MODE_GENERIC_GEOMETRY_F16  REDUCED PRECISION, outside the 1e-4 pA bound, opt-in (never chosen by default):
+ *                   S2S_MODE_GENERIC_GEOMETRY's sizes and chunk geometries (max_dna_len 1..S2S_GEOMETRY_MAX_DNA_LEN,
+ *                   max_signal_len 1..S2S_GEOMETRY_MAX_SIGNAL_LEN, the checkpoint's own) at S2S_MODE_GENERIC_F16's precision class,
+ *                   the reference's 16-mixed GPU path (inference.py:403-404).  The encoder side is S2S_MODE_GENERIC_GEOMETRY's exact
+ *                   fp32 code (emb_out, enc_out, sigma, conc, rate, g and the dwell indices are bit-equal to it); in the decoder
+ *                   FFT blocks every matrix product takes its operands rounded to f16 once and accumulates in fp32
+ *                   (v_mfma_f32_16x16x32_f16), with fp32 bias, ReLU, residual, LayerNorm and softmax (exact row maximum).  Up to
+ *                   256 samples the decoder attention is S2S_MODE_GENERIC_F16's kernel; beyond, gen_attention_long_h_kernel
+ *                   (csrc/s2s_generic_h.h) rounds the unnormalised P = exp(s - max) to f16 and divides O by the fp32 row sum.
+ *                   At 16 / 250 it computes S2S_MODE_GENERIC_F16's numbers bit for bit.  Range: a decoder activation or weight
+ *                   of magnitude >= 65,504 becomes inf in f16 -- the limit of the reference's own 16-mixed run. */
+#define S2S_MODE_GENERIC_GEOMETRY_F16 7
 #define S2S_GEOMETRY_MAX_DNA_LEN 64
 #define S2S_GEOMETRY_MAX_SIGNAL_LEN 1024
 
@@ -73,19 +85,21 @@ extern "C" {
 #define S2S_HEADS 8          /* config.yaml:28,30             */
 
 /* Model hyper-parameters that change the predict arithmetic (config.yaml:17-31; the keys
- * Encoder/Decoder.__init__ read, modules.py:22-63, 97-131).  Every mode but S2S_MODE_GENERIC_GEOMETRY: 16 k-mers in,
- * 250 samples out (the chunk geometry of the export kernels and the host framing); S2S_MODE_GENERIC_GEOMETRY: max_dna_len
- * 1..64, max_signal_len 1..1024.  Every mode: seq_kmer 1..16, encoder and decoder layers 1..4, pre_layers 0..4.  Sizes:
+ * Encoder/Decoder.__init__ read, modules.py:22-63, 97-131).  Every mode but S2S_MODE_GENERIC_GEOMETRY and
+ * S2S_MODE_GENERIC_GEOMETRY_F16: 16 k-mers in, 250 samples out (the chunk geometry of the export kernels and the host framing);
+ * those two: max_dna_len 1..64, max_signal_len 1..1024.  Every mode: seq_kmer 1..16, encoder and decoder layers 1..4,
+ * pre_layers 0..4.  Sizes:
  *   tuned modes (F32, F16X3, F16): the shipped architecture family only -- dmodel 64, dff 256,
  *                   8 heads in encoder and decoder;
- *   S2S_MODE_GENERIC, S2S_MODE_GENERIC_F16 and S2S_MODE_GENERIC_GEOMETRY: dmodel a multiple of 16 in 16..512, dff a multiple of 8 in
- *                   8..2048, encoder and decoder heads each 1..16 and a divisor of dmodel (head_dim = dmodel / heads).
+ *   S2S_MODE_GENERIC, S2S_MODE_GENERIC_F16, S2S_MODE_GENERIC_GEOMETRY and S2S_MODE_GENERIC_GEOMETRY_F16: dmodel a multiple of 16
+ *                   in 16..512, dff a multiple of 8 in 8..2048, encoder and decoder heads each 1..16 and a divisor of dmodel
+ *                   (head_dim = dmodel / heads).
  * A refused configuration is S2S_ERR_ARG from s2s_create (the message names the key) and
  * s2s_blob_floats returns 0 for it. */
 typedef struct s2s_config {
     int32_t seq_kmer;          /* 9 (dna-r10*, rna-004*) or 6 (dna-r9*), utils.py:257-260 */
-    int32_t max_dna_len;       /* must be 16;  S2S_MODE_GENERIC_GEOMETRY: 1..64   */
-    int32_t max_signal_len;    /* must be 250; S2S_MODE_GENERIC_GEOMETRY: 1..1024 */
+    int32_t max_dna_len;       /* must be 16;  S2S_MODE_GENERIC_GEOMETRY(_F16): 1..64   */
+    int32_t max_signal_len;    /* must be 250; S2S_MODE_GENERIC_GEOMETRY(_F16): 1..1024 */
     int32_t dmodel;            /* tuned: 64;  generic: 16..512, a multiple of 16 */
     int32_t dff;               /* tuned: 256; generic: 8..2048, a multiple of 8 */
     int32_t n_heads;           /* encoder heads; tuned: 8; generic: 1..16, divides dmodel */
@@ -111,7 +125,7 @@ typedef struct s2s_params {
 } s2s_params;
 
 /* Optional stage outputs for parity tests (all nullable, device).  [64] below is [dmodel] for a generic handle; [16] and [250]
- * are [max_dna_len] and [max_signal_len] for a S2S_MODE_GENERIC_GEOMETRY handle. */
+ * are [max_dna_len] and [max_signal_len] for a S2S_MODE_GENERIC_GEOMETRY or S2S_MODE_GENERIC_GEOMETRY_F16 handle. */
 typedef struct s2s_debug {
     float* emb_out;            /* [B][16][64]  Encoder.forward 2nd result (modules.py:72-77) */
     float* enc_out;            /* [B][16][64]  Encoder.forward 1st result (modules.py:80-89) */
@@ -130,8 +144,9 @@ typedef struct s2s_debug {
 typedef struct s2s_handle s2s_handle;
 
 /* Number of fp32 values the weight blob must hold for `cfg` (0 for a refused configuration), and the order, written for the
- * tuned sizes -- for S2S_MODE_GENERIC, S2S_MODE_GENERIC_F16 and S2S_MODE_GENERIC_GEOMETRY (the same blob) read every 64 as dmodel
- * and every 256 as dff, and for S2S_MODE_GENERIC_GEOMETRY 16 as max_dna_len and 250 as max_signal_len in the position tables:
+ * tuned sizes -- for S2S_MODE_GENERIC, S2S_MODE_GENERIC_F16, S2S_MODE_GENERIC_GEOMETRY and S2S_MODE_GENERIC_GEOMETRY_F16 (the
+ * same blob) read every 64 as dmodel and every 256 as dff, and for the two geometry modes 16 as max_dna_len and 250 as
+ * max_signal_len in the position tables:
  *   encoders.position_enc[16*64]; src_emb.weight[64][5k], .bias[64];
  *   pre_net_stack.i.weight[64][64], .bias[64]                               (i < pre_layers)
  *   per encoder layer: LAYER (below)
@@ -146,7 +161,7 @@ typedef struct s2s_handle s2s_handle;
  *
  * A generic handle runs a launch in slices of at most S2S_GENERIC_WORKSPACE_BYTES / (4 * per-chunk floats) chunks, per-chunk
  * floats = te dmodel + ts dmodel + max(te, ts) max(3 dmodel, dff) + te + ts, te / ts = max_dna_len / max_signal_len (16 / 250
- * outside S2S_MODE_GENERIC_GEOMETRY; each buffer is then rounded up to a multiple of
+ * outside the two geometry modes; each buffer is then rounded up to a multiple of
  * 64 floats); the workspace grows on demand (the first launch of a larger batch synchronises the stream) and is reused. */
 #define S2S_GENERIC_WORKSPACE_BYTES (512u << 20)
 size_t s2s_blob_floats(const s2s_config* cfg);
@@ -202,7 +217,7 @@ int s2s_predict_packed(s2s_handle* h, void* stream, const uint8_t* read_bytes, c
  *  out_dac      nullable device int16 [capacity]: round_half_even(pa*digitisation/range - offset)
  *               wrapped to int16; reversed per read when rna != 0 (signal_io.py:140-141);
  *  capacity     size of out_pa/out_dac in samples (B*250 always suffices).
- * Rows are 250 samples, max_signal_len for a S2S_MODE_GENERIC_GEOMETRY handle.
+ * Rows are 250 samples, max_signal_len for a S2S_MODE_GENERIC_GEOMETRY(_F16) handle.
  */
 int s2s_export_reads(s2s_handle* h, void* stream, const float* signal, int32_t B,
                      const int32_t* read_first, int32_t R, int64_t* out_offsets, float* out_pa,

@@ -80,15 +80,17 @@ def state_dict_to_blob(sd: Dict[str, torch.Tensor], cfg: dict) -> np.ndarray:
 
 
 # f16: reduced precision; generic: any size; generic-f16: any size, reduced precision, opt-in only; generic-geometry: any size at any
-# chunk geometry (max_dna_len / max_signal_len), exact fp32 (see include/s2s_hip.h)
-MODES = {"f32": 0, "f16x3": 1, "f16": 3, "generic": 4, "generic-f16": 5, "generic-geometry": 6}
+# chunk geometry (max_dna_len / max_signal_len), exact fp32; generic-geometry-f16: the same at reduced precision, opt-in only (see
+# include/s2s_hip.h)
+MODES = {"f32": 0, "f16x3": 1, "f16": 3, "generic": 4, "generic-f16": 5, "generic-geometry": 6, "generic-geometry-f16": 7}
 TUNED_MODES = ("f32", "f16x3", "f16")
+GEOMETRY_MODES = ("generic-geometry", "generic-geometry-f16")     # the modes that run a chunk geometry other than 16 / 250
 TUNED_SIZES = {"dmodel": 64, "dff": 256, "encoder_heads": 8, "decoder_heads": 8}
 DEFAULT_GEOMETRY = {"max_dna_len": 16, "max_signal_len": 250}     # the only chunk geometry of every mode but generic-geometry
 
 
 def is_default_geometry(cfg: dict) -> bool:
-    """Does `cfg` chunk reads as 16 k-mers -> 250 samples?  Other geometries run on "generic-geometry" only."""
+    """Does `cfg` chunk reads as 16 k-mers -> 250 samples?  Other geometries run on the GEOMETRY_MODES only."""
     return all(int(cfg[k]) == v for k, v in DEFAULT_GEOMETRY.items())
 
 

@@ -6,7 +6,7 @@ Reference: split_sequence (utils.py:350-356) = extract_kmers (334-339) + add_rem
 takes the raw bases instead: chunk c is read[16c : 16c+15+k] plus the number of real k-mers in
 it (k-mers past the read's end are the all-"_" pad k-mer, which is NOT a window over padded
 bases, so it cannot be expressed by padding the bytes alone).  16 is the config's max_dna_len: every
-function takes it as `t_enc` (default 16; a "generic-geometry" checkpoint chunks at its own).
+function takes it as `t_enc` (default 16; a checkpoint run in a geometry mode chunks at its own).
 """
 from typing import Iterable, List, Sequence, Tuple
 

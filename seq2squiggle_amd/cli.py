@@ -80,10 +80,11 @@ def version():
 @click.option("-y", "--config", help="YAML configuration file overriding the defaults.")
 @click.option("-v", "--verbosity", type=click.Choice(["debug", "info", "warning", "error"], case_sensitive=False), default="info")
 @click.option("--compute-mode", default=None,
-              type=click.Choice(["f16x3", "f32", "f16", "generic", "generic-f16", "generic-geometry"]),
+              type=click.Choice(["f16x3", "f32", "f16", "generic", "generic-f16", "generic-geometry", "generic-geometry-f16"]),
               hidden=True, help="Decoder arithmetic of the MI355X engine (default: f16x3 for the shipped model sizes, generic for any "
                                 "other; generic-f16: any size, reduced precision; generic-geometry: any size and any "
-                                "max_dna_len / max_signal_len, the default for a geometry other than 16 / 250).")
+                                "max_dna_len / max_signal_len, the default for a geometry other than 16 / 250; "
+                                "generic-geometry-f16: the same at reduced precision, opt-in only).")
 @click.option("--attention-path", default="auto", type=click.Choice(["auto", "fast", "exact"]), hidden=True,
               help="Softmax path of the split-f16 decoder: auto = chosen per checkpoint by the engine's calibration launch "
                    "(include/s2s_hip.h: s2s_set_attention_path); exact = the same time whatever the weights.")

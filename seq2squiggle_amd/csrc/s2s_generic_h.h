@@ -1,11 +1,13 @@
-// s2s_generic_h.h -- the decoder FFT blocks of the reduced-precision size-generic instance (S2S_MODE_GENERIC_F16), included by
-// s2s_hip.hip after s2s_generic.h.
+// s2s_generic_h.h -- the decoder FFT blocks of the reduced-precision generic instances (S2S_MODE_GENERIC_F16 and, at any chunk
+// geometry, S2S_MODE_GENERIC_GEOMETRY_F16), included by s2s_hip.hip after s2s_generic.h.
 //
-// Everything else of that instance -- embedding, pre-net, the encoder FFT blocks, the heads, dwell, the length regulator and
+// Everything else of those instances -- embedding, pre-net, the encoder FFT blocks, the heads, dwell, the length regulator and
 // out_linear / noise / clamp -- is S2S_MODE_GENERIC's fp32 code (s2s_generic.h), launched the same way.  In the decoder every matrix
 // product takes its two operands rounded to f16 once (round to nearest even) and accumulates in fp32 on v_mfma_f32_16x16x32_f16:
-//   gen_gemm_h_kernel<EPI>   QKV, fc, w_1, w_2: the epilogues of gen_gemm_kernel<EPI> (bias, ReLU, residual) in fp32
-//   gen_attention_h_kernel   Q.K^T and P.V of one (chunk, head) over the 250 decoder keys, fp32 softmax with its exact row maximum
+//   gen_gemm_h_kernel<EPI>         QKV, fc, w_1, w_2: the epilogues of gen_gemm_kernel<EPI> (bias, ReLU, residual) in fp32
+//   gen_attention_h_kernel         Q.K^T and P.V of one (chunk, head) over the 250 decoder keys, fp32 softmax with its exact row
+//                                  maximum; gen_attention_h_any_kernel the same over T <= 256 keys, T at run time
+//   gen_attention_long_h_kernel<NT>  the same over 257..1024 keys: one workgroup per (chunk, head, 64 queries), two passes over K
 // The LayerNorms stay gen_layernorm_kernel (fp32).
 //
 // 16x16x32 f16 operand layout (lane l = 16g + c): A[row c][k 8g + j], B[k 8g + j][col c] in element j = 0..7; the result
@@ -100,8 +102,11 @@ __global__ void __launch_bounds__(256) gen_gemm_h_kernel(const float* __restrict
 }
 
 // ---- scaled dot-product attention of one decoder (chunk, head) on the matrix cores (layers.py:19-41, 64-88; no mask in predict),
-//      on the QKV rows [row][3d] = q | k | v as gen_attention_kernel reads them; O overwrites Q in place.
-//      16 waves, wave w the queries 16w .. 16w+15 (queries 250..255 are computed on zero rows and never stored); the 250 keys padded to
+//      on the QKV rows [row][3d] = q | k | v as gen_attention_kernel reads them; O overwrites Q in place.  T <= 256 keys and queries
+//      per chunk: the constant 250 in gen_attention_h_kernel (S2S_MODE_GENERIC_F16's instance, whose code a run-time T would
+//      change: the select of a run-time mask keeps the compiler from contracting s * sc - max into one fma), max_signal_len at run
+//      time in gen_attention_h_any_kernel (S2S_MODE_GENERIC_GEOMETRY_F16 at other lengths up to 256).
+//      16 waves, wave w the queries 16w .. 16w+15 (queries T..255 are computed on zero rows and never stored); the T keys padded to
 //      256.  Scores are computed transposed, S^T = K Q^T (A = K, B = Q^T): lane (g, c) then holds query 16w + c against keys
 //      16jt + 4g + r in register r of tile jt = 0..15, 64 fp32 scores, so a query's whole row sits in the 4 lanes c, c+16, c+32, c+48
 //      and no online rescale is needed.  Padding keys are masked to -inf; softmax in fp32 with the exact row maximum
@@ -117,7 +122,9 @@ __global__ void __launch_bounds__(256) gen_gemm_h_kernel(const float* __restrict
 #define GENH_LDQ (GENH_EK + 8)
 #define GENH_EV 64
 #define GENH_LDV (GENH_TP + 8)
-__global__ void __launch_bounds__(1024) gen_attention_h_kernel(float* __restrict__ QKV, int d, int H) {
+template <int TD>
+__device__ __forceinline__ void gen_attention_h_body(float* __restrict__ QKV, int d, int H, int T_) {
+    const int T = TD ? TD : T_;
     __shared__ __attribute__((aligned(16))) _Float16 lds[2 * GENH_TP * GENH_LDQ];
     _Float16* Ks = lds;
     _Float16* Qs = lds + GENH_TP * GENH_LDQ;
@@ -126,7 +133,7 @@ __global__ void __launch_bounds__(1024) gen_attention_h_kernel(float* __restrict
     const int b = blockIdx.x / H, h = blockIdx.x % H;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 4, c = lane & 15;
-    float* base = QKV + (long long)b * GEN_T_DEC * ld + h * hd;
+    float* base = QKV + (long long)b * T * ld + h * hd;
     f32x4 s[16];
 #pragma unroll
     for (int jt = 0; jt < 16; ++jt) s[jt] = f32x4{0, 0, 0, 0};
@@ -138,7 +145,7 @@ __global__ void __launch_bounds__(1024) gen_attention_h_kernel(float* __restrict
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const int e = e0 + se + i;
-            const bool in = sr < GEN_T_DEC && e < hd;
+            const bool in = sr < T && e < hd;
             k4[i >> 2][i & 3] = in ? krow[e] : 0.0f;
             q4[i >> 2][i & 3] = in ? qrow[e] : 0.0f;
         }
@@ -158,7 +165,7 @@ __global__ void __launch_bounds__(1024) gen_attention_h_kernel(float* __restrict
     for (int jt = 0; jt < 16; ++jt)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const float v = 16 * jt + 4 * g + r < GEN_T_DEC ? s[jt][r] * sc : -__builtin_inff();
+            const float v = 16 * jt + 4 * g + r < T ? s[jt][r] * sc : -__builtin_inff();
             s[jt][r] = v;
             mx = fmaxf(mx, v);
         }
@@ -188,8 +195,8 @@ __global__ void __launch_bounds__(1024) gen_attention_h_kernel(float* __restrict
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const int k0 = vk + i, k1 = vk + 8 + i;
-            v0[i] = (_Float16)(k0 < GEN_T_DEC && e < hd ? base[(long long)k0 * ld + 2 * d + e] : 0.0f);
-            v1[i] = (_Float16)(k1 < GEN_T_DEC && e < hd ? base[(long long)k1 * ld + 2 * d + e] : 0.0f);
+            v0[i] = (_Float16)(k0 < T && e < hd ? base[(long long)k0 * ld + 2 * d + e] : 0.0f);
+            v1[i] = (_Float16)(k1 < T && e < hd ? base[(long long)k1 * ld + 2 * d + e] : 0.0f);
         }
         __syncthreads();                                      // Q.K^T's (or the previous step's) reads of these bytes are done
         *reinterpret_cast<gen_h8*>(Vt + ve * GENH_LDV + vk) = v0;
@@ -210,8 +217,173 @@ __global__ void __launch_bounds__(1024) gen_attention_h_kernel(float* __restrict
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int q = 16 * wave + 4 * g + r;
-                if (q < GEN_T_DEC && eo < hd) base[(long long)q * ld + eo] = o[r];
+                if (q < T && eo < hd) base[(long long)q * ld + eo] = o[r];
             }
+        }
+    }
+}
+
+
+// S2S_MODE_GENERIC_F16 (and S2S_MODE_GENERIC_GEOMETRY_F16 at 250 samples): the 250-key instance, T a constant
+__global__ void __launch_bounds__(1024) gen_attention_h_kernel(float* __restrict__ QKV, int d, int H) {
+    gen_attention_h_body<GEN_T_DEC>(QKV, d, H, GEN_T_DEC);
+}
+// S2S_MODE_GENERIC_GEOMETRY_F16 at any other max_signal_len <= 256: T at run time
+__global__ void __launch_bounds__(1024) gen_attention_h_any_kernel(float* __restrict__ QKV, int d, int H, int T) {
+    gen_attention_h_body<0>(QKV, d, H, T);
+}
+// ---- scaled dot-product attention of one decoder (chunk, head) over T = 257..1024 keys on the matrix cores
+//      (S2S_MODE_GENERIC_GEOMETRY_F16 beyond 256 samples, where gen_attention_h_kernel's 64 score registers per lane no longer hold a
+//      query's row); O overwrites Q in place.  One workgroup per (chunk, head, 64 queries), gen_attention_long_kernel's layout: wave w
+//      owns queries 16w .. 16w+15 of the tile, scores transposed, S^T = K Q^T (A = 16 keys x 32 head dims of K from LDS, B = the
+//      wave's Q^T fragment), so lane (g, c) holds query c against keys 16kt + 4g + r in register r of key tile kt.
+//      Keys go in blocks of 64: K [64][32 head dims] (and V^T [64 head dims][64]) are staged through LDS as f16, shared by the four
+//      waves.  Two passes over the blocks:
+//        1. S^T, the exact row maximum (of the unscaled scores; the scale 1/sqrt(d_k) > 0 keeps the argmax).
+//        2. S^T again, p = exp2(s log2(e)/sqrt(d_k) - max log2(e)/sqrt(d_k)) in fp32 (one v_fma + one v_exp per score: every exp is
+//           computed once), the fp32 row sum, p rounded to f16 once -- p lies in [0, 1], unnormalised -- and O^T += V^T P^T
+//           (A = V^T from LDS, B = P as it sits in the score registers: element j of k-block kb is key 32kb + 16(j>>2) + 4g + (j&3),
+//           as in gen_attention_h_kernel); at the end O = O^T^T / sum in fp32.
+//      Dividing at the end, not normalising P before its rounding as gen_attention_h_kernel and the reference's autocast do: the sum
+//      is only known after the last block, and normalising first would take a third pass (or a second exp) per score.  Both round
+//      one value of [0, 1] per score to f16; the two conventions differ by that rounding, within the 16-mixed bar.  No online
+//      rescaling of O.  The price of the exact maximum is the score product done twice -- at small head_dim the exp, not the matrix
+//      pipe, bounds the kernel (4 scores per lane per MFMA), so the second product is nearly free there.
+//      NT output tiles of 16 head dims, 16 NT >= hd (NT 1 | 8 | 32 for hd <= 16 | 128 | 512); Q in registers as QS = 1 | 4 fragments
+//      of 32 head dims for NT = 1 | 8; for NT = 32 read again for every step from the L1 / L2 (held, its 64 registers made the
+//      instance spill).
+//      Q, K and V are read through a buffer resource over the chunk's rows (no load leaves them): keys past T are zero rows in LDS
+//      with p = 0, queries past T compute on zero rows and are not stored.
+//        LDS   K [64][40] + V^T [64][72] halves = 5,120 + 9,216 = 14,336 bytes per workgroup (rows padded by 8 halves: the 16-byte
+//              and 8-byte operand reads of 16 lanes start on different banks).
+//        VGPR  4 NT accumulators + 4 QS for Q + 16 scores + 8 for P + 8 K / 16 V staging registers: 57 + 20 AGPRs (NT = 1),
+//              108 + 48 (NT = 8), 139 + 144 (NT = 32); no scratch, no spills (tests/test_geometry_f16_cpu.py).  At most 6 | 3 | 1
+//              waves per SIMD by registers; by LDS 11 workgroups fit a CU.
+#define GENHL_KB 64
+#define GENHL_LDV (GENHL_KB + 8)
+template <int NT>
+__global__ void __launch_bounds__(256) gen_attention_long_h_kernel(float* __restrict__ QKV, int d, int H, int T) {
+    constexpr int QS = NT == 1 ? 1 : NT == 8 ? 4 : 0;          // Q fragments held in registers
+    __shared__ __attribute__((aligned(16))) _Float16 Ks[GENHL_KB * GENH_LDQ];
+    __shared__ __attribute__((aligned(16))) _Float16 Vt[GENH_EV * GENHL_LDV];
+    const int nqt = (T + 63) / 64;
+    const int b = blockIdx.x / (H * nqt), h = (blockIdx.x / nqt) % H, qt = blockIdx.x % nqt;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int g = lane >> 4, c = lane & 15;
+    const int hd = d / H, ld = 3 * d;
+    float* base = QKV + (long long)b * T * ld + h * hd;
+    // The chunk's rows as a buffer resource: a load past their end returns 0, so the rows of keys and queries past T read as zeros.
+    // Columns past the head's hd are other data of the same rows: zeroed for Q and K (bitwise, no branch), left as they are for V
+    // (V^T row e >= hd only feeds output rows that are not stored).
+    const __amdgpu_buffer_rsrc_t rows = __builtin_amdgcn_make_buffer_rsrc(QKV + (long long)b * T * ld, 0, T * ld * 4, 0x00020000);
+    auto ldb = [&](int row, int part, int e) {                // QKV[chunk b][row][part + h * hd + e], 0 for row >= T
+        return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rows, (unsigned)((row * ld + part + h * hd + e) * 4), 0, 0));
+    };
+    auto in_head = [&](float x, int e) { return __uint_as_float(__float_as_uint(x) & (unsigned)((e - hd) >> 31)); };   // e < hd ? x : 0
+    const int q = qt * 64 + wave * 16 + c;                     // this lane's query: B-operand column c
+    const bool qin = q < T;
+    auto q_frag = [&](int e0) {                                // Q^T fragment of head dims e0 .. e0+31: B[k 8g + j][col c] = Q[q][e0 + 8g + j]
+        gen_h8 f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) f[j] = (_Float16)in_head(ldb(q, 0, e0 + 8 * g + j), e0 + 8 * g + j);
+        return f;
+    };
+    gen_h8 qf[QS > 0 ? QS : 1];                                // (QS = 0: read for every step instead, from the L1 / L2)
+#pragma unroll
+    for (int i = 0; i < QS; ++i) qf[i] = q_frag(32 * i);
+    const int sr = tid >> 2, se = (tid & 3) * 8;              // staging: key sr of the block, head dims se .. se+7 of a K step
+                                                              // (16 (tid & 3) .. +15 of a V step)
+    f32x4 s[4];
+    auto k_step = [&](int key, int e0, const gen_h8 qv) {     // s += K[keys of the block][e0 .. e0+31] Q^T
+        f32x4 k4[2];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) k4[i >> 2][i & 3] = in_head(ldb(key, d, e0 + se + i), e0 + se + i);
+        __syncthreads();                                      // the previous reads of Ks are done
+        *reinterpret_cast<gen_h8*>(Ks + sr * GENH_LDQ + se) = gen_to_h8(k4[0], k4[1]);
+        __syncthreads();
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt)
+            s[kt] = GEN_MFMA_H(*reinterpret_cast<const gen_h8*>(Ks + (16 * kt + c) * GENH_LDQ + 8 * g), qv, s[kt]);
+    };
+    auto scores = [&](int j0) {                                // s[kt][r] = S[query c][key j0 + 16kt + 4g + r] (unscaled)
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt) s[kt] = f32x4{0, 0, 0, 0};
+        if (QS > 0) {
+#pragma unroll
+            for (int i = 0; i < QS; ++i) {
+                if (32 * i >= hd) break;
+                k_step(j0 + sr, 32 * i, qf[i]);
+            }
+        } else {
+            for (int e0 = 0; e0 < hd; e0 += 32) k_step(j0 + sr, e0, q_frag(e0));
+        }
+    };
+    float mx = -__builtin_inff();
+    for (int j0 = 0; j0 < T; j0 += GENHL_KB) {
+        scores(j0);
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (j0 + 16 * kt + 4 * g + r < T) mx = fmaxf(mx, s[kt][r]);
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));                    // the four lanes of query c: c, c + 16, c + 32, c + 48
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float sc = 1.4426950408889634f / sqrtf((float)hd);   // log2(e) / temperature (d_k ** 0.5, layers.py:58)
+    const float nms = -(mx * sc);
+    f32x4 acc[NT];                                             // acc[t][r] = O[query c][16t + 4g + r]
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc[t] = f32x4{0, 0, 0, 0};
+    float sum = 0.0f;
+    const int nt = (hd + 15) / 16;
+    for (int j0 = 0; j0 < T; j0 += GENHL_KB) {
+        scores(j0);
+        gen_h8 p[2];
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float v = j0 + 16 * kt + 4 * g + r < T ? exp2f(fmaf(s[kt][r], sc, nms)) : 0.0f;
+                sum += v;
+                p[kt >> 1][4 * (kt & 1) + r] = (_Float16)v;
+            }
+#pragma unroll
+        for (int vs = 0; vs < (NT + 3) / 4; ++vs) {            // V^T in steps of 64 head dims
+            if (64 * vs >= hd) break;
+            float v[16];
+            const int key = j0 + sr, e0 = 64 * vs + 16 * (tid & 3);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) v[i] = ldb(key, 2 * d, e0 + i);
+            __syncthreads();                                  // the previous reads of Vt are done
+#pragma unroll
+            for (int i = 0; i < 16; ++i) Vt[(16 * (tid & 3) + i) * GENHL_LDV + sr] = (_Float16)v[i];
+            __syncthreads();
+#pragma unroll
+            for (int et = 0; et < 4; ++et) {
+                const int t = 4 * vs + et;
+                if (t >= NT || t >= nt) break;
+                const _Float16* vr = Vt + (16 * et + c) * GENHL_LDV + 4 * g;
+#pragma unroll
+                for (int kb = 0; kb < 2; ++kb) {
+                    const gen_h4 lo = *reinterpret_cast<const gen_h4*>(vr + 32 * kb);
+                    const gen_h4 hi = *reinterpret_cast<const gen_h4*>(vr + 32 * kb + 16);
+                    acc[t] = GEN_MFMA_H((gen_h8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]}), p[kb], acc[t]);
+                }
+            }
+        }
+    }
+    sum += __shfl_xor(sum, 16, 64);
+    sum += __shfl_xor(sum, 32, 64);
+    if (!qin) return;                                          // (no barriers below)
+    float* orow = base + (long long)q * ld;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        if (16 * t >= hd) break;
+        const bool full = 16 * t + 16 <= hd;                   // (uniform: no per-element test but in the last, partial tile)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int e = 16 * t + 4 * g + r;
+            if (full || e < hd) orow[e] = acc[t][r] / sum;
         }
     }
 }

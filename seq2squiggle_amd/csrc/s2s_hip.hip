@@ -857,12 +857,12 @@ struct s2s_handle {
     double calib_redo_rate = -1.0;          // share of the calibration launch's softmax runs that overflowed the fast path (-1: not calibrated)
     std::vector<EventPair> events;
     std::string err;
-    // S2S_MODE_GENERIC / _GENERIC_F16 (s2s_generic.h, s2s_generic_h.h): blob offsets into d_arena, and the slice workspace (grown on
+    // S2S_MODE_GENERIC / _GENERIC_F16 / _GENERIC_GEOMETRY / _GENERIC_GEOMETRY_F16 (s2s_generic.h, s2s_generic_h.h): blob offsets into d_arena, and the slice workspace (grown on
     // demand, s2s_predict_*)
     struct Generic {
         int d = 0, dff = 0, h_enc = 0, h_dec = 0;
-        int te = 16, ts = 250;        // chunk geometry: max_dna_len, max_signal_len (the checkpoint's in S2S_MODE_GENERIC_GEOMETRY)
-        bool f16 = false;             // S2S_MODE_GENERIC_F16: the decoder FFT blocks on f16 operands (dech)
+        int te = 16, ts = 250;        // chunk geometry: max_dna_len, max_signal_len (the checkpoint's in the two geometry modes)
+        bool f16 = false;             // S2S_MODE_GENERIC_F16 / _GEOMETRY_F16: the decoder FFT blocks on f16 operands (dech)
         long long pe_enc = 0, pe_dec = 0, emb_wt = 0, emb_b = 0, out_w = 0, out_b = 0, w0cat = 0, b0cat = 0;
         long long pre_w[S2S_MAX_LAYERS] = {}, pre_b[S2S_MAX_LAYERS] = {};
         GenLayer enc[S2S_MAX_LAYERS] = {}, dec[S2S_MAX_LAYERS] = {};
@@ -910,29 +910,36 @@ struct DeviceGuard {
 size_t layer_floats() { return 4 * (64 * 64 + 64) + 2 * 64 + (256 * 64 + 256) + (64 * 256 + 64) + 2 * 64; }
 size_t mlp_floats() { return 64 * 64 + 64 + 64 + 1; }
 
-bool mode_generic(int m) { return m == S2S_MODE_GENERIC || m == S2S_MODE_GENERIC_F16 || m == S2S_MODE_GENERIC_GEOMETRY; }
+bool mode_generic(int m) {
+    return m == S2S_MODE_GENERIC || m == S2S_MODE_GENERIC_F16 || m == S2S_MODE_GENERIC_GEOMETRY || m == S2S_MODE_GENERIC_GEOMETRY_F16;
+}
+bool mode_geometry(int m) { return m == S2S_MODE_GENERIC_GEOMETRY || m == S2S_MODE_GENERIC_GEOMETRY_F16; }
 
+// S2S_MODE_GENERIC_GEOMETRY_F16 has S2S_MODE_GENERIC_GEOMETRY's limits; its refusals name it instead (the other modes' messages
+// are unchanged: text + tag)
+#define GEN_REFUSE(text, tag) return g7 ? text " (S2S_MODE_GENERIC_GEOMETRY_F16)" : text tag
 const char* check_cfg_generic(const s2s_config* c) {
-    if (c->compute_mode == S2S_MODE_GENERIC_GEOMETRY) {
-        if (c->max_dna_len < 1 || c->max_dna_len > S2S_GEOMETRY_MAX_DNA_LEN)
-            return "max_dna_len must be 1..64 (S2S_MODE_GENERIC_GEOMETRY)";
+    const bool g7 = c->compute_mode == S2S_MODE_GENERIC_GEOMETRY_F16;
+    if (mode_geometry(c->compute_mode)) {
+        if (c->max_dna_len < 1 || c->max_dna_len > S2S_GEOMETRY_MAX_DNA_LEN) GEN_REFUSE("max_dna_len must be 1..64", " (S2S_MODE_GENERIC_GEOMETRY)");
         if (c->max_signal_len < 1 || c->max_signal_len > S2S_GEOMETRY_MAX_SIGNAL_LEN)
-            return "max_signal_len must be 1..1024 (S2S_MODE_GENERIC_GEOMETRY)";
+            GEN_REFUSE("max_signal_len must be 1..1024", " (S2S_MODE_GENERIC_GEOMETRY)");
     } else {
         if (c->max_dna_len != S2S_T_ENC) return "max_dna_len must be 16";
         if (c->max_signal_len != S2S_T_DEC) return "max_signal_len must be 250";
     }
-    if (c->dmodel < 16 || c->dmodel > 512 || c->dmodel % 16) return "dmodel must be a multiple of 16 in 16..512 (S2S_MODE_GENERIC)";
-    if (c->dff < 8 || c->dff > 2048 || c->dff % 8) return "dff must be a multiple of 8 in 8..2048 (S2S_MODE_GENERIC)";
+    if (c->dmodel < 16 || c->dmodel > 512 || c->dmodel % 16) GEN_REFUSE("dmodel must be a multiple of 16 in 16..512", " (S2S_MODE_GENERIC)");
+    if (c->dff < 8 || c->dff > 2048 || c->dff % 8) GEN_REFUSE("dff must be a multiple of 8 in 8..2048", " (S2S_MODE_GENERIC)");
     if (c->n_heads < 1 || c->n_heads > 16 || c->dmodel % c->n_heads)
-        return "n_heads (encoder heads) must be 1..16 and divide dmodel (S2S_MODE_GENERIC)";
+        GEN_REFUSE("n_heads (encoder heads) must be 1..16 and divide dmodel", " (S2S_MODE_GENERIC)");
     if (c->decoder_heads < 0 || c->decoder_heads > 16 || (c->decoder_heads && c->dmodel % c->decoder_heads))
-        return "decoder_heads must be 0 (= n_heads) or 1..16 and divide dmodel (S2S_MODE_GENERIC)";
-    if (c->encoder_layers < 1 || c->encoder_layers > S2S_MAX_LAYERS) return "encoder_layers must be 1..4";
-    if (c->decoder_layers < 1 || c->decoder_layers > S2S_MAX_LAYERS) return "decoder_layers must be 1..4";
-    if (c->pre_layers < 0 || c->pre_layers > S2S_MAX_LAYERS) return "pre_layers must be 0..4";
+        GEN_REFUSE("decoder_heads must be 0 (= n_heads) or 1..16 and divide dmodel", " (S2S_MODE_GENERIC)");
+    if (c->encoder_layers < 1 || c->encoder_layers > S2S_MAX_LAYERS) GEN_REFUSE("encoder_layers must be 1..4", "");
+    if (c->decoder_layers < 1 || c->decoder_layers > S2S_MAX_LAYERS) GEN_REFUSE("decoder_layers must be 1..4", "");
+    if (c->pre_layers < 0 || c->pre_layers > S2S_MAX_LAYERS) GEN_REFUSE("pre_layers must be 0..4", "");
     return nullptr;
 }
+#undef GEN_REFUSE
 
 const char* check_cfg(const s2s_config* c) {
     if (!c) return "config is NULL";
@@ -957,7 +964,7 @@ int cfg_dec_heads(const s2s_config* c) { return c->decoder_heads ? c->decoder_he
 size_t generic_layer_floats(size_t d, size_t f) { return 4 * (d * d + d) + 2 * d + (f * d + f) + (d * f + d) + 2 * d; }
 
 // fp32 floats of one chunk in the generic workspace: XE [te][d], SIG [te], XD [ts][d], SE [ts], BIG [max(te, ts)][max(3d, dff)]
-// (te / ts = max_dna_len / max_signal_len: 16 / 250 outside S2S_MODE_GENERIC_GEOMETRY)
+// (te / ts = max_dna_len / max_signal_len: 16 / 250 outside S2S_MODE_GENERIC_GEOMETRY and S2S_MODE_GENERIC_GEOMETRY_F16)
 size_t generic_chunk_floats(const s2s_config* c) {
     const size_t d = c->dmodel, big = 3 * d > (size_t)c->dff ? 3 * d : (size_t)c->dff;
     const size_t te = c->max_dna_len, ts = c->max_signal_len, tb = te > ts ? te : ts;
@@ -1207,7 +1214,7 @@ void pack_generic(Arena& A, s2s_handle::Generic& G, const s2s_config* cfg, const
     }
     G.pe_dec = A.put(take(p, G.ts * (size_t)d), G.ts * (size_t)d);
     for (int l = 0; l < cfg->decoder_layers; ++l) layer(G.dec[l]);
-    G.f16 = cfg->compute_mode == S2S_MODE_GENERIC_F16;
+    G.f16 = cfg->compute_mode == S2S_MODE_GENERIC_F16 || cfg->compute_mode == S2S_MODE_GENERIC_GEOMETRY_F16;
     if (G.f16) {   // the decoder's four weight matrices once more, rounded to f16, rows zero-padded to K rounded up to 32 (gen_gemm_h_kernel)
         G.ld_d = (d + 31) & ~31;
         G.ld_f = (f + 31) & ~31;
@@ -1276,8 +1283,8 @@ void gen_fft_block(hipStream_t st, const float* W, const GenLayer& L, float* X, 
     hipLaunchKernelGGL(gen_layernorm_kernel, dim3((M + 3) / 4), dim3(256), 0, st, X, W + L.ln2g, W + L.ln2b, (long long)M, d);
 }
 
-// S2S_MODE_GENERIC_F16's decoder FFTBlock: gen_fft_block with the matrix products on f16 operands (s2s_generic_h.h); the
-// LayerNorms, the biases, ReLU and the residuals stay fp32.  T = 250.
+// S2S_MODE_GENERIC_F16's and S2S_MODE_GENERIC_GEOMETRY_F16's decoder FFTBlock: gen_fft_block with the matrix products on f16
+// operands (s2s_generic_h.h); the LayerNorms, the biases, ReLU and the residuals stay fp32.  T = ts: 250 for S2S_MODE_GENERIC_F16.
 template <int EPI>
 void gen_gemm_h(hipStream_t st, const float* A, int lda, const float* Wh, int ldw, const float* bias, float* C, int ldc, const float* R, int M, int N,
                 int K) {
@@ -1287,10 +1294,22 @@ void gen_gemm_h(hipStream_t st, const float* A, int lda, const float* Wh, int ld
 }
 
 void gen_fft_block_h(hipStream_t st, const float* W, const GenLayer& L, const GenLayerH& LH, int ld_d, int ld_f, float* X, float* BIG, int n,
-                     int d, int dff, int H) {
-    const int M = n * GEN_T_DEC;
+                     int T, int d, int dff, int H) {
+    const int M = n * T, hd = d / H;
     gen_gemm_h<0>(st, X, d, W + LH.wqkv, ld_d, W + L.bqkv, BIG, 3 * d, nullptr, M, 3 * d, d);
-    hipLaunchKernelGGL(gen_attention_h_kernel, dim3(n * H), dim3(1024), 0, st, BIG, d, H);
+    if (T > GENH_TP) {                        // (S2S_MODE_GENERIC_GEOMETRY_F16's decoder beyond 256 samples)
+        const dim3 grid((unsigned)n * H * ((T + 63) / 64));
+        if (hd <= 16)
+            hipLaunchKernelGGL(gen_attention_long_h_kernel<1>, grid, dim3(256), 0, st, BIG, d, H, T);
+        else if (hd <= 128)
+            hipLaunchKernelGGL(gen_attention_long_h_kernel<8>, grid, dim3(256), 0, st, BIG, d, H, T);
+        else
+            hipLaunchKernelGGL(gen_attention_long_h_kernel<32>, grid, dim3(256), 0, st, BIG, d, H, T);
+    } else if (T == GEN_T_DEC) {              // (S2S_MODE_GENERIC_F16's instance: mode 7 at 250 samples computes mode 5's numbers)
+        hipLaunchKernelGGL(gen_attention_h_kernel, dim3(n * H), dim3(1024), 0, st, BIG, d, H);
+    } else {
+        hipLaunchKernelGGL(gen_attention_h_any_kernel, dim3(n * H), dim3(1024), 0, st, BIG, d, H, T);
+    }
     gen_gemm_h<2>(st, BIG, 3 * d, W + LH.wfc, ld_d, W + L.bfc, X, d, X, M, d, d);
     hipLaunchKernelGGL(gen_layernorm_kernel, dim3((M + 3) / 4), dim3(256), 0, st, X, W + L.ln1g, W + L.ln1b, (long long)M, d);
     gen_gemm_h<1>(st, X, d, W + LH.w1, ld_d, W + L.b1, BIG, dff, nullptr, M, dff, d);
@@ -1368,7 +1387,7 @@ static int predict_generic(s2s_handle* h, hipStream_t st, const uint8_t* bases, 
                            D.dec_in ? D.dec_in + (size_t)s * ts * d : nullptr, te, ts);
         for (int l = 0; l < h->cfg.decoder_layers; ++l) {
             if (G.f16)
-                gen_fft_block_h(st, W, G.dec[l], G.dech[l], G.ld_d, G.ld_f, XD, BIG, n, d, dff, G.h_dec);
+                gen_fft_block_h(st, W, G.dec[l], G.dech[l], G.ld_d, G.ld_f, XD, BIG, n, ts, d, dff, G.h_dec);
             else
                 gen_fft_block(st, W, G.dec[l], XD, BIG, n, ts, d, dff, G.h_dec);
         }
@@ -1390,7 +1409,7 @@ size_t s2s_blob_floats(const s2s_config* c) {
     if (check_cfg(c)) return 0;
     if (mode_generic(c->compute_mode)) {
         const size_t d = c->dmodel, f = c->dff;
-        const size_t te = c->max_dna_len, ts = c->max_signal_len;     // 16 / 250 outside S2S_MODE_GENERIC_GEOMETRY
+        const size_t te = c->max_dna_len, ts = c->max_signal_len;     // 16 / 250 outside the two geometry modes
         return te * d + d * 5 * c->seq_kmer + d + (size_t)c->pre_layers * (d * d + d) +
                (size_t)(c->encoder_layers + c->decoder_layers) * generic_layer_floats(d, f) + 3 * (d * d + d + d + 1) + ts * d + d + 1;
     }
@@ -1712,7 +1731,7 @@ int s2s_export_reads(s2s_handle* h, void* stream_, const float* signal, int32_t 
         HIP_TRY(h, hipMalloc(&h->ws_offs, (size_t)cap * sizeof(long long)));
         h->ws_export_cap = cap;
     }
-    const int ts = h->cfg.max_signal_len;    // S2S_T_DEC except for a S2S_MODE_GENERIC_GEOMETRY handle
+    const int ts = h->cfg.max_signal_len;    // S2S_T_DEC except for a S2S_MODE_GENERIC_GEOMETRY(_F16) handle
     const bool tuned_rows = ts == S2S_T_DEC;
     if (B > 0)
         hipLaunchKernelGGL(tuned_rows ? s2s_count_kernel<S2S_T_DEC> : s2s_count_kernel<0>, dim3((B + 3) / 4), dim3(256), 0, stream, signal, B,

@@ -13,10 +13,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from .checkpoint import (DEFAULT_GEOMETRY, TUNED_MODES, TUNED_SIZES, config_to_c, default_mode, is_default_geometry, is_tuned_family,
-                         load_checkpoint, state_dict_to_blob)
+from .checkpoint import (DEFAULT_GEOMETRY, GEOMETRY_MODES, TUNED_MODES, TUNED_SIZES, config_to_c, default_mode, is_default_geometry,
+                         is_tuned_family, load_checkpoint, state_dict_to_blob)
 
-T_ENC, T_DEC = 16, 250          # the chunk geometry of every mode but "generic-geometry" (Engine.t_enc / t_dec: the engine's own)
+T_ENC, T_DEC = 16, 250          # the chunk geometry of every mode but the GEOMETRY_MODES (Engine.t_enc / t_dec: the engine's own)
 
 
 @dataclass
@@ -48,16 +48,18 @@ class Engine:
                  mode: Optional[str] = None):
         """mode: "f16x3", "f32", "f16" (the tuned instances, shipped sizes only), "generic" (any size within the limits of
         include/s2s_hip.h), "generic-f16" (the same sizes, the decoder's matrix products on f16 operands: reduced precision, never
-        picked by default) or "generic-geometry" (the sizes of "generic" at any max_dna_len 1-64 / max_signal_len 1-1024, exact
-        fp32); None picks "generic-geometry" for a chunk geometry other than 16 / 250, else "f16x3" for the shipped sizes and
-        "generic" otherwise."""
+        picked by default), "generic-geometry" (the sizes of "generic" at any max_dna_len 1-64 / max_signal_len 1-1024, exact
+        fp32) or "generic-geometry-f16" (the same sizes and geometries, the decoder's matrix products on f16 operands: reduced
+        precision, never picked by default; at 16 / 250 the numbers of "generic-f16"); None picks "generic-geometry" for a chunk
+        geometry other than 16 / 250, else "f16x3" for the shipped sizes and "generic" otherwise."""
         self._h = None
         if mode is None:
             mode = default_mode(config)
-        elif mode != "generic-geometry" and not is_default_geometry(config):
+        elif mode not in GEOMETRY_MODES and not is_default_geometry(config):
             geo = ", ".join(f"{k} {config[k]}" for k in DEFAULT_GEOMETRY)
             raise ValueError(f"mode {mode!r} runs only max_dna_len 16 / max_signal_len 250; this checkpoint has {geo}: "
-                             "use mode 'generic-geometry'")
+                             "use mode 'generic-geometry'"
+                             + (" (exact fp32) or 'generic-geometry-f16' (reduced precision)" if mode in ("f16", "generic-f16") else ""))
         elif mode in TUNED_MODES and not is_tuned_family(config):
             sizes = ", ".join(f"{k} {config[k]}" for k in TUNED_SIZES)
             raise ValueError(f"mode {mode!r} runs only dmodel 64, dff 256, 8 encoder / decoder heads; this checkpoint has {sizes}: "

@@ -12,7 +12,7 @@ from typing import Optional
 
 import torch
 
-from .checkpoint import load_checkpoint
+from .checkpoint import GEOMETRY_MODES, load_checkpoint
 from .engine import Engine, PredictParams
 from .signal_io import BLOW5Writer
 
@@ -73,7 +73,7 @@ class seq2squiggle:
         logging.getLogger("seq2squiggle").info(
             f"predict instance: {self.engine.mode} (dmodel {config['dmodel']}, dff {config['dff']}, "
             f"heads {config['encoder_heads']} / {config['decoder_heads']}"
-            + (f", max_dna_len {self.engine.t_enc} / max_signal_len {self.engine.t_dec})" if self.engine.mode == "generic-geometry" else ")"))
+            + (f", max_dna_len {self.engine.t_enc} / max_signal_len {self.engine.t_dec})" if self.engine.mode in GEOMETRY_MODES else ")"))
         self.device = self.engine.device
 
     @classmethod

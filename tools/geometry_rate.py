@@ -1,8 +1,9 @@
 #!/usr/bin/env python
 """Throughput of the chunk-geometry instance (GPU box): chunks/s and padded samples/s (chunks x max_signal_len) of predict_chunks
 in mode "generic-geometry" for every case of tests/_geometry_models.py, each beside mode "generic" at the same sizes and 16 / 250,
-with the built-in samplers.  One JSON line per case; the device clock is read with amd-smi where available (read-only).
-    python tools/geometry_rate.py [chunks] [tag ...]     (default: every case)"""
+with the built-in samplers.  --f16: also mode "generic-geometry-f16" on the same chunks in the same process, and its ratio to
+"generic-geometry".  One JSON line per case and mode; the device clock is read with amd-smi where available (read-only).
+    python tools/geometry_rate.py [--f16] [chunks] [tag ...]     (default: every case)"""
 import json, os, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -12,7 +13,9 @@ import seq2squiggle_amd as S
 from _geometry_models import CASES, geometry_config, geometry_state_dict
 from _sized_models import _sinusoid
 
-B = int(sys.argv[1]) if len(sys.argv) > 1 else 8192
+F16 = "--f16" in sys.argv[1:]
+ARGS = [a for a in sys.argv[1:] if a != "--f16"]
+B = int(ARGS[0]) if ARGS else 8192
 
 
 def clock():
@@ -46,10 +49,14 @@ def rate(sd, cfg, mode):
 
 
 print(json.dumps({"device": torch.cuda.get_device_name(0), "clock_before": clock()}))
-for tag in (sys.argv[2:] or list(CASES)):
+for tag in (ARGS[1:] or list(CASES)):
     sd, cfg = geometry_state_dict(tag), geometry_config(tag)
     sizes = {k: cfg[k] for k in ("dmodel", "dff", "encoder_heads", "decoder_heads", "pre_layers", "encoder_layers", "decoder_layers")}
-    print(json.dumps(dict(tag=tag, **sizes, **rate(sd, cfg, "generic-geometry"))), flush=True)
+    r6 = rate(sd, cfg, "generic-geometry")
+    print(json.dumps(dict(tag=tag, **sizes, **r6)), flush=True)
+    if F16:
+        r7 = rate(sd, cfg, "generic-geometry-f16")
+        print(json.dumps(dict(tag=tag, **sizes, **r7, vs_generic_geometry=r7["chunks_per_s"] / r6["chunks_per_s"])), flush=True)
     # the same weights at 16 / 250: position tables of the default sizes (the timing does not depend on their values)
     base = dict(sd, **{"encoders.position_enc": _sinusoid(16, cfg["dmodel"])[None],
                        "decoders.position_enc": _sinusoid(250, cfg["dmodel"])[None]})

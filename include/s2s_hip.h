@@ -205,6 +205,26 @@ int s2s_predict_packed(s2s_handle* h, void* stream, const uint8_t* read_bytes, c
                        const uint8_t* n_valid, int64_t first_global_chunk, int32_t B, const s2s_params* params,
                        float* out_signal, int32_t* out_dur);
 
+/* Replaces the first (teacher-forced) pass of seq2squiggle.validation_step + get_loss (model.py:107-143, 419-480) for B
+ * chunks: encoder, noise and duration heads, the length regulator on the MEASURED dwell of every k-mer (LR(x, ..., target),
+ * modules.py:434-435), decoder, and the three per-chunk loss sums.  Every compute mode, at the handle's te / ts (16 / 250, the
+ * checkpoint's max_dna_len / max_signal_len in the two geometry modes); the same model arithmetic as s2s_predict_chunks in that mode.
+ *  kmers    device [B][te][k]: the letters of each k-mer ('_','A','C','G','T'; any other byte = an all-zero one-hot row,
+ *           utils.py:86); k-mers are independent (no window overlap assumed) and every position counts (pads are explicit
+ *           "_"*k k-mers);
+ *  dwell    device [B][te] int32 >= 0: the measured samples per k-mer (chunks_lengths), used as they are (0 = k-mer skipped,
+ *           the cumulative sum cropped at ts);
+ *  target   device [B][ts] fp32, already divided by scaling_max_value; stdev device [B][te] fp32, likewise;
+ *  out_loss device [B][3] fp32 per chunk: sum over ts of (y - target)^2; sum over te of -Gamma(conc, rate).log_prob(max(dwell, 1))
+ *           (unscaled: get_loss's 0.0005 is the caller's); sum over te of (stdev - sigma)^2.  conc and rate are clamped at 1e-8
+ *           (modules.py:215-218), sigma enters unclamped (min_noise plays no part);
+ *  out_y    nullable device [B][ts]: the decoder output y (scaled units, modules.py:140-141: no scale, noise or clamp);
+ *  dbg      nullable: sigma, conc, rate ([B][te]) as for s2s_predict_chunks; a call that sets any other field is refused.
+ * Deterministic: a chunk's sums are formed in a fixed order from its own rows only, so they do not depend on B, on how the
+ * chunks are sliced or on their neighbours (no float atomics). */
+int s2s_evaluate_chunks(s2s_handle* h, void* stream, const uint8_t* kmers, const int32_t* dwell, const float* target,
+                        const float* stdev, int32_t B, float* out_loss, float* out_y, const s2s_debug* dbg);
+
 /* Replaces the per-read cat + zero-strip of export_and_clear_results (model.py:284-286) and the
  * pA -> int16 conversion of BLOW5Writer/POD5Writer.save (signal_io.py:134-141, 246-253).
  *

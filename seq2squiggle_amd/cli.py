@@ -2,6 +2,7 @@
 Same option names and defaults; the other commands of the reference (preprocess, train, sweep) are training
 and out of scope."""
 import logging
+import os
 import pathlib
 import sys
 
@@ -417,6 +418,62 @@ def merge_shards(shards, out, threads, consume):
     st = _merge.last
     click.echo(f"{n} records -> {out}  [{st.get('bytes', 0) / 1e9:.3f} GB in {st.get('seconds', 0):.2f} s]")
 
+
+
+MODES = ["f16x3", "f32", "f16", "generic", "generic-f16", "generic-geometry", "generic-geometry-f16"]
+
+
+@main.command()
+@click.argument("data_dir", type=click.Path(file_okay=False, path_type=pathlib.Path))
+@click.option("-m", "--model", "models", multiple=True, required=True, type=click.Path(dir_okay=False),
+              help="Checkpoint (.ckpt); repeat for several (one row each).")
+@click.option("--compute-mode", default=None, type=click.Choice(MODES),
+              help="Engine instance, as for predict (default: f16x3 for the shipped sizes, generic for others, generic-geometry for a "
+                   "chunk geometry other than 16 / 250).")
+@click.option("--max-chunks", default=0, type=int, show_default=True,
+              help="Evaluate the first N chunks in file order (the reference's valid_limit); 0 = all.")
+@click.option("--batch-size", default=65536, type=int, show_default=True, help="Chunks per GPU call.")
+@click.option("--per-chunk", "per_chunk", default=None, type=click.Path(dir_okay=False),
+              help="Write the per-chunk sums (signal, duration NLL, noise) of every checkpoint to this .npz.")
+@click.option("--json", "as_json", is_flag=True, help="Print one JSON object per checkpoint instead of the table.")
+def evaluate(data_dir, models, compute_mode, max_chunks, batch_size, per_chunk, as_json):
+    """Teacher-forced validation losses (valid_signal / duration / noise / total_loss of the reference's validation_step) of
+    one or more checkpoints on a preprocess directory (chunks-NNNN.npy ... or chunks.npy ...), on the GPU."""
+    if batch_size < 1:
+        raise click.BadParameter("must be >= 1", param_hint="--batch-size")
+    if max_chunks < 0:
+        raise click.BadParameter("must be >= 0", param_hint="--max-chunks")
+    if not data_dir.is_dir():
+        raise click.BadParameter(f"{data_dir} is not a directory", param_hint="DATA_DIR")
+    for m in models:
+        if not os.path.isfile(m):
+            raise click.BadParameter(f"{m} does not exist", param_hint="--model")
+    import json
+    import numpy as np
+    import torch  # noqa: F401  (before the library: see engine.py)
+    from .checkpoint import load_checkpoint
+    from .engine import Engine
+    from .evaluate import EvalData, evaluate as run
+    arrays = {}
+    for i, m in enumerate(models):
+        sd, cfg = load_checkpoint(m)
+        try:
+            data = EvalData(str(data_dir), cfg, max_chunks)
+        except ValueError as e:
+            raise click.ClickException(f"{m}: {e}")
+        eng = Engine(sd, cfg, mode=compute_mode)
+        losses, sums, secs = run(eng, data, batch_size)
+        eng.close()
+        row = dict(model=str(m), mode=eng.mode, chunks=int(data.n), chunks_per_s=data.n / secs if secs > 0 else None, **losses)
+        arrays[f"model{i}"] = sums
+        if as_json:
+            click.echo(json.dumps(row))
+        else:
+            click.echo(f"{m}  [{eng.mode}, {data.n} chunks, {row['chunks_per_s']:,.0f} chunks/s]  signal {losses['valid_signal_loss']:.6g}  "
+                       f"duration {losses['valid_duration_loss']:.6g}  noise {losses['valid_noise_loss']:.6g}  "
+                       f"total {losses['valid_total_loss']:.6g}")
+    if per_chunk:
+        np.savez(per_chunk, models=np.array([str(m) for m in models]), **arrays)
 
 if __name__ == "__main__":
     main()

@@ -463,3 +463,59 @@ __global__ void __launch_bounds__(256) gen_emit_kernel(const float* __restrict__
     }
     out_signal[row] = fmaxf(y, 0.0f);
 }
+
+// ---- s2s_evaluate_chunks (teacher forcing, modules.py:434-435) on this pipeline: three kernels take the place of gen_embed_kernel,
+//      gen_dwell_kernel and gen_emit_kernel; gen_lenreg_kernel reads the measured dwell counts as they are.
+// src_emb of a preprocess chunk: letter j of k-mer (b, c) at kmers[(b * te + c) * k + j], every position counts.  One thread per
+// (row, feature), the k columns added in k order as in gen_embed_kernel.
+__global__ void __launch_bounds__(256) gen_embed_kmers_kernel(const float* __restrict__ emb_wt, const float* __restrict__ emb_b, int k, int d,
+                                                              const uint8_t* __restrict__ kmers, int S, int te, float* __restrict__ X) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long long)S * te * d) return;
+    const int f = (int)(i % d);
+    const long long row = i / d;
+    const uint8_t* kp = kmers + row * k;
+    float x = emb_b[f];
+    for (int j = 0; j < k; ++j) {
+        const int code = gen_base_code(kp[j]);
+        if (code >= 0) x += emb_wt[(long long)(5 * j + code) * d + f];        // unknown letter: all-zero one-hot row (utils.py:86)
+    }
+    X[i] = relu1(x);
+}
+
+// gen_dwell_kernel's heads and + position_enc without a dwell source: sigma, and conc / rate clamped at 1e-8 (modules.py:215-218),
+// whatever a predict call would sample.  One wave per encoder row.
+__global__ void __launch_bounds__(256) gen_dwell_teacher_kernel(const float* __restrict__ W, GenHeads hw, long long pe_enc, int d, int S,
+                                                                const float* __restrict__ hid, float* __restrict__ X,
+                                                                float* __restrict__ sigma_out, float* __restrict__ conc_out,
+                                                                float* __restrict__ rate_out, int te) {
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= (long long)S * te) return;
+    const int c = (int)(row % te);
+    float hv[3];
+    for (int q = 0; q < 3; ++q) {
+        float part = 0.0f;
+        for (int f = lane; f < d; f += 64) part += hid[row * 3 * d + q * d + f] * W[hw.w3[q] + f];
+        hv[q] = softplus_t(gen_wave_sum(part) + W[hw.b3[q]]);
+    }
+    float* xr = X + row * d;
+    const float* pe = W + pe_enc + (long long)c * d;
+    for (int f = lane; f < d; f += 64) xr[f] += pe[f];
+    if (lane != 0) return;
+    sigma_out[row] = hv[0];
+    conc_out[row] = fmaxf(hv[1], 1e-8f);
+    rate_out[row] = fmaxf(hv[2], 1e-8f);
+}
+
+// out_linear + ReLU (modules.py:140-141): the decoder output y in scaled units, no scale, noise or clamp.  One wave per decoder row.
+__global__ void __launch_bounds__(256) gen_emit_y_kernel(const float* __restrict__ W, long long out_w, long long out_b, int d, int S,
+                                                         const float* __restrict__ Xd, float* __restrict__ y, int ts) {
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= (long long)S * ts) return;
+    float part = 0.0f;
+    for (int f = lane; f < d; f += 64) part += Xd[row * d + f] * W[out_w + f];
+    const float ys = relu1(gen_wave_sum(part) + W[out_b]);
+    if (lane == 0) y[row] = ys;
+}

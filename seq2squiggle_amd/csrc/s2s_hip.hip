@@ -45,6 +45,8 @@ __device__ __forceinline__ int base_code(unsigned char ch) {       // utils.py:7
 // One chunk as the frontend sees it.  bp: its 16+k-1 bases; inj_g / inj_zdw: its 16 injected variates (or null); slot: where
 // the decoder picks it up -- enc_out [16][64], sigma [16] at +1024, dur [16] (int32) at +1040; out_dur: the caller's [16] row;
 // dbg_idx: its row in the debug arrays; live = false: a filler (an odd chunk count), computed and thrown away.
+// s2s_eval_kernel (EVAL = true): bp is the chunk's [16][k] k-mer letters and out_dur its [16] measured dwell counts (read, not
+// written); nv is unused.
 struct FrontChunk {
     const uint8_t* bp;
     int nv;
@@ -58,8 +60,9 @@ struct FrontChunk {
 };
 #define S2S_SLOT_FLOATS S2S_PF_FLOATS
 
-// ---- src_emb on the one-hot k-mer == bias + sum of k gathered columns of W_emb, then ReLU (modules.py:70-73)
-template <int NQ>
+// ---- src_emb on the one-hot k-mer == bias + sum of k gathered columns of W_emb, then ReLU (modules.py:70-73).  EVAL: letter j
+//      of k-mer c at bp[c * k + j] (independent k-mers of a preprocess chunk), every position counts
+template <int NQ, bool EVAL = false>
 __device__ __forceinline__ void front_embed(const ModelDev& M, const float* __restrict__ W, const FrontChunk (&io)[NQ], const int lane,
                                             f32x4 (&X)[NQ][4]) {
     const int g = lane >> 4, c = lane & 15;
@@ -73,7 +76,8 @@ __device__ __forceinline__ void front_embed(const ModelDev& M, const float* __re
     for (int j = 0; j < M.k; ++j) {
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
-            const int code = (c < io[q].nv) ? base_code(io[q].bp[c + j]) : 0;   // pad k-mer = "_" * k (utils.py:342-347)
+            const int code = EVAL ? base_code(io[q].bp[c * M.k + j])
+                                  : (c < io[q].nv) ? base_code(io[q].bp[c + j]) : 0;   // pad k-mer = "_" * k (utils.py:342-347)
             const float* row = W + M.emb_wt + (5 * j + (code < 0 ? 0 : code)) * 64 + 4 * g;
 #pragma unroll
             for (int ft = 0; ft < 4; ++ft) {
@@ -107,7 +111,8 @@ __device__ __forceinline__ void head_out(const float* __restrict__ W, const MlpO
 
 // ---- the dwell source (modules.py:396-438) and the sigma / dur stores, given the heads' values.  Every lane group holds the
 //      heads' values of all tiles (sum_g is an all-reduce), so lane group q finishes chunk q: ONE pass of the sampler per wave.
-template <int NQ>
+//      EVAL (teacher forcing, modules.py:434-435): conc / rate clamped and stored, the measured dwell goes to the slot, no sampler.
+template <int NQ, bool EVAL = false>
 __device__ __forceinline__ void front_dwell(const FrontChunk (&io)[NQ], const ParamsDev& P, const float (&sig)[NQ], const float (&cq)[NQ],
                                             const float (&rq)[NQ], const DebugDev& dbg, const int lane) {
     const int g = lane >> 4, c = lane & 15;
@@ -120,6 +125,14 @@ __device__ __forceinline__ void front_dwell(const FrontChunk (&io)[NQ], const Pa
     if (mine) {
         me.slot[1024 + c] = sigma;
         if (dbg.sigma) dbg.sigma[me.dbg_idx * 16 + c] = sigma;
+    }
+    if constexpr (EVAL) {
+        if (mine) {
+            dbg.conc[me.dbg_idx * 16 + c] = fmaxf(conc, 1e-8f);          // modules.py:215-218
+            dbg.rate[me.dbg_idx * 16 + c] = fmaxf(rate, 1e-8f);
+            reinterpret_cast<int*>(me.slot + 1040)[c] = me.out_dur[c];
+        }
+        return;
     }
     float gv;
     if (P.duration_sampling) {
@@ -194,11 +207,12 @@ __device__ __forceinline__ void front_store(const FrontChunk (&io)[NQ], const De
 // ---- f32 mode: one chunk per wave, every product on the f32-input MFMA, weights as f32 fragments from L2, encoder K/V in the
 //      wave's own slice of LDS (AttnLds<1>)
 struct FrontLdsF32 { static constexpr int BYTES = AttnLds<1>::BYTES; };
+template <bool EVAL = false>
 __device__ __forceinline__ void frontend_f32(const ModelDev& M, const float* __restrict__ W, const FrontChunk (&io)[1],
                                              const ParamsDev& P, char* __restrict__ lds_raw, const DebugDev& dbg, const int lane) {
     const int g = lane >> 4, c = lane & 15;
     f32x4 X[1][4];
-    front_embed<1>(M, W, io, lane, X);
+    front_embed<1, EVAL>(M, W, io, lane, X);
 #pragma unroll 1
     for (int i = 0; i < M.pre_layers; ++i) {                         // modules.py:74-77
         f32x4 Y[1][4];
@@ -221,7 +235,7 @@ __device__ __forceinline__ void frontend_f32(const ModelDev& M, const float* __r
     };
     head(M.noise, sig);                                              // modules.py:275-278
     if (P.duration_sampling) { head(M.conc, cq); head(M.rate, rq); }
-    front_dwell<1>(io, P, sig, cq, rq, dbg, lane);
+    front_dwell<1, EVAL>(io, P, sig, cq, rq, dbg, lane);
 #pragma unroll
     for (int ft = 0; ft < 4; ++ft) X[0][ft] += ldg4(W + M.pe_enc + c * 64 + 16 * ft + 4 * g);   // modules.py:80
 #pragma unroll 1
@@ -233,14 +247,14 @@ __device__ __forceinline__ void frontend_f32(const ModelDev& M, const float* __r
 //      in registers (s2s_device_h.h: enc_attention_h) -- no LDS at all.  (Measured: the phase is bound by its instruction count,
 //      about 6 k per chunk, like the decoder's; where the weights come from -- eight copies through the vector L1, or one copy
 //      staged in LDS behind ten barriers per group -- made no difference to its 71 us per 16 chunks.)
-template <int NQ>
+template <int NQ, bool EVAL = false>
 __device__ __forceinline__ void frontend_h16(const ModelDev& M, const float* __restrict__ W, const FrontChunk (&io)[NQ],
                                              const ParamsDev& P, const DebugDev& dbg, const int lane, const float one) {
     const int g = lane >> 4, c = lane & 15;
     DIAG_DECL;
 #define FDIAG(slot) DIAG_STAMP(32 + (slot))
     f32x4 X[NQ][4];
-    front_embed<NQ>(M, W, io, lane, X);
+    front_embed<NQ, EVAL>(M, W, io, lane, X);
     FDIAG(0);
 #pragma unroll 1
     for (int i = 0; i < M.pre_layers; ++i) {                         // modules.py:74-77
@@ -274,7 +288,7 @@ __device__ __forceinline__ void frontend_h16(const ModelDev& M, const float* __r
         head(M.noise, sig);
         if (P.duration_sampling) { head(M.conc, cq); head(M.rate, rq); }
         FDIAG(4);
-        front_dwell<NQ>(io, P, sig, cq, rq, dbg, lane);
+        front_dwell<NQ, EVAL>(io, P, sig, cq, rq, dbg, lane);
     }
 #pragma unroll
     for (int ft = 0; ft < 4; ++ft) {
@@ -610,6 +624,123 @@ __global__ __launch_bounds__(DEC_WAVES * 64, DEC_WPS) void s2s_fused_kernel(
     }
 }
 
+// ================================================================================ evaluate
+// s2s_evaluate_chunks on the tuned instances: s2s_fused_kernel's group walk with the teacher-forced frontend (EVAL: k-mer rows,
+// measured dwell into the slot, conc / rate always formed) and the decoder output y stored where dec_emit would draw noise.  The
+// decoder arithmetic is the predict instance's (the same dec_gather / dec_blocks / dec_project), so y is that mode's; the loss sums
+// are s2s_eval_loss_kernel's.  dbg_.sigma / conc / rate are required ([B][16]), its other fields are ignored; y: [B][250].
+template <int MODE, bool EXACT>
+__global__ __launch_bounds__(DEC_WAVES * 64, DEC_WPS) void s2s_eval_kernel(
+    const ModelDev M, const float* __restrict__ W, const uint8_t* __restrict__ kmers, const int* __restrict__ dwell, int n_chunks,
+    ParamsDev P, float* __restrict__ handoff, float* __restrict__ y, DebugDev dbg_) {
+    using F = Fused<MODE>;
+    extern __shared__ __attribute__((aligned(16))) char lds_raw[];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if constexpr (MODE != 0) att32_consts<AttnLdsH<DEC_NQ, DEC_WAVES, DEC_NKT>>(lds_raw, threadIdx.x, DEC_WAVES * 64);
+    if constexpr (MODE != 0) {
+        if (threadIdx.x < S2S_PROG_INTS + S2S_Z2_FLOATS)
+            reinterpret_cast<int*>(lds_raw + DEC_LDS_H + (S2S_SLOT_FLOATS + S2S_SV_FLOATS) * 4)[threadIdx.x] = 0;
+    }
+    if (threadIdx.x == 0) s2s_stats_lds[0] = 0;
+    DebugDev dbg{};                                                // the three head outputs only: no stage images in the hot loop
+    dbg.sigma = dbg_.sigma; dbg.conc = dbg_.conc; dbg.rate = dbg_.rate;
+    float* const slot0 = handoff + (size_t)blockIdx.x * S2S_MAX_GROUP * S2S_SLOT_FLOATS;
+    const int lo = (int)((long long)blockIdx.x * n_chunks / gridDim.x), hi = (int)((long long)(blockIdx.x + 1) * n_chunks / gridDim.x);
+    const int kb = S2S_T_ENC * M.k;                                 // k-mer letters per chunk
+#pragma unroll 1
+    for (int g0 = lo; g0 < hi; g0 += F::GROUP) {
+        const int n_here = hi - g0 < F::GROUP ? hi - g0 : F::GROUP;
+        float one = 1.0f;
+        asm volatile("" : "+s"(one));
+        __syncthreads();
+        {
+            int lnf = lane;
+            asm volatile("" : "+v"(lnf));
+            auto chunk_of = [&](const int j, const int j_filler) {
+                const bool live = j < n_here;
+                const int b = g0 + (live ? j : j_filler);
+                return FrontChunk{kmers + (size_t)b * kb, S2S_T_ENC, (unsigned long long)b, nullptr, nullptr, slot0 + j * S2S_SLOT_FLOATS,
+                                  const_cast<int*>(dwell) + (size_t)b * S2S_T_ENC, (long long)b, live};
+            };
+            if constexpr (F::FMODE == 1) {
+                if (n_here > DEC_WAVES) {
+                    const FrontChunk io[2] = {chunk_of(2 * wave, 2 * wave), chunk_of(2 * wave + 1, 2 * wave)};
+                    if (2 * wave < n_here) frontend_h16<2, true>(M, W, io, P, dbg, lnf, one);
+                } else {
+                    const FrontChunk io[1] = {chunk_of(wave, 0)};
+                    if (wave < n_here) frontend_h16<1, true>(M, W, io, P, dbg, lnf, one);
+                }
+            } else {
+                const FrontChunk io[1] = {chunk_of(wave, 0)};
+                if (wave < n_here) frontend_f32<true>(M, W, io, P, lds_raw + wave * FrontLdsF32::BYTES, dbg, lnf);
+            }
+        }
+        __syncthreads();
+        f32x4 X[DEC_NQ][4];
+        float sig_ext[DEC_NQ];
+        {
+            int lg = lane;
+            asm volatile("" : "+v"(lg));
+            GatherRaw R;
+            dec_gather_issue(M, W, slot0, wave, lg, R);
+            dec_gather_finish(R, wave, lg, X, sig_ext);
+        }
+#pragma unroll 1
+        for (int j = 0; j < n_here; ++j) {
+            const int b = g0 + j;
+            const float* next = slot0 + (j + 1 < n_here ? j + 1 : j) * S2S_SLOT_FLOATS;
+            dec_blocks<MODE, EXACT>(M, W, X, lds_raw, wave, lane, one, nullptr, F::PF ? next : nullptr);
+            int ln = lane;
+            asm volatile("" : "+v"(ln));
+            float ys, se;
+            dec_project(M, W, X, sig_ext, ln, ys, se);
+            GatherRaw R;
+            if constexpr (F::PF) dec_gather_issue(M, W, reinterpret_cast<const float*>(lds_raw + DEC_LDS_H), wave, ln, R);
+            else                 dec_gather_issue(M, W, next, wave, ln, R);
+            {
+                const int g = ln >> 4, t = 16 * (DEC_NQ * wave + g) + (ln & 15);
+                if (g < DEC_NQ && t < S2S_T_DEC) store_stream(y + (size_t)b * S2S_T_DEC + t, ys);
+            }
+            dec_gather_finish(R, wave, ln, X, sig_ext);
+        }
+    }
+}
+
+// The three per-chunk sums of get_loss (model.py:458-475) from the stage outputs, one wave per chunk, each in a fixed order (lane
+// partials in index order, then the butterfly of gen_wave_sum): a chunk's sums depend on its own rows only.
+//   [0] sum_t (y - target)^2   [1] sum_c -Gamma(conc, rate).log_prob(|d| + (d == 0))   [2] sum_c (stdev - sigma)^2
+// log_prob in torch's form: xlogy(conc, rate) + xlogy(conc - 1, x) - rate * x - lgamma(conc), fp32.  te <= 64: one lane per k-mer.
+__global__ __launch_bounds__(256) void s2s_eval_loss_kernel(const float* __restrict__ y, const float* __restrict__ target,
+                                                            const float* __restrict__ sigma, const float* __restrict__ stdev,
+                                                            const float* __restrict__ conc, const float* __restrict__ rate,
+                                                            const int* __restrict__ dwell, int B, int te, int ts, float* __restrict__ out_loss) {
+    const long long b = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (b >= B) return;
+    float se = 0.0f;
+    for (int t = lane; t < ts; t += 64) {
+        const float e = y[b * ts + t] - target[b * ts + t];
+        se += e * e;
+    }
+    float nll = 0.0f, ne = 0.0f;
+    if (lane < te) {
+        const long long i = b * te + lane;
+        const int dv = dwell[i];
+        const float x = dv == 0 ? 1.0f : (float)(dv < 0 ? -dv : dv);
+        const float a = conc[i], r = rate[i];
+        const float am1 = a - 1.0f;
+        const float lp = a * logf(r) + (am1 == 0.0f ? 0.0f : am1 * logf(x)) - r * x - lgammaf(a);
+        nll = -lp;
+        const float e = stdev[i] - sigma[i];
+        ne = e * e;
+    }
+    se = gen_wave_sum(se);
+    nll = gen_wave_sum(nll);
+    ne = gen_wave_sum(ne);
+    if (lane == 0) { out_loss[b * 3 + 0] = se; out_loss[b * 3 + 1] = nll; out_loss[b * 3 + 2] = ne; }
+}
+
 // ================================================================================ export
 // per-chunk count of non-zero samples (model.py:286 strips by value).  The export kernels take rows of TD samples: the tuned
 // instance TD = S2S_T_DEC, and TD = 0 for the row length `ts` of a S2S_MODE_GENERIC_GEOMETRY handle at another max_signal_len.
@@ -873,6 +1004,8 @@ struct s2s_handle {
         float* ws = nullptr;
         int ws_chunks = 0;            // slice capacity of ws
     } gen;
+    float* ev_ws = nullptr;           // s2s_evaluate_chunks: y, sigma, conc, rate of one slice (grown on demand)
+    int ev_chunks = 0;
 };
 
 namespace {
@@ -1572,7 +1705,10 @@ int s2s_create(const s2s_config* cfg, const void* blob, size_t blob_bytes, int d
         {reinterpret_cast<const void*>(s2s_fused_kernel<3, false>), Fused<3>::LDS}, {reinterpret_cast<const void*>(s2s_fused_kernel<0, true>), Fused<0>::LDS},
         {reinterpret_cast<const void*>(s2s_fused_kernel<1, true>), Fused<1>::LDS},  {reinterpret_cast<const void*>(s2s_fused_kernel<3, true>), Fused<3>::LDS},
         {reinterpret_cast<const void*>(s2s_fused_kernel<1, false, true>), Fused<1>::LDS}, {reinterpret_cast<const void*>(s2s_fused_kernel<3, false, true>), Fused<3>::LDS},
-        {reinterpret_cast<const void*>(s2s_fused_kernel<1, true, true>), Fused<1>::LDS},  {reinterpret_cast<const void*>(s2s_fused_kernel<3, true, true>), Fused<3>::LDS}};
+        {reinterpret_cast<const void*>(s2s_fused_kernel<1, true, true>), Fused<1>::LDS},  {reinterpret_cast<const void*>(s2s_fused_kernel<3, true, true>), Fused<3>::LDS},
+        {reinterpret_cast<const void*>(s2s_eval_kernel<0, false>), Fused<0>::LDS}, {reinterpret_cast<const void*>(s2s_eval_kernel<1, false>), Fused<1>::LDS},
+        {reinterpret_cast<const void*>(s2s_eval_kernel<3, false>), Fused<3>::LDS}, {reinterpret_cast<const void*>(s2s_eval_kernel<1, true>), Fused<1>::LDS},
+        {reinterpret_cast<const void*>(s2s_eval_kernel<3, true>), Fused<3>::LDS}};
     for (const auto& k : dyn_lds)
         if ((e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.bytes)) != hipSuccess)
             return bail(e, "hipFuncSetAttribute(dynamic LDS)");
@@ -1626,6 +1762,7 @@ void s2s_destroy(s2s_handle* h) {
     free_scratch(h, h->ws_offs);
     free_scratch(h, h->ws_svb);
     if (h->gen.ws) (void)hipFree(h->gen.ws);
+    if (h->ev_ws) (void)hipFree(h->ev_ws);
     if (h->slab) (void)hipFree(h->slab);
     if (h->d_diag) (void)hipFree(h->d_diag);
     delete h;
@@ -1692,6 +1829,131 @@ static int predict_impl(s2s_handle* h, void* stream_, const uint8_t* bases, cons
             ev.chunks = n;
             h->events.push_back(ev);
         }
+    }
+    HIP_TRY(h, hipGetLastError());
+    return S2S_OK;
+}
+
+// s2s_evaluate_chunks on the generic pipeline: predict_generic's stages with the teacher-forced embed / heads / emit kernels
+// (s2s_generic.h); gen_lenreg_kernel reads the measured dwell.  y [B][ts], sigma / conc / rate [B][te] (the caller's slice).
+static int evaluate_generic(s2s_handle* h, hipStream_t st, const uint8_t* kmers, const int32_t* dwell, int32_t B, float* y, float* sigma,
+                            float* conc, float* rate) {
+    s2s_handle::Generic& G = h->gen;
+    const int d = G.d, dff = G.dff, k = h->cfg.seq_kmer, te = G.te, ts = G.ts;
+    const size_t big_w = (size_t)(3 * d > dff ? 3 * d : dff), tb = te > ts ? te : ts;
+    const int want = B < G.slice_max ? B : G.slice_max;
+    if (want > G.ws_chunks) {                 // (as predict_generic)
+        HIP_TRY(h, hipStreamSynchronize(st));
+        if (G.ws) (void)hipFree(G.ws);
+        G.ws = nullptr; G.ws_chunks = 0;
+        const size_t n = want;
+        const size_t floats = up64(n * te * d) + up64(n * te) + up64(n * ts * d) + up64(n * ts) + up64(n * tb * big_w);
+        HIP_TRY(h, hipMalloc(&G.ws, floats * sizeof(float)));
+        G.ws_chunks = want;
+    }
+    const size_t S = G.ws_chunks;
+    float* XE = G.ws;
+    float* XD = XE + up64(S * te * d) + up64(S * te);
+    float* SE = XD + up64(S * ts * d);
+    float* BIG = SE + up64(S * ts);
+    const float* W = h->d_arena;
+    for (int64_t s = 0; s < B; s += S) {
+        const int n = (int)((B - s < (int64_t)S) ? (B - s) : (int64_t)S);
+        const int Me = n * te, Md = n * ts;
+        const long long tot = (long long)Me * d;
+        hipLaunchKernelGGL(gen_embed_kmers_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, W + G.emb_wt, W + G.emb_b, k, d,
+                           kmers + (size_t)s * te * k, n, te, XE);
+        float* cur = XE;
+        for (int i = 0; i < h->cfg.pre_layers; ++i) {
+            float* nxt = cur == XE ? BIG : XE;
+            gen_gemm<1>(st, cur, d, W + G.pre_w[i], W + G.pre_b[i], nxt, d, nullptr, Me, d, d);
+            cur = nxt;
+        }
+        if (cur != XE) HIP_TRY(h, hipMemcpyAsync(XE, cur, (size_t)Me * d * sizeof(float), hipMemcpyDeviceToDevice, st));
+        gen_gemm<1>(st, XE, d, W + G.w0cat, W + G.b0cat, BIG, 3 * d, nullptr, Me, 3 * d, d);
+        float* sg = sigma + (size_t)s * te;
+        hipLaunchKernelGGL(gen_dwell_teacher_kernel, dim3((Me + 3) / 4), dim3(256), 0, st, W, G.heads, G.pe_enc, d, n, BIG, XE, sg,
+                           conc + (size_t)s * te, rate + (size_t)s * te, te);
+        for (int l = 0; l < h->cfg.encoder_layers; ++l) gen_fft_block(st, W, G.enc[l], XE, BIG, n, te, d, dff, G.h_enc);
+        hipLaunchKernelGGL(gen_lenreg_kernel, dim3((Md + 3) / 4), dim3(256), 0, st, W, G.pe_dec, d, n, XE, sg, dwell + (size_t)s * te, XD, SE,
+                           nullptr, te, ts);
+        for (int l = 0; l < h->cfg.decoder_layers; ++l) {
+            if (G.f16)
+                gen_fft_block_h(st, W, G.dec[l], G.dech[l], G.ld_d, G.ld_f, XD, BIG, n, ts, d, dff, G.h_dec);
+            else
+                gen_fft_block(st, W, G.dec[l], XD, BIG, n, ts, d, dff, G.h_dec);
+        }
+        hipLaunchKernelGGL(gen_emit_y_kernel, dim3((Md + 3) / 4), dim3(256), 0, st, W, G.out_w, G.out_b, d, n, XD, y + (size_t)s * ts, ts);
+    }
+    return S2S_OK;
+}
+
+#define S2S_EVAL_SLICE 32768                  // chunks per slice of s2s_evaluate_chunks (its y / sigma / conc / rate scratch)
+
+int s2s_evaluate_chunks(s2s_handle* h, void* stream_, const uint8_t* kmers, const int32_t* dwell, const float* target, const float* stdev,
+                        int32_t B, float* out_loss, float* out_y, const s2s_debug* dbg) {
+    if (!h) return S2S_ERR_ARG;
+    if (B < 0) return fail(h, S2S_ERR_ARG, "B < 0");
+    if (B == 0) return S2S_OK;
+    if (!kmers || !dwell || !target || !stdev || !out_loss) return fail(h, S2S_ERR_ARG, "NULL argument");
+    if (dbg && (dbg->emb_in || dbg->dec_in || dbg->emb_out || dbg->enc_out || dbg->g || dbg->y_scaled || dbg->z01))
+        return fail(h, S2S_ERR_ARG, "s2s_evaluate_chunks writes only dbg->sigma / conc / rate (and y through out_y)");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(h, S2S_ERR_HIP, "hipSetDevice failed");
+    hipStream_t st = static_cast<hipStream_t>(stream_);
+    const int mode = h->cfg.compute_mode, k = h->cfg.seq_kmer;
+    const bool gen = mode_generic(mode);
+    const int te = gen ? h->gen.te : S2S_T_ENC, ts = gen ? h->gen.ts : S2S_T_DEC;
+    const int want = B < S2S_EVAL_SLICE ? B : S2S_EVAL_SLICE;
+    const size_t per = (size_t)ts + 3 * (size_t)te;
+    if (want > h->ev_chunks) {                // grows outside of the steady state only
+        HIP_TRY(h, hipStreamSynchronize(st));
+        if (h->ev_ws) (void)hipFree(h->ev_ws);
+        h->ev_ws = nullptr; h->ev_chunks = 0;
+        HIP_TRY(h, hipMalloc(&h->ev_ws, (size_t)want * per * sizeof(float)));
+        h->ev_chunks = want;
+    }
+    const size_t S = h->ev_chunks;
+    ParamsDev P;
+    std::memset(&P, 0, sizeof P);
+    P.duration_sampling = 1;                  // the heads run; the sampler does not (teacher forcing)
+    EventPair ev{};
+    if (h->profiling) {
+        HIP_TRY(h, hipEventCreate(&ev.a));
+        HIP_TRY(h, hipEventCreate(&ev.b));
+        HIP_TRY(h, hipEventRecord(ev.a, st));
+    }
+    for (int64_t s = 0; s < B; s += S) {
+        const int n = (int)((B - s < (int64_t)S) ? (B - s) : (int64_t)S);
+        auto pick = [&](float* user, size_t row, float* scratch) { return user ? user + (size_t)s * row : scratch; };
+        float* y = pick(out_y, ts, h->ev_ws);
+        float* sg = pick(dbg ? dbg->sigma : nullptr, te, h->ev_ws + S * ts);
+        float* cq = pick(dbg ? dbg->conc : nullptr, te, h->ev_ws + S * ts + S * te);
+        float* rq = pick(dbg ? dbg->rate : nullptr, te, h->ev_ws + S * ts + 2 * S * te);
+        const uint8_t* km = kmers + (size_t)s * te * k;
+        const int32_t* dw = dwell + (size_t)s * te;
+        if (gen) {
+            const int rc = evaluate_generic(h, st, km, dw, n, y, sg, cq, rq);
+            if (rc != S2S_OK) return rc;
+        } else {
+            DebugDev D;
+            std::memset(&D, 0, sizeof D);
+            D.sigma = sg; D.conc = cq; D.rate = rq;
+            const dim3 grid(n < h->n_wg ? n : h->n_wg), block(DEC_WAVES * 64);
+            const bool exact = h->attn_exact && mode != S2S_MODE_F32;
+            auto kern = mode == S2S_MODE_F32 ? s2s_eval_kernel<0, false>
+                        : mode == S2S_MODE_F16 ? (exact ? s2s_eval_kernel<3, true> : s2s_eval_kernel<3, false>)
+                                               : (exact ? s2s_eval_kernel<1, true> : s2s_eval_kernel<1, false>);
+            hipLaunchKernelGGL(kern, grid, block, mode == S2S_MODE_F16 ? Fused<3>::LDS : mode == S2S_MODE_F16X3 ? Fused<1>::LDS : Fused<0>::LDS,
+                               st, h->model, h->d_arena, km, dw, n, P, h->handoff, y, D);
+        }
+        hipLaunchKernelGGL(s2s_eval_loss_kernel, dim3((n + 3) / 4), dim3(256), 0, st, y, target + (size_t)s * ts, sg, stdev + (size_t)s * te,
+                           cq, rq, dw, n, te, ts, out_loss + (size_t)s * 3);
+    }
+    if (h->profiling) {
+        HIP_TRY(h, hipEventRecord(ev.b, st));
+        ev.chunks = B;
+        h->events.push_back(ev);
     }
     HIP_TRY(h, hipGetLastError());
     return S2S_OK;

@@ -179,6 +179,35 @@ class Engine:
         self._check(rc, "s2s_predict_chunks")
         return out
 
+    # ------------------------------------------------------------------ evaluate
+    def evaluate_chunks(self, kmers: torch.Tensor, dwell: torch.Tensor, target: torch.Tensor, stdev: torch.Tensor,
+                        want_y: bool = False, debug: bool = False):
+        """The teacher-forced pass of validation_step + get_loss (model.py:107-143, 419-480) on the GPU (s2s_evaluate_chunks).
+        kmers uint8 [B,t_enc,k] (letters, onehot_to_kmers), dwell int32 [B,t_enc] >= 0 (measured samples per k-mer), target float32
+        [B,t_dec] and stdev float32 [B,t_enc] (both already divided by scaling_max_value), all contiguous on the engine's device ->
+        dict(loss float32 [B,3]: per chunk sum (y - target)^2, sum -log_prob(max(dwell, 1)), sum (stdev - sigma)^2
+        [, y [B,t_dec]] [, sigma / conc / rate [B,t_enc]]).  Every chunk's sums are independent of B and of its neighbours."""
+        B = int(kmers.shape[0])
+        T_ENC, T_DEC = self.t_enc, self.t_dec
+        for name, t, dt, shape in (("kmers", kmers, torch.uint8, (B, T_ENC, self.k)), ("dwell", dwell, torch.int32, (B, T_ENC)),
+                                   ("target", target, torch.float32, (B, T_DEC)), ("stdev", stdev, torch.float32, (B, T_ENC))):
+            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f"{name} must be contiguous {dt} {shape} on {self.device}")
+        f = dict(dtype=torch.float32, device=self.device)
+        out = {"loss": torch.empty(B, 3, **f)}
+        if want_y:
+            out["y"] = torch.empty(B, T_DEC, **f)
+        dbg = None
+        if debug:
+            out.update(sigma=torch.empty(B, T_ENC, **f), conc=torch.empty(B, T_ENC, **f), rate=torch.empty(B, T_ENC, **f))
+            dbg = _lib.S2SDebug()
+            dbg.sigma, dbg.conc, dbg.rate = (out[n].data_ptr() for n in ("sigma", "conc", "rate"))
+        with torch.cuda.device(self.device):
+            rc = _lib.lib().s2s_evaluate_chunks(self._h, self._stream(), _ptr(kmers), _ptr(dwell), _ptr(target), _ptr(stdev), B,
+                                                _ptr(out["loss"]), _ptr(out.get("y")), C.byref(dbg) if dbg else None)
+        self._check(rc, "s2s_evaluate_chunks")
+        return out
+
     def predict_packed(self, read_bytes: torch.Tensor, chunk_start: torch.Tensor, n_valid: torch.Tensor,
                        params: PredictParams, first_global_chunk: int = 0):
         """Chunks addressed inside a packed read buffer (chunker.pack_reads): read_bytes uint8 [N], chunk_start int64

@@ -2,7 +2,7 @@
 (model.py:25-63, 195-307) without Lightning, with `predict_step` running on the HIP engine.
 
 Same constructor keywords, same attributes (`results`, `total_samples`, `out_writer`, `hparams.config`),
-same methods (`predict_step`, `export_and_clear_results`, `on_predict_epoch_end`), same writer
+same methods (`predict_step`, `export_and_clear_results`, `on_predict_epoch_end`, and `validation_step`'s losses), same writer
 hand-off (`writer.signals = {read_id: 1-D fp32 tensor}; writer.save()`).  Training is out of scope.
 """
 import logging
@@ -114,6 +114,17 @@ class seq2squiggle:
         if isinstance(self.out_writer, BLOW5Writer) and self.total_samples >= self.export_every_n_samples:
             self.export_and_clear_results(keep_last=True)
             self.total_samples = 0
+
+    def validation_step(self, batch, batch_idx: int = 0):
+        """The first (teacher-forced) pass of model.py:107-143 and get_loss (:419-480) on the engine, for a reference-shaped batch
+        (data, targets, data_ls, targets_ls, noise_std, ...): data one-hot [B,te,k,5] or [B,te,5k], targets [B,ts(,1)] and noise_std
+        [B,te] already divided by scaling_max_value (ChunkDataSetMemmap.__getitem__), data_ls [B,te] samples per k-mer.  -> the
+        four losses get_loss logs for this batch, {"valid_signal_loss", "valid_duration_loss", "valid_noise_loss",
+        "valid_total_loss"} as floats.  No plots are drawn, and the second (predicted-duration) pass, which feeds only them, is not run."""
+        from .evaluate import evaluate_batch, finalize
+        data, targets, data_ls, targets_ls, noise_std, *_ = batch
+        r = evaluate_batch(self.engine, data, data_ls, targets, noise_std)
+        return finalize(r["loss"].cpu().numpy(), self.engine.t_enc, self.engine.t_dec)
 
     def export_and_clear_results(self, keep_last: bool = True):
         """model.py:253-302: merge the per-batch dicts, hold back the last read while batches are still coming,

@@ -14,6 +14,12 @@ as the last leg that touches a GPU so that nothing it does can cost a measuremen
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py ...`), before
 anything in the parent has touched the GPU, relays rank 0's JSON line and exits with the children's code.
 
+A plain run does only what the headline needs: set up, warm up, time the steps, write --dump-outputs, print the line (its roofline
+object is the timed launches' own kernel time and counters, beside constants from committed profiles).  Everything that takes runs
+of its own -- the reference-batch rate, the CPU baseline with its live parity check, the end-to-end runs, power, the k = 6 workload,
+weight sensitivity, the f16 mode; at N > 1 the sharded end-to-end leg, the CPU baseline and the RCCL self-test -- runs after the timed
+region, and only with --full.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -948,7 +954,12 @@ def main():
                     help="reads per GPU and step: config2 = 1000 x 5 kb (BASELINE configs[1]), config3 = 12500 x 5 kb "
                          "(configs[2]: each GPU's share of 100,000 reads over 8)")
     ap.add_argument("--reads", type=int, default=None, help="override the workload's reads per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the secondary legs: N = 1: the reference-batch rate, CPU baseline with its "
+                         "parity check, end-to-end runs, power, the k = 6 workload, weight sensitivity, the f16 mode; N > 1: the "
+                         "sharded end-to-end leg, the CPU baseline, the RCCL self-test")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave out the legs that a plain run leaves out (the RCCL self-test still runs at N > 1)")
     ap.add_argument("--dry-launch", action="store_true", help="print the child command --gpus N would start, run nothing")
     ap.add_argument("--launch-selftest", action="store_true",
                     help="CPU-only pass through the multi-rank plumbing of the line (host group, device identities, RCCL self-test, "
@@ -973,6 +984,7 @@ def main():
         print(json.dumps({"rccl_selftest": rccl_selftest(a.rccl_selftest_only, a.rccl_selftest_limit)}))
         return
     n_reads = a.reads if a.reads is not None else WORKLOADS[a.workload]
+    legs = a.full and not a.no_cpu_baseline                # the secondary legs after the timed region (--launch-selftest: its own rule)
 
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -1078,10 +1090,10 @@ def main():
     ranks_seen = host.size()
     per_rank = [float(x) for x in host.gather(B * a.steps / own)]
     emitted = int((sig != 0).sum().item())
-    # the reference's default batch (1024 chunks per call), reported for transparency only; skipped with
-    # --no-cpu-baseline so that a rocprofv3 --stats of that command averages the bench launches alone
+    # the reference's default batch (1024 chunks per call), reported for transparency only; --full only, so that a rocprofv3 --stats
+    # of a plain run averages the bench launches alone
     small_rate = None
-    if world == 1 and not a.no_cpu_baseline:
+    if world == 1 and legs:
         small, reps = 1024, 200
         b1, n1, s1, d1 = bases_d[:small].contiguous(), nv_d[:small].contiguous(), sig[:small], dur[:small]
         for i in range(reps + 3):
@@ -1134,8 +1146,8 @@ def main():
                            "f16": "REDUCED PRECISION (outside the 1e-4 pA parity bound): decoder operands rounded to f16 once, one "
                                   "f16 MFMA product per product, fp32 accumulate; frontend f16x3"}.get(
                 a.mode, "every operand split into two f16 halves, three f16 MFMA products per product, fp32 accumulate: "
-                        "fp32-class accuracy, see cpu_baseline.parity"),
-            "data": "synthetic",
+                        "fp32-class accuracy, see cpu_baseline.parity (--full)"),
+            "data": "synthetic", "full": a.full,
             "config": {"mode": a.mode, "workload": f"{n_reads} synthetic reads x {READ_LEN} nt per GPU ({B} chunks/step/GPU), "
                                    "default noise+duration samplers, synthetic k=9 checkpoint",
                        "chunks_per_step_per_gpu": B, "profile": "dna-r10-prom", "seed": 42},
@@ -1162,7 +1174,7 @@ def main():
             print(f"bench.py: {name} failed: {type(e).__name__}: {e}", file=sys.stderr)
 
     sharded_failed = False
-    if host.dist and not a.no_cpu_baseline:
+    if host.dist and legs:
         sharded = None
         try:
             sharded = end_to_end_sharded(a.mode, host.dist, rank, world, dev)
@@ -1181,7 +1193,7 @@ def main():
         if rank == 0:
             line.write()
         os._exit(0)
-    if rank == 0 and not a.no_cpu_baseline:
+    if rank == 0 and legs:
         if world == 1:
             leg("end_to_end", end_to_end, a.mode)
         # (N > 1: rank 0 alone, on the node's whole CPU share, while the others wait at the host barrier below)
@@ -1199,7 +1211,7 @@ def main():
     selftest_clean = 1.0
     try:
         host.barrier()                                         # (N > 1: the others waited here while rank 0 ran its legs)
-        if world > 1:
+        if world > 1 and a.full:
             # RCCL, reported: the LAST thing that touches the GPUs, in processes of their own (rank 0 starts them, the others wait at the
             # host barrier inside rccl_leg): whatever it does to a device, every other field of the line has been measured by now
             try:

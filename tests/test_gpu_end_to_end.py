@@ -195,9 +195,9 @@ def test_cli_pod5_output_equals_blow5_output(tmp_path):
 
 
 def test_bench_contract_line():
-    """bench.py prints ONE JSON line with the driver's keys, the roofline object and (at N=1) the CPU baseline."""
+    """bench.py --full prints ONE JSON line with the driver's keys, the roofline object and (at N=1) the CPU baseline."""
     import json
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--reads", "60"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--reads", "60", "--full"],
                        cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -245,6 +245,24 @@ def test_bench_steps_and_dumped_outputs(tmp_path):
     assert sig.dtype == dur.dtype == np.float32 and sig.shape == (bases.shape[0], 250)
     assert np.array_equal(sig, out["signal"].cpu().numpy()) and np.array_equal(dur, out["dur"].cpu().numpy().astype(np.float32))
     eng.close()
+
+
+def test_plain_bench_runs_only_the_headline():
+    """Without --full the bench sets up, warms up, times its steps and prints the line: the headline fields and the roofline of
+    the timed launches are there, none of the secondary legs ran."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--reads", "60"],
+                       cwd=ROOT, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["full"] is False and d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["unit"] == "samples/s" and d["higher_is_better"] is True and d["dtype"] == "f16x3"
+    assert d["roofline"]["launches"] == 2 and d["roofline"]["avg_launch_ms"] > 0
+    assert d["chunks_per_sec_at_reference_batch_1024"] is None
+    for key in ("cpu_baseline", "gpu_over_cpu", "end_to_end", "power", "config4_k6", "weight_sensitivity", "reduced_precision",
+                "end_to_end_sharded", "rccl_selftest", "secondary_legs_timed_out"):
+        assert key not in d, key
 
 
 def test_rna_profile_streaming_equals_reference_flow(tmp_path):
@@ -414,7 +432,7 @@ def test_rank_shards_in_read_mode_skip_dropped_reads(tmp_path):
 
 
 def test_two_ranks_on_one_gpu_bench_rehearsal(tmp_path):
-    """`bench.py --gpus 2` exactly as the driver starts it (children of an untouched parent, torchrun rendezvous on
+    """`bench.py --gpus 2 --full` exactly as the driver starts it (children of an untouched parent, torchrun rendezvous on
     127.0.0.1), rehearsed on this box's ONE GPU (S2S_BENCH_ONE_GPU: both ranks on cuda:0; the barrier is a host group at any N).  It cannot measure scaling (the ranks share the GPU) but it runs everything the 8-GPU line will run:
     the N > 1 code path of the timed loop, the sharded end-to-end leg (each rank: FASTA parse, native sampler skip-ahead,
     its read shard, cpu_share() = quota / LOCAL_WORLD_SIZE threads, its own shard file) and the max-over-ranks timing.
@@ -422,8 +440,8 @@ def test_two_ranks_on_one_gpu_bench_rehearsal(tmp_path):
     least 70 % of what one rank moves end to end (a host-side collapse under halved thread counts would show here)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env["S2S_BENCH_ONE_GPU"] = "1"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--reads", "500"],
-                       cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--reads", "500",
+                        "--full"], cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1

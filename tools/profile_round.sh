@@ -2,11 +2,12 @@
 # Everything profiles/rNN holds, in one GPU-box call: tools/profile_round.sh <tag>
 #   gpurun_out/<tag>/stats_{f16x3,f32}: rocprofv3 --kernel-trace --stats of bench.py --steps 3 (+ the bench line it printed)
 #   gpurun_out/<tag>/pmc_{f16x3,f32}:   the PMC passes of tools/pmc_run.sh
-#   gpurun_out/<tag>/bench_f16x3.json:  the plain default bench line (CPU baseline + end-to-end included)
+#   bench_f16x3.json in the same tag directory:  the bench line with --full (CPU baseline + end-to-end included)
 #   gpurun_out/<tag>/power_<mode>.txt:   rocm-smi power / clock samples under the kernel (tools/power_probe.sh)
 R=${GRAFT_REPO_ROOT:-/root/repo}
 T=$1
 mkdir -p $R/gpurun_out/$T
+OUT=$_                     # (the tag directory just made: every output of this call lands there)
 cd /tmp && export TMPDIR=/tmp
 for m in f16x3 f32; do
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/$T/stats_$m -o s -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --mode $m > $R/gpurun_out/$T/bench_${m}_under_rocprof.json 2> $R/gpurun_out/$T/stats_$m.err
@@ -15,7 +16,7 @@ done
 # the exact attention instance (s2s_fused_kernel<1, false, true>) forced on the same workload: kernel stats only
 S2S_ATTENTION_PATH=exact timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/$T/stats_f16x3_exact -o s -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --mode f16x3 > $R/gpurun_out/$T/bench_f16x3_exact_under_rocprof.json 2> $R/gpurun_out/$T/stats_f16x3_exact.err
 S2S_ATTENTION_PATH=exact bash $R/tools/pmc_run.sh $T/pmc_f16x3_exact --mode f16x3
-cd $R && python3 bench.py > gpurun_out/$T/bench_f16x3.json 2> gpurun_out/$T/bench_f16x3.err
+cd $R && timeout -k 10 900 python3 bench.py --full > $OUT/bench_f16x3.json 2> $OUT/bench_f16x3.err
 python3 tools/pmc_summarize.py f32=gpurun_out/$T/pmc_f32:65520 f16x3=gpurun_out/$T/pmc_f16x3:65520 f16x3_exact=gpurun_out/$T/pmc_f16x3_exact:65520 > gpurun_out/$T/pmc_summary.json
 # the un-profiled diagnostic build: per-wave phase stamps + the clock the SIMDs held (s_memtime / s_memrealtime)
 S2S_DIAG_HEAT=3 python3 tools/diag_phases.py f16x3 > gpurun_out/$T/diag_phases.txt 2>&1

@@ -8,7 +8,7 @@
 cd ${GRAFT_REPO_ROOT:-$(dirname "$0")/..}
 N=${1:-5}; out=${2:-gpurun_out/rehearsal}; mkdir -p $out
 echo "NOT A SCALING MEASUREMENT: $N ranks on ONE GPU (host-side rehearsal of the multi-GPU paths)" | tee $out/README.txt
-S2S_BENCH_ONE_GPU=1 timeout -k 10 900 python bench.py --gpus $N --steps 3 --warmup 1 > $out/bench_${N}ranks_one_gpu.json 2> $out/bench_${N}ranks_one_gpu.err || { echo "bench --gpus $N failed"; tail -5 $out/bench_${N}ranks_one_gpu.err; exit 1; }
+S2S_BENCH_ONE_GPU=1 timeout -k 10 900 python bench.py --gpus $N --steps 3 --warmup 1 --full > $out/bench_${N}ranks_one_gpu.json 2> $out/bench_${N}ranks_one_gpu.err || { echo "bench --gpus $N failed"; tail -5 $out/bench_${N}ranks_one_gpu.err; exit 1; }
 python - $out/bench_${N}ranks_one_gpu.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

@@ -52,12 +52,8 @@ struct DebugDev {
 // signalling NaN first (v_max_f32 x, x, x), which it cannot rule out for a value that comes out of an MFMA: 590 such
 // instructions in the f16x3 kernel, 256 of them per wave and chunk in the FFN loops.  Same bits for every non-NaN input.
 __device__ __forceinline__ float relu1(const float x) {
-#ifdef S2S_RELU_FMAX
-    return fmaxf(x, 0.0f);
-#else
     const int i = __builtin_bit_cast(int, x);
     return __builtin_bit_cast(float, i > 0 ? i : 0);
-#endif
 }
 
 #ifdef S2S_DIAG

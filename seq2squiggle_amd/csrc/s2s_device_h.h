@@ -23,15 +23,7 @@ typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 // Fast softmax path: the shift is the pass-0 max plus this many log2 units, so the f16 window of P_hi is 2^18 above
 // the pass-0 max instead of 2^16 (fewer safe-path redos).  The largest P is then >= 2^-2, whose lo half is still a normal
 // f16: measured distance to the fp64 oracle is unchanged up to 4 and grows from 6 (tools/cmp_mae.sh).
-#ifndef S2S_SHIFT_BIAS
-#define S2S_SHIFT_BIAS 2.0f
-#endif
-#ifndef S2S_ALWAYS_RESCALE
-#define S2S_ALWAYS_RESCALE 0
-#endif
-#ifndef S2S_FFN_LDS
-#define S2S_FFN_LDS 1           // decoder FFN weights staged once per workgroup in the dead K/V region (0: every wave streams them from L2)
-#endif
+static constexpr float S2S_SHIFT_BIAS = 2.0f;
 #define S2S_PF_FLOATS (1024 + 16 + 16)   // one frontend -> decoder hand-off slot (s2s_hip.hip: S2S_SLOT_FLOATS)
 #define S2S_Z2_FLOATS (256 + 64)         // a second all-zeros V^T row (264 halves) + room to start it on 16-byte bank slot 4: see vp in fft_block_h
 #define S2S_PROG_INTS 16                 // per-wave progress counters of the attention loop (prio_balance), behind the small vectors
@@ -50,35 +42,10 @@ typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 #define SB_GEMM()
 #endif
 #define MFMAH(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16((a), (b), (c), 0, 0, 0)
-#ifndef S2S_ATT32
-#define S2S_ATT32 1
-#endif
-#ifndef S2S_ATT32_MSLOT
-#define S2S_ATT32_MSLOT 1
-#endif
-#ifndef S2S_PRIO_MODE
-#define S2S_PRIO_MODE 4      // 4: the two waves of a SIMD balance their progress through the attention loop (prio_balance); 0: off (A/B builds)
-#endif
-#ifndef S2S_ONLINE2
-#define S2S_ONLINE2 1           // the exact instance runs softmax_pv32_online (0: the fast instance's out-of-line fallback, A/B)
-#endif
-#ifndef S2S_FAST_HI_MAX
-#define S2S_FAST_HI_MAX 1       // the fast path's pass 0 takes its row maxima from the first score MFMA alone (0: from the full score; + 1.05 %, same MAE)
-#endif
-#ifndef S2S_ONLINE_HI_MAX
-#define S2S_ONLINE_HI_MAX 1     // softmax_pv32_online takes a pass's row maxima from the FIRST score MFMA alone (0: from the full score, A/B)
-#endif
-#ifndef S2S_INT_SHIFT
-#define S2S_INT_SHIFT 1         // softmax_pv32_online rounds its shift UP to an integer: one f16 half carries it -- no lo half, no re-encoding (round 6:
-                                // 201.6 k -> 200.25 k cycles per chunk at the same clock, + 0.8 % chunks/s, MAE unchanged; 0: the two-half shift, A/B)
-#endif
 #ifndef S2S_MFMA_SPLIT
 #define S2S_MFMA_SPLIT 0        // 1: the lo half of P comes from the matrix pipe (pv_split_mfma below) instead of v_fma_mix.  Round 6, same-box A/B
                                 // (profiles/r06/ab_mfma_split.txt): 190.2 k -> 180.5 k cycles per chunk (exact: 201.6 k -> 191.2 k), MAE unchanged -- and the
                                 // clock under the kernel falls from 2.29 to 2.18 GHz: the same chunks per second to 0.1 %.  The kernel is ENERGY bound.
-#endif
-#ifndef S2S_ONE_ZEROS_ROW
-#define S2S_ONE_ZEROS_ROW 0     // 1: round 2's single zeros row (2-way LDS bank conflict on every V read; kept for the counter A/B)
 #endif
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define MFMAW(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16((a), (b), (c), 0, 0, 0)
@@ -145,7 +112,7 @@ __device__ __forceinline__ void split4(const f32x4 t, const float one, h4& hi, h
     lo = __builtin_bit_cast(h4, (uv2{l0, l1}));
 }
 
-// Key ORDER inside the decoder's K and V^T images (ATT32 layout): the blocks of four consecutive keys are dealt out over the
+// Key ORDER inside the decoder's K and V^T images: the blocks of four consecutive keys are dealt out over the
 // four 64-key passes of the attention loop -- pass j holds the key blocks b = j (mod 4), i.e. keys 4j .. 4j+3, 16+4j .., 32+4j ..
 // -- so that pass 0, whose row maxima are the fast path's softmax shift, is a sample of the WHOLE row instead of its first 64
 // keys.  A softmax does not care about the order of its keys; the images are written in this order (an address, nothing
@@ -174,28 +141,25 @@ __device__ __forceinline__ void att32_mask_tile(f32x16& t, const int tile, const
     }
 }
 
-// LDS of the f16 block: K [head][hi|lo][key][8 d] halves, V^T [head][16 rows: 0-7 hi d, 8-15 lo d][VS keys]
-// halves, and a per-wave scratch for the Q^T operand re-layout.
+// LDS of the decoder's f16 block: K [head][hi|lo][key][8 d] halves, V^T [head][16 rows: 0-7 hi d, 8-15 lo d][VS keys] halves,
+// the constant rows, and a per-wave scratch for the Q^T operand re-layout.  The attention core (softmax_pv32) runs on
+// v_mfma_f32_32x32x16_f16 over the wave's two 16-query tiles and all 16 key tiles, which is the only shape this layout serves.
 template <int NQ, int WAVES, int NKT = 16> struct AttnLdsH {
+    static_assert(NQ == 2 && NKT == 16, "the 32x32x16 attention core: 32 queries per wave, 256 keys");
     static constexpr int KEYS = 16 * NKT;
     static constexpr int K_BYTES = 8 * 2 * KEYS * 8 * 2;
-    // halves per V^T row.  NKT even (the decoder): a row is stored as [32-key block][lane group g][8 halves] -- the 4 keys 4g..4g+3 of
-    // the block's first tile, then those of its second -- so the P.V operand of a K = 32 block is ONE ds_read_b128 per lane;
-    // 272 halves = 136 dwords == 8 (mod 64) makes the 16 lanes of every b128 lane group hit 16 distinct 4-dword bank slots.
-    // (The natural key order needed two b64 reads, which hipcc fuses into ds_read2_b64: banked mod 32, 2-way conflicts on
-    // every access -- the 11,264 SQ_LDS_BANK_CONFLICT cycles per chunk of profiles/r01.)  Odd NKT: natural order.
-    static constexpr bool V128 = (NKT % 2) == 0;
-    // ATT32 (the decoder with S2S_ATT32): the attention core runs on v_mfma_f32_32x32x16_f16 (softmax_pv32).  A V^T row is then
-    // stored as [16-key step][lane half h][8 halves] -- keys 4h..4h+3 and 8+4h..8+4h+3 of the step: the 8 k-slots a lane half feeds
-    // -- 264 halves = 132 dwords == 4 (mod 64): V^T row r lands in 16-byte bank slot r mod 16, so the 16 data rows of a head never collide
-    // (the constant rows the other lanes read are placed per lane group: see vp in fft_block_h).  Constant rows follow the V region (all ones: the A-operand row that makes the MFMA add up P; all zeros: rows 17-31 of that
-    // operand and the unused k-slots of the second Q operand; {1, 1, 0, 0, 0, 0, 0, 0} repeated: the k-slots of the second score
-    // MFMA's A operand that take the softmax shift), written once per kernel (att32_consts).
-    static constexpr bool ATT32 = S2S_ATT32 && NQ == 2 && NKT == 16;
-    static constexpr int VS = ATT32 ? KEYS + 8 : V128 ? KEYS + 16 : KEYS + 8;
+    // halves per V^T row.  A row is stored as [16-key step][lane half h][8 halves] -- keys 4h..4h+3 and 8+4h..8+4h+3 of the step:
+    // the 8 k-slots a lane half feeds -- so the P.V operand of a step is ONE ds_read_b128 per lane; 264 halves = 132 dwords == 4
+    // (mod 64): V^T row r lands in 16-byte bank slot r mod 16, so the 16 data rows of a head never collide (the constant rows the
+    // other lanes read are placed per lane group: see vp in fft_block_h).  (Round 1's natural key order needed two b64 reads, which
+    // hipcc fused into ds_read2_b64: banked mod 32, 2-way conflicts on every access -- the 11,264 SQ_LDS_BANK_CONFLICT cycles per
+    // chunk of profiles/r01.)  Constant rows follow the V region (all ones: the A-operand row that makes the MFMA add up P; all
+    // zeros: rows 17-31 of that operand and the unused k-slots of the second Q operand; {1, 1, 0, 0, 0, 0, 0, 0} repeated: the
+    // k-slots of the second score MFMA's A operand that take the softmax shift), written once per kernel (att32_consts).
+    static constexpr int VS = KEYS + 8;
     static constexpr int V_BYTES = 8 * 16 * VS * 2;
     static constexpr int C_ROWS = 3;                               // rows: ones | zeros | {1, 1, 0, 0, 0, 0, 0, 0} repeated (a second zeros row: S2S_Z2_*)
-    static constexpr int C_BYTES = ATT32 ? C_ROWS * VS * 2 : 0;
+    static constexpr int C_BYTES = C_ROWS * VS * 2;
     static constexpr int Q_WAVE_BYTES = NQ * 2 * 2 * 16 * 8 * 2;
     static constexpr int BYTES = K_BYTES + V_BYTES + C_BYTES + WAVES * Q_WAVE_BYTES;
 };
@@ -255,120 +219,7 @@ __device__ __forceinline__ void linear64_h(const float* __restrict__ wu, const f
     }
 }
 
-// Softmax(Q K^T) V of one head for this wave's NQ query tiles: sums of V.P (oH: P_hi, oL: P_lo; rows 0-7 against V_hi,
-// rows 8-15 against V_lo) and of P (lH, lL), over NH passes of HK key tiles.  Pass 0 subtracts its own column max; later
-// passes get "score - m" straight out of the MFMA (the accumulator starts at -m).
-//   SAFE = false (fast): m stays the pass-0 max (+ S2S_SHIFT_BIAS) and later passes compute no max at all.  Softmax is
-//     shift-invariant, so this is exact as long as no later score beats m by the f16 range of P_hi; if one does, the
-//     row sum turns inf/NaN, which the caller checks once per head, and then runs
-//   SAFE = true (rare): a textbook online softmax, the running max raised and the sums rescaled in every pass.
-template <int NQ, int NKT, int TV, bool SAFE, bool LO = true>
-__device__ __forceinline__ void softmax_pv(const _Float16* __restrict__ kp, const _Float16* __restrict__ vp, const h8 (&qb)[NQ],
-                                           const h8 ones, const float one, const int g, f32x4 (&oH)[NQ], f32x4 (&oL)[NQ],
-                                           f32x4 (&lH)[NQ], f32x4 (&lL)[NQ]) {
-    constexpr int NH = (NKT >= 16) ? 4 : 1, HK = NKT / NH, HB = (HK + 1) / 2;
-    f32x4 negm[NQ];
-    float m[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-        oH[q] = f32x4{0, 0, 0, 0}; oL[q] = f32x4{0, 0, 0, 0};
-        lH[q] = f32x4{0, 0, 0, 0}; lL[q] = f32x4{0, 0, 0, 0};
-        negm[q] = f32x4{0, 0, 0, 0};
-        m[q] = 0.0f;
-    }
-#pragma unroll
-    for (int h2 = 0; h2 < ((S2S_ABL & 256) ? 1 : NH); ++h2) {
-        h8 ka[HK], va[HB];
-#pragma unroll
-        for (int kt = 0; kt < HK; ++kt) ka[kt] = *reinterpret_cast<const h8*>(kp + 16 * (h2 * HK + kt) * 8);
-#pragma unroll
-        for (int kb = 0; kb < HB; ++kb) {
-            if (AttnLdsH<NQ, 1, NKT>::V128) {              // (vp already points at this lane group's 8 halves of block 0)
-                va[kb] = *reinterpret_cast<const h8*>(vp + 32 * (h2 * HB + kb));
-            } else {
-                const h4 v0 = *reinterpret_cast<const h4*>(vp + 16 * (h2 * HK + 2 * kb));
-                h4 v1 = h4{0, 0, 0, 0};                    // a K = 32 block past the last key tile: zero keys
-                if (2 * kb + 1 < HK) v1 = *reinterpret_cast<const h4*>(vp + 16 * (h2 * HK + 2 * kb + 1));
-                va[kb] = h8{v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-            }
-        }
-        SB_ATT();
-        // all NQ time tiles go through a pass together, so that one tile's MFMAs can run
-        // beside the other's exponentials inside the same wave
-        f32x4 s[NQ][HK];
-#pragma unroll
-        for (int q = 0; q < NQ; ++q)
-#pragma unroll
-            for (int kt = 0; kt < HK; ++kt)
-                s[q][kt] = (S2S_ABL & 1024) ? (negm[q] + __builtin_bit_cast(f32x4, ka[kt])) : (h2 == 0) ? MFMAH(ka[kt], qb[q], (f32x4{0, 0, 0, 0})) : MFMAH(ka[kt], qb[q], negm[q]);
-        if (TV < 16 * NKT && h2 == NH - 1) {       // phantom keys -> -inf (only the last key tile has any)
-#pragma unroll
-            for (int q = 0; q < NQ; ++q)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    if (16 * (NKT - 1) + 4 * g + r >= TV) s[q][HK - 1][r] = -__builtin_inff();
-        }
-        if (h2 == 0 || SAFE) {
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) {
-                float mh = s[q][0][0];
-                if (!(S2S_ABL & 32)) {
-#pragma unroll
-                    for (int kt = 0; kt < HK; ++kt)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) mh = fmaxf(mh, s[q][kt][r]);
-                    mh = max_g(mh);
-                }
-                if (h2 == 0) {
-                    if (!SAFE) mh += S2S_SHIFT_BIAS;
-                    m[q] = mh;
-                    negm[q] = f32x4{-mh, -mh, -mh, -mh};
-                    // "score - m" comes from the matrix cores again: 8 issue cycles per tile instead of four subtractions (16)
-                    if (!SAFE && !(TV < 16 * NKT && NH == 1)) {
-#pragma unroll
-                        for (int kt = 0; kt < HK; ++kt) s[q][kt] = MFMAH(ka[kt], qb[q], negm[q]);
-                    } else {                                      // (a single-pass block has already masked its phantom keys in s)
-#pragma unroll
-                        for (int kt = 0; kt < HK; ++kt) s[q][kt] -= mh;
-                    }
-                } else {                              // safe attempt: raise the running max, rescale the sums
-                    const float delta = fmaxf(mh, 0.0f);
-                    const float alpha = __builtin_amdgcn_exp2f(-delta);
-                    oH[q] *= alpha; lH[q] *= alpha;
-                    if (LO) { oL[q] *= alpha; lL[q] *= alpha; }
-                    m[q] += delta;
-                    negm[q] = f32x4{-m[q], -m[q], -m[q], -m[q]};
-#pragma unroll
-                    for (int kt = 0; kt < HK; ++kt) s[q][kt] -= delta;
-                }
-            }
-        }
-        HL P[NQ][HB];
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-#pragma unroll
-            for (int kb = 0; kb < HB; ++kb) {
-                unsigned h0, h1, h2_ = 0, h3 = 0, l0, l1, l2 = 0, l3 = 0;
-                exp_split4<LO>(s[q][2 * kb], one, h0, h1, l0, l1);
-                if (2 * kb + 1 < HK) exp_split4<LO>(s[q][2 * kb + 1], one, h2_, h3, l2, l3);
-                P[q][kb].hi = __builtin_bit_cast(h8, (uv4{h0, h1, h2_, h3}));
-                P[q][kb].lo = __builtin_bit_cast(h8, (uv4{l0, l1, l2, l3}));
-            }
-#pragma unroll
-            for (int kb = 0; kb < HB; ++kb) {
-                if (S2S_ABL & 512) { asm volatile("" ::"v"(P[q][kb].hi), "v"(P[q][kb].lo)); continue; }
-                oH[q] = MFMAH(va[kb], P[q][kb].hi, oH[q]);  // rows 0-7: V_hi.P_hi, rows 8-15: V_lo.P_hi
-                if (LO) oL[q] = MFMAH(va[kb], P[q][kb].lo, oL[q]);  // rows 0-7: V_hi.P_lo, rows 8-15: V_lo.P_lo
-                if (!(S2S_ABL & 64)) {
-                lH[q] = MFMAH(ones, P[q][kb].hi, lH[q]);    // every row: sum of the P actually used
-                if (LO) lL[q] = MFMAH(ones, P[q][kb].lo, lL[q]);
-                }
-            }
-        }
-    }
-}
-
-// ---- The decoder's attention core on the 32x32x16 MFMA (S2S_ATT32): Softmax(Q K^T) V of one head for the wave's 32 queries.
+// ---- The decoder's attention core on the 32x32x16 MFMA: Softmax(Q K^T) V of one head for the wave's 32 queries.
 // A SIMD issues matrix and vector instructions through one port, a well-spaced MFMA holds it for ~8 cycles whatever its shape
 // (tools/probes/issue_probe.hip), and the attention loop is bound by exactly that port: the 32x32x16 shape does the same flops
 // in half the instructions.  Lane (h = lane >> 5, n = lane & 31); an accumulator tile (f32x16) holds rows (r & 3) + 8 (r >> 2) + 4h
@@ -378,7 +229,12 @@ __device__ __forceinline__ void softmax_pv(const _Float16* __restrict__ kp, cons
 //     -> K_hi.Q_hi + K_lo.Q_hi + K_hi.Q_lo - m in two MFMAs (the SAFE path passes -m as the C operand instead);
 //   P.V (16 keys per MFMA): A rows 0-7 V_hi d, 8-15 V_lo d, 16 ones, 17-31 zeros (constant LDS rows); B = P_hi, then P_lo, into ONE
 //     accumulator: O[d] = row d + row 8+d is an in-lane add and row 16 is the softmax row sum (V_lo.P_lo rides along: 2^-22).
-// 52 MFMAs per head instead of 104, no cross-lane traffic between the score tile and the P.V operand.  SAFE as in softmax_pv.
+// 52 MFMAs per head where round 1's 16x16x32 core took 104, no cross-lane traffic between the score tile and the P.V operand.
+// Pass 0 takes the row maxima; later passes get "score - m" straight out of the MFMAs.
+//   SAFE = false (fast): m stays the pass-0 max (+ S2S_SHIFT_BIAS) and later passes compute no max at all.  Softmax is
+//     shift-invariant, so this is exact as long as no later score beats m by the f16 range of P_hi; if one does, the
+//     row sum turns inf/NaN, which the caller checks once per head, and then runs
+//   SAFE = true (rare): a textbook online softmax, the running max raised and the sums rescaled in every pass.
 __device__ __forceinline__ float max_h(float v) {              // over the two lane halves
     const unsigned u = __float_as_uint(v);
     auto t = __builtin_amdgcn_permlane32_swap(u, u, false, false);
@@ -437,7 +293,7 @@ __device__ __forceinline__ void pv_split_mfma(f32x16 sc, const h8 (&va)[2], cons
         O = MFMAW(va[1], hb1, O);
     }
 }
-template <int TV, bool SAFE, bool LO, bool NATURAL = false>
+template <int TV, bool SAFE, bool LO>
 __device__ __forceinline__ void softmax_pv32(const _Float16* __restrict__ kp, const _Float16* __restrict__ kp2, const _Float16* __restrict__ vp,
                                              const h8 qb1, const h8 qb2, const float one, const int h, f32x16& O,
                                              [[maybe_unused]] const int layer = 0) {
@@ -448,8 +304,8 @@ __device__ __forceinline__ void softmax_pv32(const _Float16* __restrict__ kp, co
     O = zero16;
     auto v_of = [&](const int t, const int st) { return *reinterpret_cast<const h8*>(vp + 16 * (2 * t + st)); };
     auto mask_pass = [&](f32x16 (&t)[2], const int h2) {                  // phantom keys -> -inf (att32_key_at: they sit in tiles 5 and 6)
-        att32_mask_tile<TV, NATURAL>(t[0], 2 * h2, h);
-        att32_mask_tile<TV, NATURAL>(t[1], 2 * h2 + 1, h);
+        att32_mask_tile<TV>(t[0], 2 * h2, h);
+        att32_mask_tile<TV>(t[1], 2 * h2 + 1, h);
     };
     auto pv = [&](const f32x16& t, const h8 (&va)[2]) {                   // O += [V_hi; V_lo; 1] . exp2(t), 16 keys per MFMA
 #pragma unroll
@@ -479,22 +335,17 @@ __device__ __forceinline__ void softmax_pv32(const _Float16* __restrict__ kp, co
                 va[i][0] = v_of(2 * h2 + i, 0); va[i][1] = v_of(2 * h2 + i, 1);
             }
             SB_ATT();
-#if S2S_ATT32_MSLOT
             // the shift rides in the second score MFMA: its A operand carries {1, 1, 0..} instead of K_lo in the upper lane half's
             // k-slots (kp2: a constant LDS row there, the K_hi row below), its B operand {-m_hi, -m_lo, 0..} where Q_lo has none
             h8 kb[2];
 #pragma unroll
             for (int i = 0; i < 2; ++i) kb[i] = *reinterpret_cast<const h8*>(kp2 + (2 * h2 + i) * (h ? 0 : 32 * 8));
             f32x16 sc[2];
-#if S2S_FAST_HI_MAX
             // (pass 0's row maxima need only the first score MFMA, as in softmax_pv32_online: the shift has 2 log2 units of head-room
-            //  and the missing K_hi . Q_lo term is 2^-11 of the score)
+            //  and the missing K_hi . Q_lo term is 2^-11 of the score.  Against maxima from the full score: + 1.05 % chunks/s, same
+            //  MAE, LABNOTES round 5)
 #pragma unroll
             for (int i = 0; i < 2; ++i) sc[i] = h2 == 0 ? MFMAW(ka[i], qb1, zero16) : MFMAW(kb[i], qb2m, MFMAW(ka[i], qb1, zero16));
-#else
-#pragma unroll
-            for (int i = 0; i < 2; ++i) sc[i] = MFMAW(kb[i], qb2m, MFMAW(ka[i], qb1, zero16));
-#endif
             mask_pass(sc, h2);
             if (h2 == 0) {
                 float mh = sc[0][0];
@@ -508,33 +359,10 @@ __device__ __forceinline__ void softmax_pv32(const _Float16* __restrict__ kp, co
                 uv4 q2 = __builtin_bit_cast(uv4, qb2);
                 q2[0] = h ? pk : q2[0];
                 qb2m = __builtin_bit_cast(h8, q2);
-#if S2S_FAST_HI_MAX
                 // (what the maxima were taken from IS the first product of the score: the second MFMA accumulates onto it)
 #pragma unroll
                 for (int i = 0; i < 2; ++i) sc[i] = MFMAW(kb[i], qb2m, sc[i]);
-#else
-#pragma unroll
-                for (int i = 0; i < 2; ++i) sc[i] = MFMAW(kb[i], qb2m, MFMAW(ka[i], qb1, zero16));
-#endif
             }
-#else
-            f32x16 sc[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) sc[i] = scores(ka[i], negm);     // (pass 0: negm = 0)
-            mask_pass(sc, h2);
-            if (h2 == 0) {
-                float mh = sc[0][0];
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) mh = fmaxf(mh, sc[i][r]);
-                mh = max_h(mh) + S2S_SHIFT_BIAS;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) negm[r] = -mh;
-#pragma unroll
-                for (int i = 0; i < 2; ++i) sc[i] = scores(ka[i], negm); // "score - m" from the matrix cores again
-            }
-#endif
 #ifdef S2S_TILEHIST
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
@@ -610,7 +438,7 @@ __device__ __forceinline__ void softmax_pv32(const _Float16* __restrict__ kp, co
 // heads overflow.  As softmax_pv32<TV, SAFE = true> (the fast instance's out-of-line fallback) it measured 221.7 k; as
 // softmax_pv32_online below 209.0 k with every pass's maxima taken from the full score (206.5 k on round 4's device, 211.8 k while
 // the exact instance still shared the fast one's dealt-out key order: the phantom-key masks sat in two passes and the kernel
-// spilled 7 registers), 203.8 k with the maxima from the first score MFMA alone (S2S_ONLINE_HI_MAX, round 5), 201.6 k with the score's second MFMA
+// spilled 7 registers), 203.8 k with the maxima from the first score MFMA alone (round 5), 201.6 k with the score's second MFMA
 // accumulating onto that product instead of both being issued again (bit-identical; the masks applied once).
 // (Round 5 also tried it in two phases -- the row maxima of all eight tiles from that first MFMA, then the fast path's body with the
 // exact shift, no update or rescale in the loop, commit 7131d25: unrolled, hipcc hoists phase 1 to the front and spills 52 registers; as
@@ -627,7 +455,7 @@ __device__ __forceinline__ void softmax_pv32(const _Float16* __restrict__ kp, co
 // softmax_pv32_online: that online softmax with the fast path's operand tricks -- the shift rides in the k-slots of the second
 // score MFMA (no 16-register C operand), a pass's scores are ISSUED AGAIN with the raised shift instead of being lowered by 32
 // subtractions (the matrix pipe has the room), and only accumulator registers 0-8 are rescaled (rows 17-31 of O are zeros).
-template <int TV, bool LO, bool NATURAL>
+template <int TV, bool LO>
 __device__ __forceinline__ void softmax_pv32_online(const _Float16* __restrict__ kp, const _Float16* __restrict__ kp2, const _Float16* __restrict__ vp,
                                                     const h8 qb1, const h8 qb2, const float one, const int h, f32x16& O) {
     constexpr int NT = 8;
@@ -639,7 +467,7 @@ __device__ __forceinline__ void softmax_pv32_online(const _Float16* __restrict__
 #if S2S_MFMA_SPLIT
     const SelA sel = split_selectors(h);
 #endif
-    float m = 0.0f;                                                       // the shift qb2m carries: exactly -(hi + lo)
+    float m = 0.0f;                                                       // the shift qb2m carries (what its f16 half encodes)
 #pragma unroll
     for (int h2 = 0; h2 < NT / 2; ++h2) {
         h8 ka[2], kb[2], va[2][2];
@@ -651,66 +479,39 @@ __device__ __forceinline__ void softmax_pv32_online(const _Float16* __restrict__
         }
         SB_ATT();
         f32x16 sc[2];
-        auto score_pass = [&]() {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) sc[i] = MFMAW(kb[i], qb2m, MFMAW(ka[i], qb1, zero16));
-            att32_mask_tile<TV, NATURAL>(sc[0], 2 * h2, h);               // phantom keys -> -inf (natural key order: tile 7 only)
-            att32_mask_tile<TV, NATURAL>(sc[1], 2 * h2 + 1, h);
-        };
-#if S2S_ONLINE_HI_MAX
         // The shift only has to keep P inside the f16 range and be the SAME in the numerator and the row sum -- it need not be the
         // exact maximum.  The first score MFMA alone ([K_hi | K_lo] . [Q_hi | Q_hi]: everything but K_hi . Q_lo, i.e. the score to
         // 2^-11 of its size, a fraction of a log2 unit) gives the pass's row maxima for half the MFMAs of a full score pass, and
         // unshifted: the new shift is max(old shift, this pass's maximum).
 #pragma unroll
         for (int i = 0; i < 2; ++i) sc[i] = MFMAW(ka[i], qb1, zero16);
-        att32_mask_tile<TV, NATURAL>(sc[0], 2 * h2, h);
-        att32_mask_tile<TV, NATURAL>(sc[1], 2 * h2 + 1, h);
-#else
-        score_pass();
-#endif
+        att32_mask_tile<TV, true>(sc[0], 2 * h2, h);                      // phantom keys -> -inf (natural key order: tile 7 only)
+        att32_mask_tile<TV, true>(sc[1], 2 * h2 + 1, h);
         float mh = sc[0][0];
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) mh = fmaxf(mh, sc[i][r]);
-        mh = max_h(mh);                                                   // the row's maximum over this pass (HI_MAX: absolute; else relative to the shift)
-#if S2S_ONLINE_HI_MAX
+        mh = max_h(mh);                                                   // the row's maximum over this pass (unshifted)
         const float nm = -(h2 == 0 ? mh : fmaxf(m, mh));
-#else
-        const float nm = -(h2 == 0 ? mh : m + fmaxf(mh, 0.0f));
-#endif
-#if S2S_INT_SHIFT
         // (the shift need not be the maximum, only no smaller: rounded up to an integer it fits ONE f16 half -- exactly below 2048,
-        //  and what the half encodes is what is used otherwise -- so the lo half, its subtraction and two conversions go)
+        //  and what the half encodes is what is used otherwise -- so the lo half, its subtraction and two conversions go.  Round 6:
+        //  201.6 k -> 200.25 k cycles per chunk at the same clock, + 0.8 % chunks/s, MAE unchanged)
         const _Float16 nh = (_Float16)(-__builtin_ceilf(-nm));
         const unsigned pk = __builtin_bit_cast(unsigned, (h2v{nh, (_Float16)0.0f}));
         uv4 q2 = __builtin_bit_cast(uv4, qb2);
         q2[0] = h ? pk : q2[0];
         qb2m = __builtin_bit_cast(h8, q2);
         const float m_enc = -(float)nh;
-#else
-        const _Float16 nh = (_Float16)nm;
-        const _Float16 nl = (_Float16)(nm - (float)nh);
-        const unsigned pk = __builtin_bit_cast(unsigned, (h2v{nh, nl}));
-        uv4 q2 = __builtin_bit_cast(uv4, qb2);
-        q2[0] = h ? pk : q2[0];
-        qb2m = __builtin_bit_cast(h8, q2);
-        const float m_enc = -((float)nh + (float)nl);                     // what the two halves encode: exact in fp32
-#endif
         if (h2 > 0) {
             const float f = __builtin_amdgcn_exp2f(m - m_enc);            // (1 for a row whose maximum did not rise)
 #pragma unroll
             for (int r = 0; r < 9; ++r) O[r] *= f;
         }
         m = m_enc;
-#if S2S_ONLINE_HI_MAX
         // the full score = what the maxima were taken from + the second MFMA (K_hi . Q_lo and the shift); the phantom keys stay -inf
 #pragma unroll
         for (int i = 0; i < 2; ++i) sc[i] = MFMAW(kb[i], qb2m, sc[i]);
-#else
-        score_pass();
-#endif
 #if S2S_MFMA_SPLIT
 #pragma unroll
         for (int i = 0; i < 2; ++i) pv_split_mfma<LO>(sc[i], va[i], sel, O);
@@ -730,11 +531,9 @@ __device__ __forceinline__ void softmax_pv32_online(const _Float16* __restrict__
 }
 // the constant rows behind the V region (see AttnLdsH): called once per kernel, before the first barrier
 template <class G> __device__ __forceinline__ void att32_consts(char* __restrict__ lds, const int tid, const int nthreads) {
-    if constexpr (G::ATT32) {
-        _Float16* cr = reinterpret_cast<_Float16*>(lds + G::K_BYTES + G::V_BYTES);
-        for (int i = tid; i < G::C_ROWS * G::VS; i += nthreads)
-            cr[i] = (i < G::VS || (i >= 2 * G::VS && i < 3 * G::VS && ((i - 2 * G::VS) & 7) < 2)) ? (_Float16)1.0f : (_Float16)0.0f;
-    }
+    _Float16* cr = reinterpret_cast<_Float16*>(lds + G::K_BYTES + G::V_BYTES);
+    for (int i = tid; i < G::C_ROWS * G::VS; i += nthreads)
+        cr[i] = (i < G::VS || (i >= 2 * G::VS && i < 3 * G::VS && ((i - 2 * G::VS) & 7) < 2)) ? (_Float16)1.0f : (_Float16)0.0f;
 }
 
 // the second zeros row (see vp in fft_block_h): behind the small vectors and the progress counters, first byte on bank slot 4
@@ -743,7 +542,7 @@ __device__ __forceinline__ const _Float16* zeros_row2(const float* sv_lds) {
     return reinterpret_cast<const _Float16*>(sv_lds + S2S_SV_FLOATS + S2S_PROG_INTS) + (((4u * 16u - (a & 255u)) & 255u) >> 1);
 }
 
-// ---- wave balancing inside a SIMD (S2S_PRIO_MODE >= 4).  The two waves of a SIMD run the same attention loop, and the SIMD's
+// ---- wave balancing inside a SIMD (the 8-wave decoder).  The two waves of a SIMD run the same attention loop, and the SIMD's
 // arbiter always prefers the OLDER wave (waves 0-3 of the workgroup): it runs at the speed of a lone wave, the younger one only
 // fills its stalls, and once the older wave has reached the barrier behind the loop the younger one runs alone with all of its
 // own stalls exposed (measured with the per-wave phase stamps: 79 k against 126 k cycles per chunk in the loop, 48 k of barrier
@@ -790,8 +589,6 @@ __device__ __forceinline__ void fft_block_h(const float* __restrict__ W, const L
     const int sv_i = wave * 64 + lane;
     f32x4 svv = f32x4{0, 0, 0, 0};
     if (SV && sv_i < S2S_SV_FLOATS / 4) svv = ldg4(W + L.bq_nat + 4 * sv_i);
-    constexpr int NH = (NKT >= 16) ? 4 : 1, HK = NKT / NH;                       // 256 keys: 4 passes of 64
-    [[maybe_unused]] constexpr int HB = (HK + 1) / 2;
     const int g = lane >> 4, c = lane & 15;
     DIAG_DECL;
     _Float16* __restrict__ Kl = reinterpret_cast<_Float16*>(lds);
@@ -836,20 +633,18 @@ __device__ __forceinline__ void fft_block_h(const float* __restrict__ W, const L
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
             const int T = qt0 + q;
-            // (ATT32, fast instance: the position of att32_key_at; the EXACT instance keeps the natural order)
-            const int key = G::ATT32 && !EXACT ? 64 * (c >> 2) + 4 * ((T + ((c >> 2) & 1)) & 15) + (c & 3) : 16 * T + c;
+            // (fast instance: the position of att32_key_at; the EXACT instance keeps the natural order)
+            const int key = EXACT ? 16 * T + c : 64 * (c >> 2) + 4 * ((T + ((c >> 2) & 1)) & 15) + (c & 3);
             h4 hi, lo;
             split4<LO>(ak[q], one, hi, lo);
             *reinterpret_cast<h4*>(Kl + ((head * 2 + 0) * G::KEYS + key) * 8 + d0) = hi;
             *reinterpret_cast<h4*>(Kl + ((head * 2 + 1) * G::KEYS + key) * 8 + d0) = lo;
             split4<LO>(av[q], one, hi, lo);                           // 4 consecutive keys of one V^T row: one b64 store each
-            // (ATT32: this lane's four keys are key block 4 T + g, at block position 16 g + Tr, Tr = (T + (g & 1)) & 15: 16-key step
-            //  4 g + (Tr >> 2), block Tr & 3 of it)
+            // (this lane's four keys are key block 4 T + g.  Fast instance: at block position 16 g + Tr, Tr = (T + (g & 1)) & 15:
+            //  16-key step 4 g + (Tr >> 2), block Tr & 3 of it; natural order (EXACT): 16-key step T, block g of it)
             const int Tr = (T + (g & 1)) & 15;
-            //  natural order (EXACT): key block 4 T + g = 16-key step T, block g of it)
-            const int vcol = G::ATT32 ? (EXACT ? 16 * T + 8 * (g & 1) + 4 * ((g >> 1) & 1)
-                                               : 16 * (4 * g + (Tr >> 2)) + 8 * (Tr & 1) + 4 * ((Tr >> 1) & 1))
-                           : G::V128 ? 32 * (T >> 1) + 8 * g + 4 * (T & 1) : 16 * T + 4 * g;   // (position inside the row: see AttnLdsH::VS)
+            const int vcol = EXACT ? 16 * T + 8 * (g & 1) + 4 * ((g >> 1) & 1)
+                                   : 16 * (4 * g + (Tr >> 2)) + 8 * (Tr & 1) + 4 * ((Tr >> 1) & 1);   // (position inside the row: see AttnLdsH::VS)
             *reinterpret_cast<h4*>(Vl + vrow * G::VS + vcol) = hi;
             *reinterpret_cast<h4*>(Vl + (vrow + 8) * G::VS + vcol) = lo;
         }
@@ -866,10 +661,6 @@ __device__ __forceinline__ void fft_block_h(const float* __restrict__ W, const L
         for (int q = 0; q < NQ; ++q) acc[q][mt] = X[q][mt] + b;
     }
 
-    [[maybe_unused]] const float c1 = 1.4426950408889634f * 0.35355339059327373f;     // log2(e) / sqrt(d_k = 8)
-    h8 ones;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) ones[j] = (_Float16)1.0f;
 #pragma unroll 1
     for (int u = 0; u < 2; ++u) {                     // two head pairs per iteration = one K = 32 block of fc
         f32x4 opair[2][NQ];
@@ -894,126 +685,66 @@ __device__ __forceinline__ void fft_block_h(const float* __restrict__ W, const L
                 *reinterpret_cast<h4*>(Ql + ((((g >> 1) * NQ + q) * 2 + 0) * 16 + c) * 8 + 4 * (g & 1)) = hi;   // [head of the pair][q][hi|lo][c][8 d]
                 *reinterpret_cast<h4*>(Ql + ((((g >> 1) * NQ + q) * 2 + 1) * 16 + c) * 8 + 4 * (g & 1)) = lo;
             }
-            if constexpr (G::ATT32) {
-                // both heads of the pair on the 32x32x16 core; a head's output (4 d per lane) goes through its own, by then dead,
-                // half of the wave's Q scratch into the pair-tile layout the fc operand wants (row 4g+r: head g >> 1, d = 4 (g & 1) + r)
-                const int hl = lane >> 5, n = lane & 31;
-                const _Float16* const crow = Vl + 8 * 16 * G::VS;         // [ones row][zeros row][{1, 1, 0..} row]
-                const _Float16* const zrow2 = zeros_row2(sv_lds);
-#pragma unroll
-                for (int hh = 0; hh < 2; ++hh) {
-                    const int head = 2 * p + hh;
-                    if constexpr (S2S_PRIO_MODE >= 4 && WAVES == 8) prio_balance(reinterpret_cast<int*>(sv_lds + S2S_SV_FLOATS), wave);
-                    const _Float16* qrow = Ql + (((hh * NQ + (n >> 4)) * 2 + 0) * 16 + (n & 15)) * 8;      // [head of the pair][q][hi|lo][c][8 d]
-                    const h8 qb1 = *reinterpret_cast<const h8*>(qrow);
-                    const h8 qb2 = *reinterpret_cast<const h8*>(hl ? crow + G::VS : qrow + 16 * 8);
-                    const _Float16* kp = Kl + ((head * 2 + hl) * G::KEYS + n) * 8;                         // K_hi rows for h = 0, K_lo for h = 1
-                    const _Float16* kp2 = hl ? crow + 2 * G::VS : kp;                                       // (second score MFMA: K_hi | {1, 1, 0..})
-                    // (rows 17-31 of the P.V operand are zeros.  A ds_read_b128 is served in the 16-lane groups {0-3, 12-15, 20-27} and
-                    // {4-11, 16-19, 28-31} of each lane half, and a V^T row r sits in 16-byte bank slot r mod 16: the zeros row the lanes of
-                    // the FIRST group read must not share a slot with rows 0-3 / 12-15, that of the second none with rows 4-11 or the
-                    // ones row -- two copies: one behind the small vectors, started on slot 4, and const row 1 (slot 1).  With a single zeros row in slot 1 lane 1's row
-                    // and the zeros row collided in every such read: 2 extra LDS cycles per read, about half of round 2's
-                    // SQ_LDS_BANK_CONFLICT count.)
-                    const _Float16* vp = (n < 16 ? Vl + (head * 16 + n) * G::VS : n == 16 ? crow : (n >= 20 && n < 28 && !S2S_ONE_ZEROS_ROW) ? zrow2 : crow + G::VS) + 8 * hl;
-                    f32x16 O;
-                    float lsum;
-                    if constexpr (EXACT) {                                 // the handle's attention path is "exact" (its own kernel instance)
-#if S2S_ONLINE2 && S2S_ATT32_MSLOT
-                        softmax_pv32_online<TV, LO, true>(kp, kp2, vp, qb1, qb2, one, hl, O);
-#else
-                        softmax_pv32<TV, true, LO, true>(kp, kp2, vp, qb1, qb2, one, hl, O);
-#endif
-                        lsum = sum_h(O[8]);                                // row 16 lives in the lower lane half
-                    } else {
-                    softmax_pv32<TV, S2S_ALWAYS_RESCALE != 0, LO>(kp, kp2, vp, qb1, qb2, one, hl, O, pf_src ? 1 : 0);
-                    lsum = sum_h(O[8]);
-#if !S2S_ALWAYS_RESCALE && !defined(S2S_NO_FALLBACK)
-                    {
-                        const bool redo = __any(!(lsum <= 3.0e38f));       // inf or NaN row sum: some P_hi left the f16 range
-#ifdef S2S_DIAG
-                        DIAG_COUNT(11, 1ull); if (redo) DIAG_COUNT(10, 1ull);
-#endif
-                        if (__builtin_expect(redo, 0)) {
-                            if (lane == 0) atomicAdd(&s2s_stats_lds[S2S_STAT_REDO], 1u);     // production counter (s2s_stats_read)
-                            // (the textbook fallback, not softmax_pv32_online: as the out-of-line branch of THIS kernel the faster function
-                            //  costs the fast path 2.2 k cycles of registers and schedule -- commit 066dc5f -- and the weights that redo much run
-                            //  the exact instance anyway)
-                            softmax_pv32<TV, true, LO>(kp, kp2, vp, qb1, qb2, one, hl, O);
-                            lsum = sum_h(O[8]);
-                        }
-                    }
-#endif
-                    }
-                    const float inv = __builtin_amdgcn_rcpf(lsum);
-                    f32x4 o;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) o[r] = (O[r] + O[4 + r]) * inv;          // V_hi row d + V_lo row d, d = 4h + r
-                    *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(Ql + hh * (NQ * 2 * 16 * 8)) + n * 8 + 4 * hl) = o;
-                }
-#pragma unroll
-                for (int q = 0; q < NQ; ++q)
-                    opair[pp][q] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(Ql + (g >> 1) * (NQ * 2 * 16 * 8)) +
-                                                                   (q * 16 + c) * 8 + 4 * (g & 1));
-            } else {
-            // The pair's fc operand takes head 2p from lanes g < 2 and head 2p+1 from lanes g >= 2.  Head 2p's output is
-            // parked, for the lanes that will use it, in the first half of the wave's Q scratch (head 2p's Q^T, dead once
-            // qb has been read) instead of eight more live registers through the second head's softmax.
-            f32x4 ohead1[NQ];
+            // both heads of the pair on the 32x32x16 core; a head's output (4 d per lane) goes through its own, by then dead,
+            // half of the wave's Q scratch into the pair-tile layout the fc operand wants (row 4g+r: head g >> 1, d = 4 (g & 1) + r)
+            const int hl = lane >> 5, n = lane & 31;
+            const _Float16* const crow = Vl + 8 * 16 * G::VS;         // [ones row][zeros row][{1, 1, 0..} row]
+            const _Float16* const zrow2 = zeros_row2(sv_lds);
 #pragma unroll
             for (int hh = 0; hh < 2; ++hh) {
                 const int head = 2 * p + hh;
-                h8 qb[NQ];
-#pragma unroll
-                for (int q = 0; q < NQ; ++q)
-                    qb[q] = *reinterpret_cast<const h8*>(Ql + (((hh * NQ + q) * 2 + (g & 1)) * 16 + c) * 8);
-                const _Float16* kp = Kl + ((head * 2 + (g >> 1)) * G::KEYS + c) * 8;   // [K_hi | K_hi | K_lo | K_lo]
-                const _Float16* vp = Vl + (head * 16 + c) * G::VS + (G::V128 ? 8 : 4) * g;   // row c: 0-7 V_hi d, 8-15 V_lo d
-                f32x4 oH[NQ], oL[NQ], lH[NQ], lL[NQ];
-                softmax_pv<NQ, NKT, TV, S2S_ALWAYS_RESCALE != 0, LO>(kp, vp, qb, ones, one, g, oH, oL, lH, lL);
-#if !S2S_ALWAYS_RESCALE && !defined(S2S_NO_FALLBACK)   // (NO_FALLBACK: test-only build, proves test_peaked_attention... needs the redo)
-                {
-                    bool bad = false;                          // inf or NaN row sum: some P_hi left the f16 range
-#pragma unroll
-                    for (int q = 0; q < NQ; ++q) bad = bad || !(lH[q][0] + (LO ? lL[q][0] : 0.0f) <= 3.0e38f);
-                    const bool redo = __any(bad);
+                if constexpr (WAVES == 8) prio_balance(reinterpret_cast<int*>(sv_lds + S2S_SV_FLOATS), wave);
+                const _Float16* qrow = Ql + (((hh * NQ + (n >> 4)) * 2 + 0) * 16 + (n & 15)) * 8;      // [head of the pair][q][hi|lo][c][8 d]
+                const h8 qb1 = *reinterpret_cast<const h8*>(qrow);
+                const h8 qb2 = *reinterpret_cast<const h8*>(hl ? crow + G::VS : qrow + 16 * 8);
+                const _Float16* kp = Kl + ((head * 2 + hl) * G::KEYS + n) * 8;                         // K_hi rows for h = 0, K_lo for h = 1
+                const _Float16* kp2 = hl ? crow + 2 * G::VS : kp;                                       // (second score MFMA: K_hi | {1, 1, 0..})
+                // (rows 17-31 of the P.V operand are zeros.  A ds_read_b128 is served in the 16-lane groups {0-3, 12-15, 20-27} and
+                // {4-11, 16-19, 28-31} of each lane half, and a V^T row r sits in 16-byte bank slot r mod 16: the zeros row the lanes of
+                // the FIRST group read must not share a slot with rows 0-3 / 12-15, that of the second none with rows 4-11 or the
+                // ones row -- two copies: one behind the small vectors, started on slot 4, and const row 1 (slot 1).  With round 2's
+                // single zeros row in slot 1, lane 1's row and the zeros row collided in every such read: 2 extra LDS cycles per read,
+                // about half of round 2's SQ_LDS_BANK_CONFLICT count.)
+                const _Float16* vp = (n < 16 ? Vl + (head * 16 + n) * G::VS : n == 16 ? crow : (n >= 20 && n < 28) ? zrow2 : crow + G::VS) + 8 * hl;
+                f32x16 O;
+                float lsum;
+                if constexpr (EXACT) {                                 // the handle's attention path is "exact" (its own kernel instance)
+                    softmax_pv32_online<TV, LO>(kp, kp2, vp, qb1, qb2, one, hl, O);
+                    lsum = sum_h(O[8]);                                // row 16 lives in the lower lane half
+                } else {
+                    softmax_pv32<TV, false, LO>(kp, kp2, vp, qb1, qb2, one, hl, O, pf_src ? 1 : 0);
+                    lsum = sum_h(O[8]);
+#ifndef S2S_NO_FALLBACK                                        // (test-only build: proves test_peaked_attention... needs the redo)
+                    const bool redo = __any(!(lsum <= 3.0e38f));       // inf or NaN row sum: some P_hi left the f16 range
 #ifdef S2S_DIAG
                     DIAG_COUNT(11, 1ull); if (redo) DIAG_COUNT(10, 1ull);
 #endif
                     if (__builtin_expect(redo, 0)) {
-                        if (lane == 0) atomicAdd(&s2s_stats_lds[S2S_STAT_REDO], 1u);
-                        softmax_pv<NQ, NKT, TV, true, LO>(kp, vp, qb, ones, one, g, oH, oL, lH, lL);
+                        if (lane == 0) atomicAdd(&s2s_stats_lds[S2S_STAT_REDO], 1u);     // production counter (s2s_stats_read)
+                        // (the textbook fallback, not softmax_pv32_online: as the out-of-line branch of THIS kernel the faster function
+                        //  costs the fast path 2.2 k cycles of registers and schedule -- commit 066dc5f -- and the weights that redo much run
+                        //  the exact instance anyway)
+                        softmax_pv32<TV, true, LO>(kp, kp2, vp, qb1, qb2, one, hl, O);
+                        lsum = sum_h(O[8]);
                     }
-                }
 #endif
-#pragma unroll
-                for (int q = 0; q < NQ; ++q) {
-                    const f32x4 t = LO ? oH[q] + oL[q] : oH[q];
-                    const float inv = __builtin_amdgcn_rcpf(LO ? lH[q][0] + lL[q][0] : lH[q][0]);   // v_rcp_f32 (1 ulp), not the 10-instruction division
-                    f32x4 o;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {            // O[d] = row d + row 8+d: the other half-wave's value
-                        const unsigned uu = __float_as_uint(t[r]);
-                        auto sw = __builtin_amdgcn_permlane32_swap(uu, uu, false, false);
-                        o[r] = (__uint_as_float(sw[0]) + __uint_as_float(sw[1])) * inv;
-                    }
-                    // lanes g and g^2 both hold d = 4(g&1) + r
-                    if (hh == 0) { if (g < 2) *reinterpret_cast<f32x4*>(Ql + (q * 32 + lane) * 8) = o; }
-                    else ohead1[q] = o;
                 }
+                const float inv = __builtin_amdgcn_rcpf(lsum);
+                f32x4 o;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) o[r] = (O[r] + O[4 + r]) * inv;          // V_hi row d + V_lo row d, d = 4h + r
+                *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(Ql + hh * (NQ * 2 * 16 * 8)) + n * 8 + 4 * hl) = o;
             }
 #pragma unroll
-            for (int q = 0; q < NQ; ++q) {                 // pair tile: row 4g+r
-                const f32x4 o0 = *reinterpret_cast<const f32x4*>(Ql + (q * 32 + (lane & 31)) * 8);
-                opair[pp][q] = (g < 2) ? o0 : ohead1[q];
-            }
-            }
+            for (int q = 0; q < NQ; ++q)
+                opair[pp][q] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(Ql + (g >> 1) * (NQ * 2 * 16 * 8)) +
+                                                               (q * 16 + c) * 8 + 4 * (g & 1));
         }
         // ---- fc, k-block u (the 4 heads just finished): acc += Wfc[:, 32u : 32u+32] * O^T
         HL ob[NQ];
 #pragma unroll
         for (int q = 0; q < NQ; ++q) ob[q] = split8<LO>(opair[0][q], opair[1][q], one);
-            load_unit_h<LO>(fb, ws); WS_ADVP(UF, 8192);                // Wfc(u), m-tiles 2-3
+        load_unit_h<LO>(fb, ws); WS_ADVP(UF, 8192);                    // Wfc(u), m-tiles 2-3
         SB_GEMM();
 #pragma unroll
         for (int half = 0; half < 2; ++half) {        // unit = [mt a hi][mt a lo][mt b hi][mt b lo]
@@ -1038,22 +769,24 @@ __device__ __forceinline__ void fft_block_h(const float* __restrict__ W, const L
             }
         }
     }
-    if (S2S_PRIO_MODE != 0 && WAVES == 8) __builtin_amdgcn_s_setprio(0);
-    if constexpr (!(S2S_FFN_LDS && WAVES == 8 && LO)) DIAG_STAMP(3);
+    if (WAVES == 8) __builtin_amdgcn_s_setprio(0);
 
     // ---- FFN 64 -> 256 -> 64 in four 64-wide slices of the hidden layer (layers.py:108-113)
+    // FFN_LDS (the 8-wave decoder of the f16x3 mode; the f16 mode's half-size hi-only stream comes from L2): every wave needs every
+    // FFN weight unit, and eight copies of the 128 KiB through the CU's 64 B/clk vector-L1 path cost more than the FFN's MFMAs
+    // (timing without these loads: +7.7 %).  The K/V region is dead once every wave has left the attention loop, so the workgroup
+    // copies the FFN stream into it ONCE -- wave w: unit 8hc + w of every slice hc, 16 KiB -- and the FFN reads its A fragments
+    // with ds_read_b128 (256 B/clk).  The copy goes through registers (global_load_dwordx4 issued before the barrier,
+    // ds_write_b128 after it): LDS-DMA lands at only ~12 B/clk per CU and cost 11 k cycles per layer when tried.  The next
+    // block's entry barrier protects the region again.
+    constexpr bool FFN_LDS = WAVES == 8 && LO;
+    static_assert(G::K_BYTES + G::V_BYTES >= 32 * 4096, "the FFN stream fits the dead K/V region");
+    if constexpr (!FFN_LDS) DIAG_STAMP(3);                               // (FFN_LDS: behind its loads, below)
     // A weight unit feeds only 6*NQ MFMAs (~200 cycles) here, less than an L2 round trip, so the stream
     // runs three units ahead through a ring of four unit buffers (8 units per slice: slots repeat).
     // (a single-tile instantiation gets a two-deep ring: 32 registers less)
     constexpr int RD = (NQ >= 2) ? 4 : 2, RM = RD - 1;               // ring depth; units in flight = RD - 1
     f32x4 ring[RD][4];
-    // FFN_LDS (the 8-wave decoder): every wave needs every FFN weight unit, and eight copies of the 128 KiB through the CU's
-    // 64 B/clk vector-L1 path cost more than the FFN's MFMAs (timing without these loads: +7.7 %).  The K/V region is dead
-    // once every wave has left the attention loop, so the workgroup copies the FFN stream into it ONCE -- wave w: unit
-    // 8hc + w of every slice hc, 16 KiB -- and the FFN reads its A fragments with ds_read_b128 (256 B/clk).  The copy goes
-    // through registers (global_load_dwordx4 issued before the barrier, ds_write_b128 after it): LDS-DMA lands at only
-    // ~12 B/clk per CU and cost 11 k cycles per layer when tried.  The next block's entry barrier protects the region again.
-    constexpr bool FFN_LDS = S2S_FFN_LDS && WAVES == 8 && LO && (G::K_BYTES + G::V_BYTES >= 32 * 4096);
     const float* wl = reinterpret_cast<const float*>(lds) + lane * 4;    // this lane's 16 B of every staged 1-KiB fragment
     if constexpr (FFN_LDS) {
         f32x4 gm[4], bt[4], b2v[4], stage[16];

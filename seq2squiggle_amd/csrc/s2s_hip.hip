@@ -315,10 +315,8 @@ __device__ __forceinline__ void frontend_h16(const ModelDev& M, const float* __r
 }
 
 // ================================================================================ decoder
-#ifndef DEC_WAVES
 #define DEC_WAVES 8
 #define DEC_NQ 2            // 16-column time tiles per wave: 8 waves x 2 x 16 = 256 >= 250
-#endif
 #define DEC_WPS (DEC_WAVES / 4)   // waves per SIMD
 #define DEC_NKT 16
 static constexpr int DEC_LDS_F32 = AttnLds<DEC_NKT>::BYTES;

@@ -162,7 +162,9 @@ typedef struct s2s_handle s2s_handle;
  * A generic handle runs a launch in slices of at most S2S_GENERIC_WORKSPACE_BYTES / (4 * per-chunk floats) chunks, per-chunk
  * floats = te dmodel + ts dmodel + max(te, ts) max(3 dmodel, dff) + te + ts, te / ts = max_dna_len / max_signal_len (16 / 250
  * outside the two geometry modes; each buffer is then rounded up to a multiple of
- * 64 floats); the workspace grows on demand (the first launch of a larger batch synchronises the stream) and is reused. */
+ * 64 floats), and of at most (2^32 - 1) / (max(n_heads, decoder_heads) * threads per (chunk, head)) chunks, threads = 1024
+ * up to 256 samples and 256 * ceil(max_signal_len / 64) beyond: an attention launch holds fewer than 2^32 threads (this binds at
+ * tiny geometries only); the workspace grows on demand (the first launch of a larger batch synchronises the stream) and is reused. */
 #define S2S_GENERIC_WORKSPACE_BYTES (512u << 20)
 size_t s2s_blob_floats(const s2s_config* cfg);
 

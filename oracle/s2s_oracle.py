@@ -162,19 +162,20 @@ def standard_gamma_to_sample(sg: torch.Tensor, rate: torch.Tensor) -> torch.Tens
 
 
 def durations(params: PredictParams, B: int, g: Optional[torch.Tensor] = None,
-              zdw: Optional[torch.Tensor] = None, dtype=torch.float32) -> torch.Tensor:
-    """LengthRegulator.forward duration source (modules.py:396-438) -> int32 [B,16].
+              zdw: Optional[torch.Tensor] = None, dtype=torch.float32, t_enc: int = T_ENC) -> torch.Tensor:
+    """LengthRegulator.forward duration source (modules.py:396-438) -> int32 [B,t_enc].
 
-    g   : Gamma sample value (pre clamp) when duration_sampling;
-    zdw : standard normals for the dwell_std > 0 mode (torch.normal(mean, std) == mean + z*std).
+    g     : Gamma sample value (pre clamp) when duration_sampling;
+    zdw   : standard normals for the dwell_std > 0 mode (torch.normal(mean, std) == mean + z*std);
+    t_enc : the encoder length (max_dna_len) the constant and Normal dwell rows are filled to.
     """
     if params.duration_sampling:
         d = g.to(dtype).clamp(min=1.0)                             # modules.py:223
         d = d.clamp(min=params.min_duration)                       # modules.py:414-416
     elif params.dwell_std <= 0:
-        d = torch.full((B, T_ENC), params.dwell_mean, dtype=dtype)  # modules.py:420-423
+        d = torch.full((B, t_enc), params.dwell_mean, dtype=dtype)  # modules.py:420-423
     else:
-        d = torch.full((B, T_ENC), params.dwell_mean, dtype=dtype) + zdw.to(dtype) * params.dwell_std
+        d = torch.full((B, t_enc), params.dwell_mean, dtype=dtype) + zdw.to(dtype) * params.dwell_std
         d = d.clamp(min=params.min_duration)                       # modules.py:425-432
     return torch.round(d).int()                                    # modules.py:437-438 (half-to-even)
 
@@ -244,8 +245,8 @@ def predict_chunks(sd: Dict[str, torch.Tensor], cfg: dict, codes: np.ndarray, pa
             g = standard_gamma_to_sample(sg, rate)
     zdw = inject_zdw
     if (not params.duration_sampling) and params.dwell_std > 0 and zdw is None:
-        zdw = torch.randn(B, T_ENC, generator=generator, dtype=dtype)
-    dur = durations(params, B, g, zdw, dtype)
+        zdw = torch.randn(B, cfg["max_dna_len"], generator=generator, dtype=dtype)
+    dur = durations(params, B, g, zdw, dtype, t_enc=cfg["max_dna_len"])
     h, sigma_ext = length_regulate(enc_out, sigma, dur, cfg["max_signal_len"])
     y_scaled = decoder(sd, cfg, h)
     z01 = inject_z01

@@ -163,7 +163,8 @@ __global__ void __launch_bounds__(256) gen_layernorm_kernel(float* __restrict__ 
 //      4 waves, wave w takes the queries t = w, w+4, ...: scores with one lane per key, the row maximum and sum over the wave,
 //      p = exp(s - max) / sum (torch.softmax), then P.V with the lanes split into 64/hp groups of keys x hp head dims (hp = hd
 //      rounded up to a power of two, at most 64) and a reduction over the groups.  STAGE: K and V are copied into LDS first
-//      (the host decides by size: always for 16 keys; for 250 keys while hd <= 30); otherwise they are read from the L2.
+//      (the host decides by size, gen_attn_lds_bytes against GEN_ATTN_STAGE_BYTES: always for 16 keys; while hd <= 38 for 250 keys,
+//      <= 37 for 256, <= 76 for 128); otherwise they are read from the L2.
 #define GEN_ATTN_STAGE_BYTES (80 * 1024)
 __host__ __device__ constexpr size_t gen_attn_lds_bytes(int T, int hd, bool stage) {
     return ((stage ? (size_t)T * (2 * hd + 1) : 0) + 4 * (size_t)(hd + T)) * sizeof(float);

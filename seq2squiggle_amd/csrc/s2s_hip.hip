@@ -1367,8 +1367,15 @@ void pack_generic(Arena& A, s2s_handle::Generic& G, const s2s_config* cfg, const
     }
     G.out_w = A.put(take(p, d), d);
     G.out_b = A.put(take(p, 1), 1);
-    G.slice_max = (int)(S2S_GENERIC_WORKSPACE_BYTES / (4 * generic_chunk_floats(cfg)));
-    if (G.slice_max < 1) G.slice_max = 1;
+    size_t slice = S2S_GENERIC_WORKSPACE_BYTES / (4 * generic_chunk_floats(cfg));
+    // The attention kernels launch one workgroup per (chunk, head) -- per (chunk, head, 64 queries) beyond 256 keys -- of up to 1024
+    // threads, and a launch holds fewer than 2^32 threads in all: at a tiny geometry (1 / 1: 82 floats per chunk) the workspace
+    // alone would allow a slice whose attention grid wraps, and the chunks past the wrap would keep Q where O belongs.
+    const size_t heads = cfg->n_heads > cfg_dec_heads(cfg) ? cfg->n_heads : cfg_dec_heads(cfg);
+    const size_t per_head = cfg->max_signal_len > 256 ? (size_t)((cfg->max_signal_len + 63) / 64) * 256 : 1024;
+    const size_t grid_cap = 0xFFFFFFFFull / (heads * per_head);
+    if (slice > grid_cap) slice = grid_cap;
+    G.slice_max = slice < 1 ? 1 : (int)slice;
 }
 
 ParamsDev to_dev(const s2s_params* p) {

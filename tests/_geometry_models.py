@@ -33,22 +33,23 @@ CASES = {
 }
 
 
-def geometry_config(tag: str, base: dict = None) -> dict:
-    """The config of case `tag`: `base` (default: the package's copy of the reference's config.yaml) with the case's keys."""
+def geometry_config(tag: str, base: dict = None, cases: dict = None) -> dict:
+    """The config of case `tag` of the table `cases` (default: CASES above; tests/_envelope_models.py passes its own): `base`
+    (default: the package's copy of the reference's config.yaml) with the case's keys."""
     if base is None:
         from seq2squiggle_amd.cli import set_config
         base = set_config(None)
     c = dict(base)
-    c.update({k: v for k, v in CASES[tag].items() if k != "seed"})
+    c.update({k: v for k, v in (cases or CASES)[tag].items() if k != "seed"})
     return c
 
 
-def geometry_state_dict(tag: str) -> dict:
+def geometry_state_dict(tag: str, cases: dict = None) -> dict:
     """The weights of case `tag`, keyed and shaped as the reference's state_dict (fp32 tensors, fp16-representable values)."""
     from seq2squiggle_amd.checkpoint import blob_names
-    cfg = geometry_config(tag)
+    cfg = geometry_config(tag, cases=cases)
     d, f, k = cfg["dmodel"], cfg["dff"], cfg["seq_kmer"]
-    rng = np.random.default_rng(CASES[tag]["seed"])
+    rng = np.random.default_rng((cases or CASES)[tag]["seed"])
 
     def linear(prefix, n_out, n_in):
         b = 1.0 / math.sqrt(n_in)                 # nn.Linear's default init range, weight and bias
@@ -94,13 +95,13 @@ def geometry_state_dict(tag: str) -> dict:
     return {n: torch.from_numpy(np.asarray(v, dtype=np.float32).astype(np.float16).astype(np.float32)) for n, v in sd.items()}
 
 
-def write_checkpoint(tag: str, path: str) -> str:
+def write_checkpoint(tag: str, path: str, cases: dict = None) -> str:
     """Case `tag` as a Lightning-layout .ckpt at `path`, weights stored as fp16."""
-    sd = geometry_state_dict(tag)
+    sd = geometry_state_dict(tag, cases)
     ckpt = {
         "epoch": 0, "global_step": 0, "pytorch-lightning_version": "2.5.1.post0",
         "state_dict": {n: t.half() for n, t in sd.items()},
-        "hyper_parameters": {"config": geometry_config(tag), "save_valid_plots": True, "out_writer": None,
+        "hyper_parameters": {"config": geometry_config(tag, cases=cases), "save_valid_plots": True, "out_writer": None,
                              "dwell_mean": 9.0, "dwell_std": 0.0, "noise_std": -1, "noise_sampling": False,
                              "duration_sampling": False, "export_every_n_samples": 2000000, "min_noise": 0.5,
                              "min_duration": 1},
@@ -114,11 +115,12 @@ def write_checkpoint(tag: str, path: str) -> str:
 _WRITTEN = {}
 
 
-def checkpoint_path(tag: str) -> str:
+def checkpoint_path(tag: str, cases: dict = None) -> str:
     """Case `tag` written once per process into a temporary directory; -> its path."""
-    if tag not in _WRITTEN:
+    key = (id(cases or CASES), tag)
+    if key not in _WRITTEN:
         import atexit, shutil, tempfile
         d = tempfile.mkdtemp(prefix="s2s_geometry_")
         atexit.register(shutil.rmtree, d, True)
-        _WRITTEN[tag] = write_checkpoint(tag, os.path.join(d, f"synthetic_{tag}.ckpt"))
-    return _WRITTEN[tag]
+        _WRITTEN[key] = write_checkpoint(tag, os.path.join(d, f"synthetic_{tag}.ckpt"), cases)
+    return _WRITTEN[key]

@@ -260,6 +260,34 @@ def predict_chunks(sd: Dict[str, torch.Tensor], cfg: dict, codes: np.ndarray, pa
     return out
 
 
+# --------------------------------------------------------------------------- validation_step
+def evaluate_chunks(sd: Dict[str, torch.Tensor], cfg: dict, codes: np.ndarray, lengths: np.ndarray, target: np.ndarray,
+                    stdev: np.ndarray, dtype=torch.float32):
+    """The teacher-forced first pass of validation_step (model.py:108-140) and the three per-chunk sums of get_loss (model.py:458-475).
+
+    codes [B,te,k] letter codes (a value >= 5: an all-zero one-hot row), lengths [B,te] the measured samples per k-mer (they take the
+    sampler's place in the length regulator, modules.py:434-435), target [B,ts] and stdev [B,te] already divided by
+    scaling_max_value.  -> dict(y [B,ts], sigma / conc / rate [B,te] in `dtype`, scaled units; per_chunk float64 [B,3]:
+    sum (y - target)^2, sum -Gamma(conc, rate).log_prob(|d| + (d == 0)), sum (stdev - sigma)^2, formed in float64 from those tensors).
+    """
+    if dtype != torch.float32:
+        sd = {k: v.to(dtype) for k, v in sd.items()}
+    enc_out, emb_out = encoder(sd, cfg, one_hot(codes, dtype))
+    sigma = noise_sampler(sd, emb_out)
+    conc, rate = duration_params(sd, emb_out)
+    dur = torch.as_tensor(np.ascontiguousarray(lengths).astype(np.int64))
+    h, _ = length_regulate(enc_out, sigma, dur, cfg["max_signal_len"])
+    y = decoder(sd, cfg, h)
+    y64, s64, c64, r64 = (t.double().numpy() for t in (y, sigma, conc, rate))
+    x = np.abs(np.asarray(lengths, dtype=np.float64))
+    x = np.where(x == 0, 1.0, x)
+    lg = np.vectorize(math.lgamma)(c64)
+    nll = -(c64 * np.log(r64) + (c64 - 1) * np.log(x) - r64 * x - lg)
+    per_chunk = np.stack([((y64 - np.asarray(target, dtype=np.float64)) ** 2).sum(1), nll.sum(1),
+                          ((np.asarray(stdev, dtype=np.float64) - s64) ** 2).sum(1)], 1)
+    return {"y": y, "sigma": sigma, "conc": conc, "rate": rate, "per_chunk": per_chunk}
+
+
 # --------------------------------------------------------------------------- export path
 def strip_zeros(rows: Sequence[torch.Tensor]) -> torch.Tensor:
     """export_and_clear_results (model.py:284-286): cat the chunk rows of a read, drop every element == 0."""

@@ -5,7 +5,8 @@ import os
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-TAGS = ("k9", "k6", "d32", "r16x500")
+TAGS = ("k9", "k6", "d32", "r16x500", "hd1", "g5x37", "hd24", "hd64", "hd96s", "g64x1024", "hd208")
+ROW_KEYS = ("codes", "lengths", "targets", "stdevs", "kind", "prediction_ref", "sigma", "conc", "rate", "per_chunk", "per_chunk16")
 LOSSES = ("valid_signal_loss", "valid_duration_loss", "valid_noise_loss", "valid_total_loss")
 
 
@@ -19,8 +20,35 @@ def checkpoint(tag: str) -> str:
     if tag == "d32":
         import _sized_models as SM
         return SM.checkpoint_path(tag)
+    import _envelope_models as EM
+    if tag in EM.CASES:
+        return EM.checkpoint_path(tag)
     import _geometry_models as GM
     return GM.checkpoint_path(tag)
+
+
+def scaled(g: dict, scale: float):
+    """-> (targets, stdevs) float32 as ChunkDataSetMemmap.__getitem__ hands them to the model: / scaling_max_value."""
+    return (g["targets"].astype(np.float32) / scale).astype(np.float32), (g["stdevs"] / scale).astype(np.float32)
+
+
+def draw_rows(g: dict, B: int, seed: int):
+    """A dataset of B rows drawn from the golden's chunks -> (idx int64 [B], the golden's per-row arrays at idx).  idx is a chain of
+    seeded permutations of the golden's chunks, so every window of N rows that starts at a multiple of N covers the golden exactly
+    once, and no two adjacent rows come from the same golden chunk: a row swapped with its neighbour, or one that took another
+    row's hand-off slot, disagrees with the reference's answer for its own chunk."""
+    N = g["codes"].shape[0]
+    assert N >= 3 and B >= 1
+    rng = np.random.default_rng(seed)
+    parts = []
+    while sum(len(p) for p in parts) < B:
+        p = rng.permutation(N)
+        if parts and p[0] == parts[-1][-1]:
+            p[[0, 1]] = p[[1, 0]]
+        parts.append(p)
+    idx = np.concatenate(parts)[:B].astype(np.int64)
+    assert B == 1 or (idx[1:] != idx[:-1]).all()
+    return idx, {k: g[k][idx] for k in ROW_KEYS}
 
 
 def onehot(codes: np.ndarray) -> np.ndarray:

@@ -1,6 +1,8 @@
 """The evaluate command without a GPU: preprocess-directory discovery and pairing (batched and single-file layouts), the one-hot ->
 k-mer letter conversion, the reference's scaling, the loader's refusals, the finalisation of per-chunk sums into the reference's
-four logged losses (tests/golden/eval_<tag>.npz, tools/make_eval_goldens.py) and the CLI's argument errors."""
+four logged losses (tests/golden/eval_<tag>.npz, tools/make_eval_goldens.py), the CLI's argument errors, and the teacher-forced CPU
+oracle (oracle.s2s_oracle.evaluate_chunks) against the reference's own tensors and logged losses at every golden -- the anchor that
+lets the GPU tests use the oracle for rows no golden holds."""
 import os
 
 import numpy as np
@@ -12,8 +14,10 @@ from seq2squiggle_amd import evaluate as EV
 from seq2squiggle_amd import _lib
 from seq2squiggle_amd.checkpoint import load_checkpoint
 from seq2squiggle_amd.cli import main
+from oracle import s2s_oracle as O
 from conftest import GOLDEN
 import _eval_data as ED
+from _bounds import MAE_TOL, MAX_TOL
 
 
 @pytest.fixture(scope="module")
@@ -118,6 +122,59 @@ def test_finalize_reproduces_logged_losses(tag):
         ref = g[f"logged_bs{bs}"]
         for i, name in enumerate(ED.LOSSES):
             assert abs(fin[name] - ref[i]) <= 1e-6 * abs(ref[i]), (tag, bs, name, fin[name], ref[i])
+
+
+@pytest.mark.parametrize("tag", ED.TAGS)
+def test_oracle_reproduces_the_reference(tag):
+    """oracle.evaluate_chunks against the reference's first-pass tensors and logged losses.  fp64: y within the project's predict
+    bounds of prediction_ref (MAE_TOL / MAX_TOL, pA), heads within 1e-5 relative.  fp32 (the reference's own arithmetic, bit-equal
+    where the BLAS sums in the same order): no further from prediction_ref than the fp64 oracle, its float64 per-chunk sums within
+    1e-4 relative + 1e-7 of the golden's (the bound of the logged losses, chunk by chunk), its finalized losses within 1e-4 relative
+    of logged_bs32.  The data hold a dwell of 32767, zero dwell, the crop, pad and unknown-letter rows (tools/make_eval_goldens.py)."""
+    torch.set_float32_matmul_precision("highest")
+    g = ED.load(tag)
+    sd, cfg = load_checkpoint(ED.checkpoint(tag))
+    scale = float(cfg["scaling_max_value"])
+    te, ts = g["lengths"].shape[1], g["targets"].shape[1]
+    assert (te, ts) == (cfg["max_dna_len"], cfg["max_signal_len"])
+    tg, sv = ED.scaled(g, scale)
+    o32 = O.evaluate_chunks(sd, cfg, g["codes"], g["lengths"], tg, sv)
+    o64 = O.evaluate_chunks(sd, cfg, g["codes"], g["lengths"], tg, sv, dtype=torch.float64)
+    ref = g["prediction_ref"].astype(np.float64)
+    d32 = np.abs(o32["y"].double().numpy() - ref) * scale
+    d64 = np.abs(o64["y"].numpy() - ref) * scale
+    rel = {n: float((np.abs(o64[n].numpy() - g[n].astype(np.float64)) / np.abs(g[n].astype(np.float64))).max()) for n in ("sigma", "conc", "rate")}
+    rel32 = {n: float((np.abs(o32[n].double().numpy() - g[n].astype(np.float64)) / np.abs(g[n].astype(np.float64))).max())
+             for n in ("sigma", "conc", "rate")}
+    pc = np.abs(o32["per_chunk"] - g["per_chunk"])
+    print(f"EVAL oracle {tag}: y to prediction_ref fp64 MAE {d64.mean():.3e} max {d64.max():.3e} pA, fp32 MAE {d32.mean():.3e} max "
+          f"{d32.max():.3e} pA | heads rel fp64 {max(rel.values()):.2e} fp32 {max(rel32.values()):.2e} | per-chunk sums rel "
+          f"{(pc / (np.abs(g['per_chunk']) + 1e-300)).max():.2e}")
+    assert o64["y"].shape == ref.shape and o32["y"].dtype == torch.float32
+    assert d64.mean() < MAE_TOL and d64.max() < MAX_TOL, (d64.mean(), d64.max())
+    assert max(rel.values()) < 1e-5, rel
+    assert d32.mean() <= d64.mean() and d32.max() <= d64.max(), (d32.mean(), d64.mean(), d32.max(), d64.max())
+    assert max(rel32.values()) <= max(rel.values()), (rel32, rel)
+    assert np.all(pc <= 1e-4 * np.abs(g["per_chunk"]) + 1e-7), pc.max(0)
+    fin = EV.finalize(o32["per_chunk"], te, ts)
+    for i, name in enumerate(ED.LOSSES):
+        r = float(g["logged_bs32"][i])
+        assert abs(fin[name] - r) <= 1e-4 * abs(r), (name, fin[name], r)
+    if tag not in ("k9", "k6", "d32", "r16x500"):
+        assert (g["lengths"] == 32767).sum() == 1                      # the stalled k-mer is in the data
+
+
+def test_draw_rows_chains_permutations():
+    g = ED.load("k9")
+    N = g["codes"].shape[0]
+    for B in (1, N, 5 * N + 17):
+        idx, rows = ED.draw_rows(g, B, seed=3)
+        assert idx.shape == (B,) and rows["codes"].shape[0] == B and np.array_equal(rows["lengths"], g["lengths"][idx])
+        assert (idx[1:] != idx[:-1]).all()
+        for lo in range(0, B - N + 1, N):
+            assert np.array_equal(np.sort(idx[lo:lo + N]), np.arange(N))
+    assert np.array_equal(ED.draw_rows(g, 300, seed=3)[0], ED.draw_rows(g, 300, seed=3)[0])
+    assert not np.array_equal(ED.draw_rows(g, 300, seed=3)[0], ED.draw_rows(g, 300, seed=4)[0])
 
 
 def test_finalize_refuses_empty():

@@ -32,7 +32,11 @@ pytestmark = pytest.mark.gpu
 
 ALL = ["f16x3", "f32", "f16", "generic", "generic-f16", "generic-geometry", "generic-geometry-f16"]
 GENERIC = ["generic", "generic-f16", "generic-geometry", "generic-geometry-f16"]
-MODES = {"k9": ALL, "k6": ALL, "d32": GENERIC, "r16x500": ["generic-geometry", "generic-geometry-f16"]}
+GEOMETRY = ["generic-geometry", "generic-geometry-f16"]
+# (the cases after r16x500: tests/_envelope_models.py and tests/_geometry_models.py -- te 1 / 5 / 23 / 16 / 64 / 64 / 17, ts 1 / 37 / 255 / 250
+#  / 251 / 1024 / 1023, seq_kmer 1 at hd64 and 16 at hd24, 4 / 4 / 4 layers at hd96s; each holds a k-mer of dwell 32767)
+MODES = {"k9": ALL, "k6": ALL, "d32": GENERIC, "r16x500": GEOMETRY, "hd1": GEOMETRY, "g5x37": GEOMETRY, "hd24": GEOMETRY, "hd64": GENERIC,
+         "hd96s": GEOMETRY, "g64x1024": GEOMETRY, "hd208": GEOMETRY}
 FP32_CLASS = {"f32", "f16x3", "generic", "generic-geometry"}
 CASES = [(t, m) for t in ED.TAGS for m in MODES[t]]
 
@@ -104,7 +108,8 @@ def test_parity_with_reference(tag, mode):
 
 
 @pytest.mark.parametrize("tag,mode", [("k9", "f16x3"), ("k9", "f32"), ("k9", "f16"), ("k6", "generic"), ("r16x500", "generic-geometry"),
-                                      ("d32", "generic-f16")])
+                                      ("d32", "generic-f16")]
+                         + [(t, m) for t in ("hd1", "g5x37", "hd24", "hd64", "hd96s", "g64x1024", "hd208") for m in MODES[t]])
 def test_deterministic_under_slicing(tag, mode):
     """A chunk's sums depend on its own rows only: bit-identical for B = all, 1, 7, 64 and across two calls."""
     g = ED.load(tag)
@@ -179,6 +184,17 @@ def test_cli_end_to_end(tmp_path):
     z = np.load(npz)
     assert z["model0"].shape == (96, 3) and np.array_equal(z["model0"], z["model1"])
     assert np.allclose(z["model0"], g["per_chunk"], rtol=1e-3, atol=1e-6)
+    # a checkpoint at another geometry (16 / 500), the compute mode chosen by the engine
+    g5 = ED.load("r16x500")
+    d5 = ED.write_dir(g5, str(tmp_path / "data500"), per_file=40)
+    r = subprocess.run([sys.executable, "-m", "seq2squiggle_amd", "evaluate", d5, "-m", ED.checkpoint("r16x500"), "--json"], cwd=ROOT,
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    rows = [json.loads(line) for line in r.stdout.splitlines() if line.startswith("{")]
+    assert len(rows) == 1 and rows[0]["mode"] == "generic-geometry" and rows[0]["chunks"] == g5["codes"].shape[0]
+    for i, name in enumerate(ED.LOSSES):
+        print(f"EVAL cli r16x500 {name}: {rows[0][name]:.9g} ref {g5['logged_bs32'][i]:.9g}")
+        assert abs(rows[0][name] - g5["logged_bs32"][i]) <= 1e-4 * abs(g5["logged_bs32"][i]), name
     # a checkpoint of another seq_kmer is refused with the expected shape
     r = subprocess.run([sys.executable, "-m", "seq2squiggle_amd", "evaluate", d, "-m", k6], cwd=ROOT, capture_output=True, text=True,
                        timeout=600)

@@ -1,8 +1,10 @@
 #!/usr/bin/env python
 """Teacher-forced validation goldens, by IMPORTING the reference (build container only).
 
-For four checkpoints -- the committed synthetic k9 / k6 ones, d32 (tests/_sized_models.py) and r16x500 (tests/_geometry_models.py) --
-a seeded dataset in the reference's preprocess layout is run through the reference's own seq2squiggle.validation_step (model.py:107-193,
+For the committed synthetic k9 / k6 checkpoints, d32 (tests/_sized_models.py), r16x500, g5x37 and g64x1024 (tests/_geometry_models.py)
+and hd1, hd24, hd64, hd96s and hd208 (tests/_envelope_models.py: te 1 / 23 / 16 / 64 / 17, ts 1 / 255 / 250 / 251 / 1023, seq_kmer 6 / 16 /
+1 / 6 / 9, hd96s with 4 / 4 / 4 layers -- every row shape of the teacher-forced generic kernels and of the loss kernel) a seeded
+dataset in the reference's preprocess layout is run through the reference's own seq2squiggle.validation_step (model.py:107-193,
 get_loss :419-480) with self.log captured.  -> tests/golden/eval_<tag>.npz, stored compactly (the tests rebuild the .npy files):
 
   codes uint8 [N,te,k]    letter codes 0-4 ("_ACGT"), 5 = an all-zero one-hot row
@@ -20,7 +22,9 @@ get_loss :419-480) with self.log captured.  -> tests/golden/eval_<tag>.npz, stor
 
 Chunk kinds: "fit" chunks, whose targets are the reference's own teacher-forced prediction x scaling + N(0, 2 pA); random targets;
 edge cases: dwell sums below, at and above ts (the crop), a zero-length k-mer, trailing "_"*k pad k-mers with length 1 and stdev 0
-(as process_df writes them), an unknown-letter row, an all-pad chunk.
+(as process_df writes them), an unknown-letter row, an all-pad chunk.  Where te < 4 the k-mer positions of these recipes are clipped
+into the chunk (fewer zero-length and pad k-mers; none at te 1).  The cases added after the first four also hold a stalled k-mer: one
+dwell of 32767, the top of the preprocess files' int16 range, in the middle of the last random-target chunk (marked kind 2).
 
     python tools/make_eval_goldens.py
 """
@@ -37,9 +41,14 @@ sys.path.insert(0, ROOT)
 import make_goldens as MG      # noqa: E402  (stubs the reference's third-party imports, imports the reference)
 import _sized_models as SM     # noqa: E402
 import _geometry_models as GM  # noqa: E402
+import _envelope_models as EM  # noqa: E402
 
 LOSSES = ("valid_signal_loss", "valid_duration_loss", "valid_noise_loss", "valid_total_loss")
-N_CHUNKS = {"k9": 96, "k6": 96, "d32": 96, "r16x500": 64}
+N_CHUNKS = {"k9": 96, "k6": 96, "d32": 96, "r16x500": 64, "hd1": 48, "g5x37": 48, "hd24": 36, "hd64": 48, "hd96s": 36, "g64x1024": 30,
+            "hd208": 30}
+SEEDS = {"k9": 901, "k6": 902, "d32": 903, "r16x500": 904, "hd1": 905, "g5x37": 906, "hd24": 907, "hd64": 908, "hd96s": 909,
+         "g64x1024": 910, "hd208": 911}
+STALLED = ("hd1", "g5x37", "hd24", "hd64", "hd96s", "g64x1024", "hd208")       # cases with a dwell-32767 chunk
 BATCHES = (32, 96)
 
 
@@ -51,6 +60,8 @@ def case(tag):
         return cfg, sd
     if tag == "d32":
         return SM.sized_config(tag, MG.base_config(SM.CASES[tag]["seq_kmer"])), SM.sized_state_dict(tag)
+    if tag in EM.CASES:
+        return EM.envelope_config(tag, MG.base_config(EM.CASES[tag]["seq_kmer"])), EM.envelope_state_dict(tag)
     return GM.geometry_config(tag, MG.base_config(GM.CASES[tag]["seq_kmer"])), GM.geometry_state_dict(tag)
 
 
@@ -106,7 +117,7 @@ def build(tag):
     m = MG.RM.seq2squiggle(config=cfg)
     m.load_state_dict(sd, strict=True)
     m.eval()
-    rng = np.random.default_rng({"k9": 901, "k6": 902, "d32": 903, "r16x500": 904}[tag])
+    rng = np.random.default_rng(SEEDS[tag])
     N = N_CHUNKS[tag]
     codes = rng.integers(1, 5, (N, te, k)).astype(np.uint8)
     mean = ts / te
@@ -121,13 +132,17 @@ def build(tag):
     lengths[e[2]] = np.full(te, 3 * ts // te)                                          # sum far above ts: cropped
     lengths[e[3], te // 2] = 0                                                          # a zero-length k-mer
     lengths[e[4], :3] = 0
+    pad0 = te - min(4, te - 1)                                                          # (te < 4: fewer pad k-mers, none at te 1)
     for r in (e[5], e[6]):                                                              # trailing pad k-mers, length 1
-        codes[r, -4:] = 0
-        lengths[r, -4:] = 1
-    codes[e[7], 3, k // 2] = 5                                                          # an unknown letter (all-zero row)
+        codes[r, pad0:] = 0
+        lengths[r, pad0:] = 1
+    codes[e[7], min(3, te - 1), k // 2] = 5                                                        # an unknown letter (all-zero row)
     codes[e[8], 0, 0] = 5
     codes[e[9]] = 0                                                                     # an all-pad chunk
     lengths[e[9]] = 1
+    if tag in STALLED:                                                                  # a stalled k-mer: the top of the int16 range
+        lengths[e[0] - 1, te // 2] = 32767
+        kind[e[0] - 1] = 2
     y, sigma, conc, rate = first_pass(m, codes, lengths, te, ts)
     targets = np.empty((N, ts), np.float32)
     fit = kind == 0

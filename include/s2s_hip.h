@@ -246,6 +246,20 @@ int s2s_export_reads(s2s_handle* h, void* stream, const float* signal, int32_t B
                      int16_t* out_dac, int64_t capacity, float digitisation, float range,
                      float offset_mean, int32_t rna);
 
+/* The ground-truth base-to-signal map of a batch: how many STORED samples (the ones s2s_export_reads keeps) every k-mer of every
+ * chunk owns.  The reference has no counterpart (it writes the signal only); the definitions are the length regulator's
+ * (DESIGN.md section 4).  With te / ts = max_dna_len / max_signal_len of the handle (16 / 250 outside the two geometry modes):
+ *
+ *  signal   device [B][ts], dur device [B][te]: out_signal / out_dur of s2s_predict_chunks / s2s_predict_packed;
+ *  c[j]     = min(ts, sum_{i<=j} max(dur[b][i], 0)), c[-1] = 0 -- saturating: no int32 dwell, however large, wraps the sum;
+ *  out_seg  device uint16 [B][te+1]: out_seg[b][j] = #{t in [c[j-1], c[j]) : signal[b][t] != 0.0f} for j < te (the rows the
+ *           regulator gathers from k-mer j), out_seg[b][te] the same count over the tail [c[te-1], ts) (rows past the last dwell:
+ *           the decoder runs unmasked, so they can be non-zero and survive the strip).
+ * A row sums to the chunk's count of stored samples; counts are exact integers that depend on the chunk's own rows only (not on
+ * B or its neighbours).  B == 0 is a successful no-op; a NULL pointer or B < 0 is S2S_ERR_ARG. */
+int s2s_align_chunks(s2s_handle* h, void* stream, const float* signal /* device [B][ts] */, const int32_t* dur /* device [B][te] */,
+                     int32_t B, uint16_t* out_seg /* device [B][te+1] */);
+
 /* Replaces the signal compression that pyslow5.write_record_batch (svb-zd) and pod5.Writer.add_reads (the svb16 stage of
  * VBZ) run on the host (reference signal_io.py:167-171, 268-282): StreamVByte encoding of the zig-zag deltas of the packed
  * int16 samples, one output blob per row, so that only ~1.1 bytes per sample cross PCIe.
@@ -299,6 +313,29 @@ int64_t s2s_blow5_pack(const uint8_t* prefix, const int64_t* prefix_offs, const 
  * out_offs [n+1].  capacity >= s2s_blow5_pack_bound(total bytes, n) always suffices.  Returns the bytes written, or < 0. */
 int64_t s2s_compress_rows(const uint8_t* in, const int64_t* in_offs, int32_t n_rows, int32_t method, int32_t level,
                           int32_t threads, uint8_t* out, int64_t capacity, int64_t* out_offs);
+
+/* ---- host-side helper (no GPU work, no handle): the base-to-signal alignment of one batch of reads as PAF text, one line per
+ * record of the signal file, formatted on `threads` threads of the same worker pool (an interpreter loop cannot keep up with the
+ * 46 M k-mers/s of a run).
+ *
+ *  seg         [B][te+1]: out_seg of s2s_align_chunks, copied to the host;
+ *  read_first  [R+1]: read r owns chunks read_first[r] .. read_first[r+1]-1;
+ *  read_kmers  [R]: the read's real k-mers K = te * (chunks - 1) + n_valid of its last chunk (the later k-mers of that chunk
+ *              are padding: their samples belong to no base);
+ *  read_offs   [R+1]: out_offsets of s2s_export_reads -- a read without samples has no record and gets no line;
+ *  ids, id_offs [n_ids+1]: the read_id of every record, in record order (n_ids = reads with samples), as one byte blob;
+ *  rna         != 0: the stored signal is reversed per read (s2s_export_reads), so the line walks the k-mers from last to first.
+ * A line, tab separated: read_id, len_raw_signal, sig_start, sig_end, "+", read_id, K, kmer_start, kmer_end (0, K; K, 0 for
+ * RNA), k-mers with samples, K, 255, "ss:Z:" + tokens in stored-signal order from sig_start to sig_end: "N," the next k-mer with
+ * its N >= 1 samples, "ND" the next N k-mers without a sample (zero dwell, cropped away, or stripped), "NI" N samples that belong
+ * to no k-mer (chunk tails, pad k-mers); adjacent D / I runs are merged; insertions in front of the first and behind the last
+ * k-mer are left out of [sig_start, sig_end), k-mers never.
+ * Returns the bytes written (lines in read order), or S2S_ERR_ARG -- also when a read's seg rows do not sum to its samples or
+ * n_ids is not the number of reads with samples.  capacity >= the bound function's value always suffices. */
+int64_t s2s_paf_format_bound(int64_t n_chunks, int32_t te, int32_t n_reads, int64_t id_bytes_total);
+int64_t s2s_paf_format(const uint16_t* seg, int32_t te, const int32_t* read_first, const int64_t* read_kmers,
+                       const int64_t* read_offs, int32_t R, const uint8_t* ids, const int64_t* id_offs, int32_t n_ids,
+                       int32_t rna, int32_t threads, uint8_t* out, int64_t capacity);
 
 /* ---- host-side helper (no GPU work, no handle): replays the DRAWS of the reference's read sampler (utils.py:415-479
  * `sampling`, with the read-length law of utils.py:325-331 `draw_expon_dis`) without building a read, so that a rank of a sharded

@@ -89,6 +89,9 @@ def version():
 @click.option("--attention-path", default="auto", type=click.Choice(["auto", "fast", "exact"]), hidden=True,
               help="Softmax path of the split-f16 decoder: auto = chosen per checkpoint by the engine's calibration launch "
                    "(include/s2s_hip.h: s2s_set_attention_path); exact = the same time whatever the weights.")
+@click.option("--alignment", default=None, type=click.Path(dir_okay=False), hidden=True,
+              help="Also write the ground-truth base-to-signal alignment: one PAF line per record of OUT with the samples of every "
+                   "k-mer in the signal as stored (ss:Z: tag; include/s2s_hip.h: s2s_paf_format). Off by default.")
 @click.option("--gpus", default=1, type=int, hidden=True,
               help="Run on this many GPUs of the node: one process per GPU, the read set sharded, one OUT.rankN file per process "
                    "(the same as starting the command under torchrun --nproc-per-node N).")
@@ -103,7 +106,7 @@ def predict(ctx, fasta, read_input, num_reads, read_length, coverage, out, profi
             duration_sampler, dwell_mean, dwell_std, noise_std, distr, predict_batch_size, export_every_n_samples,
             sample_rate, bps, digitisation, range_val, offset_mean, offset_std, median_before_mean, median_before_std,
             min_noise, min_duration, min_read_len, preserve_read_ids, seed, model, config, verbosity, compute_mode, attention_path,
-            gpus, keep_shards, join_mode):
+            alignment, gpus, keep_shards, join_mode):
     """Generate nanopore signals from a reference genome (default) or from reads (--read-input)."""
     import os
     if gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -117,6 +120,8 @@ def predict(ctx, fasta, read_input, num_reads, read_length, coverage, out, profi
         import time
         t0 = time.time()
         live, make_live = None, None
+        ext_a = os.path.splitext(str(alignment))[1] if alignment else ""
+        align_shards = [f"{str(alignment)[:len(str(alignment)) - len(ext_a)]}.rank{r}{ext_a}" for r in range(gpus)] if alignment else []
         if join_mode == "live" and not keep_shards and not os.environ.get("S2S_DRY_LAUNCH"):
             if not str(out).endswith((".blow5", ".pod5")):
                 raise click.UsageError("--join live handles .blow5 and .pod5 outputs")
@@ -124,7 +129,7 @@ def predict(ctx, fasta, read_input, num_reads, read_length, coverage, out, profi
             base_name = str(out)[:len(str(out)) - len(ext)]
             partial = base_name + ".partial" + ext
             shard_paths = [f"{base_name}.rank{r}{ext}" for r in range(gpus)]       # (parallel.rank_output_path, without its imports)
-            for stale in [partial] + shard_paths:           # (a rank file left by an earlier run must not be mistaken for this run's)
+            for stale in [partial] + shard_paths + align_shards:   # (a rank file left by an earlier run must not be mistaken for this run's)
                 if os.path.exists(stale):
                     os.remove(stale)
             holder = {}
@@ -174,6 +179,10 @@ def predict(ctx, fasta, read_input, num_reads, read_length, coverage, out, profi
                 click.echo(f"{n} reads from {gpus} ranks -> {out}  [launch {launch if launch is None else round(launch, 2)} s, "
                            f"ranks {timing['ranks_seconds']:.2f} s in all, merge {timing['merge_seconds']:.2f} s for "
                            f"{timing['merge_bytes'] / 1e9:.2f} GB]")
+            if alignment and rc == 0 and not keep_shards and not os.environ.get("S2S_DRY_LAUNCH"):
+                # the ranks own contiguous shares of the reads: their alignment files in rank order are the single-process file
+                from .alignment import join_rank_files
+                join_rank_files(align_shards, str(alignment))
             late = reap()                                       # (the merge did not wait for the ranks' teardown: see _launch_ranks)
             rc = rc or late
             timing["total_seconds"] = time.time() - t0
@@ -228,7 +237,7 @@ def predict(ctx, fasta, read_input, num_reads, read_length, coverage, out, profi
                   offset_mean=offset_mean, offset_std=offset_std, median_before_mean=median_before_mean,
                   median_before_std=median_before_std, min_noise=min_noise, min_duration=min_duration,
                   min_read_len=min_read_len, preserve_read_ids=preserve_read_ids, seed=seed, mode=compute_mode,
-                  attention_path=attention_path)
+                  attention_path=attention_path, alignment=alignment)
     logger.info("Prediction finished.")
     if os.environ.get("S2S_TIMING_DIR"):       # a rank of `predict --gpus N`: when it was ready and when it was done, for the parent's summary
         import json

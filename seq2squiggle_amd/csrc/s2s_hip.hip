@@ -836,6 +836,42 @@ __global__ __launch_bounds__(256) void s2s_compact_kernel(const float* __restric
     }
 }
 
+// s2s_align_chunks: where every k-mer of a chunk ended up in the stored signal.  One wave per chunk, lane j owns k-mer j (te <= 64).
+// c[j] = min(T, sum_{i<=j} max(dur[i], 0)) is the length regulator's cumulative dwell cropped at the window; every dwell is clamped
+// to T BEFORE the scan, which gives the same minimum and keeps the sum below 64 * 1024 (no wrap for any int32 input).  The rows
+// the export keeps are one ballot mask per 64 samples (wave-uniform), P(x) = kept samples in rows [0, x) a sum of popcounts over
+// the masks; k-mer j holds P(c[j]) - P(c[j-1]) of them and the tail P(T) - P(c[te-1]).  Integers only, no LDS, no atomics.
+template <int TD>
+__global__ __launch_bounds__(256) void s2s_align_kernel(const float* __restrict__ signal, const int* __restrict__ dur, int B,
+                                                        unsigned short* __restrict__ out_seg, int te, int ts) {
+    const int T = TD ? TD : ts;
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (b >= B) return;
+    int c = 0;
+    if (lane < te) {
+        const int d = dur[(size_t)b * te + lane];
+        c = d < 0 ? 0 : (d > T ? T : d);
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(c, o, 64); if (lane >= o) c += y; }
+    c = c > T ? T : c;                          // lanes >= te carry c[te-1]
+    int below = 0, total = 0;                   // P(c) of this lane; P(T)
+    for (int t0 = 0; t0 < T; t0 += 64) {
+        const int t = t0 + lane;
+        const float v = (t < T) ? signal[(size_t)b * T + t] : 0.0f;
+        const unsigned long long mask = __ballot(v != 0.0f);
+        const int k = c - t0;                   // rows of this mask in front of c: all 64, none, or the low k bits
+        const unsigned long long low = k >= 64 ? ~0ull : (k <= 0 ? 0ull : ((1ull << k) - 1ull));
+        below += __popcll(mask & low);
+        total += __popcll(mask);
+    }
+    const int before = __shfl_up(below, 1, 64);
+    const int last = __shfl(below, te - 1, 64);
+    unsigned short* row = out_seg + (size_t)b * (te + 1);
+    if (lane < te) row[lane] = (unsigned short)(below - (lane ? before : 0));
+    if (lane == 0) row[te] = (unsigned short)(total - last);
+}
+
 // ---- StreamVByte encoders of the output containers (codecs.py states the formats): one 256-thread workgroup per row.
 // VARIANT 32 (slow5 svb-zd): [u32 n][(n+3)/4 control bytes, 2 bits per value][data: 1..4 bytes per value] of the zig-zag
 // deltas widened to 32 bits; VARIANT 16 (pod5 VBZ before zstd): [(n+7)/8 control bytes, 1 bit per value][1..2 bytes per value]
@@ -2010,6 +2046,20 @@ int s2s_export_reads(s2s_handle* h, void* stream_, const float* signal, int32_t 
         hipLaunchKernelGGL(tuned_rows ? s2s_compact_kernel<S2S_T_DEC> : s2s_compact_kernel<0>, dim3((B + 3) / 4), dim3(256), 0, stream,
                            signal, B, h->ws_offs, read_first, R, out_pa, reinterpret_cast<short*>(out_dac), (long long)capacity,
                            digitisation, range, offset_mean, rna, ts);
+    HIP_TRY(h, hipGetLastError());
+    return S2S_OK;
+}
+
+int s2s_align_chunks(s2s_handle* h, void* stream_, const float* signal, const int32_t* dur, int32_t B, uint16_t* out_seg) {
+    if (!h) return S2S_ERR_ARG;
+    if (B < 0) return fail(h, S2S_ERR_ARG, "negative size");
+    if (!signal || !dur || !out_seg) return fail(h, S2S_ERR_ARG, "NULL argument");
+    if (B == 0) return S2S_OK;
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(h, S2S_ERR_HIP, "hipSetDevice failed");
+    const int te = h->cfg.max_dna_len, ts = h->cfg.max_signal_len;    // S2S_T_ENC / S2S_T_DEC except for a geometry-mode handle
+    hipLaunchKernelGGL(ts == S2S_T_DEC ? s2s_align_kernel<S2S_T_DEC> : s2s_align_kernel<0>, dim3((B + 3) / 4), dim3(256), 0,
+                       static_cast<hipStream_t>(stream_), signal, dur, B, reinterpret_cast<unsigned short*>(out_seg), te, ts);
     HIP_TRY(h, hipGetLastError());
     return S2S_OK;
 }

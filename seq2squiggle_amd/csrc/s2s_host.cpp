@@ -504,6 +504,123 @@ int64_t s2s_compress_rows(const uint8_t* in, const int64_t* in_offs, int32_t n, 
 
 }  // extern "C"
 
+// ================================================================================ base-to-signal alignment (PAF)
+// One line per record of the signal file from the per-chunk counts of s2s_align_chunks.  A read is a walk over events in the
+// order of its STORED signal: per chunk its te k-mer segments (a real k-mer while fewer than K have been seen, else a pad k-mer of
+// the last chunk: an insertion) and then the chunk's tail (an insertion); an RNA read is stored reversed, so its walk runs
+// backwards.  Insertions in front of the first and behind the last real k-mer are trimmed into sig_start / sig_end.
+namespace {
+
+inline uint8_t* put_u64(uint8_t* p, uint64_t v) {
+    char tmp[20];
+    int n = 0;
+    do { tmp[n++] = (char)('0' + v % 10); v /= 10; } while (v);
+    while (n) *p++ = (uint8_t)tmp[--n];
+    return p;
+}
+
+// bytes one read's line may take: <= 6 per event (any uint16 count and its letter: "65535,"; a merged run of m insertions or of m
+// empty k-mers never needs more than 6 m) + the fixed columns (seven numbers of <= 20 digits, tabs, "+", "255", "ss:Z:", the line end)
+inline int64_t paf_line_bound(int64_t chunks, int32_t te, int64_t id_len) { return 6 * chunks * (te + 1) + 2 * id_len + 256; }
+
+}  // namespace
+
+extern "C" int64_t s2s_paf_format_bound(int64_t n_chunks, int32_t te, int32_t n_reads, int64_t id_bytes_total) {
+    if (n_chunks < 0 || te < 1 || n_reads < 0 || id_bytes_total < 0) return S2S_ERR_ARG;
+    return 6 * n_chunks * (te + 1) + 2 * id_bytes_total + (int64_t)n_reads * 256;
+}
+
+extern "C" int64_t s2s_paf_format(const uint16_t* seg, int32_t te, const int32_t* read_first, const int64_t* read_kmers,
+                                  const int64_t* read_offs, int32_t R, const uint8_t* ids, const int64_t* id_offs, int32_t n_ids,
+                                  int32_t rna, int32_t threads, uint8_t* out, int64_t capacity) {
+    if (R < 0 || n_ids < 0 || te < 1 || threads < 1 || capacity < 0) return S2S_ERR_ARG;
+    if (R == 0) return n_ids == 0 ? 0 : S2S_ERR_ARG;
+    if (!seg || !read_first || !read_kmers || !read_offs || !id_offs || !out || (n_ids > 0 && !ids)) return S2S_ERR_ARG;
+    // the records of the signal file are the reads with samples, in read order: read r's id is the next unused one
+    std::vector<int32_t> id_of(R);
+    std::vector<int64_t> slot(R + 1), size(R, 0);
+    int32_t used = 0;
+    slot[0] = 0;
+    for (int r = 0; r < R; ++r) {
+        const int64_t chunks = (int64_t)read_first[r + 1] - read_first[r], n = read_offs[r + 1] - read_offs[r];
+        if (chunks < 0 || n < 0 || read_kmers[r] < 0 || read_kmers[r] > chunks * te) return S2S_ERR_ARG;
+        id_of[r] = -1;
+        slot[r + 1] = slot[r];
+        if (n == 0) continue;                                    // no samples: no record, no line
+        if (used >= n_ids || id_offs[used + 1] < id_offs[used] || read_kmers[r] < 1) return S2S_ERR_ARG;
+        id_of[r] = used++;
+        slot[r + 1] += paf_line_bound(chunks, te, id_offs[used] - id_offs[used - 1]);
+    }
+    if (used != n_ids || slot[R] > capacity) return S2S_ERR_ARG;
+    std::atomic<int> failed{0};
+    {
+        std::lock_guard<std::mutex> guard(g_pool_mutex);
+        if (!g_pool || g_pool->size() < threads) { delete g_pool; g_pool = new Pool(threads); }
+        g_pool->run(R, [&](int r, int) {
+            if (id_of[r] < 0) return;
+            const int64_t b0 = read_first[r], chunks = (int64_t)read_first[r + 1] - b0, n_ev = chunks * (te + 1);
+            const int64_t K = read_kmers[r], len = read_offs[r + 1] - read_offs[r];
+            // event e of the forward walk: chunk e / (te+1), slot e % (te+1); a k-mer when slot < te and chunk * te + slot < K
+            auto count = [&](int64_t e) { return (int64_t)seg[(b0 + e / (te + 1)) * (te + 1) + e % (te + 1)]; };
+            auto is_kmer = [&](int64_t e) { const int64_t j = e % (te + 1); return j < te && (e / (te + 1)) * te + j < K; };
+            // forward event 0 is k-mer 0 and e_last the last real k-mer (K >= 1): what lies behind it is trimmed
+            const int64_t e_last = ((K - 1) / te) * (te + 1) + (K - 1) % te;
+            int64_t lead = 0, trail = 0, total = 0, mapped = 0;
+            for (int64_t e = 0; e < n_ev; ++e) {
+                const int64_t c = count(e);
+                total += c;
+                if (e > e_last) trail += c;
+                else if (c && is_kmer(e)) ++mapped;
+            }
+            if (total != len) { failed = 1; return; }            // seg and the export's offsets describe different signals
+            if (rna) std::swap(lead, trail);
+            uint8_t* p = out + slot[r];
+            const uint8_t* id = ids + id_offs[id_of[r]];
+            const int64_t id_len = id_offs[id_of[r] + 1] - id_offs[id_of[r]];
+            auto tab = [&] { *p++ = '\t'; };
+            std::memcpy(p, id, id_len); p += id_len; tab();
+            p = put_u64(p, len); tab();
+            p = put_u64(p, lead); tab();
+            p = put_u64(p, len - trail); tab();
+            *p++ = '+'; tab();
+            std::memcpy(p, id, id_len); p += id_len; tab();
+            p = put_u64(p, K); tab();
+            p = put_u64(p, rna ? K : 0); tab();
+            p = put_u64(p, rna ? 0 : K); tab();
+            p = put_u64(p, mapped); tab();
+            p = put_u64(p, K); tab();
+            std::memcpy(p, "255\tss:Z:", 9); p += 9;
+            int64_t run_d = 0, run_i = 0;
+            for (int64_t s = 0; s <= e_last; ++s) {
+                const int64_t e = rna ? e_last - s : s, c = count(e);
+                if (is_kmer(e)) {
+                    if (run_i) { p = put_u64(p, run_i); *p++ = 'I'; run_i = 0; }
+                    if (c) {
+                        if (run_d) { p = put_u64(p, run_d); *p++ = 'D'; run_d = 0; }
+                        p = put_u64(p, c); *p++ = ',';
+                    } else {
+                        ++run_d;
+                    }
+                } else if (c) {
+                    if (run_d) { p = put_u64(p, run_d); *p++ = 'D'; run_d = 0; }
+                    run_i += c;
+                }
+            }
+            if (run_d) { p = put_u64(p, run_d); *p++ = 'D'; }      // (the walk ends on a k-mer: no insertion is pending)
+            *p++ = '\n';
+            size[r] = p - (out + slot[r]);
+            if (size[r] > slot[r + 1] - slot[r]) failed = 1;     // (cannot happen with paf_line_bound)
+        });
+    }
+    if (failed) return S2S_ERR_ARG;
+    int64_t pos = 0;
+    for (int r = 0; r < R; ++r) {                               // close the gaps, in read order
+        if (size[r] && pos != slot[r]) std::memmove(out + pos, out + slot[r], size[r]);
+        pos += size[r];
+    }
+    return pos;
+}
+
 // ================================================================================ read-sampler replay
 // The reference samples reads one after the other from Python's global `random` (Mersenne Twister): per attempt a start
 // position (random.randint), a strand (random.choice, DNA only), and per N of an accepted read a replacement base; the read

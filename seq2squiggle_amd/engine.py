@@ -261,6 +261,30 @@ class Engine:
         self._check(rc, "s2s_export_reads")
         return {"offsets": offs, "pa": pa, "dac": dac}
 
+    def align_chunks(self, signal: torch.Tensor, dur: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
+        """The base-to-signal map of a batch (s2s_align_chunks): signal float32 [B,250] and dur int32 [B,16] as predict returns
+        them -> uint16 [B,17]: per chunk the stored (non-zero) samples of each of its 16 k-mers, then of the tail behind the last
+        dwell; a row sums to the samples export_reads keeps of the chunk.  out: write there (contiguous uint16, at least B*17
+        elements, e.g. a view into the buffer that leaves the device as one copy).  16 / 250 are the engine's t_enc / t_dec."""
+        B = int(signal.shape[0]) if signal.dim() == 2 else -1
+        T_ENC, T_DEC = self.t_enc, self.t_dec
+        if signal.dtype != torch.float32 or not signal.is_contiguous() or signal.dim() != 2 or signal.shape[1] != T_DEC:
+            raise ValueError(f"signal must be contiguous float32 [B,{T_DEC}]")
+        if dur.dtype != torch.int32 or not dur.is_contiguous() or tuple(dur.shape) != (B, T_ENC):
+            raise ValueError(f"dur must be contiguous int32 [{B},{T_ENC}]")
+        if signal.device != self.device or dur.device != self.device:
+            raise ValueError(f"signal and dur must live on {self.device}")
+        n = B * (T_ENC + 1)
+        if out is not None and (out.dtype != torch.uint16 or not out.is_contiguous() or out.device != self.device or out.numel() < n):
+            raise ValueError(f"out must be a contiguous uint16 tensor of at least {n} elements on {self.device}")
+        seg = out.reshape(-1)[:n].view(B, T_ENC + 1) if out is not None else torch.empty(B, T_ENC + 1, dtype=torch.uint16, device=self.device)
+        if B == 0:                      # (an empty tensor has no address to pass)
+            return seg
+        with torch.cuda.device(self.device):
+            rc = _lib.lib().s2s_align_chunks(self._h, self._stream(), _ptr(signal), _ptr(dur), B, _ptr(seg))
+        self._check(rc, "s2s_align_chunks")
+        return seg
+
     @staticmethod
     def svb_capacity(total_samples_bound: int, n_rows: int, variant: int) -> int:
         """Bytes s2s_svb_encode may write for n_rows rows holding at most total_samples_bound samples together."""

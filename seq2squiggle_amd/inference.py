@@ -251,7 +251,7 @@ def super_batches(reads: Iterable[Tuple[str, str]], k: int, max_chunks: int, t_e
 
 
 def run_streaming(model, reads: Iterable[Tuple[str, str]], writer, profile_dict: dict, profile_name: str,
-                  max_chunks: int = 32768, trace: list = None) -> int:
+                  max_chunks: int = 32768, trace: list = None, alignment=None) -> int:
     """The predict loop without per-chunk Python objects: whole reads are grouped into super-batches of about
     `max_chunks` chunks; per super-batch one H2D of the packed read bytes, s2s_predict_packed, s2s_export_reads
     (zero-strip + int16 conversion on the GPU), one D2H of the packed int16 samples on a copy stream, then the writer.  Produces the
@@ -260,7 +260,12 @@ def run_streaming(model, reads: Iterable[Tuple[str, str]], writer, profile_dict:
     Three stages overlap: while the GPU works on super-batch i the host samples/packs i+1, and a writer thread
     compresses and writes i-1.  Record metadata (the np.random offset draws of signal_io.py:129-132) is built on the
     calling thread in read order, so the output does not depend on thread timing.  `trace`: a list that receives
-    (event, seconds) pairs for tools/e2e_timeline.py."""
+    (event, seconds) pairs for tools/e2e_timeline.py.
+
+    `alignment`: a path or a binary file object that receives the base-to-signal alignment, one PAF line per record in record order
+    (alignment.py).  Only then s2s_align_chunks runs, straight after the export on the same `signal` / `dur`, and its counts
+    travel as one more 16-byte-aligned section at the END of the super-batch's device buffer; without it no kernel is added and the
+    buffer is byte for byte what it was."""
     import time
 
     def mark(ev):
@@ -284,6 +289,13 @@ def run_streaming(model, reads: Iterable[Tuple[str, str]], writer, profile_dict:
     n_launched = 0
 
     gpu_rows = writer.gpu_signal_rows() if hasattr(writer, "gpu_signal_rows") else None   # (svb variant, samples per row) | None
+    align_f, align_own = None, False
+    if alignment is not None:
+        from .alignment import format_alignment
+        from .signal_io import cpu_share
+        align_own = not hasattr(alignment, "write")
+        align_f = open(os.fspath(alignment), "wb") if align_own else alignment
+        align_threads = cpu_share()
 
     def launch(group):
         nonlocal total, n_launched
@@ -319,35 +331,54 @@ def run_streaming(model, reads: Iterable[Tuple[str, str]], writer, profile_dict:
         # kernel to end; a large copy goes through the DMA engines beside it.  The whole capacity is copied (its size is known
         # without a sync: 16 MB of int16 / 17 MB of coded signal per 32 k chunks) into pinned memory.
         cap = B * t_dec
+        # (--alignment only) the k-mer counts ride in the same buffer, behind the payload: a second, small copy would be the shader
+        # copy described above
+        seg_bytes = 2 * B * (t_enc + 1) if align_f is not None else 0
+
+        def with_seg(size):
+            """-> (bytes of the buffer, where the counts start | None)"""
+            if not seg_bytes:
+                return size, None
+            at = size + -size % 16
+            return at + seg_bytes, at
         if gpu_rows:
             N = int(row_read.shape[0])
             blob_cap = model.engine.svb_capacity(cap, N, gpu_rows[0])
             head = 8 * (R + 1) + 8 * (N + 1)
             head += -head % 16
-            buf = torch.empty(head + max(blob_cap, 1), dtype=torch.uint8, device=dev)
+            size, seg_at = with_seg(head + max(blob_cap, 1))
+            buf = torch.empty(size, dtype=torch.uint8, device=dev)
             offs_d = buf[:8 * (R + 1)].view(torch.int64)
             rows_d = buf[8 * (R + 1): 8 * (R + 1) + 8 * (N + 1)].view(torch.int64)
             ex = model.engine.export_reads(out["signal"], ins[3], profile_dict["digitisation"], profile_dict["range"],
                                            profile_dict["offset_mean"], rna=rna, want_pa=False, want_dac=True, out_offsets=offs_d)
             mark("export queued")
+            if seg_bytes:
+                model.engine.align_chunks(out["signal"], out["dur"], out=buf[seg_at: seg_at + seg_bytes].view(torch.uint16))
             # the signal leaves the GPU StreamVByte-coded (~1.1-1.3 bytes per sample)
-            model.engine.svb_encode(ex["dac"], ex["offsets"], ins[4], ins[5], gpu_rows[1], gpu_rows[0], cap, out=buf[head:],
-                                    out_offsets=rows_d)
+            model.engine.svb_encode(ex["dac"], ex["offsets"], ins[4], ins[5], gpu_rows[1], gpu_rows[0], cap,
+                                    out=buf[head: head + max(blob_cap, 1)], out_offsets=rows_d)
         else:
             head = 8 * (R + 1)
             head += -head % 16
-            buf = torch.empty(head + 2 * cap, dtype=torch.uint8, device=dev)
+            size, seg_at = with_seg(head + 2 * cap)
+            buf = torch.empty(size, dtype=torch.uint8, device=dev)
             model.engine.export_reads(out["signal"], ins[3], profile_dict["digitisation"], profile_dict["range"],
                                       profile_dict["offset_mean"], rna=rna, want_pa=False, want_dac=True,
-                                      out_offsets=buf[:8 * (R + 1)].view(torch.int64), out_dac=buf[head:].view(torch.int16))
+                                      out_offsets=buf[:8 * (R + 1)].view(torch.int64),
+                                      out_dac=buf[head: head + 2 * cap].view(torch.int16))
             mark("export queued")
+            if seg_bytes:
+                model.engine.align_chunks(out["signal"], out["dur"], out=buf[seg_at: seg_at + seg_bytes].view(torch.uint16))
         ready = torch.cuda.Event()
         ready.record(main)
         mark("launched")
-        return names, buf, (R, head, row_read if gpu_rows else None), ready
+        # (--alignment) what the formatter needs beside the counts: the chunk ranges and the real k-mers of every read
+        align = (seg_at, read_first, np.fromiter((len(s) - k + 1 for s, _ in group), np.int64, R)) if seg_bytes else None
+        return names, buf, (R, head, row_read if gpu_rows else None), ready, align
 
     def collect(job):
-        ids, buf, (R, head, row_read), ready = job
+        ids, buf, (R, head, row_read), ready, align = job
         # The D2H is issued only once the super-batch's kernels have FINISHED (the calling thread has nothing else to do at this
         # point: the next super-batch is already queued behind them).  Queued earlier, behind a stream-side wait for `ready`, the
         # runtime carries the copy out as a 256-workgroup shader copy, and no wave of it fits on a CU while the next predict kernel
@@ -376,14 +407,24 @@ def run_streaming(model, reads: Iterable[Tuple[str, str]], writer, profile_dict:
             recs = writer.svb_records(ids, offs, row_read, row_offs, host[head: head + int(row_offs[-1])])
         else:
             recs = writer.dac_records(ids, host[head: head + 2 * int(offs[-1])].view(np.int16), offs)
+        text = None
+        if align is not None:
+            # one line per record, with the id the writer has just given it (generated or preserved)
+            mark("alignment")
+            seg_at, read_first, kmers = align
+            B = int(read_first[-1])
+            text = format_alignment(host[seg_at: seg_at + 2 * B * (t_enc + 1)].view(np.uint16), t_enc, read_first, kmers, offs,
+                                    [str(r["read_id"]) for r in recs], rna, align_threads)
         mark("wait writer")
         while pending and (pending[0].done() or len(pending) >= MAX_PENDING):
             pending.popleft().result()              # (re-raises what the writer thread raised)
         mark("submit")
 
-        def job_(recs=recs):
+        def job_(recs=recs, text=text):
             mark("writer start")
             writer.write_records(recs)
+            if text is not None:                    # behind the batch's records: both files stay in read order
+                align_f.write(text)
             mark("writer end")
         pending.append(io.submit(job_))
 
@@ -409,6 +450,8 @@ def run_streaming(model, reads: Iterable[Tuple[str, str]], writer, profile_dict:
     finally:
         if hasattr(writer, "close"):               # POD5: run-info and reads tables, footer (on the writer thread as well)
             io.submit(writer.close).result()
+        if align_f is not None:                    # (on the writer thread: behind every write queued there)
+            io.submit(align_f.close if align_own else align_f.flush).result()
         mark("done")
     return total
 
@@ -419,12 +462,16 @@ def inference_run(config: dict, saved_weights: str, fasta: str, read_input: bool
                   sample_rate: int, bps: int, digitisation: int, range_val: float, offset_mean: float, offset_std: float,
                   median_before_mean: float, median_before_std: float, min_noise: float, min_duration: float,
                   min_read_len: int, preserve_read_ids: bool, seed: int, mode: Optional[str] = None, streaming: bool = True,
-                  attention_path: str = "auto"):
+                  attention_path: str = "auto", alignment: Optional[str] = None):
     """Same 30 parameters as the reference (inference.py:270-301) plus `mode` (decoder arithmetic), `streaming`
     (True: run_streaming; False: the reference's predict_step / export_and_clear_results flow, batch by batch) and
-    `attention_path` ("auto": the engine's calibration decides; "fast" / "exact": Engine.attention_path is set to it)."""
+    `attention_path` ("auto": the engine's calibration decides; "fast" / "exact": Engine.attention_path is set to it) and
+    `alignment` (a path: the base-to-signal alignment of every record as PAF, alignment.py; a rank of a multi-process run writes
+    rank_output_path(alignment); streaming runs only)."""
     if attention_path not in ("auto", "fast", "exact"):
         raise ValueError("attention_path must be 'auto', 'fast' or 'exact'")
+    if alignment is not None and not streaming:
+        raise ValueError("alignment needs the streaming path (streaming=True): the batch-by-batch flow keeps no k-mer counts")
     profile_dict = get_profile(profile)
     profile_dict = update_profile(profile_dict, sample_rate=sample_rate, bps=bps, digitisation=digitisation, range=range_val,
                                   offset_mean=offset_mean, offset_std=offset_std, median_before_mean=median_before_mean,
@@ -439,6 +486,8 @@ def inference_run(config: dict, saved_weights: str, fasta: str, read_input: bool
     writer, export_every_n_samples = get_writer(rank_output_path(str(out), rank, world), profile_dict, ideal_mode,
                                                 export_every_n_samples, profile_name=profile,
                                                 preserve_read_ids=preserve_read_ids)
+    if alignment is not None and not hasattr(writer, "dac_records"):
+        raise ValueError(f"alignment needs a writer with dac_records (the streaming path); {type(writer).__name__} has none")
     if saved_weights is None:
         saved_weights = get_saved_weights(profile)             # (inference.py:370-372; the cache only: no network here)
     first_chunk, first_read, total_l = 0, 0, 0
@@ -511,7 +560,9 @@ def inference_run(config: dict, saved_weights: str, fasta: str, read_input: bool
         import time
         _TRACE.append(("model ready", time.perf_counter()))
     if streaming and hasattr(writer, "dac_records"):
-        n_chunks = run_streaming(load_model, reads, writer, profile_dict, profile, trace=_TRACE)
+        # (a rank without reads still leaves its -- empty -- alignment file: run_streaming opens it before the first read)
+        n_chunks = run_streaming(load_model, reads, writer, profile_dict, profile, trace=_TRACE,
+                                 alignment=None if alignment is None else rank_output_path(str(alignment), rank, world))
     else:
         for batch in iter_batches(reads, config["seq_kmer"], predict_batch_size, load_model.device, load_model.engine.t_enc):
             load_model.predict_step(batch)

@@ -31,10 +31,25 @@ extern "C" {
 #define S2S_ERR_BLOB (-3)    /* weight blob has the wrong size            */
 #define S2S_ERR_CODEC (-4)   /* a host compression codec is unavailable (libzstd.so.1 not loadable) or failed */
 
-/* Decoder arithmetic.  F32 and F16X3 stay inside the 1e-4 pA MAE parity bound.
+/* Decoder arithmetic.  F32 stays inside the 1e-4 pA MAE parity bound whatever the magnitudes of the weights (it is bit-invariant
+ * under the power-of-two rescalings below); F16X3 stays inside it over the measured range stated with the mode.
  *   S2S_MODE_F32    every product on the f32-input MFMA (v_mfma_f32_16x16x4_f32), exact fp32;
- *   S2S_MODE_F16X3  operands split into two f16 halves (22 bits), three f16 MFMA products with
- *                   fp32 accumulation per original product (v_mfma_f32_16x16x32_f16). */
+ *   S2S_MODE_F16X3  operands split into two f16 halves, three f16 MFMA products with fp32 accumulation per original product
+ *                   (v_mfma_f32_16x16x32_f16).  The pair carries 22 significant bits only while |x| >= 2^-3 (the lo half a normal
+ *                   f16); below, the lo half is a subnormal and the pair has an absolute error near 2^-25 whatever the size of
+ *                   x.  Nothing rescales before the split, so the bound depends on where a checkpoint puts its magnitudes.
+ *                   Measured range (one MI355X, the synthetic k = 9 checkpoint, tests/test_gpu_magnitudes.py, LABNOTES.md round
+ *                   16): with a function-preserving rewrite by s = 2^e in every FFT block of the decoder and the encoder, the
+ *                   parity bounds (MAE < 1e-4 pA, max < 2e-3 pA, within 5 x the fp32 oracle's distance to fp64, dwell indices
+ *                   exact) hold for
+ *                     pos_ffn.w_1 x s, w_2 / s      e = -3 ... +2   (decoder alone -4 ... +3, encoder alone -4 ... +2)
+ *                     slf_attn.w_vs x s, fc / s     e = -3 ... +2   (decoder alone -4 ... +2, encoder alone -3 ... +4)
+ *                     slf_attn.w_qs x s, w_ks / s   e = -4 ... +6   (decoder alone -4 ... +4, encoder alone -6 ... +4)
+ *                   Outside, the error grows by about 2 x per binade (MAE 4e-4 ... 1e-3 pA at e = +-6, 3e-3 ... 8e-3 pA at
+ *                   e = +-10) while the signal stays finite and the dwell indices exact.  Range: a value of magnitude >= 65,504
+ *                   in the FFN hidden activation, V, the attention output, Q or K (or in a weight) becomes inf in its hi half and
+ *                   NaN in the product; the ReLU turns that into 0 and the zero-strip removes the sample, so the read gets
+ *                   shorter without an error -- such a checkpoint is outside the mode's range; use S2S_MODE_F32. */
 #define S2S_MODE_F32 0
 #define S2S_MODE_F16X3 1
 /* (value 2 is retired: a 32x32x16-tiled variant of F16X3 that never beat it) */

@@ -97,8 +97,18 @@ def sinusoid_table(n_position: int, d_hid: int) -> torch.Tensor:
     return tab.float()
 
 
-def mha(sd: Dict[str, torch.Tensor], p: str, x: torch.Tensor, n_head: int) -> torch.Tensor:
-    """MultiHeadAttention.forward (layers.py:64-88) + ScaledDotProductAttention (layers.py:19-41), eval, mask=None."""
+def _tap(taps, key: str, t: torch.Tensor) -> None:
+    """taps[key] = max |t| as a Python float (``taps`` None: nothing is recorded)."""
+    if taps is not None:
+        taps[key] = float(t.abs().max()) if t.numel() else 0.0
+
+
+def mha(sd: Dict[str, torch.Tensor], p: str, x: torch.Tensor, n_head: int, taps: Optional[dict] = None) -> torch.Tensor:
+    """MultiHeadAttention.forward (layers.py:64-88) + ScaledDotProductAttention (layers.py:19-41), eval, mask=None.
+
+    taps: a dict that receives the largest magnitude of Q, K, V (``p + "q"`` / ``"k"`` / ``"v"``) and of the attention output in
+    front of ``fc`` (``p + "attn_out"``).
+    """
     B, T, D = x.shape
     d_k = D // n_head
     q = F.linear(x, sd[p + "w_qs.weight"], sd[p + "w_qs.bias"]).view(B, T, n_head, d_k)
@@ -107,35 +117,40 @@ def mha(sd: Dict[str, torch.Tensor], p: str, x: torch.Tensor, n_head: int) -> to
     q = q.permute(2, 0, 1, 3).contiguous().view(-1, T, d_k)
     k = k.permute(2, 0, 1, 3).contiguous().view(-1, T, d_k)
     v = v.permute(2, 0, 1, 3).contiguous().view(-1, T, d_k)
+    _tap(taps, p + "q", q)
+    _tap(taps, p + "k", k)
+    _tap(taps, p + "v", v)
     attn = torch.bmm(q, k.transpose(1, 2)) / (d_k ** 0.5)          # layers.py:20-21, temperature layers.py:58
     attn = torch.softmax(attn, dim=2)                             # layers.py:39
     out = torch.bmm(attn, v)                                      # layers.py:40
     out = out.view(n_head, B, T, d_k).permute(1, 2, 0, 3).contiguous().view(B, T, -1)
+    _tap(taps, p + "attn_out", out)
     out = F.linear(out, sd[p + "fc.weight"], sd[p + "fc.bias"])   # layers.py:85
     return F.layer_norm(out + x, (D,), sd[p + "layer_norm.weight"], sd[p + "layer_norm.bias"], 1e-5)
 
 
-def ffn(sd, p: str, x: torch.Tensor) -> torch.Tensor:
-    """PositionwiseFeedForward.forward (layers.py:108-113), eval."""
-    h = F.linear(torch.relu(F.linear(x, sd[p + "w_1.weight"], sd[p + "w_1.bias"])),
-                 sd[p + "w_2.weight"], sd[p + "w_2.bias"])
+def ffn(sd, p: str, x: torch.Tensor, taps: Optional[dict] = None) -> torch.Tensor:
+    """PositionwiseFeedForward.forward (layers.py:108-113), eval.  taps: receives max |hidden activation| as ``p + "hidden"``."""
+    hid = torch.relu(F.linear(x, sd[p + "w_1.weight"], sd[p + "w_1.bias"]))
+    _tap(taps, p + "hidden", hid)
+    h = F.linear(hid, sd[p + "w_2.weight"], sd[p + "w_2.bias"])
     return F.layer_norm(h + x, (x.shape[-1],), sd[p + "layer_norm.weight"], sd[p + "layer_norm.bias"], 1e-5)
 
 
-def fft_block(sd, p: str, x: torch.Tensor, n_head: int) -> torch.Tensor:
+def fft_block(sd, p: str, x: torch.Tensor, n_head: int, taps: Optional[dict] = None) -> torch.Tensor:
     """FFTBlock.forward (layers.py:135-142)."""
-    return ffn(sd, p + "pos_ffn.", mha(sd, p + "slf_attn.", x, n_head))
+    return ffn(sd, p + "pos_ffn.", mha(sd, p + "slf_attn.", x, n_head, taps), taps)
 
 
 # --------------------------------------------------------------------------- modules.py
-def encoder(sd, cfg, x: torch.Tensor):
+def encoder(sd, cfg, x: torch.Tensor, taps: Optional[dict] = None):
     """Encoder.forward (modules.py:65-89) -> (enc_out, emb_out)."""
     s = torch.relu(F.linear(x, sd["encoders.src_emb.weight"], sd["encoders.src_emb.bias"]))
     for i in range(cfg["pre_layers"]):
         s = torch.relu(F.linear(s, sd[f"encoders.pre_net_stack.{i}.weight"], sd[f"encoders.pre_net_stack.{i}.bias"]))
     e = s + sd["encoders.position_enc"][0]                         # modules.py:80 (slice is a no-op)
     for l in range(cfg["encoder_layers"]):
-        e = fft_block(sd, f"encoders.layer_stack.{l}.", e, cfg["encoder_heads"])
+        e = fft_block(sd, f"encoders.layer_stack.{l}.", e, cfg["encoder_heads"], taps)
     return e, s
 
 
@@ -198,11 +213,11 @@ def length_regulate(x: torch.Tensor, sigma: torch.Tensor, dur: torch.Tensor, max
     return out, sx
 
 
-def decoder(sd, cfg, h: torch.Tensor) -> torch.Tensor:
+def decoder(sd, cfg, h: torch.Tensor, taps: Optional[dict] = None) -> torch.Tensor:
     """Decoder.forward (modules.py:133-142) -> [B,250] scaled units."""
     h = h + sd["decoders.position_enc"][0]                         # modules.py:136
     for l in range(cfg["decoder_layers"]):
-        h = fft_block(sd, f"decoders.layer_stack_FFT.{l}.", h, cfg["decoder_heads"])
+        h = fft_block(sd, f"decoders.layer_stack_FFT.{l}.", h, cfg["decoder_heads"], taps)
     return torch.relu(F.linear(h, sd["decoders.out_linear.weight"], sd["decoders.out_linear.bias"])).squeeze(-1)
 
 
@@ -224,17 +239,19 @@ def finish(y_scaled: torch.Tensor, sigma_ext: torch.Tensor, z01: Optional[torch.
 def predict_chunks(sd: Dict[str, torch.Tensor], cfg: dict, codes: np.ndarray, params: PredictParams,
                    inject_g: Optional[torch.Tensor] = None, inject_z01: Optional[torch.Tensor] = None,
                    inject_zdw: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None,
-                   dtype=torch.float32, stages: bool = False):
+                   dtype=torch.float32, stages: bool = False, taps: Optional[dict] = None):
     """predict_step (model.py:195-250) for a batch of chunks given as codes [B,16,k].
 
     Returns dict with at least ``signal`` [B,250] (pA, fp) and ``dur`` [B,16] int32.
     With ``inject_*`` None the oracle draws from torch's own generators (statistical use only).
+    ``taps``: a dict that receives, per FFT block of the encoder and the decoder, the largest magnitude of the intermediates
+    its Linear layers produce (see ``mha`` and ``ffn``), keyed by the block's state_dict prefix + name.
     """
     if dtype != torch.float32:
         sd = {k: v.to(dtype) for k, v in sd.items()}
     B = codes.shape[0]
     x = one_hot(codes, dtype)
-    enc_out, emb_out = encoder(sd, cfg, x)
+    enc_out, emb_out = encoder(sd, cfg, x, taps)
     sigma = noise_sampler(sd, emb_out)
     conc = rate = None
     g = inject_g
@@ -248,7 +265,7 @@ def predict_chunks(sd: Dict[str, torch.Tensor], cfg: dict, codes: np.ndarray, pa
         zdw = torch.randn(B, cfg["max_dna_len"], generator=generator, dtype=dtype)
     dur = durations(params, B, g, zdw, dtype, t_enc=cfg["max_dna_len"])
     h, sigma_ext = length_regulate(enc_out, sigma, dur, cfg["max_signal_len"])
-    y_scaled = decoder(sd, cfg, h)
+    y_scaled = decoder(sd, cfg, h, taps)
     z01 = inject_z01
     if params.noise_std > 0 and z01 is None:
         z01 = torch.randn(B, cfg["max_signal_len"], generator=generator, dtype=dtype)

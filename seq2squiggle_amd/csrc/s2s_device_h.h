@@ -3,9 +3,10 @@
 // The f32-input MFMA (s2s_device.h) runs on the same FMA lanes as the vector ALU: softmax VALU
 // work and matrix work serialise and the block tops out near 57 % of the f32 matrix rate.  Here
 // every product a*b is evaluated as  a_hi*b_hi + a_hi*b_lo + a_lo*b_hi  with a = a_hi + a_lo split
-// into two f16 values (22 significant bits), on v_mfma_f32_16x16x32_f16 with fp32 accumulation:
+// into two f16 values (22 significant bits while |a| >= 2^-3; below, a_lo is a subnormal f16 and the
+// pair has an absolute error near 2^-25 instead), on v_mfma_f32_16x16x32_f16 with fp32 accumulation:
 // products of two f16 are exact in fp32, so the only errors are the 2^-22 representation error of
-// each operand and the dropped lo*lo term.  Measured end to end (tests/test_gpu_parity.py) the
+// each operand (for |a| >= 2^-3) and the dropped lo*lo term.  Measured end to end (tests/test_gpu_parity.py) the
 // signal stays within the same 1e-4 pA MAE bound as the f32 path.  The matrix cores run beside the
 // vector ALU, which is left with the softmax, the hi/lo splits and the LayerNorms.
 //
@@ -54,7 +55,8 @@ struct HL { h8 hi, lo; };
 
 __device__ __forceinline__ h8 as_h8(const f32x4 v) { return __builtin_bit_cast(h8, v); }
 
-// x = hi + lo with hi = f16(x) (round to nearest), lo = f16(x - hi): 22 significant bits, in three
+// x = hi + lo with hi = f16(x) (round to nearest), lo = f16(x - hi): 22 significant bits for |x| >= 2^-3
+// (a subnormal lo below that: absolute error near 2^-25; include/s2s_hip.h states the measured range), in three
 // VALU instructions per pair of values: v_cvt_pk_f16_f32, then v_fma_mix{lo,hi}_f16 computes
 // x * 1.0 - f32(hi) from the fp32 value and the f16 half with a single rounding straight to f16.
 // Written in C so that every instruction stays visible to the compiler's hazard recogniser (MFMA <->

@@ -275,6 +275,22 @@ int s2s_export_reads(s2s_handle* h, void* stream, const float* signal, int32_t B
 int s2s_align_chunks(s2s_handle* h, void* stream, const float* signal /* device [B][ts] */, const int32_t* dur /* device [B][te] */,
                      int32_t B, uint16_t* out_seg /* device [B][te+1] */);
 
+/* The level statistics of every k-mer's STORED samples: what s2s_align_chunks counts, summed.  No counterpart in the reference.
+ *
+ *  signal, dur, B, te / ts   as for s2s_align_chunks;
+ *  digitisation, range, offset   the calibration s2s_export_reads is given (offset_mean there);
+ *  q(t)       for a stored sample t (signal[b][t] != 0.0f) the int16 s2s_export_reads stores for it: the same float32 expression,
+ *             round-half-even and int16 wrap (one device function serves both kernels);
+ *  out_seg    device uint16 [B][te+1]: by definition what s2s_align_chunks writes (same c[j], saturation and tail slot te);
+ *  out_sum    device int32 [B][te+1]: the sum of q(t) over the stored samples of slot j;
+ *  out_sumsq  device int64 [B][te+1]: the sum of q(t)^2 over the same samples.
+ * Integers only: |sum| <= 1024 * 32768 = 2^25 and sumsq <= 2^40, so both are exact for every input and depend neither on the
+ * order of summation nor on B or a chunk's neighbours.  B == 0 is a successful no-op; a NULL pointer, B < 0, range == 0 or
+ * digitisation == 0 is S2S_ERR_ARG. */
+int s2s_event_stats(s2s_handle* h, void* stream, const float* signal /* device [B][ts] */, const int32_t* dur /* device [B][te] */,
+                    int32_t B, float digitisation, float range, float offset, uint16_t* out_seg /* device [B][te+1] */,
+                    int32_t* out_sum /* device [B][te+1] */, int64_t* out_sumsq /* device [B][te+1] */);
+
 /* Replaces the signal compression that pyslow5.write_record_batch (svb-zd) and pod5.Writer.add_reads (the svb16 stage of
  * VBZ) run on the host (reference signal_io.py:167-171, 268-282): StreamVByte encoding of the zig-zag deltas of the packed
  * int16 samples, one output blob per row, so that only ~1.1 bytes per sample cross PCIe.
@@ -351,6 +367,44 @@ int64_t s2s_paf_format_bound(int64_t n_chunks, int32_t te, int32_t n_reads, int6
 int64_t s2s_paf_format(const uint16_t* seg, int32_t te, const int32_t* read_first, const int64_t* read_kmers,
                        const int64_t* read_offs, int32_t R, const uint8_t* ids, const int64_t* id_offs, int32_t n_ids,
                        int32_t rna, int32_t threads, uint8_t* out, int64_t capacity);
+
+/* ---- host-side helper (no GPU work, no handle): the per-k-mer event table of one batch of reads (`predict --events`) as text, on
+ * `threads` threads of the same worker pool.  seg, te, read_first, read_kmers, read_offs, R, ids, id_offs, n_ids, rna, threads, out
+ * and capacity are those of s2s_paf_format; further:
+ *
+ *  sum, sumsq   [B][te+1]: out_sum / out_sumsq of s2s_event_stats, copied to the host;
+ *  letters, letter_offs [R+1]: the cleaned letters of every read as one byte blob (the bytes s2s_predict_packed reads); read r owns
+ *               letters[letter_offs[r] .. letter_offs[r+1]), at least K + k - 1 of them;   k: the k-mer length;
+ *  digitisation, range, offset   the record calibration (floats, widened to double);
+ *  dac          NULL, or the packed int16 samples of the batch (out_dac of s2s_export_reads: read r at read_offs[r]);
+ *  with_header  != 0: the text starts with the header line.
+ * Tab separated, "\n" ended; the header is
+ *      read_name  position  model_kmer  start_idx  end_idx  event_level_mean  event_stdv  [samples]
+ * and there is one row per REAL k-mer (position < K) that owns >= 1 stored sample, reads in order, k-mers in order; a k-mer
+ * without samples, pad k-mers and chunk tails get no row.  read_name: the record's id; position: 0-based k-mer index in the read;
+ * model_kmer: the k letters at [position, position + k); [start_idx, end_idx): the k-mer's samples in the record's stored signal,
+ * by the walk of s2s_paf_format (insertions advance the cursor and get no row; an RNA signal is stored reversed, so k-mer j with
+ * forward range [s, e) gets [L - e, L - s) and start_idx falls as position rises).  With n, S, Q the slot's count, sum and sum of
+ * squares, in double and in exactly this order:
+ *      event_level_mean = ((double)S / n + offset) * range / digitisation
+ *      event_stdv       = sqrt((double)max(n*Q - S*S, 0)) / n * range / digitisation      (n*Q - S*S in int64: at most 2^50)
+ * both printed "%.4f".  The deviation is the POPULATION deviation (ddof 0), so it is defined -- 0.0000 -- for a one-sample event.
+ * The expressions are taken as written: a negative range prints a negative event_stdv.  These are the levels a reader computes from
+ * the stored integers with the `digitisation`, `range` and `offset` GIVEN HERE -- the numbers the conversion to int16 ran with.
+ * The signal writers store a per-record draw around that offset as the record's own: a reader that uses the record's offset sees
+ * every mean of the record shifted by (offset_record - offset) * range / digitisation, and the deviations unchanged.  samples: only
+ * with dac (column and header field are absent without it): the event's samples in stored order, each
+ * ((double)q + offset) * range / digitisation printed "%.3f", comma separated.
+ * Returns the bytes written, or S2S_ERR_ARG -- also when a read's seg rows do not sum to its samples, its letters are too few, or
+ * capacity is below what the rows may take (nothing is written then).  capacity >= the bound function's value always suffices:
+ * id_len_max the longest record id, n_samples the stored samples of the batch if dac is given, else 0. */
+int64_t s2s_events_format_bound(int64_t n_chunks, int32_t te, int64_t id_len_max, int32_t k, float digitisation, float range,
+                                float offset, int64_t n_samples, int32_t with_header);
+int64_t s2s_events_format(const uint16_t* seg, const int32_t* sum, const int64_t* sumsq, int32_t te, const int32_t* read_first,
+                          const int64_t* read_kmers, const int64_t* read_offs, int32_t R, const uint8_t* ids, const int64_t* id_offs,
+                          int32_t n_ids, const uint8_t* letters, const int64_t* letter_offs, int32_t k, float digitisation,
+                          float range, float offset, const int16_t* dac, int32_t rna, int32_t with_header, int32_t threads,
+                          uint8_t* out, int64_t capacity);
 
 /* ---- host-side helper (no GPU work, no handle): replays the DRAWS of the reference's read sampler (utils.py:415-479
  * `sampling`, with the read-length law of utils.py:325-331 `draw_expon_dis`) without building a read, so that a rank of a sharded

@@ -92,6 +92,12 @@ def version():
 @click.option("--alignment", default=None, type=click.Path(dir_okay=False), hidden=True,
               help="Also write the ground-truth base-to-signal alignment: one PAF line per record of OUT with the samples of every "
                    "k-mer in the signal as stored (ss:Z: tag; include/s2s_hip.h: s2s_paf_format). Off by default.")
+@click.option("--events", default=None, type=click.Path(dir_okay=False), hidden=True,
+              help="Also write the per-k-mer event table of the simulated reads: one tab-separated row per k-mer with samples "
+                   "(read_name, position, model_kmer, start_idx, end_idx, event_level_mean, event_stdv; include/s2s_hip.h: "
+                   "s2s_events_format). Off by default.")
+@click.option("--events-samples", is_flag=True, hidden=True,
+              help="With --events: add the samples column (every stored sample of the event in pA, comma separated).")
 @click.option("--gpus", default=1, type=int, hidden=True,
               help="Run on this many GPUs of the node: one process per GPU, the read set sharded, one OUT.rankN file per process "
                    "(the same as starting the command under torchrun --nproc-per-node N).")
@@ -106,9 +112,11 @@ def predict(ctx, fasta, read_input, num_reads, read_length, coverage, out, profi
             duration_sampler, dwell_mean, dwell_std, noise_std, distr, predict_batch_size, export_every_n_samples,
             sample_rate, bps, digitisation, range_val, offset_mean, offset_std, median_before_mean, median_before_std,
             min_noise, min_duration, min_read_len, preserve_read_ids, seed, model, config, verbosity, compute_mode, attention_path,
-            alignment, gpus, keep_shards, join_mode):
+            alignment, events, events_samples, gpus, keep_shards, join_mode):
     """Generate nanopore signals from a reference genome (default) or from reads (--read-input)."""
     import os
+    if events_samples and not events:
+        raise click.UsageError("--events-samples needs --events OUT.tsv")
     if gpus > 1 and "WORLD_SIZE" not in os.environ:
         # The reference leaves multi-GPU runs to Lightning (devices="auto", DDP: inference.py:430-445); here the command starts its
         # own ranks as CHILD processes -- before anything in this process has touched the GPU -- and returns their exit code.
@@ -122,6 +130,11 @@ def predict(ctx, fasta, read_input, num_reads, read_length, coverage, out, profi
         live, make_live = None, None
         ext_a = os.path.splitext(str(alignment))[1] if alignment else ""
         align_shards = [f"{str(alignment)[:len(str(alignment)) - len(ext_a)]}.rank{r}{ext_a}" for r in range(gpus)] if alignment else []
+        ext_e = os.path.splitext(str(events))[1] if events else ""
+        events_shards = [f"{str(events)[:len(str(events)) - len(ext_e)]}.rank{r}{ext_e}" for r in range(gpus)] if events else []
+        if events and os.environ.get("S2S_DRY_LAUNCH"):
+            import json
+            click.echo(json.dumps({"events_rank_files": events_shards}))
         if join_mode == "live" and not keep_shards and not os.environ.get("S2S_DRY_LAUNCH"):
             if not str(out).endswith((".blow5", ".pod5")):
                 raise click.UsageError("--join live handles .blow5 and .pod5 outputs")
@@ -129,7 +142,7 @@ def predict(ctx, fasta, read_input, num_reads, read_length, coverage, out, profi
             base_name = str(out)[:len(str(out)) - len(ext)]
             partial = base_name + ".partial" + ext
             shard_paths = [f"{base_name}.rank{r}{ext}" for r in range(gpus)]       # (parallel.rank_output_path, without its imports)
-            for stale in [partial] + shard_paths + align_shards:   # (a rank file left by an earlier run must not be mistaken for this run's)
+            for stale in [partial] + shard_paths + align_shards + events_shards:   # (a rank file left by an earlier run must not be mistaken for this run's)
                 if os.path.exists(stale):
                     os.remove(stale)
             holder = {}
@@ -183,6 +196,9 @@ def predict(ctx, fasta, read_input, num_reads, read_length, coverage, out, profi
                 # the ranks own contiguous shares of the reads: their alignment files in rank order are the single-process file
                 from .alignment import join_rank_files
                 join_rank_files(align_shards, str(alignment))
+            if events and rc == 0 and not keep_shards and not os.environ.get("S2S_DRY_LAUNCH"):
+                from .events import join_rank_files as join_event_files     # (the header of rank 0 only)
+                join_event_files(events_shards, str(events))
             late = reap()                                       # (the merge did not wait for the ranks' teardown: see _launch_ranks)
             rc = rc or late
             timing["total_seconds"] = time.time() - t0
@@ -237,7 +253,7 @@ def predict(ctx, fasta, read_input, num_reads, read_length, coverage, out, profi
                   offset_mean=offset_mean, offset_std=offset_std, median_before_mean=median_before_mean,
                   median_before_std=median_before_std, min_noise=min_noise, min_duration=min_duration,
                   min_read_len=min_read_len, preserve_read_ids=preserve_read_ids, seed=seed, mode=compute_mode,
-                  attention_path=attention_path, alignment=alignment)
+                  attention_path=attention_path, alignment=alignment, events=events, events_samples=events_samples)
     logger.info("Prediction finished.")
     if os.environ.get("S2S_TIMING_DIR"):       # a rank of `predict --gpus N`: when it was ready and when it was done, for the parent's summary
         import json

@@ -801,6 +801,13 @@ __global__ __launch_bounds__(256) void s2s_read_offsets_kernel(const long long* 
     if (r <= R) out_offsets[r] = offs[read_first[r]];
 }
 
+// The int16 a stored sample becomes (s2s_export_reads) -- the ONE place that states it: s2s_compact_kernel stores it,
+// s2s_event_stats_kernel sums it.  signal_io.py:135-138: float32 ops, no contraction; round half-to-even; int16 wrap.
+__device__ __forceinline__ short s2s_dac_of(float v, float dig, float range, float offset) {
+    const float raw = rintf(__fsub_rn(__fdiv_rn(__fmul_rn(v, dig), range), offset));
+    return (short)(int)fminf(fmaxf(raw, -2147483648.0f), 2147483520.0f);
+}
+
 template <int TD>
 __global__ __launch_bounds__(256) void s2s_compact_kernel(const float* __restrict__ signal, int B, const long long* __restrict__ offs,
                                                           const int* __restrict__ read_first, int R, float* __restrict__ out_pa,
@@ -826,10 +833,7 @@ __global__ __launch_bounds__(256) void s2s_compact_kernel(const float* __restric
         if (keep && dst < capacity) {
             if (out_pa) out_pa[dst] = v;
             if (out_dac) {
-                // signal_io.py:135-138: float32 ops, no contraction; round half-to-even; int16 wrap
-                const float raw = rintf(__fsub_rn(__fdiv_rn(__fmul_rn(v, dig), range), offset));
-                const short s = (short)(int)fminf(fmaxf(raw, -2147483648.0f), 2147483520.0f);
-                out_dac[rna ? (r_lo + (r_hi - 1 - dst)) : dst] = s;
+                out_dac[rna ? (r_lo + (r_hi - 1 - dst)) : dst] = s2s_dac_of(v, dig, range, offset);
             }
         }
         pos += __popcll(mask);
@@ -870,6 +874,72 @@ __global__ __launch_bounds__(256) void s2s_align_kernel(const float* __restrict_
     unsigned short* row = out_seg + (size_t)b * (te + 1);
     if (lane < te) row[lane] = (unsigned short)(below - (lane ? before : 0));
     if (lane == 0) row[te] = (unsigned short)(total - last);
+}
+
+// s2s_event_stats: the level statistics of every k-mer's STORED samples.  Same wave-per-chunk layout and the same c[] and counts as
+// s2s_align_kernel; beside the ballot of a 64-sample pass the wave forms inclusive prefix sums of q and q^2 over the pass (q the
+// int16 of s2s_dac_of, 0 for a stripped row), and lane j adds the prefix in front of its c[j]: S(x) = sum of q over rows [0, x) is
+// additive over passes exactly like the popcount prefix P(x), and slot j holds S(c[j]) - S(c[j-1]), the tail S(T) - S(c[te-1]).
+// A k-mer's run is contiguous in t, so differences of prefixes replace any per-slot accumulation: no LDS array, no atomics, and
+// every sum is an exact integer (|S| <= 1024 * 2^15 in int32, Q <= 1024 * 2^30 in int64) whatever the order.
+template <int TD>
+__global__ __launch_bounds__(256) void s2s_event_stats_kernel(const float* __restrict__ signal, const int* __restrict__ dur, int B,
+                                                              float dig, float range, float offset,
+                                                              unsigned short* __restrict__ out_seg, int* __restrict__ out_sum,
+                                                              long long* __restrict__ out_sumsq, int te, int ts) {
+    const int T = TD ? TD : ts;
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (b >= B) return;
+    int c = 0;
+    if (lane < te) {
+        const int d = dur[(size_t)b * te + lane];
+        c = d < 0 ? 0 : (d > T ? T : d);
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(c, o, 64); if (lane >= o) c += y; }
+    c = c > T ? T : c;                          // lanes >= te carry c[te-1]
+    int below = 0, total = 0;                   // P(c) of this lane; P(T)
+    int s_below = 0, s_total = 0;               // S(c), S(T)
+    long long q_below = 0, q_total = 0;         // the same of q^2
+    for (int t0 = 0; t0 < T; t0 += 64) {
+        const int t = t0 + lane;
+        const float v = (t < T) ? signal[(size_t)b * T + t] : 0.0f;
+        const bool keep = v != 0.0f;
+        const unsigned long long mask = __ballot(keep);
+        const int q = keep ? (int)s2s_dac_of(v, dig, range, offset) : 0;
+        int s = q;                              // inclusive prefixes over the pass: |s| <= 64 * 2^15, qq <= 64 * 2^30
+        long long qq = (long long)(q * q);
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int ys = __shfl_up(s, o, 64);
+            const long long yq = __shfl_up(qq, o, 64);
+            if (lane >= o) { s += ys; qq += yq; }
+        }
+        const int k = c - t0;                   // rows of this pass in front of c: all 64, none, or the first k
+        const int src = k >= 64 ? 63 : (k <= 0 ? 0 : k - 1);
+        const int ps = __shfl(s, src, 64);
+        const long long pq = __shfl(qq, src, 64);
+        const unsigned long long low = k >= 64 ? ~0ull : (k <= 0 ? 0ull : ((1ull << k) - 1ull));
+        below += __popcll(mask & low);
+        total += __popcll(mask);
+        if (k > 0) { s_below += ps; q_below += pq; }
+        s_total += __shfl(s, 63, 64);
+        q_total += __shfl(qq, 63, 64);
+    }
+    const int before = __shfl_up(below, 1, 64), last = __shfl(below, te - 1, 64);
+    const int s_before = __shfl_up(s_below, 1, 64), s_last = __shfl(s_below, te - 1, 64);
+    const long long q_before = __shfl_up(q_below, 1, 64), q_last = __shfl(q_below, te - 1, 64);
+    const size_t row = (size_t)b * (te + 1);
+    if (lane < te) {
+        out_seg[row + lane] = (unsigned short)(below - (lane ? before : 0));
+        out_sum[row + lane] = s_below - (lane ? s_before : 0);
+        out_sumsq[row + lane] = q_below - (lane ? q_before : 0);
+    }
+    if (lane == 0) {
+        out_seg[row + te] = (unsigned short)(total - last);
+        out_sum[row + te] = s_total - s_last;
+        out_sumsq[row + te] = q_total - q_last;
+    }
 }
 
 // ---- StreamVByte encoders of the output containers (codecs.py states the formats): one 256-thread workgroup per row.
@@ -2060,6 +2130,23 @@ int s2s_align_chunks(s2s_handle* h, void* stream_, const float* signal, const in
     const int te = h->cfg.max_dna_len, ts = h->cfg.max_signal_len;    // S2S_T_ENC / S2S_T_DEC except for a geometry-mode handle
     hipLaunchKernelGGL(ts == S2S_T_DEC ? s2s_align_kernel<S2S_T_DEC> : s2s_align_kernel<0>, dim3((B + 3) / 4), dim3(256), 0,
                        static_cast<hipStream_t>(stream_), signal, dur, B, reinterpret_cast<unsigned short*>(out_seg), te, ts);
+    HIP_TRY(h, hipGetLastError());
+    return S2S_OK;
+}
+
+int s2s_event_stats(s2s_handle* h, void* stream_, const float* signal, const int32_t* dur, int32_t B, float digitisation, float range,
+                    float offset, uint16_t* out_seg, int32_t* out_sum, int64_t* out_sumsq) {
+    if (!h) return S2S_ERR_ARG;
+    if (B < 0) return fail(h, S2S_ERR_ARG, "negative size");
+    if (!signal || !dur || !out_seg || !out_sum || !out_sumsq) return fail(h, S2S_ERR_ARG, "NULL argument");
+    if (range == 0.0f || digitisation == 0.0f) return fail(h, S2S_ERR_ARG, "range and digitisation must not be 0");
+    if (B == 0) return S2S_OK;
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(h, S2S_ERR_HIP, "hipSetDevice failed");
+    const int te = h->cfg.max_dna_len, ts = h->cfg.max_signal_len;    // S2S_T_ENC / S2S_T_DEC except for a geometry-mode handle
+    hipLaunchKernelGGL(ts == S2S_T_DEC ? s2s_event_stats_kernel<S2S_T_DEC> : s2s_event_stats_kernel<0>, dim3((B + 3) / 4), dim3(256), 0,
+                       static_cast<hipStream_t>(stream_), signal, dur, B, digitisation, range, offset,
+                       reinterpret_cast<unsigned short*>(out_seg), out_sum, reinterpret_cast<long long*>(out_sumsq), te, ts);
     HIP_TRY(h, hipGetLastError());
     return S2S_OK;
 }

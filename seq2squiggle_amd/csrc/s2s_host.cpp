@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cmath>
+#include <cstdio>
 #include <condition_variable>
 #include <cstring>
 #include <functional>
@@ -614,6 +615,154 @@ extern "C" int64_t s2s_paf_format(const uint16_t* seg, int32_t te, const int32_t
     }
     if (failed) return S2S_ERR_ARG;
     int64_t pos = 0;
+    for (int r = 0; r < R; ++r) {                               // close the gaps, in read order
+        if (size[r] && pos != slot[r]) std::memmove(out + pos, out + slot[r], size[r]);
+        pos += size[r];
+    }
+    return pos;
+}
+
+// ================================================================================ per-k-mer event table (predict --events)
+// One row per real k-mer with samples, from the counts and integer sums of s2s_event_stats; include/s2s_hip.h states the columns.
+// The walk over a read's events is s2s_paf_format's: per chunk te k-mer slots, then the tail; the cursor advances over every slot,
+// a row is written for a slot that is a real k-mer and holds samples.
+namespace {
+
+constexpr char kEventsHeader[] = "read_name\tposition\tmodel_kmer\tstart_idx\tend_idx\tevent_level_mean\tevent_stdv";
+
+inline int dec_digits(uint64_t v) { int n = 1; while (v >= 10) { v /= 10; ++n; } return n; }
+
+// Widths the numbers of a table can take with this calibration.  Every level is (x + offset) * range / digitisation with |x| <=
+// 32768, every deviation at most 32768 * |range / digitisation|: none exceeds M in magnitude (the 1 + 1e-9 covers the roundings).
+struct EventWidths {
+    bool ok;
+    int level;      // a "%.4f" column: sign, integer digits, point, four decimals
+    int sample;     // a "%.3f" sample and the comma (or tab, or line end) after it
+};
+inline EventWidths event_widths(double dig, double range, double offset) {
+    EventWidths w{false, 0, 0};
+    if (!(dig == dig) || !(range == range) || !(offset == offset) || dig == 0.0 || range == 0.0) return w;
+    const double M = (32768.0 + std::fabs(offset)) * std::fabs(range) / std::fabs(dig) * (1.0 + 1e-9) + 1.0;
+    char tmp[400];
+    const int digits = (M < 1e300) ? std::snprintf(tmp, sizeof tmp, "%.0f", M) : 312;    // (inf prints shorter than this)
+    w.ok = true;
+    w.level = 1 + digits + 5;
+    w.sample = 1 + digits + 4 + 1;
+    return w;
+}
+
+// bytes the rows of one read may take: `rows` rows of id, position, k-mer, two indices (each <= idx_digits digits), two levels, the
+// seven separators and the line end, and `samples` sample fields
+inline int64_t event_rows_bound(int64_t rows, int64_t id_len, int32_t k, int idx_digits, const EventWidths& w, int64_t samples) {
+    return rows * (id_len + k + 3 * (int64_t)idx_digits + 2 * (int64_t)w.level + 8) + samples * w.sample;
+}
+
+}  // namespace
+
+extern "C" int64_t s2s_events_format_bound(int64_t n_chunks, int32_t te, int64_t id_len_max, int32_t k, float digitisation, float range,
+                                           float offset, int64_t n_samples, int32_t with_header) {
+    const EventWidths w = event_widths(digitisation, range, offset);
+    if (n_chunks < 0 || te < 1 || id_len_max < 0 || k < 1 || n_samples < 0 || !w.ok) return S2S_ERR_ARG;
+    const int idx_digits = dec_digits((uint64_t)n_chunks * (uint64_t)(te + 1) * 65535u);
+    return (with_header ? (int64_t)sizeof kEventsHeader + 16 : 0) + event_rows_bound(n_chunks * te, id_len_max, k, idx_digits, w, n_samples);
+}
+
+extern "C" int64_t s2s_events_format(const uint16_t* seg, const int32_t* sum, const int64_t* sumsq, int32_t te, const int32_t* read_first,
+                                     const int64_t* read_kmers, const int64_t* read_offs, int32_t R, const uint8_t* ids,
+                                     const int64_t* id_offs, int32_t n_ids, const uint8_t* letters, const int64_t* letter_offs, int32_t k,
+                                     float digitisation, float range, float offset, const int16_t* dac, int32_t rna,
+                                     int32_t with_header, int32_t threads, uint8_t* out, int64_t capacity) {
+    const double dig_d = digitisation, range_d = range, offset_d = offset;
+    const EventWidths w = event_widths(dig_d, range_d, offset_d);
+    if (R < 0 || n_ids < 0 || te < 1 || k < 1 || threads < 1 || capacity < 0 || !w.ok) return S2S_ERR_ARG;
+    if (!out) return S2S_ERR_ARG;
+    int64_t head = 0;
+    char header[sizeof kEventsHeader + 16];
+    if (with_header) head = std::snprintf(header, sizeof header, "%s%s\n", kEventsHeader, dac ? "\tsamples" : "");
+    if (R == 0) {
+        if (n_ids != 0 || head > capacity) return S2S_ERR_ARG;
+        std::memcpy(out, header, head);
+        return head;
+    }
+    if (!seg || !sum || !sumsq || !read_first || !read_kmers || !read_offs || !id_offs || !letters || !letter_offs || (n_ids > 0 && !ids))
+        return S2S_ERR_ARG;
+    std::vector<int32_t> id_of(R);
+    std::vector<int64_t> slot(R + 1), size(R, 0);
+    int32_t used = 0;
+    slot[0] = head;
+    for (int r = 0; r < R; ++r) {
+        const int64_t chunks = (int64_t)read_first[r + 1] - read_first[r], n = read_offs[r + 1] - read_offs[r];
+        if (chunks < 0 || n < 0 || read_kmers[r] < 0 || read_kmers[r] > chunks * te) return S2S_ERR_ARG;
+        id_of[r] = -1;
+        slot[r + 1] = slot[r];
+        if (n == 0) continue;                                    // no samples: no record, no rows
+        if (used >= n_ids || id_offs[used + 1] < id_offs[used] || read_kmers[r] < 1) return S2S_ERR_ARG;
+        if (letter_offs[r + 1] - letter_offs[r] < read_kmers[r] + k - 1) return S2S_ERR_ARG;
+        id_of[r] = used++;
+        const int idx_digits = dec_digits((uint64_t)std::max(read_kmers[r], n));
+        slot[r + 1] += event_rows_bound(std::min(read_kmers[r], n), id_offs[used] - id_offs[used - 1], k, idx_digits, w, dac ? n : 0);
+    }
+    if (used != n_ids || slot[R] > capacity) return S2S_ERR_ARG;
+    std::atomic<int> failed{0};
+    {
+        std::lock_guard<std::mutex> guard(g_pool_mutex);
+        if (!g_pool || g_pool->size() < threads) { delete g_pool; g_pool = new Pool(threads); }
+        g_pool->run(R, [&](int r, int) {
+            if (id_of[r] < 0) return;
+            const int64_t b0 = read_first[r], chunks = (int64_t)read_first[r + 1] - b0;
+            const int64_t K = read_kmers[r], len = read_offs[r + 1] - read_offs[r];
+            int64_t total = 0;
+            for (int64_t e = b0 * (te + 1); e < (b0 + chunks) * (te + 1); ++e) total += seg[e];
+            if (total != len) { failed = 1; return; }            // seg and the export's offsets describe different signals
+            uint8_t* p = out + slot[r];
+            uint8_t* const end = out + slot[r + 1];
+            const uint8_t* id = ids + id_offs[id_of[r]];
+            const int64_t id_len = id_offs[id_of[r] + 1] - id_offs[id_of[r]];
+            const uint8_t* seq = letters + letter_offs[r];
+            const int16_t* stored = dac ? dac + read_offs[r] : nullptr;
+            // a number of at most `width` characters and the separator behind it, or the read fails and nothing is written
+            // (cannot happen within event_widths' bound)
+            auto put_f = [&](const char* fmt, double v, int width, char sep) {
+                char tmp[400];
+                const int n = std::snprintf(tmp, sizeof tmp, fmt, v);
+                if (n < 0 || n > width || end - p < n + 1) { failed = 1; return false; }
+                std::memcpy(p, tmp, n); p += n; *p++ = (uint8_t)sep;
+                return true;
+            };
+            int64_t cur = 0;                                      // forward cursor in the read's stored samples
+            for (int64_t c = 0; c < chunks && !failed; ++c) {
+                const int64_t row = (b0 + c) * (te + 1);
+                for (int j = 0; j <= te; ++j) {
+                    const int64_t n = seg[row + j], pos = c * te + j, s0 = cur;
+                    cur += n;
+                    if (!n || j == te || pos >= K) continue;      // an empty k-mer; a tail or a pad k-mer: an insertion
+                    const int64_t start = rna ? len - (s0 + n) : s0, stop = start + n;
+                    const int64_t S = sum[row + j], Q = sumsq[row + j];
+                    const int64_t var = std::max<int64_t>(n * Q - S * S, 0);
+                    const double mean = ((double)S / (double)n + offset_d) * range_d / dig_d;
+                    const double stdv = std::sqrt((double)var) / (double)n * range_d / dig_d;
+                    if (end - p < id_len + k + dec_digits((uint64_t)pos) + dec_digits((uint64_t)start) + dec_digits((uint64_t)stop) + 5) {
+                        failed = 1; return;                       // (the slot's bound holds every row: not reached)
+                    }
+                    std::memcpy(p, id, id_len); p += id_len; *p++ = '\t';
+                    p = put_u64(p, pos); *p++ = '\t';
+                    std::memcpy(p, seq + pos, k); p += k; *p++ = '\t';
+                    p = put_u64(p, start); *p++ = '\t';
+                    p = put_u64(p, stop); *p++ = '\t';
+                    if (!put_f("%.4f", mean, w.level, '\t')) return;
+                    if (!put_f("%.4f", stdv, w.level, stored ? '\t' : '\n')) return;
+                    if (stored)
+                        for (int64_t t = start; t < stop; ++t)
+                            if (!put_f("%.3f", ((double)stored[t] + offset_d) * range_d / dig_d, w.sample - 1, t + 1 < stop ? ',' : '\n'))
+                                return;
+                }
+            }
+            size[r] = p - (out + slot[r]);
+        });
+    }
+    if (failed) return S2S_ERR_ARG;
+    std::memcpy(out, header, head);
+    int64_t pos = head;
     for (int r = 0; r < R; ++r) {                               // close the gaps, in read order
         if (size[r] && pos != slot[r]) std::memmove(out + pos, out + slot[r], size[r]);
         pos += size[r];

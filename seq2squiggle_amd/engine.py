@@ -286,6 +286,50 @@ class Engine:
         return seg
 
     @staticmethod
+    def event_stats_layout(B: int, t_enc: int):
+        """Where event_stats puts its three sections in a byte buffer: -> (seg_at, sum_at, sumsq_at, bytes); uint16, int32 and int64
+        [B, t_enc+1], each starting on a multiple of 16 bytes."""
+        n = B * (t_enc + 1)
+        sum_at = 2 * n + -(2 * n) % 16
+        sumsq_at = sum_at + 4 * n + -(4 * n) % 16
+        return 0, sum_at, sumsq_at, sumsq_at + 8 * n
+
+    def event_stats(self, signal: torch.Tensor, dur: torch.Tensor, digitisation: float, signal_range: float, offset: float,
+                    out: torch.Tensor = None) -> dict:
+        """The level statistics of every k-mer's stored samples (s2s_event_stats): signal float32 [B,250] and dur int32 [B,16] as
+        predict returns them, the calibration export_reads is given -> dict(seg uint16, sum int32, sumsq int64), each [B,17]: per
+        slot (16 k-mers, then the tail) the count align_chunks gives, the sum and the sum of squares of the int16 samples
+        export_reads stores.  The three are views of ONE byte buffer (event_stats_layout): `out` (contiguous uint8, 16-byte
+        aligned, at least that many bytes, e.g. a slice of the buffer that leaves the device as one copy) or a fresh one."""
+        B = int(signal.shape[0]) if signal.dim() == 2 else -1
+        T_ENC, T_DEC = self.t_enc, self.t_dec
+        if signal.dtype != torch.float32 or not signal.is_contiguous() or signal.dim() != 2 or signal.shape[1] != T_DEC:
+            raise ValueError(f"signal must be contiguous float32 [B,{T_DEC}]")
+        if dur.dtype != torch.int32 or not dur.is_contiguous() or tuple(dur.shape) != (B, T_ENC):
+            raise ValueError(f"dur must be contiguous int32 [{B},{T_ENC}]")
+        if signal.device != self.device or dur.device != self.device:
+            raise ValueError(f"signal and dur must live on {self.device}")
+        if float(signal_range) == 0.0 or float(digitisation) == 0.0:
+            raise ValueError("range and digitisation must not be 0")
+        _, sum_at, sumsq_at, size = self.event_stats_layout(B, T_ENC)
+        if out is None:
+            out = torch.empty(max(size, 16), dtype=torch.uint8, device=self.device)
+        elif (out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.device != self.device or out.numel() < size
+              or out.data_ptr() % 16):
+            raise ValueError(f"out must be a contiguous 16-byte aligned uint8 tensor of at least {size} bytes on {self.device}")
+        n = B * (T_ENC + 1)
+        res = {"seg": out[:2 * n].view(torch.uint16).view(B, T_ENC + 1),
+               "sum": out[sum_at: sum_at + 4 * n].view(torch.int32).view(B, T_ENC + 1),
+               "sumsq": out[sumsq_at: sumsq_at + 8 * n].view(torch.int64).view(B, T_ENC + 1)}
+        if B == 0:                      # (an empty tensor has no address to pass)
+            return res
+        with torch.cuda.device(self.device):
+            rc = _lib.lib().s2s_event_stats(self._h, self._stream(), _ptr(signal), _ptr(dur), B, float(digitisation),
+                                            float(signal_range), float(offset), _ptr(res["seg"]), _ptr(res["sum"]), _ptr(res["sumsq"]))
+        self._check(rc, "s2s_event_stats")
+        return res
+
+    @staticmethod
     def svb_capacity(total_samples_bound: int, n_rows: int, variant: int) -> int:
         """Bytes s2s_svb_encode may write for n_rows rows holding at most total_samples_bound samples together."""
         if variant == 32:      # per row: u32 count + ceil(n/4) control bytes + up to 3 bytes per zig-zag delta of int16 samples

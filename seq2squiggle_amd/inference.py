@@ -251,7 +251,7 @@ def super_batches(reads: Iterable[Tuple[str, str]], k: int, max_chunks: int, t_e
 
 
 def run_streaming(model, reads: Iterable[Tuple[str, str]], writer, profile_dict: dict, profile_name: str,
-                  max_chunks: int = 32768, trace: list = None, alignment=None) -> int:
+                  max_chunks: int = 32768, trace: list = None, alignment=None, events=None, events_samples: bool = False) -> int:
     """The predict loop without per-chunk Python objects: whole reads are grouped into super-batches of about
     `max_chunks` chunks; per super-batch one H2D of the packed read bytes, s2s_predict_packed, s2s_export_reads
     (zero-strip + int16 conversion on the GPU), one D2H of the packed int16 samples on a copy stream, then the writer.  Produces the
@@ -265,7 +265,13 @@ def run_streaming(model, reads: Iterable[Tuple[str, str]], writer, profile_dict:
     `alignment`: a path or a binary file object that receives the base-to-signal alignment, one PAF line per record in record order
     (alignment.py).  Only then s2s_align_chunks runs, straight after the export on the same `signal` / `dur`, and its counts
     travel as one more 16-byte-aligned section at the END of the super-batch's device buffer; without it no kernel is added and the
-    buffer is byte for byte what it was."""
+    buffer is byte for byte what it was.
+
+    `events`: a path or a binary file object that receives the per-k-mer event table (events.py): a header line, then the rows of
+    every record in record order.  Then s2s_event_stats runs in that place instead and its three sections (counts, sums, sums of
+    squares) travel there; its counts ARE the alignment's, so with `alignment` as well s2s_align_chunks is not launched.
+    `events_samples`: the table gets the `samples` column; on the coded-signal path the packed int16 samples then ride behind the
+    blobs as one more section (the export writes them there), on the plain path they are the payload."""
     import time
 
     def mark(ev):
@@ -296,6 +302,18 @@ def run_streaming(model, reads: Iterable[Tuple[str, str]], writer, profile_dict:
         align_own = not hasattr(alignment, "write")
         align_f = open(os.fspath(alignment), "wb") if align_own else alignment
         align_threads = cpu_share()
+    events_f, events_own = None, False
+    if events is not None:
+        from .events import format_events
+        from .signal_io import cpu_share
+        events_own = not hasattr(events, "write")
+        events_f = open(os.fspath(events), "wb") if events_own else events
+        events_threads = cpu_share()
+        cal = (profile_dict["digitisation"], profile_dict["range"], profile_dict["offset_mean"])
+        # the header, once, in front of the first batch's rows (a run without reads leaves a header-only file)
+        events_f.write(format_events(np.zeros(0, np.uint16), np.zeros(0, np.int32), np.zeros(0, np.int64), t_enc, np.zeros(1, np.int32),
+                                     [], np.zeros(1, np.int64), [], np.zeros(1, np.uint8), np.zeros(1, np.int64), k, *cal, rna,
+                                     dac=np.zeros(1, np.int16) if events_samples else None, with_header=True, threads=1))
 
     def launch(group):
         nonlocal total, n_launched
@@ -334,51 +352,66 @@ def run_streaming(model, reads: Iterable[Tuple[str, str]], writer, profile_dict:
         # (--alignment only) the k-mer counts ride in the same buffer, behind the payload: a second, small copy would be the shader
         # copy described above
         seg_bytes = 2 * B * (t_enc + 1) if align_f is not None else 0
+        # (--events) the counts are the first of event_stats' three sections; (--events-samples, coded signal) the samples behind them
+        stats_bytes = model.engine.event_stats_layout(B, t_enc)[3] if events_f is not None else 0
+        dac_bytes = 2 * cap if events_f is not None and events_samples and gpu_rows else 0
 
         def with_seg(size):
-            """-> (bytes of the buffer, where the counts start | None)"""
-            if not seg_bytes:
-                return size, None
+            """-> (bytes of the buffer, where the counts start | None, where the samples' copy starts | None)"""
+            if not seg_bytes and not stats_bytes:
+                return size, None, None
             at = size + -size % 16
-            return at + seg_bytes, at
+            size = at + (stats_bytes or seg_bytes)
+            if not dac_bytes:
+                return size, at, None
+            dac_at = size + -size % 16
+            return dac_at + dac_bytes, at, dac_at
+
+        def counts():
+            if stats_bytes:
+                model.engine.event_stats(out["signal"], out["dur"], profile_dict["digitisation"], profile_dict["range"],
+                                         profile_dict["offset_mean"], out=buf[seg_at: seg_at + stats_bytes])
+            elif seg_bytes:
+                model.engine.align_chunks(out["signal"], out["dur"], out=buf[seg_at: seg_at + seg_bytes].view(torch.uint16))
         if gpu_rows:
             N = int(row_read.shape[0])
             blob_cap = model.engine.svb_capacity(cap, N, gpu_rows[0])
             head = 8 * (R + 1) + 8 * (N + 1)
             head += -head % 16
-            size, seg_at = with_seg(head + max(blob_cap, 1))
+            size, seg_at, dac_at = with_seg(head + max(blob_cap, 1))
             buf = torch.empty(size, dtype=torch.uint8, device=dev)
             offs_d = buf[:8 * (R + 1)].view(torch.int64)
             rows_d = buf[8 * (R + 1): 8 * (R + 1) + 8 * (N + 1)].view(torch.int64)
             ex = model.engine.export_reads(out["signal"], ins[3], profile_dict["digitisation"], profile_dict["range"],
-                                           profile_dict["offset_mean"], rna=rna, want_pa=False, want_dac=True, out_offsets=offs_d)
+                                           profile_dict["offset_mean"], rna=rna, want_pa=False, want_dac=True, out_offsets=offs_d,
+                                           out_dac=buf[dac_at: dac_at + dac_bytes].view(torch.int16) if dac_bytes else None)
             mark("export queued")
-            if seg_bytes:
-                model.engine.align_chunks(out["signal"], out["dur"], out=buf[seg_at: seg_at + seg_bytes].view(torch.uint16))
+            counts()
             # the signal leaves the GPU StreamVByte-coded (~1.1-1.3 bytes per sample)
             model.engine.svb_encode(ex["dac"], ex["offsets"], ins[4], ins[5], gpu_rows[1], gpu_rows[0], cap,
                                     out=buf[head: head + max(blob_cap, 1)], out_offsets=rows_d)
         else:
             head = 8 * (R + 1)
             head += -head % 16
-            size, seg_at = with_seg(head + 2 * cap)
+            size, seg_at, dac_at = with_seg(head + 2 * cap)
             buf = torch.empty(size, dtype=torch.uint8, device=dev)
             model.engine.export_reads(out["signal"], ins[3], profile_dict["digitisation"], profile_dict["range"],
                                       profile_dict["offset_mean"], rna=rna, want_pa=False, want_dac=True,
                                       out_offsets=buf[:8 * (R + 1)].view(torch.int64),
                                       out_dac=buf[head: head + 2 * cap].view(torch.int16))
             mark("export queued")
-            if seg_bytes:
-                model.engine.align_chunks(out["signal"], out["dur"], out=buf[seg_at: seg_at + seg_bytes].view(torch.uint16))
+            counts()
         ready = torch.cuda.Event()
         ready.record(main)
         mark("launched")
         # (--alignment) what the formatter needs beside the counts: the chunk ranges and the real k-mers of every read
-        align = (seg_at, read_first, np.fromiter((len(s) - k + 1 for s, _ in group), np.int64, R)) if seg_bytes else None
-        return names, buf, (R, head, row_read if gpu_rows else None), ready, align
+        align = (seg_at, read_first, np.fromiter((len(s) - k + 1 for s, _ in group), np.int64, R)) if seg_at is not None else None
+        # (--events) and the reads' letters: the packed blob and where every read starts in it
+        letters = (flat, np.append(chunk_start[read_first[:-1]], flat.shape[0] - 1), dac_at) if stats_bytes else None
+        return names, buf, (R, head, row_read if gpu_rows else None), ready, align, letters
 
     def collect(job):
-        ids, buf, (R, head, row_read), ready, align = job
+        ids, buf, (R, head, row_read), ready, align, letters = job
         # The D2H is issued only once the super-batch's kernels have FINISHED (the calling thread has nothing else to do at this
         # point: the next super-batch is already queued behind them).  Queued earlier, behind a stream-side wait for `ready`, the
         # runtime carries the copy out as a 256-workgroup shader copy, and no wave of it fits on a CU while the next predict kernel
@@ -407,24 +440,40 @@ def run_streaming(model, reads: Iterable[Tuple[str, str]], writer, profile_dict:
             recs = writer.svb_records(ids, offs, row_read, row_offs, host[head: head + int(row_offs[-1])])
         else:
             recs = writer.dac_records(ids, host[head: head + 2 * int(offs[-1])].view(np.int16), offs)
-        text = None
+        text = rows = None
         if align is not None:
             # one line per record, with the id the writer has just given it (generated or preserved)
-            mark("alignment")
             seg_at, read_first, kmers = align
             B = int(read_first[-1])
-            text = format_alignment(host[seg_at: seg_at + 2 * B * (t_enc + 1)].view(np.uint16), t_enc, read_first, kmers, offs,
-                                    [str(r["read_id"]) for r in recs], rna, align_threads)
+            rec_ids = [str(r["read_id"]) for r in recs]
+            seg_h = host[seg_at: seg_at + 2 * B * (t_enc + 1)].view(np.uint16)
+        if align_f is not None:
+            mark("alignment")
+            text = format_alignment(seg_h, t_enc, read_first, kmers, offs, rec_ids, rna, align_threads)
+        if events_f is not None:
+            mark("events")
+            flat, letter_offs, dac_at = letters
+            n = B * (t_enc + 1)
+            _, sum_at, sumsq_at, _ = model.engine.event_stats_layout(B, t_enc)
+            dac_h = None
+            if events_samples:
+                at = dac_at if gpu_rows else head
+                dac_h = host[at: at + 2 * int(offs[-1])].view(np.int16)
+            rows = format_events(seg_h, host[seg_at + sum_at: seg_at + sum_at + 4 * n].view(np.int32),
+                                 host[seg_at + sumsq_at: seg_at + sumsq_at + 8 * n].view(np.int64), t_enc, read_first, kmers, offs,
+                                 rec_ids, flat, letter_offs, k, *cal, rna, dac=dac_h, threads=events_threads)
         mark("wait writer")
         while pending and (pending[0].done() or len(pending) >= MAX_PENDING):
             pending.popleft().result()              # (re-raises what the writer thread raised)
         mark("submit")
 
-        def job_(recs=recs, text=text):
+        def job_(recs=recs, text=text, rows=rows):
             mark("writer start")
             writer.write_records(recs)
             if text is not None:                    # behind the batch's records: both files stay in read order
                 align_f.write(text)
+            if rows is not None:
+                events_f.write(rows)
             mark("writer end")
         pending.append(io.submit(job_))
 
@@ -452,6 +501,8 @@ def run_streaming(model, reads: Iterable[Tuple[str, str]], writer, profile_dict:
             io.submit(writer.close).result()
         if align_f is not None:                    # (on the writer thread: behind every write queued there)
             io.submit(align_f.close if align_own else align_f.flush).result()
+        if events_f is not None:
+            io.submit(events_f.close if events_own else events_f.flush).result()
         mark("done")
     return total
 
@@ -462,16 +513,22 @@ def inference_run(config: dict, saved_weights: str, fasta: str, read_input: bool
                   sample_rate: int, bps: int, digitisation: int, range_val: float, offset_mean: float, offset_std: float,
                   median_before_mean: float, median_before_std: float, min_noise: float, min_duration: float,
                   min_read_len: int, preserve_read_ids: bool, seed: int, mode: Optional[str] = None, streaming: bool = True,
-                  attention_path: str = "auto", alignment: Optional[str] = None):
+                  attention_path: str = "auto", alignment: Optional[str] = None, events: Optional[str] = None,
+                  events_samples: bool = False):
     """Same 30 parameters as the reference (inference.py:270-301) plus `mode` (decoder arithmetic), `streaming`
     (True: run_streaming; False: the reference's predict_step / export_and_clear_results flow, batch by batch) and
     `attention_path` ("auto": the engine's calibration decides; "fast" / "exact": Engine.attention_path is set to it) and
     `alignment` (a path: the base-to-signal alignment of every record as PAF, alignment.py; a rank of a multi-process run writes
-    rank_output_path(alignment); streaming runs only)."""
+    rank_output_path(alignment); streaming runs only) and `events` / `events_samples` (a path: the per-k-mer event table of every
+    record, events.py, with the `samples` column if events_samples; the same rank naming and restrictions as `alignment`)."""
     if attention_path not in ("auto", "fast", "exact"):
         raise ValueError("attention_path must be 'auto', 'fast' or 'exact'")
     if alignment is not None and not streaming:
         raise ValueError("alignment needs the streaming path (streaming=True): the batch-by-batch flow keeps no k-mer counts")
+    if events is not None and not streaming:
+        raise ValueError("events needs the streaming path (streaming=True): the batch-by-batch flow keeps no k-mer sums")
+    if events_samples and events is None:
+        raise ValueError("events_samples needs events")
     profile_dict = get_profile(profile)
     profile_dict = update_profile(profile_dict, sample_rate=sample_rate, bps=bps, digitisation=digitisation, range=range_val,
                                   offset_mean=offset_mean, offset_std=offset_std, median_before_mean=median_before_mean,
@@ -488,6 +545,8 @@ def inference_run(config: dict, saved_weights: str, fasta: str, read_input: bool
                                                 preserve_read_ids=preserve_read_ids)
     if alignment is not None and not hasattr(writer, "dac_records"):
         raise ValueError(f"alignment needs a writer with dac_records (the streaming path); {type(writer).__name__} has none")
+    if events is not None and not hasattr(writer, "dac_records"):
+        raise ValueError(f"events needs a writer with dac_records (the streaming path); {type(writer).__name__} has none")
     if saved_weights is None:
         saved_weights = get_saved_weights(profile)             # (inference.py:370-372; the cache only: no network here)
     first_chunk, first_read, total_l = 0, 0, 0
@@ -562,7 +621,9 @@ def inference_run(config: dict, saved_weights: str, fasta: str, read_input: bool
     if streaming and hasattr(writer, "dac_records"):
         # (a rank without reads still leaves its -- empty -- alignment file: run_streaming opens it before the first read)
         n_chunks = run_streaming(load_model, reads, writer, profile_dict, profile, trace=_TRACE,
-                                 alignment=None if alignment is None else rank_output_path(str(alignment), rank, world))
+                                 alignment=None if alignment is None else rank_output_path(str(alignment), rank, world),
+                                 events=None if events is None else rank_output_path(str(events), rank, world),
+                                 events_samples=events_samples)
     else:
         for batch in iter_batches(reads, config["seq_kmer"], predict_batch_size, load_model.device, load_model.engine.t_enc):
             load_model.predict_step(batch)

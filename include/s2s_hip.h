@@ -291,6 +291,40 @@ int s2s_event_stats(s2s_handle* h, void* stream, const float* signal /* device [
                     int32_t B, float digitisation, float range, float offset, uint16_t* out_seg /* device [B][te+1] */,
                     int32_t* out_sum /* device [B][te+1] */, int64_t* out_sumsq /* device [B][te+1] */);
 
+/* The k-mer table of a run (`predict --kmer-table`): the slot statistics of s2s_event_stats, summed per k-mer over every chunk
+ * handed to it.  No counterpart in the reference.
+ *
+ *  k          the handle's seq_kmer, 1..S2S_KMER_TABLE_MAX_K (above: S2S_ERR_ARG, s2s_last_error names the limit); te / ts the
+ *             handle's geometry, as for s2s_event_stats;
+ *  signal, dur, digitisation, range, offset   as for s2s_event_stats;
+ *  read_bytes, chunk_start, n_valid   those of s2s_predict_packed: chunk b's k-mer j is the k bytes at
+ *             read_bytes[chunk_start[b] + j ..], real for j < n_valid[b];
+ *  n, S, Q    slot j's count, sum and sum of squares of the stored int16 samples: by definition what s2s_event_stats writes to
+ *             out_seg / out_sum / out_sumsq for the same inputs (same c[j], saturation and s2s_dac_of; one wave routine serves both);
+ *  code       the base-4 number of the k letters, A, C, G, T = 0..3, the FIRST letter most significant -- the row order of a
+ *             published k-mer model; a k-mer with any other byte (genome mode maps non-ACGT to N) has code 4^k, the extra row;
+ *  table      device int64 [4^k + 1][S2S_KMER_TABLE_FIELDS], zeroed by the caller once, ADDED to by every call.  Every real slot
+ *             (j < n_valid[b]) adds to row `code`:
+ *                 [0] occ += 1
+ *             and, if n >= 1,
+ *                 [1] events += 1   [2] samples += n   [3] samples_sq += n*n   [4] sum += S   [5] sumsq += Q
+ *             The tail slot te and pad k-mers (j >= n_valid[b]) add nothing.
+ * All fields are 64-bit integers added with integer atomics (never float atomics): the table depends only on the SET of chunks, not
+ * on B, slicing, call order, neighbours or the number of GPUs whose tables are summed.  Ranges: per slot n <= 1024, |S| <= 2^25,
+ * Q <= 2^40; occ, events, samples and samples_sq are far from 2^63 for any run; |sum| <= 2^15 * samples; sumsq <= 2^30 * samples
+ * stays exact up to 2^33 full-scale samples per k-mer.  Beyond that the fields wrap; there is no check.
+ * Two paths, chosen by k alone: k <= 5 -- the table (at most 1,025 rows, 49,200 bytes) is kept per workgroup in LDS, at most 512
+ * workgroups walk the chunks and each adds its non-zero words to `table` once at the end; k >= 6 -- one workgroup per four chunks
+ * adds straight to `table`.  On both a wave first merges the slots of its chunk that share a row.
+ * B == 0 is a successful no-op; a NULL pointer, B < 0, range == 0 or digitisation == 0 is S2S_ERR_ARG. */
+#define S2S_KMER_TABLE_MAX_K   10
+#define S2S_KMER_TABLE_FIELDS  6
+int64_t s2s_kmer_table_rows(int32_t k);          /* 4^k + 1 for 1 <= k <= S2S_KMER_TABLE_MAX_K, else -1 */
+int s2s_kmer_table_accumulate(s2s_handle* h, void* stream, const float* signal /* device [B][ts] */,
+                              const int32_t* dur /* device [B][te] */, const uint8_t* read_bytes, const int64_t* chunk_start /* device [B] */,
+                              const uint8_t* n_valid /* device [B] */, int32_t B, float digitisation, float range, float offset,
+                              int64_t* table /* device [4^k + 1][6] */);
+
 /* Replaces the signal compression that pyslow5.write_record_batch (svb-zd) and pod5.Writer.add_reads (the svb16 stage of
  * VBZ) run on the host (reference signal_io.py:167-171, 268-282): StreamVByte encoding of the zig-zag deltas of the packed
  * int16 samples, one output blob per row, so that only ~1.1 bytes per sample cross PCIe.
@@ -405,6 +439,35 @@ int64_t s2s_events_format(const uint16_t* seg, const int32_t* sum, const int64_t
                           int32_t n_ids, const uint8_t* letters, const int64_t* letter_offs, int32_t k, float digitisation,
                           float range, float offset, const int16_t* dac, int32_t rna, int32_t with_header, int32_t threads,
                           uint8_t* out, int64_t capacity);
+
+/* ---- host-side helper (no GPU work, no handle): the k-mer table of a run (`predict --kmer-table`) as text.
+ *
+ *  table      int64 [4^k + 1][S2S_KMER_TABLE_FIELDS]: what s2s_kmer_table_accumulate built, copied to the host (or the sum of
+ *             several such tables);   k: 1..S2S_KMER_TABLE_MAX_K;
+ *  digitisation, range, offset   the calibration the table was accumulated with (floats, widened to double);
+ *  with_header  != 0: the text starts with the header line.
+ * Tab separated, "\n" ended; the header is
+ *      kmer  n_occ  n_events  n_samples  level_mean  level_stdv  dwell_mean  dwell_stdv
+ * and there is one row per k-mer with n_occ >= 1, in code order (AA..A first, the first letter most significant); the extra row
+ * prints as k times `N`, last.  n_occ: how often the k-mer occurred as a real k-mer of a chunk; n_events: how often it got at
+ * least one stored sample; n_samples: the stored samples it got.  With e, n, nn, S, Q the row's events, samples, samples_sq, sum
+ * and sumsq, the products formed in 128-bit integers, then converted to double, exactly as written:
+ *      level_mean = ((double)S / (double)n + offset) * range / digitisation
+ *      level_stdv = sqrt((double)max(n*Q - S*S, 0)) / (double)n * range / digitisation
+ *      dwell_mean = (double)n / (double)e
+ *      dwell_stdv = sqrt((double)max(e*nn - n*n, 0)) / (double)e
+ * each printed "%.4f"; the four print `nan` when n_events == 0.  Definitions: level_mean / level_stdv are POOLED SAMPLE statistics
+ * of the stored int16 levels -- every stored sample of the k-mer counts once, whichever event it belongs to -- with the
+ * population deviation (ddof 0); they are not statistics of event means.  "Dwell" is an event's STORED sample count after crop and
+ * strip, i.e. end_idx - start_idx of the event table (s2s_events_format), not the drawn duration; its deviation is over the
+ * events (ddof 0), so events without samples do not enter.  The levels are those a reader computes from the stored integers with
+ * the calibration GIVEN HERE; the remark of s2s_events_format on the per-record offset draw applies unchanged.
+ * Returns the bytes written, or S2S_ERR_ARG -- a NULL pointer, k outside 1..10, a calibration that is NaN or has range or
+ * digitisation 0, a negative counter other than sum, or capacity below s2s_kmer_table_format_bound's value for the same arguments
+ * (nothing is written then); the bound counts the rows with n_occ >= 1 and holds for any counters. */
+int64_t s2s_kmer_table_format_bound(const int64_t* table, int32_t k, float digitisation, float range, float offset, int32_t with_header);
+int64_t s2s_kmer_table_format(const int64_t* table, int32_t k, float digitisation, float range, float offset, int32_t with_header,
+                              uint8_t* out, int64_t capacity);
 
 /* ---- host-side helper (no GPU work, no handle): replays the DRAWS of the reference's read sampler (utils.py:415-479
  * `sampling`, with the read-length law of utils.py:325-331 `draw_expon_dis`) without building a read, so that a rank of a sharded

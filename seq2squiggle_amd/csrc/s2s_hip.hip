@@ -882,14 +882,13 @@ __global__ __launch_bounds__(256) void s2s_align_kernel(const float* __restrict_
 // additive over passes exactly like the popcount prefix P(x), and slot j holds S(c[j]) - S(c[j-1]), the tail S(T) - S(c[te-1]).
 // A k-mer's run is contiguous in t, so differences of prefixes replace any per-slot accumulation: no LDS array, no atomics, and
 // every sum is an exact integer (|S| <= 1024 * 2^15 in int32, Q <= 1024 * 2^30 in int64) whatever the order.
+// The wave routine (one wave, one chunk b; every lane of the wave calls it): lane j < te returns slot j's n / S / Q, lane 0 also
+// the tail's.  s2s_event_stats_kernel stores them, s2s_kmer_table_kernel adds them to the table row of the slot's k-mer.
 template <int TD>
-__global__ __launch_bounds__(256) void s2s_event_stats_kernel(const float* __restrict__ signal, const int* __restrict__ dur, int B,
-                                                              float dig, float range, float offset,
-                                                              unsigned short* __restrict__ out_seg, int* __restrict__ out_sum,
-                                                              long long* __restrict__ out_sumsq, int te, int ts) {
+__device__ __forceinline__ void s2s_slot_stats_wave(const float* __restrict__ signal, const int* __restrict__ dur, int b, int lane,
+                                                    float dig, float range, float offset, int te, int ts, int& n, int& S, long long& Q,
+                                                    int& n_tail, int& s_tail, long long& q_tail) {
     const int T = TD ? TD : ts;
-    const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (b >= B) return;
     int c = 0;
     if (lane < te) {
         const int d = dur[(size_t)b * te + lane];
@@ -929,16 +928,132 @@ __global__ __launch_bounds__(256) void s2s_event_stats_kernel(const float* __res
     const int before = __shfl_up(below, 1, 64), last = __shfl(below, te - 1, 64);
     const int s_before = __shfl_up(s_below, 1, 64), s_last = __shfl(s_below, te - 1, 64);
     const long long q_before = __shfl_up(q_below, 1, 64), q_last = __shfl(q_below, te - 1, 64);
+    n = below - (lane ? before : 0);
+    S = s_below - (lane ? s_before : 0);
+    Q = q_below - (lane ? q_before : 0);
+    n_tail = total - last;
+    s_tail = s_total - s_last;
+    q_tail = q_total - q_last;
+}
+
+template <int TD>
+__global__ __launch_bounds__(256) void s2s_event_stats_kernel(const float* __restrict__ signal, const int* __restrict__ dur, int B,
+                                                              float dig, float range, float offset,
+                                                              unsigned short* __restrict__ out_seg, int* __restrict__ out_sum,
+                                                              long long* __restrict__ out_sumsq, int te, int ts) {
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (b >= B) return;
+    int n, S, n_tail, s_tail;
+    long long Q, q_tail;
+    s2s_slot_stats_wave<TD>(signal, dur, b, lane, dig, range, offset, te, ts, n, S, Q, n_tail, s_tail, q_tail);
     const size_t row = (size_t)b * (te + 1);
     if (lane < te) {
-        out_seg[row + lane] = (unsigned short)(below - (lane ? before : 0));
-        out_sum[row + lane] = s_below - (lane ? s_before : 0);
-        out_sumsq[row + lane] = q_below - (lane ? q_before : 0);
+        out_seg[row + lane] = (unsigned short)n;
+        out_sum[row + lane] = S;
+        out_sumsq[row + lane] = Q;
     }
     if (lane == 0) {
-        out_seg[row + te] = (unsigned short)(total - last);
-        out_sum[row + te] = s_total - s_last;
-        out_sumsq[row + te] = q_total - q_last;
+        out_seg[row + te] = (unsigned short)n_tail;
+        out_sum[row + te] = s_tail;
+        out_sumsq[row + te] = q_tail;
+    }
+}
+
+// s2s_kmer_table_accumulate: every real k-mer slot's n / S / Q (the wave routine above) ADDED to the table row of the slot's k-mer.
+// One wave per chunk.  Lane j < n_valid[b] forms the base-4 code of its k letters (row 4^k for a k-mer with a byte outside ACGT).
+// Then the wave merges the lanes that share a row: per distinct code one ballot; a code held by one lane costs nothing more, a
+// code held by several lanes is summed into its first lane by a wave reduction, so that a homopolymer or a tandem repeat issues
+// one set of adds per wave and not one per slot.  The first lane of every code then adds its six fields with return-less 64-bit
+// integer atomics: integer adds commute, so the table does not depend on the order, the grid or the batching.
+//   LDS == false (k >= S2S_KMER_TABLE_LDS_MAX_K + 1): the adds go to the table in global memory, one workgroup per four chunks.
+//   LDS == true  (k <= S2S_KMER_TABLE_LDS_MAX_K): the (4^k + 1) * 6 counters fit in 49,200 bytes of LDS; a workgroup walks its share
+//       of the chunks adding into its own zeroed copy and adds the copy's non-zero words to the global table once at the end, so
+//       that the few rows of a short k do not take every global atomic of the launch.  At most 512 workgroups.
+#define S2S_KMER_TABLE_LDS_MAX_K 5
+template <int TD, bool LDS>
+__global__ __launch_bounds__(256) void s2s_kmer_table_kernel(const float* __restrict__ signal, const int* __restrict__ dur,
+                                                             const unsigned char* __restrict__ read_bytes,
+                                                             const long long* __restrict__ chunk_start,
+                                                             const unsigned char* __restrict__ n_valid, int B, float dig, float range,
+                                                             float offset, unsigned long long* __restrict__ table, int te, int ts, int k) {
+    extern __shared__ unsigned long long s2s_kmer_lds[];        // LDS only: [4^k + 1][6]
+    const int lane = threadIdx.x & 63, rows = (1 << (2 * k)) + 1;
+    if (LDS) {
+        for (int i = threadIdx.x; i < rows * S2S_KMER_TABLE_FIELDS; i += 256) s2s_kmer_lds[i] = 0ull;
+        __syncthreads();
+    }
+    // (every wave of a workgroup runs the same number of rounds; a wave without a chunk skips the body -- wave-uniformly)
+    for (int b0 = blockIdx.x * 4; b0 < B; b0 += gridDim.x * 4) {
+        const int b = b0 + (threadIdx.x >> 6);
+        if (b >= B) continue;
+        int n, S, n_tail, s_tail;
+        long long Q, q_tail;
+        s2s_slot_stats_wave<TD>(signal, dur, b, lane, dig, range, offset, te, ts, n, S, Q, n_tail, s_tail, q_tail);
+        int nv = n_valid[b];
+        nv = nv > te ? te : nv;
+        const bool real = lane < nv;
+        int code = 0;
+        if (real) {
+            const unsigned char* p = read_bytes + chunk_start[b] + lane;
+            bool other = false;
+            for (int i = 0; i < k; ++i) {
+                const unsigned char ch = p[i];
+                const int d = ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'G' ? 2 : ch == 'T' ? 3 : -1;
+                other |= d < 0;
+                code = code * 4 + (d & 3);
+            }
+            if (other) code = rows - 1;
+        }
+        // the six fields of this lane's slot; a lane that is no real slot holds zeros and takes no part
+        int occ = real ? 1 : 0, ev = (real && n > 0) ? 1 : 0;
+        if (!ev) { n = 0; S = 0; Q = 0; }
+        long long nn = (long long)n * n;
+        bool issue = real;
+        unsigned long long todo = __ballot(real);
+        while (todo) {                                          // wave-uniform: one round per distinct code of the chunk
+            const int first = __ffsll((long long)todo) - 1;
+            const int lc = __shfl(code, first, 64);
+            const bool mine = real && code == lc;
+            const unsigned long long same = __ballot(mine);
+            todo &= ~same;
+            if (__popcll(same) < 2) continue;
+            int r_ev = mine ? ev : 0, r_n = mine ? n : 0, r_s = mine ? S : 0;
+            long long r_nn = mine ? nn : 0, r_q = mine ? Q : 0;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                r_ev += __shfl_xor(r_ev, o, 64);
+                r_n += __shfl_xor(r_n, o, 64);
+                r_s += __shfl_xor(r_s, o, 64);
+                r_nn += __shfl_xor(r_nn, o, 64);
+                r_q += __shfl_xor(r_q, o, 64);
+            }
+            if (lane == first) { occ = __popcll(same); ev = r_ev; n = r_n; S = r_s; nn = r_nn; Q = r_q; }
+            else if (mine) issue = false;
+        }
+        if (issue) {
+            const unsigned long long f[S2S_KMER_TABLE_FIELDS] = {(unsigned long long)occ, (unsigned long long)ev, (unsigned long long)(long long)n,
+                                                                 (unsigned long long)nn, (unsigned long long)(long long)S,
+                                                                 (unsigned long long)Q};
+            const int fields = ev ? S2S_KMER_TABLE_FIELDS : 1;  // a k-mer without samples counts as an occurrence only
+            if (LDS) {
+                unsigned long long* row = s2s_kmer_lds + code * S2S_KMER_TABLE_FIELDS;
+#pragma unroll
+                for (int i = 0; i < S2S_KMER_TABLE_FIELDS; ++i)
+                    if (i < fields) atomicAdd(row + i, f[i]);
+            } else {
+                unsigned long long* row = table + (size_t)code * S2S_KMER_TABLE_FIELDS;
+#pragma unroll
+                for (int i = 0; i < S2S_KMER_TABLE_FIELDS; ++i)
+                    if (i < fields) __hip_atomic_fetch_add(row + i, f[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    }
+    if (LDS) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < rows * S2S_KMER_TABLE_FIELDS; i += 256) {
+            const unsigned long long v = s2s_kmer_lds[i];
+            if (v) __hip_atomic_fetch_add(table + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
     }
 }
 
@@ -2147,6 +2262,37 @@ int s2s_event_stats(s2s_handle* h, void* stream_, const float* signal, const int
     hipLaunchKernelGGL(ts == S2S_T_DEC ? s2s_event_stats_kernel<S2S_T_DEC> : s2s_event_stats_kernel<0>, dim3((B + 3) / 4), dim3(256), 0,
                        static_cast<hipStream_t>(stream_), signal, dur, B, digitisation, range, offset,
                        reinterpret_cast<unsigned short*>(out_seg), out_sum, reinterpret_cast<long long*>(out_sumsq), te, ts);
+    HIP_TRY(h, hipGetLastError());
+    return S2S_OK;
+}
+
+int64_t s2s_kmer_table_rows(int32_t k) {
+    return (k < 1 || k > S2S_KMER_TABLE_MAX_K) ? -1 : ((int64_t)1 << (2 * k)) + 1;
+}
+
+int s2s_kmer_table_accumulate(s2s_handle* h, void* stream_, const float* signal, const int32_t* dur, const uint8_t* read_bytes,
+                              const int64_t* chunk_start, const uint8_t* n_valid, int32_t B, float digitisation, float range,
+                              float offset, int64_t* table) {
+    if (!h) return S2S_ERR_ARG;
+    const int k = h->cfg.seq_kmer;
+    if (k > S2S_KMER_TABLE_MAX_K)
+        return fail(h, S2S_ERR_ARG, "the k-mer table takes seq_kmer 1.." + std::to_string(S2S_KMER_TABLE_MAX_K) + " (4^k + 1 rows), this model has " +
+                                        std::to_string(k));
+    if (B < 0) return fail(h, S2S_ERR_ARG, "negative size");
+    if (!signal || !dur || !read_bytes || !chunk_start || !n_valid || !table) return fail(h, S2S_ERR_ARG, "NULL argument");
+    if (range == 0.0f || digitisation == 0.0f) return fail(h, S2S_ERR_ARG, "range and digitisation must not be 0");
+    if (B == 0) return S2S_OK;
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(h, S2S_ERR_HIP, "hipSetDevice failed");
+    const int te = h->cfg.max_dna_len, ts = h->cfg.max_signal_len;    // S2S_T_ENC / S2S_T_DEC except for a geometry-mode handle
+    const bool lds = k <= S2S_KMER_TABLE_LDS_MAX_K, tuned_rows = ts == S2S_T_DEC;
+    const int groups = (B + 3) / 4;
+    const size_t lds_bytes = lds ? (size_t)s2s_kmer_table_rows(k) * S2S_KMER_TABLE_FIELDS * sizeof(unsigned long long) : 0;
+    auto kernel = lds ? (tuned_rows ? s2s_kmer_table_kernel<S2S_T_DEC, true> : s2s_kmer_table_kernel<0, true>)
+                      : (tuned_rows ? s2s_kmer_table_kernel<S2S_T_DEC, false> : s2s_kmer_table_kernel<0, false>);
+    hipLaunchKernelGGL(kernel, dim3(lds && groups > 512 ? 512 : groups), dim3(256), lds_bytes, static_cast<hipStream_t>(stream_), signal,
+                       dur, read_bytes, reinterpret_cast<const long long*>(chunk_start), n_valid, B, digitisation, range, offset,
+                       reinterpret_cast<unsigned long long*>(table), te, ts, k);
     HIP_TRY(h, hipGetLastError());
     return S2S_OK;
 }

@@ -770,6 +770,84 @@ extern "C" int64_t s2s_events_format(const uint16_t* seg, const int32_t* sum, co
     return pos;
 }
 
+// ================================================================================ k-mer table (predict --kmer-table)
+// The finished table of s2s_kmer_table_accumulate as text, one row per k-mer that occurred; include/s2s_hip.h states the columns.
+// At most 4^10 + 1 rows, once per run: one thread.
+namespace {
+
+constexpr char kKmerTableHeader[] = "kmer\tn_occ\tn_events\tn_samples\tlevel_mean\tlevel_stdv\tdwell_mean\tdwell_stdv\n";
+constexpr int kKmerFields = 6, kKmerMaxK = 10;
+
+// The width a "%.4f" column can take for ANY int64 counters with this calibration: a level is at most (2^63 + |offset|) *
+// |range / digitisation| in magnitude, a dwell at most 2^63.  -> 0 for a calibration that is refused.
+inline int kmer_table_width(double dig, double range, double offset) {
+    if (!(dig == dig) || !(range == range) || !(offset == offset) || dig == 0.0 || range == 0.0) return 0;
+    const double M = std::max((9.3e18 + std::fabs(offset)) * std::fabs(range) / std::fabs(dig) * (1.0 + 1e-9) + 1.0, 9.3e18);
+    char tmp[400];
+    const int digits = (M < 1e300) ? std::snprintf(tmp, sizeof tmp, "%.0f", M) : 312;
+    return 1 + digits + 5;
+}
+
+// -> the bytes the rows may take, or -1 for a negative counter (sum alone may be negative)
+inline int64_t kmer_table_rows_bound(const int64_t* table, int32_t k, int width) {
+    const int64_t rows = ((int64_t)1 << (2 * k)) + 1;
+    int64_t used = 0;
+    for (int64_t r = 0; r < rows; ++r) {
+        const int64_t* f = table + r * kKmerFields;
+        if (f[0] < 0 || f[1] < 0 || f[2] < 0 || f[3] < 0 || f[5] < 0) return -1;
+        used += f[0] >= 1;
+    }
+    return used * (k + 3 * 20 + 4 * (int64_t)width + 8);
+}
+
+}  // namespace
+
+extern "C" int64_t s2s_kmer_table_format_bound(const int64_t* table, int32_t k, float digitisation, float range, float offset,
+                                               int32_t with_header) {
+    const int width = kmer_table_width(digitisation, range, offset);
+    if (!table || k < 1 || k > kKmerMaxK || !width) return S2S_ERR_ARG;
+    const int64_t body = kmer_table_rows_bound(table, k, width);
+    if (body < 0) return S2S_ERR_ARG;
+    return body + (with_header ? (int64_t)sizeof kKmerTableHeader - 1 : 0);
+}
+
+extern "C" int64_t s2s_kmer_table_format(const int64_t* table, int32_t k, float digitisation, float range, float offset,
+                                         int32_t with_header, uint8_t* out, int64_t capacity) {
+    const double dig_d = digitisation, range_d = range, offset_d = offset;
+    const int64_t bound = s2s_kmer_table_format_bound(table, k, digitisation, range, offset, with_header);
+    if (bound < 0 || !out || capacity < bound) return S2S_ERR_ARG;
+    typedef __int128 i128;
+    uint8_t* p = out;
+    if (with_header) { std::memcpy(p, kKmerTableHeader, sizeof kKmerTableHeader - 1); p += sizeof kKmerTableHeader - 1; }
+    const int64_t rows = ((int64_t)1 << (2 * k)) + 1;
+    for (int64_t r = 0; r < rows; ++r) {
+        const int64_t* f = table + r * kKmerFields;
+        if (f[0] < 1) continue;
+        for (int i = 0; i < k; ++i) *p++ = (r == rows - 1) ? 'N' : "ACGT"[(r >> (2 * (k - 1 - i))) & 3];
+        *p++ = '\t';
+        p = put_u64(p, (uint64_t)f[0]); *p++ = '\t';
+        p = put_u64(p, (uint64_t)f[1]); *p++ = '\t';
+        p = put_u64(p, (uint64_t)f[2]); *p++ = '\t';
+        const i128 e = f[1], n = f[2], nn = f[3], S = f[4], Q = f[5];
+        if (e == 0) {
+            std::memcpy(p, "nan\tnan\tnan\tnan\n", 16); p += 16;
+            continue;
+        }
+        const i128 lv = n * Q - S * S, dv = e * nn - n * n;
+        const double v[4] = {((double)S / (double)n + offset_d) * range_d / dig_d,
+                             std::sqrt((double)(lv > 0 ? lv : (i128)0)) / (double)n * range_d / dig_d,
+                             (double)n / (double)e,
+                             std::sqrt((double)(dv > 0 ? dv : (i128)0)) / (double)e};
+        for (int i = 0; i < 4; ++i) {
+            char tmp[400];
+            const int len = std::snprintf(tmp, sizeof tmp, "%.4f", v[i]);
+            if (len < 0 || out + capacity - p < len + 1) return S2S_ERR_ARG;      // (the bound holds every number: not reached)
+            std::memcpy(p, tmp, len); p += len; *p++ = i < 3 ? '\t' : '\n';
+        }
+    }
+    return p - out;
+}
+
 // ================================================================================ read-sampler replay
 // The reference samples reads one after the other from Python's global `random` (Mersenne Twister): per attempt a start
 // position (random.randint), a strand (random.choice, DNA only), and per N of an accepted read a replacement base; the read

@@ -11,6 +11,7 @@ import torch
 from .checkpoint import load_checkpoint
 from .chunker import encode_read, n_chunks as _n_chunks, pack_reads
 from .model import seq2squiggle
+from .kmer_table import rank_counts_path
 from .parallel import local_device, rank_output_path, rank_world, shard_reads
 from .signal_io import BLOW5Writer, POD5Writer
 from .utils import get_profile, get_reads, update_config, update_profile
@@ -251,7 +252,8 @@ def super_batches(reads: Iterable[Tuple[str, str]], k: int, max_chunks: int, t_e
 
 
 def run_streaming(model, reads: Iterable[Tuple[str, str]], writer, profile_dict: dict, profile_name: str,
-                  max_chunks: int = 32768, trace: list = None, alignment=None, events=None, events_samples: bool = False) -> int:
+                  max_chunks: int = 32768, trace: list = None, alignment=None, events=None, events_samples: bool = False,
+                  kmer_table=None) -> int:
     """The predict loop without per-chunk Python objects: whole reads are grouped into super-batches of about
     `max_chunks` chunks; per super-batch one H2D of the packed read bytes, s2s_predict_packed, s2s_export_reads
     (zero-strip + int16 conversion on the GPU), one D2H of the packed int16 samples on a copy stream, then the writer.  Produces the
@@ -271,7 +273,14 @@ def run_streaming(model, reads: Iterable[Tuple[str, str]], writer, profile_dict:
     every record in record order.  Then s2s_event_stats runs in that place instead and its three sections (counts, sums, sums of
     squares) travel there; its counts ARE the alignment's, so with `alignment` as well s2s_align_chunks is not launched.
     `events_samples`: the table gets the `samples` column; on the coded-signal path the packed int16 samples then ride behind the
-    blobs as one more section (the export writes them there), on the plain path they are the payload."""
+    blobs as one more section (the export writes them there), on the plain path they are the payload.
+
+    `kmer_table`: a path or a binary file object that receives the k-mer table of the run (kmer_table.py); a path that ends in
+    ".npz" receives the integer counts instead (a rank of a multi-process run: the parent sums them).  Then
+    s2s_kmer_table_accumulate runs where the counts' kernel runs, on the same `signal` / `dur` and the read letters, chunk starts
+    and n_valid already uploaded for the predict kernel, adding into ONE device table for the whole run: nothing is added to a
+    super-batch's buffer and nothing is formatted per batch.  After the last batch: one sync, one D2H of the table, the text.  It
+    is independent of `alignment` / `events`: any combination gives each file exactly as it is alone."""
     import time
 
     def mark(ev):
@@ -314,6 +323,11 @@ def run_streaming(model, reads: Iterable[Tuple[str, str]], writer, profile_dict:
         events_f.write(format_events(np.zeros(0, np.uint16), np.zeros(0, np.int32), np.zeros(0, np.int64), t_enc, np.zeros(1, np.int32),
                                      [], np.zeros(1, np.int64), [], np.zeros(1, np.uint8), np.zeros(1, np.int64), k, *cal, rna,
                                      dac=np.zeros(1, np.int16) if events_samples else None, with_header=True, threads=1))
+
+    table_d = None
+    if kmer_table is not None:
+        table_d = model.engine.kmer_table_new()    # (refuses a model whose k-mers are longer than the table's limit)
+        table_cal = (profile_dict["digitisation"], profile_dict["range"], profile_dict["offset_mean"])
 
     def launch(group):
         nonlocal total, n_launched
@@ -373,6 +387,8 @@ def run_streaming(model, reads: Iterable[Tuple[str, str]], writer, profile_dict:
                                          profile_dict["offset_mean"], out=buf[seg_at: seg_at + stats_bytes])
             elif seg_bytes:
                 model.engine.align_chunks(out["signal"], out["dur"], out=buf[seg_at: seg_at + seg_bytes].view(torch.uint16))
+            if table_d is not None:
+                model.engine.kmer_table_accumulate(out["signal"], out["dur"], ins[0], ins[1], ins[2], *table_cal, table_d)
         if gpu_rows:
             N = int(row_read.shape[0])
             blob_cap = model.engine.svb_capacity(cap, N, gpu_rows[0])
@@ -496,6 +512,20 @@ def run_streaming(model, reads: Iterable[Tuple[str, str]], writer, profile_dict:
             collect(inflight)
         while pending:
             pending.popleft().result()
+        if table_d is not None:
+            mark("kmer table")
+            from .kmer_table import format_table, save_counts
+            counts_h = table_d.cpu().numpy()        # (synchronises: the one D2H of the table)
+            if not hasattr(kmer_table, "write") and os.fspath(kmer_table).endswith(".npz"):
+                save_counts(os.fspath(kmer_table), counts_h, k, *table_cal)
+            else:
+                text = format_table(counts_h, k, *table_cal)
+                if hasattr(kmer_table, "write"):
+                    kmer_table.write(text)
+                    kmer_table.flush()
+                else:
+                    with open(os.fspath(kmer_table), "wb") as f:
+                        f.write(text)
     finally:
         if hasattr(writer, "close"):               # POD5: run-info and reads tables, footer (on the writer thread as well)
             io.submit(writer.close).result()
@@ -514,13 +544,15 @@ def inference_run(config: dict, saved_weights: str, fasta: str, read_input: bool
                   median_before_mean: float, median_before_std: float, min_noise: float, min_duration: float,
                   min_read_len: int, preserve_read_ids: bool, seed: int, mode: Optional[str] = None, streaming: bool = True,
                   attention_path: str = "auto", alignment: Optional[str] = None, events: Optional[str] = None,
-                  events_samples: bool = False):
+                  events_samples: bool = False, kmer_table: Optional[str] = None):
     """Same 30 parameters as the reference (inference.py:270-301) plus `mode` (decoder arithmetic), `streaming`
     (True: run_streaming; False: the reference's predict_step / export_and_clear_results flow, batch by batch) and
     `attention_path` ("auto": the engine's calibration decides; "fast" / "exact": Engine.attention_path is set to it) and
     `alignment` (a path: the base-to-signal alignment of every record as PAF, alignment.py; a rank of a multi-process run writes
     rank_output_path(alignment); streaming runs only) and `events` / `events_samples` (a path: the per-k-mer event table of every
-    record, events.py, with the `samples` column if events_samples; the same rank naming and restrictions as `alignment`)."""
+    record, events.py, with the `samples` column if events_samples; the same rank naming and restrictions as `alignment`) and
+    `kmer_table` (a path: the k-mer table of the run, kmer_table.py; a rank of a multi-process run writes its integer counts to
+    kmer_table.rank_counts_path(kmer_table, rank) for the parent to sum; streaming runs only)."""
     if attention_path not in ("auto", "fast", "exact"):
         raise ValueError("attention_path must be 'auto', 'fast' or 'exact'")
     if alignment is not None and not streaming:
@@ -529,6 +561,8 @@ def inference_run(config: dict, saved_weights: str, fasta: str, read_input: bool
         raise ValueError("events needs the streaming path (streaming=True): the batch-by-batch flow keeps no k-mer sums")
     if events_samples and events is None:
         raise ValueError("events_samples needs events")
+    if kmer_table is not None and not streaming:
+        raise ValueError("kmer_table needs the streaming path (streaming=True): the batch-by-batch flow keeps no k-mer sums")
     profile_dict = get_profile(profile)
     profile_dict = update_profile(profile_dict, sample_rate=sample_rate, bps=bps, digitisation=digitisation, range=range_val,
                                   offset_mean=offset_mean, offset_std=offset_std, median_before_mean=median_before_mean,
@@ -547,6 +581,8 @@ def inference_run(config: dict, saved_weights: str, fasta: str, read_input: bool
         raise ValueError(f"alignment needs a writer with dac_records (the streaming path); {type(writer).__name__} has none")
     if events is not None and not hasattr(writer, "dac_records"):
         raise ValueError(f"events needs a writer with dac_records (the streaming path); {type(writer).__name__} has none")
+    if kmer_table is not None and not hasattr(writer, "dac_records"):
+        raise ValueError(f"kmer_table needs a writer with dac_records (the streaming path); {type(writer).__name__} has none")
     if saved_weights is None:
         saved_weights = get_saved_weights(profile)             # (inference.py:370-372; the cache only: no network here)
     first_chunk, first_read, total_l = 0, 0, 0
@@ -623,7 +659,9 @@ def inference_run(config: dict, saved_weights: str, fasta: str, read_input: bool
         n_chunks = run_streaming(load_model, reads, writer, profile_dict, profile, trace=_TRACE,
                                  alignment=None if alignment is None else rank_output_path(str(alignment), rank, world),
                                  events=None if events is None else rank_output_path(str(events), rank, world),
-                                 events_samples=events_samples)
+                                 events_samples=events_samples,
+                                 kmer_table=None if kmer_table is None else
+                                 (rank_counts_path(str(kmer_table), rank) if world > 1 else str(kmer_table)))
     else:
         for batch in iter_batches(reads, config["seq_kmer"], predict_batch_size, load_model.device, load_model.engine.t_enc):
             load_model.predict_step(batch)

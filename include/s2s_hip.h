@@ -325,6 +325,49 @@ int s2s_kmer_table_accumulate(s2s_handle* h, void* stream, const float* signal /
                               const uint8_t* n_valid /* device [B] */, int32_t B, float digitisation, float range, float offset,
                               int64_t* table /* device [4^k + 1][6] */);
 
+/* The k-mer model of a run (`predict --kmer-model`): the statistics of event MEANS per k-mer -- what the `level_mean level_stdv
+ * sd_mean sd_stdv` columns of a nanopolish-style model file hold -- summed over every chunk handed to it.  No counterpart in the
+ * reference.  The k-mer table above pools SAMPLES; here every EVENT counts once.
+ *
+ * The fixed-point statistics of one event (s2s_event_fixed: no handle, no GPU; the kernel calls the same inline function).  For a
+ * slot with 1 <= n <= 1024 stored samples, S and Q the n / S / Q of s2s_event_stats, in 64-bit integers only:
+ *   M   the event mean in units of 2^-8 ADC counts: round-half-even of 256*S / n.  num = 256*S; q = floor_div(num, n);
+ *       r = num - q*n (0 <= r < n); q += 1 if 2r > n, or if 2r == n and q is odd.  |M| <= 2^23.
+ *   D   the event's population deviation in the same units: floor(sqrt(x)), x = floor(V * 2^16 / n^2), V = n*Q - S*S (>= 0,
+ *       <= 2^50; a negative V, which no samples give, counts as 0), x formed as (a << 16) + ((b << 16) / n^2) with a = V / n^2,
+ *       b = V % n^2 (b << 16 < 2^36, x <= 2^46); D from a double sqrt, corrected by integer comparison until
+ *       D*D <= x < (D+1)*(D+1).  D <= 2^23.
+ * s2s_event_fixed returns S2S_ERR_ARG for n < 1, n > 1024 or a NULL pointer.
+ *
+ * s2s_kmer_model_accumulate takes the arguments of s2s_kmer_table_accumulate (same k, code, extra row 4^k, slot statistics and
+ * errors), except
+ *  table      device int64 [4^k + 1][S2S_KMER_MODEL_FIELDS], zeroed by the caller once, ADDED to by every call.  Every real slot
+ *             (j < n_valid[b]) with n >= 1 adds to row `code`:
+ *                 [0] events += 1   [1] sum_m += M   [2] sum_m2 += M*M   [3] sum_d += D   [4] sum_d2 += D*D
+ *             Slots without samples, pad slots and the tail add nothing.
+ * All adds are 64-bit integer adds: the table depends only on the SET of chunks.  Ranges: M*M, D*D <= 2^46, exact up to 2^17
+ * full-scale events per k-mer; beyond that the fields wrap; there is no check.
+ * One path for every k.  At most S2S_KMER_MODEL_MAX_WORKGROUPS persistent workgroups of four waves walk the chunks, four per
+ * round.  A wave merges the slots of its chunk that share a row; the first lane of every code then adds its five fields into the
+ * workgroup's write-combining cache in LDS: S2S_KMER_MODEL_SLOTS slots of a key and five counters.  Slot of a code: the code
+ * itself for k <= S2S_KMER_MODEL_DIRECT_MAX_K (4^k + 1 <= the slot count), otherwise
+ *                 (uint64)(uint32)(code * S2S_KMER_MODEL_HASH_MUL) * S2S_KMER_MODEL_SLOTS >> 32
+ * and on a slot held by another code the next one (cyclically), S2S_KMER_MODEL_PROBES slots in all; a code that finds no place
+ * adds straight to `table`.  The cache is added to `table` and cleared every S2S_KMER_MODEL_FLUSH_ROUNDS rounds and at the end
+ * of the walk: at the model's 16 k-mers per chunk that is at most 512 insertions into 1,025 slots between two flushes. */
+#define S2S_KMER_MODEL_FIELDS          5
+#define S2S_KMER_MODEL_SLOTS           1025
+#define S2S_KMER_MODEL_DIRECT_MAX_K    5
+#define S2S_KMER_MODEL_PROBES          4
+#define S2S_KMER_MODEL_HASH_MUL        2654435761u
+#define S2S_KMER_MODEL_FLUSH_ROUNDS    8
+#define S2S_KMER_MODEL_MAX_WORKGROUPS  768
+int s2s_event_fixed(int32_t n, int32_t S, int64_t Q, int64_t* M, int64_t* D);
+int s2s_kmer_model_accumulate(s2s_handle* h, void* stream, const float* signal /* device [B][ts] */,
+                              const int32_t* dur /* device [B][te] */, const uint8_t* read_bytes, const int64_t* chunk_start /* device [B] */,
+                              const uint8_t* n_valid /* device [B] */, int32_t B, float digitisation, float range, float offset,
+                              int64_t* table /* device [4^k + 1][5] */);
+
 /* Replaces the signal compression that pyslow5.write_record_batch (svb-zd) and pod5.Writer.add_reads (the svb16 stage of
  * VBZ) run on the host (reference signal_io.py:167-171, 268-282): StreamVByte encoding of the zig-zag deltas of the packed
  * int16 samples, one output blob per row, so that only ~1.1 bytes per sample cross PCIe.
@@ -467,6 +510,31 @@ int64_t s2s_events_format(const uint16_t* seg, const int32_t* sum, const int64_t
  * (nothing is written then); the bound counts the rows with n_occ >= 1 and holds for any counters. */
 int64_t s2s_kmer_table_format_bound(const int64_t* table, int32_t k, float digitisation, float range, float offset, int32_t with_header);
 int64_t s2s_kmer_table_format(const int64_t* table, int32_t k, float digitisation, float range, float offset, int32_t with_header,
+                              uint8_t* out, int64_t capacity);
+
+/* ---- host-side helper (no GPU work, no handle): the k-mer model of a run (`predict --kmer-model`) as text.
+ *
+ *  table      int64 [4^k + 1][S2S_KMER_MODEL_FIELDS]: what s2s_kmer_model_accumulate built, copied to the host (or the sum of
+ *             several such tables);   k: 1..S2S_KMER_TABLE_MAX_K;
+ *  digitisation, range, offset   the calibration the table was accumulated with (floats, widened to double);
+ *  with_header  != 0: the text starts with the comment lines "#k\t<k>" and "#alphabet\tnucleotide" and the column line
+ *      kmer  level_mean  level_stdv  sd_mean  sd_stdv  n_events
+ * Tab separated, "\n" ended; one row per ACGT k-mer with events >= 1, in code order.  The extra row 4^k is never printed: a model
+ * has no such k-mer.  With e, A, A2, Bs, B2 the row's events, sum_m, sum_m2, sum_d and sum_d2, the products formed in 128-bit
+ * integers, then converted to double, exactly as written:
+ *      level_mean = ((double)A / (256.0 * e) + offset) * range / digitisation
+ *      level_stdv = sqrt((double)max(e*A2 - A*A, 0)) / (256.0 * e) * range / digitisation
+ *      sd_mean    = (double)Bs / (256.0 * e) * range / digitisation
+ *      sd_stdv    = sqrt((double)max(e*B2 - Bs*Bs, 0)) / (256.0 * e) * range / digitisation
+ * each printed "%.4f".  level_mean / level_stdv are the mean and the population deviation (ddof 0) of the k-mer's EVENT MEANS,
+ * sd_mean / sd_stdv those of its events' own sample deviations (s2s_events_format's event_stdv, in fixed point): every event
+ * counts once, however many samples it has.  The levels are those of the calibration GIVEN HERE; the remark of s2s_events_format
+ * on the per-record offset draw applies unchanged.
+ * Returns the bytes written, or S2S_ERR_ARG -- a NULL pointer, k outside 1..10, a calibration that is NaN or has range or
+ * digitisation 0, a negative counter other than sum_m, or capacity below s2s_kmer_model_format_bound's value for the same
+ * arguments (nothing is written then); the bound counts the rows with events >= 1 and holds for any counters. */
+int64_t s2s_kmer_model_format_bound(const int64_t* table, int32_t k, float digitisation, float range, float offset, int32_t with_header);
+int64_t s2s_kmer_model_format(const int64_t* table, int32_t k, float digitisation, float range, float offset, int32_t with_header,
                               uint8_t* out, int64_t capacity);
 
 /* ---- host-side helper (no GPU work, no handle): replays the DRAWS of the reference's read sampler (utils.py:415-479

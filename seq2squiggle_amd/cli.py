@@ -102,6 +102,10 @@ def version():
               help="Also write the k-mer table of the run: one tab-separated row per k-mer that occurred (kmer, n_occ, n_events, "
                    "n_samples, level_mean, level_stdv, dwell_mean, dwell_stdv; include/s2s_hip.h: s2s_kmer_table_format), summed on "
                    "the GPU over all reads. Off by default.")
+@click.option("--kmer-model", default=None, type=click.Path(dir_okay=False), hidden=True,
+              help="Also write the k-mer model of the run: a nanopolish-style pore model with one tab-separated row per ACGT k-mer "
+                   "that got events (kmer, level_mean, level_stdv, sd_mean, sd_stdv, n_events: statistics of EVENT means, "
+                   "include/s2s_hip.h: s2s_kmer_model_format), summed on the GPU over all reads. Off by default.")
 @click.option("--gpus", default=1, type=int, hidden=True,
               help="Run on this many GPUs of the node: one process per GPU, the read set sharded, one OUT.rankN file per process "
                    "(the same as starting the command under torchrun --nproc-per-node N).")
@@ -116,7 +120,7 @@ def predict(ctx, fasta, read_input, num_reads, read_length, coverage, out, profi
             duration_sampler, dwell_mean, dwell_std, noise_std, distr, predict_batch_size, export_every_n_samples,
             sample_rate, bps, digitisation, range_val, offset_mean, offset_std, median_before_mean, median_before_std,
             min_noise, min_duration, min_read_len, preserve_read_ids, seed, model, config, verbosity, compute_mode, attention_path,
-            alignment, events, events_samples, kmer_table, gpus, keep_shards, join_mode):
+            alignment, events, events_samples, kmer_table, kmer_model, gpus, keep_shards, join_mode):
     """Generate nanopore signals from a reference genome (default) or from reads (--read-input)."""
     import os
     if events_samples and not events:
@@ -139,6 +143,10 @@ def predict(ctx, fasta, read_input, num_reads, read_length, coverage, out, profi
         if events and os.environ.get("S2S_DRY_LAUNCH"):
             import json
             click.echo(json.dumps({"events_rank_files": events_shards}))
+        model_shards = [f"{os.path.splitext(str(kmer_model))[0]}.rank{r}.npz" for r in range(gpus)] if kmer_model else []
+        if kmer_model and os.environ.get("S2S_DRY_LAUNCH"):
+            import json
+            click.echo(json.dumps({"kmer_model_rank_files": model_shards}))
         table_shards = [f"{os.path.splitext(str(kmer_table))[0]}.rank{r}.npz" for r in range(gpus)] if kmer_table else []
         if kmer_table and os.environ.get("S2S_DRY_LAUNCH"):
             import json
@@ -150,7 +158,7 @@ def predict(ctx, fasta, read_input, num_reads, read_length, coverage, out, profi
             base_name = str(out)[:len(str(out)) - len(ext)]
             partial = base_name + ".partial" + ext
             shard_paths = [f"{base_name}.rank{r}{ext}" for r in range(gpus)]       # (parallel.rank_output_path, without its imports)
-            for stale in [partial] + shard_paths + align_shards + events_shards + table_shards:   # (a rank file left by an earlier run must not be mistaken for this run's)
+            for stale in [partial] + shard_paths + align_shards + events_shards + table_shards + model_shards:   # (a rank file left by an earlier run must not be mistaken for this run's)
                 if os.path.exists(stale):
                     os.remove(stale)
             holder = {}
@@ -211,6 +219,9 @@ def predict(ctx, fasta, read_input, num_reads, read_length, coverage, out, profi
                 # integer counts: their sum over the ranks is the single-process table (--keep-shards leaves the .npz beside it)
                 from .kmer_table import join_rank_files as join_table_files
                 join_table_files(table_shards, str(kmer_table), keep=keep_shards)
+            if kmer_model and rc == 0 and not os.environ.get("S2S_DRY_LAUNCH"):
+                from .kmer_model import join_rank_files as join_model_files
+                join_model_files(model_shards, str(kmer_model), keep=keep_shards)
             late = reap()                                       # (the merge did not wait for the ranks' teardown: see _launch_ranks)
             rc = rc or late
             timing["total_seconds"] = time.time() - t0
@@ -266,7 +277,7 @@ def predict(ctx, fasta, read_input, num_reads, read_length, coverage, out, profi
                   median_before_std=median_before_std, min_noise=min_noise, min_duration=min_duration,
                   min_read_len=min_read_len, preserve_read_ids=preserve_read_ids, seed=seed, mode=compute_mode,
                   attention_path=attention_path, alignment=alignment, events=events, events_samples=events_samples,
-                  kmer_table=kmer_table)
+                  kmer_table=kmer_table, kmer_model=kmer_model)
     logger.info("Prediction finished.")
     if os.environ.get("S2S_TIMING_DIR"):       # a rank of `predict --gpus N`: when it was ready and when it was done, for the parent's summary
         import json

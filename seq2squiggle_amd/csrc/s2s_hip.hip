@@ -13,6 +13,7 @@
 #include "s2s_generic.h"
 #include "s2s_generic_h.h"
 #include "../../include/s2s_hip.h"
+#include "s2s_event_fixed.h"
 
 #include <cctype>
 #include <cstdio>
@@ -1055,6 +1056,138 @@ __global__ __launch_bounds__(256) void s2s_kmer_table_kernel(const float* __rest
             if (v) __hip_atomic_fetch_add(table + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
+}
+
+// s2s_kmer_model_accumulate: every real k-mer slot with samples adds its event to the row of its k-mer -- 1, the fixed-point
+// event mean M and deviation D (s2s_event_fixed_point) and their squares.  The slot statistics, the code and the wave merge of
+// equal codes are those of s2s_kmer_table_kernel; what differs is where the first lane of every code adds: into a write-combining
+// cache in LDS, one per workgroup, so that a homopolymer or a repeat that sends every chunk's adds to one row costs one set of
+// global adds per flush and not one per wave.
+//   The cache: S2S_KMER_MODEL_SLOTS slots, each a key (the code, or EMPTY) and five counters (field-major: one bank pattern per
+//   field).  A code's slot is the code itself up to k = S2S_KMER_MODEL_DIRECT_MAX_K, else a multiplicative hash of it.
+//   Insertion: atomicCAS(key, EMPTY, code); EMPTY or `code` back means the slot is this code's (its counters are zero or hold this
+//   code's sums) and the five adds are LDS atomics; any other value: the next slot, S2S_KMER_MODEL_PROBES in all; no place found:
+//   the adds go to the global table as in the table kernel.  Nothing waits for another wave.
+//   Flush: every S2S_KMER_MODEL_FLUSH_ROUNDS rounds and after the walk every occupied slot adds its non-zero counters to the global
+//   table and is cleared.  Whether a round flushes depends on the round number, the grid and B alone: uniform over the workgroup,
+//   with a barrier before (every insertion of the interval has landed) and after (no insertion meets a half-cleared slot).
+// Persistent workgroups: at most S2S_KMER_MODEL_MAX_WORKGROUPS (three per CU by LDS: 3 * 45,100 bytes of 160 KiB).
+#define S2S_KMER_MODEL_EMPTY (-1)
+__device__ __forceinline__ void s2s_kmer_model_flush(int* keys, unsigned long long (*cnt)[S2S_KMER_MODEL_SLOTS],
+                                                     unsigned long long* __restrict__ table) {
+    for (int i = threadIdx.x; i < S2S_KMER_MODEL_SLOTS; i += 256) {
+        const int key = keys[i];
+        if (key == S2S_KMER_MODEL_EMPTY) continue;
+        unsigned long long* row = table + (size_t)key * S2S_KMER_MODEL_FIELDS;
+#pragma unroll
+        for (int f = 0; f < S2S_KMER_MODEL_FIELDS; ++f) {
+            const unsigned long long v = cnt[f][i];
+            if (v) __hip_atomic_fetch_add(row + f, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            cnt[f][i] = 0ull;
+        }
+        keys[i] = S2S_KMER_MODEL_EMPTY;
+    }
+}
+
+template <int TD>
+__global__ __launch_bounds__(256) void s2s_kmer_model_kernel(const float* __restrict__ signal, const int* __restrict__ dur,
+                                                             const unsigned char* __restrict__ read_bytes,
+                                                             const long long* __restrict__ chunk_start,
+                                                             const unsigned char* __restrict__ n_valid, int B, float dig, float range,
+                                                             float offset, unsigned long long* __restrict__ table, int te, int ts, int k) {
+    __shared__ int keys[S2S_KMER_MODEL_SLOTS];
+    __shared__ unsigned long long cnt[S2S_KMER_MODEL_FIELDS][S2S_KMER_MODEL_SLOTS];
+    const int lane = threadIdx.x & 63, rows = (1 << (2 * k)) + 1;
+    const bool direct = k <= S2S_KMER_MODEL_DIRECT_MAX_K;
+    for (int i = threadIdx.x; i < S2S_KMER_MODEL_SLOTS; i += 256) {
+        keys[i] = S2S_KMER_MODEL_EMPTY;
+#pragma unroll
+        for (int f = 0; f < S2S_KMER_MODEL_FIELDS; ++f) cnt[f][i] = 0ull;
+    }
+    __syncthreads();
+    int round = 0;
+    // (every wave of a workgroup runs the same rounds; a wave without a chunk skips the body -- wave-uniformly -- not the barriers)
+    for (int b0 = blockIdx.x * 4; b0 < B; b0 += gridDim.x * 4) {
+        const int b = b0 + (threadIdx.x >> 6);
+        if (b < B) {
+            int n, S, n_tail, s_tail;
+            long long Q, q_tail;
+            s2s_slot_stats_wave<TD>(signal, dur, b, lane, dig, range, offset, te, ts, n, S, Q, n_tail, s_tail, q_tail);
+            int nv = n_valid[b];
+            nv = nv > te ? te : nv;
+            const bool real = lane < nv && n > 0;                   // an event: a real slot that owns stored samples
+            int code = 0;
+            long long ev = 0, m = 0, d = 0;
+            if (real) {
+                const unsigned char* p = read_bytes + chunk_start[b] + lane;
+                bool other = false;
+                for (int i = 0; i < k; ++i) {
+                    const unsigned char ch = p[i];
+                    const int dg = ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'G' ? 2 : ch == 'T' ? 3 : -1;
+                    other |= dg < 0;
+                    code = code * 4 + (dg & 3);
+                }
+                if (other) code = rows - 1;
+                int64_t M, D;
+                s2s_event_fixed_point(n, S, Q, M, D);
+                ev = 1; m = M; d = D;
+            }
+            long long m2 = m * m, d2 = d * d;
+            bool issue = real;
+            unsigned long long todo = __ballot(real);
+            while (todo) {                                          // wave-uniform: one round per distinct code of the chunk
+                const int first = __ffsll((long long)todo) - 1;
+                const int lc = __shfl(code, first, 64);
+                const bool mine = real && code == lc;
+                const unsigned long long same = __ballot(mine);
+                todo &= ~same;
+                if (__popcll(same) < 2) continue;
+                long long r_m = mine ? m : 0, r_m2 = mine ? m2 : 0, r_d = mine ? d : 0, r_d2 = mine ? d2 : 0;
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) {
+                    r_m += __shfl_xor(r_m, o, 64);
+                    r_m2 += __shfl_xor(r_m2, o, 64);
+                    r_d += __shfl_xor(r_d, o, 64);
+                    r_d2 += __shfl_xor(r_d2, o, 64);
+                }
+                if (lane == first) { ev = __popcll(same); m = r_m; m2 = r_m2; d = r_d; d2 = r_d2; }
+                else if (mine) issue = false;
+            }
+            if (issue) {
+                const unsigned long long f[S2S_KMER_MODEL_FIELDS] = {(unsigned long long)ev, (unsigned long long)m, (unsigned long long)m2,
+                                                                     (unsigned long long)d, (unsigned long long)d2};
+                unsigned slot = direct ? (unsigned)code
+                                       : (unsigned)(((unsigned long long)((unsigned)code * S2S_KMER_MODEL_HASH_MUL) * S2S_KMER_MODEL_SLOTS) >> 32);
+                bool placed = false;
+#pragma unroll
+                for (int probe = 0; probe < S2S_KMER_MODEL_PROBES; ++probe) {
+                    if (!placed) {
+                        const int old = atomicCAS(&keys[slot], S2S_KMER_MODEL_EMPTY, code);
+                        if (old == S2S_KMER_MODEL_EMPTY || old == code) placed = true;
+                        else slot = slot + 1 == S2S_KMER_MODEL_SLOTS ? 0u : slot + 1;
+                    }
+                }
+                if (placed) {
+#pragma unroll
+                    for (int i = 0; i < S2S_KMER_MODEL_FIELDS; ++i)
+                        atomicAdd(&cnt[i][slot], f[i]);
+                } else {
+                    unsigned long long* row = table + (size_t)code * S2S_KMER_MODEL_FIELDS;
+#pragma unroll
+                    for (int i = 0; i < S2S_KMER_MODEL_FIELDS; ++i)
+                        if (f[i]) __hip_atomic_fetch_add(row + i, f[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            }
+        }
+        ++round;
+        if (round % S2S_KMER_MODEL_FLUSH_ROUNDS == 0 && b0 + (int)gridDim.x * 4 < B) {     // (the last round's flush is the one below)
+            __syncthreads();
+            s2s_kmer_model_flush(keys, cnt, table);
+            __syncthreads();
+        }
+    }
+    __syncthreads();
+    s2s_kmer_model_flush(keys, cnt, table);
 }
 
 // ---- StreamVByte encoders of the output containers (codecs.py states the formats): one 256-thread workgroup per row.
@@ -2293,6 +2426,30 @@ int s2s_kmer_table_accumulate(s2s_handle* h, void* stream_, const float* signal,
     hipLaunchKernelGGL(kernel, dim3(lds && groups > 512 ? 512 : groups), dim3(256), lds_bytes, static_cast<hipStream_t>(stream_), signal,
                        dur, read_bytes, reinterpret_cast<const long long*>(chunk_start), n_valid, B, digitisation, range, offset,
                        reinterpret_cast<unsigned long long*>(table), te, ts, k);
+    HIP_TRY(h, hipGetLastError());
+    return S2S_OK;
+}
+
+int s2s_kmer_model_accumulate(s2s_handle* h, void* stream_, const float* signal, const int32_t* dur, const uint8_t* read_bytes,
+                              const int64_t* chunk_start, const uint8_t* n_valid, int32_t B, float digitisation, float range,
+                              float offset, int64_t* table) {
+    if (!h) return S2S_ERR_ARG;
+    const int k = h->cfg.seq_kmer;
+    if (k > S2S_KMER_TABLE_MAX_K)
+        return fail(h, S2S_ERR_ARG, "the k-mer model takes seq_kmer 1.." + std::to_string(S2S_KMER_TABLE_MAX_K) + " (4^k + 1 rows), this model has " +
+                                        std::to_string(k));
+    if (B < 0) return fail(h, S2S_ERR_ARG, "negative size");
+    if (!signal || !dur || !read_bytes || !chunk_start || !n_valid || !table) return fail(h, S2S_ERR_ARG, "NULL argument");
+    if (range == 0.0f || digitisation == 0.0f) return fail(h, S2S_ERR_ARG, "range and digitisation must not be 0");
+    if (B == 0) return S2S_OK;
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(h, S2S_ERR_HIP, "hipSetDevice failed");
+    const int te = h->cfg.max_dna_len, ts = h->cfg.max_signal_len;    // S2S_T_ENC / S2S_T_DEC except for a geometry-mode handle
+    const int groups = (B + 3) / 4;
+    auto kernel = ts == S2S_T_DEC ? s2s_kmer_model_kernel<S2S_T_DEC> : s2s_kmer_model_kernel<0>;
+    hipLaunchKernelGGL(kernel, dim3(groups > S2S_KMER_MODEL_MAX_WORKGROUPS ? S2S_KMER_MODEL_MAX_WORKGROUPS : groups), dim3(256), 0,
+                       static_cast<hipStream_t>(stream_), signal, dur, read_bytes, reinterpret_cast<const long long*>(chunk_start),
+                       n_valid, B, digitisation, range, offset, reinterpret_cast<unsigned long long*>(table), te, ts, k);
     HIP_TRY(h, hipGetLastError());
     return S2S_OK;
 }

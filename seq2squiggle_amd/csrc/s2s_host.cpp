@@ -5,6 +5,7 @@
 // per-record field bytes (ids, calibration, auxiliary fields -- signal_io.py:143-161) and hands over the packed int16 samples
 // as they came off the GPU; nothing here runs under the interpreter lock.
 #include "../../include/s2s_hip.h"
+#include "s2s_event_fixed.h"
 
 #include <dlfcn.h>
 #include <zlib.h>
@@ -844,6 +845,83 @@ extern "C" int64_t s2s_kmer_table_format(const int64_t* table, int32_t k, float 
             if (len < 0 || out + capacity - p < len + 1) return S2S_ERR_ARG;      // (the bound holds every number: not reached)
             std::memcpy(p, tmp, len); p += len; *p++ = i < 3 ? '\t' : '\n';
         }
+    }
+    return p - out;
+}
+
+// ================================================================================ k-mer model (predict --kmer-model)
+// The fixed-point statistics of one event as a plain entry (the kernel calls the same inline function), and the finished table of
+// s2s_kmer_model_accumulate as a nanopolish-style model file; include/s2s_hip.h states both.  One thread, once per run.
+extern "C" int s2s_event_fixed(int32_t n, int32_t S, int64_t Q, int64_t* M, int64_t* D) {
+    if (n < 1 || n > 1024 || !M || !D) return S2S_ERR_ARG;
+    s2s_event_fixed_point(n, S, Q, *M, *D);
+    return S2S_OK;
+}
+
+namespace {
+
+constexpr char kKmerModelColumns[] = "kmer\tlevel_mean\tlevel_stdv\tsd_mean\tsd_stdv\tn_events\n";
+constexpr int kModelFields = 5;
+
+inline int64_t kmer_model_header_bytes(int32_t k) {
+    char tmp[64];
+    return std::snprintf(tmp, sizeof tmp, "#k\t%d\n#alphabet\tnucleotide\n", k) + (int64_t)sizeof kKmerModelColumns - 1;
+}
+
+// -> the bytes the rows may take, or -1 for a negative counter (sum_m alone may be negative); the row 4^k is never printed
+inline int64_t kmer_model_rows_bound(const int64_t* table, int32_t k, int width) {
+    const int64_t rows = ((int64_t)1 << (2 * k)) + 1;
+    int64_t used = 0;
+    for (int64_t r = 0; r < rows; ++r) {
+        const int64_t* f = table + r * kModelFields;
+        if (f[0] < 0 || f[2] < 0 || f[3] < 0 || f[4] < 0) return -1;
+        used += (f[0] >= 1 && r < rows - 1);
+    }
+    return used * (k + 20 + 4 * (int64_t)width + 6);
+}
+
+}  // namespace
+
+extern "C" int64_t s2s_kmer_model_format_bound(const int64_t* table, int32_t k, float digitisation, float range, float offset,
+                                               int32_t with_header) {
+    const int width = kmer_table_width(digitisation, range, offset);       // (a level is at most 2^63 / 256 counts: the table's width holds)
+    if (!table || k < 1 || k > kKmerMaxK || !width) return S2S_ERR_ARG;
+    const int64_t body = kmer_model_rows_bound(table, k, width);
+    if (body < 0) return S2S_ERR_ARG;
+    return body + (with_header ? kmer_model_header_bytes(k) : 0);
+}
+
+extern "C" int64_t s2s_kmer_model_format(const int64_t* table, int32_t k, float digitisation, float range, float offset,
+                                         int32_t with_header, uint8_t* out, int64_t capacity) {
+    const double dig_d = digitisation, range_d = range, offset_d = offset;
+    const int64_t bound = s2s_kmer_model_format_bound(table, k, digitisation, range, offset, with_header);
+    if (bound < 0 || !out || capacity < bound) return S2S_ERR_ARG;
+    typedef __int128 i128;
+    uint8_t* p = out;
+    if (with_header) {
+        p += std::snprintf(reinterpret_cast<char*>(p), 64, "#k\t%d\n#alphabet\tnucleotide\n", k);
+        std::memcpy(p, kKmerModelColumns, sizeof kKmerModelColumns - 1); p += sizeof kKmerModelColumns - 1;
+    }
+    const int64_t rows = (int64_t)1 << (2 * k);                 // (without the extra row)
+    for (int64_t r = 0; r < rows; ++r) {
+        const int64_t* f = table + r * kModelFields;
+        if (f[0] < 1) continue;
+        for (int i = 0; i < k; ++i) *p++ = "ACGT"[(r >> (2 * (k - 1 - i))) & 3];
+        *p++ = '\t';
+        const i128 e = f[0], A = f[1], A2 = f[2], Bs = f[3], B2 = f[4];
+        const i128 lv = e * A2 - A * A, sv = e * B2 - Bs * Bs;
+        const double den = 256.0 * (double)e;
+        const double v[4] = {((double)A / den + offset_d) * range_d / dig_d,
+                             std::sqrt((double)(lv > 0 ? lv : (i128)0)) / den * range_d / dig_d,
+                             (double)Bs / den * range_d / dig_d,
+                             std::sqrt((double)(sv > 0 ? sv : (i128)0)) / den * range_d / dig_d};
+        for (int i = 0; i < 4; ++i) {
+            char tmp[400];
+            const int len = std::snprintf(tmp, sizeof tmp, "%.4f", v[i]);
+            if (len < 0 || out + capacity - p < len + 22) return S2S_ERR_ARG;     // (the bound holds every number: not reached)
+            std::memcpy(p, tmp, len); p += len; *p++ = '\t';
+        }
+        p = put_u64(p, (uint64_t)f[0]); *p++ = '\n';
     }
     return p - out;
 }

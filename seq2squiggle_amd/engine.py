@@ -377,6 +377,54 @@ class Engine:
         self._check(rc, "s2s_kmer_table_accumulate")
         return table
 
+    KMER_MODEL_FIELDS = 5                             # (S2S_KMER_MODEL_FIELDS of include/s2s_hip.h)
+
+    def kmer_model_new(self) -> torch.Tensor:
+        """A zeroed k-mer model table for kmer_model_accumulate: int64 [4^k + 1, 5] on the engine's device (k the model's seq_kmer;
+        row 4^k takes the k-mers with a letter outside ACGT; columns events, sum_m, sum_m2, sum_d, sum_d2)."""
+        rows = int(_lib.lib().s2s_kmer_table_rows(self.k))
+        if rows < 0:
+            raise ValueError(f"the k-mer model takes seq_kmer 1..{self.KMER_TABLE_MAX_K} (4^k + 1 rows), this model has {self.k}")
+        return torch.zeros(rows, self.KMER_MODEL_FIELDS, dtype=torch.int64, device=self.device)
+
+    def kmer_model_accumulate(self, signal: torch.Tensor, dur: torch.Tensor, read_bytes: torch.Tensor, chunk_start: torch.Tensor,
+                              n_valid: torch.Tensor, digitisation: float, signal_range: float, offset: float,
+                              table: torch.Tensor) -> torch.Tensor:
+        """ADDS the chunks' per-k-mer EVENT statistics to `table` (s2s_kmer_model_accumulate; kmer_model_new makes one): the
+        arguments of kmer_table_accumulate.  Every real k-mer slot that owns stored samples adds 1, its fixed-point event mean M
+        and deviation D (s2s_event_fixed of event_stats' n / S / Q, units of 2^-8 ADC counts) and their squares to the row of its k
+        letters.  Integer adds, combined per workgroup in LDS before they reach the table: the table depends on the set of chunks
+        only.  -> table."""
+        B = int(signal.shape[0]) if signal.dim() == 2 else -1
+        T_ENC, T_DEC = self.t_enc, self.t_dec
+        if signal.dtype != torch.float32 or not signal.is_contiguous() or signal.dim() != 2 or signal.shape[1] != T_DEC:
+            raise ValueError(f"signal must be contiguous float32 [B,{T_DEC}]")
+        if dur.dtype != torch.int32 or not dur.is_contiguous() or tuple(dur.shape) != (B, T_ENC):
+            raise ValueError(f"dur must be contiguous int32 [{B},{T_ENC}]")
+        for name, t, dt in (("read_bytes", read_bytes, torch.uint8), ("chunk_start", chunk_start, torch.int64),
+                            ("n_valid", n_valid, torch.uint8)):
+            if t.dtype != dt or not t.is_contiguous() or t.dim() != 1:
+                raise ValueError(f"{name} must be a contiguous 1-D {dt} tensor")
+        if chunk_start.shape[0] != B or n_valid.shape[0] != B:
+            raise ValueError(f"chunk_start and n_valid must have {B} entries")
+        if self.k > self.KMER_TABLE_MAX_K:
+            raise ValueError(f"the k-mer model takes seq_kmer 1..{self.KMER_TABLE_MAX_K} (4^k + 1 rows), this model has {self.k}")
+        if (table.dtype != torch.int64 or not table.is_contiguous()
+                or tuple(table.shape) != (4 ** self.k + 1, self.KMER_MODEL_FIELDS)):
+            raise ValueError(f"table must be contiguous int64 [{4 ** self.k + 1},{self.KMER_MODEL_FIELDS}]")
+        if any(t.device != self.device for t in (signal, dur, read_bytes, chunk_start, n_valid, table)):
+            raise ValueError(f"every tensor must live on {self.device}")
+        if float(signal_range) == 0.0 or float(digitisation) == 0.0:
+            raise ValueError("range and digitisation must not be 0")
+        if B == 0:                      # (an empty tensor has no address to pass)
+            return table
+        with torch.cuda.device(self.device):
+            rc = _lib.lib().s2s_kmer_model_accumulate(self._h, self._stream(), _ptr(signal), _ptr(dur), _ptr(read_bytes),
+                                                      _ptr(chunk_start), _ptr(n_valid), B, float(digitisation), float(signal_range),
+                                                      float(offset), _ptr(table))
+        self._check(rc, "s2s_kmer_model_accumulate")
+        return table
+
     @staticmethod
     def svb_capacity(total_samples_bound: int, n_rows: int, variant: int) -> int:
         """Bytes s2s_svb_encode may write for n_rows rows holding at most total_samples_bound samples together."""

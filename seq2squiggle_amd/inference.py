@@ -12,6 +12,7 @@ from .checkpoint import load_checkpoint
 from .chunker import encode_read, n_chunks as _n_chunks, pack_reads
 from .model import seq2squiggle
 from .kmer_table import rank_counts_path
+from .kmer_model import rank_counts_path as model_counts_path
 from .parallel import local_device, rank_output_path, rank_world, shard_reads
 from .signal_io import BLOW5Writer, POD5Writer
 from .utils import get_profile, get_reads, update_config, update_profile
@@ -253,7 +254,7 @@ def super_batches(reads: Iterable[Tuple[str, str]], k: int, max_chunks: int, t_e
 
 def run_streaming(model, reads: Iterable[Tuple[str, str]], writer, profile_dict: dict, profile_name: str,
                   max_chunks: int = 32768, trace: list = None, alignment=None, events=None, events_samples: bool = False,
-                  kmer_table=None) -> int:
+                  kmer_table=None, kmer_model=None) -> int:
     """The predict loop without per-chunk Python objects: whole reads are grouped into super-batches of about
     `max_chunks` chunks; per super-batch one H2D of the packed read bytes, s2s_predict_packed, s2s_export_reads
     (zero-strip + int16 conversion on the GPU), one D2H of the packed int16 samples on a copy stream, then the writer.  Produces the
@@ -280,7 +281,12 @@ def run_streaming(model, reads: Iterable[Tuple[str, str]], writer, profile_dict:
     s2s_kmer_table_accumulate runs where the counts' kernel runs, on the same `signal` / `dur` and the read letters, chunk starts
     and n_valid already uploaded for the predict kernel, adding into ONE device table for the whole run: nothing is added to a
     super-batch's buffer and nothing is formatted per batch.  After the last batch: one sync, one D2H of the table, the text.  It
-    is independent of `alignment` / `events`: any combination gives each file exactly as it is alone."""
+    is independent of `alignment` / `events`: any combination gives each file exactly as it is alone.
+
+    `kmer_model`: a path or a binary file object that receives the k-mer model of the run (kmer_model.py: the statistics of event
+    means per k-mer); a path that ends in ".npz" receives the integer counts instead.  s2s_kmer_model_accumulate runs beside the
+    k-mer table's kernel, on the same resident `signal` / `dur` / letters, adding into ONE device table of its own; after the last
+    batch one D2H and one format.  Independent of `alignment` / `events` / `kmer_table` in the same way."""
     import time
 
     def mark(ev):
@@ -328,6 +334,10 @@ def run_streaming(model, reads: Iterable[Tuple[str, str]], writer, profile_dict:
     if kmer_table is not None:
         table_d = model.engine.kmer_table_new()    # (refuses a model whose k-mers are longer than the table's limit)
         table_cal = (profile_dict["digitisation"], profile_dict["range"], profile_dict["offset_mean"])
+    model_d = None
+    if kmer_model is not None:
+        model_d = model.engine.kmer_model_new()    # (refuses a model whose k-mers are longer than the table's limit)
+        model_cal = (profile_dict["digitisation"], profile_dict["range"], profile_dict["offset_mean"])
 
     def launch(group):
         nonlocal total, n_launched
@@ -389,6 +399,8 @@ def run_streaming(model, reads: Iterable[Tuple[str, str]], writer, profile_dict:
                 model.engine.align_chunks(out["signal"], out["dur"], out=buf[seg_at: seg_at + seg_bytes].view(torch.uint16))
             if table_d is not None:
                 model.engine.kmer_table_accumulate(out["signal"], out["dur"], ins[0], ins[1], ins[2], *table_cal, table_d)
+            if model_d is not None:
+                model.engine.kmer_model_accumulate(out["signal"], out["dur"], ins[0], ins[1], ins[2], *model_cal, model_d)
         if gpu_rows:
             N = int(row_read.shape[0])
             blob_cap = model.engine.svb_capacity(cap, N, gpu_rows[0])
@@ -526,6 +538,21 @@ def run_streaming(model, reads: Iterable[Tuple[str, str]], writer, profile_dict:
                 else:
                     with open(os.fspath(kmer_table), "wb") as f:
                         f.write(text)
+        if model_d is not None:
+            mark("kmer model")
+            from .kmer_model import format_model, log_missing, save_counts as save_model_counts
+            counts_h = model_d.cpu().numpy()        # (synchronises: the one D2H of the model's counters)
+            if not hasattr(kmer_model, "write") and os.fspath(kmer_model).endswith(".npz"):
+                save_model_counts(os.fspath(kmer_model), counts_h, k, *model_cal)
+            else:
+                text = format_model(counts_h, k, *model_cal)
+                if hasattr(kmer_model, "write"):
+                    kmer_model.write(text)
+                    kmer_model.flush()
+                else:
+                    with open(os.fspath(kmer_model), "wb") as f:
+                        f.write(text)
+                log_missing(counts_h, k, getattr(kmer_model, "name", kmer_model))
     finally:
         if hasattr(writer, "close"):               # POD5: run-info and reads tables, footer (on the writer thread as well)
             io.submit(writer.close).result()
@@ -544,7 +571,7 @@ def inference_run(config: dict, saved_weights: str, fasta: str, read_input: bool
                   median_before_mean: float, median_before_std: float, min_noise: float, min_duration: float,
                   min_read_len: int, preserve_read_ids: bool, seed: int, mode: Optional[str] = None, streaming: bool = True,
                   attention_path: str = "auto", alignment: Optional[str] = None, events: Optional[str] = None,
-                  events_samples: bool = False, kmer_table: Optional[str] = None):
+                  events_samples: bool = False, kmer_table: Optional[str] = None, kmer_model: Optional[str] = None):
     """Same 30 parameters as the reference (inference.py:270-301) plus `mode` (decoder arithmetic), `streaming`
     (True: run_streaming; False: the reference's predict_step / export_and_clear_results flow, batch by batch) and
     `attention_path` ("auto": the engine's calibration decides; "fast" / "exact": Engine.attention_path is set to it) and
@@ -552,7 +579,8 @@ def inference_run(config: dict, saved_weights: str, fasta: str, read_input: bool
     rank_output_path(alignment); streaming runs only) and `events` / `events_samples` (a path: the per-k-mer event table of every
     record, events.py, with the `samples` column if events_samples; the same rank naming and restrictions as `alignment`) and
     `kmer_table` (a path: the k-mer table of the run, kmer_table.py; a rank of a multi-process run writes its integer counts to
-    kmer_table.rank_counts_path(kmer_table, rank) for the parent to sum; streaming runs only)."""
+    kmer_table.rank_counts_path(kmer_table, rank) for the parent to sum; streaming runs only) and `kmer_model` (a path: the k-mer
+    model of the run, kmer_model.py; ranks write kmer_model.rank_counts_path(kmer_model, rank); streaming runs only)."""
     if attention_path not in ("auto", "fast", "exact"):
         raise ValueError("attention_path must be 'auto', 'fast' or 'exact'")
     if alignment is not None and not streaming:
@@ -563,6 +591,8 @@ def inference_run(config: dict, saved_weights: str, fasta: str, read_input: bool
         raise ValueError("events_samples needs events")
     if kmer_table is not None and not streaming:
         raise ValueError("kmer_table needs the streaming path (streaming=True): the batch-by-batch flow keeps no k-mer sums")
+    if kmer_model is not None and not streaming:
+        raise ValueError("kmer_model needs the streaming path (streaming=True): the batch-by-batch flow keeps no k-mer sums")
     profile_dict = get_profile(profile)
     profile_dict = update_profile(profile_dict, sample_rate=sample_rate, bps=bps, digitisation=digitisation, range=range_val,
                                   offset_mean=offset_mean, offset_std=offset_std, median_before_mean=median_before_mean,
@@ -583,6 +613,8 @@ def inference_run(config: dict, saved_weights: str, fasta: str, read_input: bool
         raise ValueError(f"events needs a writer with dac_records (the streaming path); {type(writer).__name__} has none")
     if kmer_table is not None and not hasattr(writer, "dac_records"):
         raise ValueError(f"kmer_table needs a writer with dac_records (the streaming path); {type(writer).__name__} has none")
+    if kmer_model is not None and not hasattr(writer, "dac_records"):
+        raise ValueError(f"kmer_model needs a writer with dac_records (the streaming path); {type(writer).__name__} has none")
     if saved_weights is None:
         saved_weights = get_saved_weights(profile)             # (inference.py:370-372; the cache only: no network here)
     first_chunk, first_read, total_l = 0, 0, 0
@@ -661,7 +693,9 @@ def inference_run(config: dict, saved_weights: str, fasta: str, read_input: bool
                                  events=None if events is None else rank_output_path(str(events), rank, world),
                                  events_samples=events_samples,
                                  kmer_table=None if kmer_table is None else
-                                 (rank_counts_path(str(kmer_table), rank) if world > 1 else str(kmer_table)))
+                                 (rank_counts_path(str(kmer_table), rank) if world > 1 else str(kmer_table)),
+                                 kmer_model=None if kmer_model is None else
+                                 (model_counts_path(str(kmer_model), rank) if world > 1 else str(kmer_model)))
     else:
         for batch in iter_batches(reads, config["seq_kmer"], predict_batch_size, load_model.device, load_model.engine.t_enc):
             load_model.predict_step(batch)

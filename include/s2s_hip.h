@@ -200,7 +200,13 @@ const char* s2s_last_error(const s2s_handle* h);
  *           (add_remainder, utils.py:342-347), not a shifted window;
  *  first_global_chunk  index of chunk 0 in the whole job: the RNG counter is
  *           (first_global_chunk + b, position, draw kind), so results do not depend on batch
- *           size or on how chunks are sharded over GPUs;
+ *           size or on how chunks are sharded over GPUs.  Word for word, in every compute mode and chunk geometry: the
+ *           Philox4x32-10 counter is {chunk low word, chunk high word, position | kind << 16, draw index} with chunk =
+ *           first_global_chunk + b as an unsigned 64-bit number, the key {seed low word, seed high word}.  position is the
+ *           k-mer c (kinds 1 and 2) or the sample t (kind 3) inside the chunk; kind is 1 for the Gamma dwell, 2 for the dwell
+ *           normal, 3 for the noise normal; the draw index is 0 except in the Gamma sampler, which counts its draws from 0
+ *           (the alpha < 1 boost first, then one per trip of the rejection loop).  A normal of output words {x, y, ..} is
+ *           sqrt(-2 ln u1) * cos(2 pi u2), u1 = ((x >> 8) + 1) * 2^-24, u2 = (y >> 8) * 2^-24;
  *  inject_g   nullable device [B][16]: value of Gamma.sample() (modules.py:221-222) to use
  *             instead of the built-in sampler (duration_sampling only);
  *  inject_zdw nullable device [B][16]: standard normals for the dwell_std > 0 mode;
@@ -253,7 +259,13 @@ int s2s_evaluate_chunks(s2s_handle* h, void* stream, const uint8_t* kmers, const
  *               writer.signals, model.py:290);
  *  out_dac      nullable device int16 [capacity]: round_half_even(pa*digitisation/range - offset)
  *               wrapped to int16; reversed per read when rna != 0 (signal_io.py:140-141);
- *  capacity     size of out_pa/out_dac in samples (B*250 always suffices).
+ *  capacity     size of out_pa/out_dac in samples (B*250 always suffices).  A capacity below the sample count truncates and
+ *               never writes out of bounds: out_offsets is complete whatever the capacity (out_offsets[R] > capacity tells the
+ *               caller), and in each of out_pa / out_dac exactly the elements whose own index is below capacity are written,
+ *               with the value a call with enough capacity puts there -- for rna != 0 too, where the element at an index is
+ *               not the sample that was found at it.  Nothing else is touched.
+ * Only out_dac is reversed when rna != 0; out_pa keeps the order of the signal.  Reads may be empty (read_first[r] ==
+ * read_first[r+1]); read_first[0] == 0, read_first[R] == B, non-decreasing.  B == 0 writes R+1 zero offsets.
  * Rows are 250 samples, max_signal_len for a S2S_MODE_GENERIC_GEOMETRY(_F16) handle.
  */
 int s2s_export_reads(s2s_handle* h, void* stream, const float* signal, int32_t B,

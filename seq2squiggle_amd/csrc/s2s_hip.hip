@@ -831,10 +831,11 @@ __global__ __launch_bounds__(256) void s2s_compact_kernel(const float* __restric
         const bool keep = v != 0.0f;
         const unsigned long long mask = __ballot(keep);
         const long long dst = pos + __popcll(mask & ((1ull << lane) - 1ull));
-        if (keep && dst < capacity) {
-            if (out_pa) out_pa[dst] = v;
+        if (keep) {                            // every store tests the index IT uses: pa is never reversed, dac is when rna
+            if (out_pa && dst < capacity) out_pa[dst] = v;
             if (out_dac) {
-                out_dac[rna ? (r_lo + (r_hi - 1 - dst)) : dst] = s2s_dac_of(v, dig, range, offset);
+                const long long at = rna ? (r_lo + (r_hi - 1 - dst)) : dst;      // r_lo <= at < r_hi
+                if (at < capacity) out_dac[at] = s2s_dac_of(v, dig, range, offset);
             }
         }
         pos += __popcll(mask);

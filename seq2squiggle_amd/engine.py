@@ -254,6 +254,9 @@ class Engine:
         dac = None
         if want_dac or out_dac is not None:
             dac = out_dac[:cap] if out_dac is not None else torch.empty(cap, dtype=torch.int16, device=self.device)
+        if B == 0:                      # (an empty tensor has no address to pass): every read is empty
+            offs.zero_()
+            return {"offsets": offs, "pa": pa, "dac": dac}
         with torch.cuda.device(self.device):
             rc = _lib.lib().s2s_export_reads(self._h, self._stream(), _ptr(signal), B, _ptr(read_first), R, _ptr(offs),
                                              _ptr(pa), _ptr(dac), cap, float(digitisation), float(signal_range),

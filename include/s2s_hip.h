@@ -549,6 +549,62 @@ int64_t s2s_kmer_model_format_bound(const int64_t* table, int32_t k, float digit
 int64_t s2s_kmer_model_format(const int64_t* table, int32_t k, float digitisation, float range, float offset, int32_t with_header,
                               uint8_t* out, int64_t capacity);
 
+/* ---- `compare`: how far two stored signals are apart -- median / MAD normalisation and the banded dynamic-time-warping (DTW)
+ * distance, all in integers, so that the same bytes come out for any batching and any workgroup shape and on the host.  The
+ * reference has no such command.  No checkpoint is involved: the entries take no handle but `device` and `stream` (a hipStream_t
+ * as void*, NULL = default stream), make the device current for their duration, are stream-ordered and asynchronous to the host,
+ * and return S2S_OK / S2S_ERR_ARG / S2S_ERR_HIP (message: s2s_last_error(NULL)).  All pointers are device pointers; offs are int64.
+ *
+ * Median and MAD of a record of n >= 1 stored int16 samples:
+ *   med = the lower median: the element of rank (n - 1) / 2 (integer division) of the sorted samples;
+ *   mad = the element of the same rank of the sorted |x - med| (0 .. 65,535: it does not fit int16);
+ *   both int32; a record with n = 0 (or with n > S2S_DTW_MAX_SAMPLES) gives med = mad = 0.
+ * Normalised sample:
+ *   q = clamp(floor((2 (x - med) S + d) / (2 d)), -32767, 32767) as int16, d = max(mad, 1), S = `scale` (S2S_DTW_SCALE = 64: one
+ *   MAD is 64 units); round-half-up on a true floor division.  1 <= scale <= 8192 (the numerator stays below 2^31); med and mad
+ *   outside what int16 samples can give are clamped to -32768 .. 32767 and 1 .. 65,535.
+ * Banded DTW of a (n samples) against b (m samples), band R >= 1:
+ *   cell (i, j) is inside the band iff |i m - j n| <= R max(n, m) (in int64): symmetric under swapping a and b, +-R samples on
+ *   the shorter signal's axis; for R >= 1 it always holds a monotone path from (0, 0) to (n - 1, m - 1) (step i while
+ *   i m - j n <= 0, else j);
+ *   cost(i, j) = |a[i] - b[j]|;  D(i, j) = cost(i, j) + min(D(i - 1, j), D(i, j - 1), D(i - 1, j - 1)) over the predecessors inside
+ *   the band and the matrix, D(0, 0) = cost(0, 0);
+ *   the result is D(n - 1, m - 1), an int64 (70,000 samples of opposite extremes pass 2^32).  No path is traced back.  The
+ *   per-sample figure of `compare` is D / (n + m) / S, formed on the host in double.
+ *   n = 0 or m = 0: S2S_DTW_COST_EMPTY (-1).
+ * Limits: 1 <= band <= S2S_DTW_MAX_BAND (s2s_dtw_max_band() returns it); n, m <= S2S_DTW_MAX_SAMPLES = 2^22; 0 <= R, P.  A band or
+ * a count outside them is S2S_ERR_ARG and nothing is launched.  The lengths of the device entries lie in device memory, which a
+ * stream-ordered call cannot read: a pair with a member longer than the limit costs no work and gets S2S_DTW_COST_TOO_LONG (-2);
+ * the host twins, which see the lengths, return S2S_ERR_ARG for it before they compute anything.
+ *
+ *  s2s_signal_median_mad   samples: the records back to back, record r = samples[offs[r] .. offs[r+1]); med, mad [R] out.  One
+ *                 workgroup per record, exact rank selection by two 256-bin histogram passes in LDS over x + 32768 (the high byte,
+ *                 then the low byte inside the selected bin) and the same two passes over |x - med|.
+ *  s2s_signal_normalise    out [offs[R]] int16 (may not alias samples).
+ *  s2s_dtw_banded          pair p = a[a_offs[p] .. a_offs[p+1]) against b[b_offs[p] .. b_offs[p+1]); cost [P] out.  One workgroup
+ *                 per pair sweeps the anti-diagonals with three rolling diagonals of int64 in LDS (3 (2 band + 2) 8 bytes) and two
+ *                 windows of the samples of the next 256 diagonals (2 (2 band + 256) 2 bytes): 58,416 B at S2S_DTW_MAX_BAND; no
+ *                 atomics, no traffic between workgroups. */
+#define S2S_DTW_SCALE 64
+#define S2S_DTW_MAX_BAND 1024
+#define S2S_DTW_MAX_SAMPLES (1 << 22)
+#define S2S_DTW_COST_EMPTY (-1)
+#define S2S_DTW_COST_TOO_LONG (-2)
+int32_t s2s_dtw_max_band(void);
+int s2s_signal_median_mad(int device, void* stream, const int16_t* samples, const int64_t* offs, int32_t R, int32_t* med, int32_t* mad);
+int s2s_signal_normalise(int device, void* stream, const int16_t* samples, const int64_t* offs, int32_t R, const int32_t* med,
+                         const int32_t* mad, int32_t scale, int16_t* out);
+int s2s_dtw_banded(int device, void* stream, const int16_t* a, const int64_t* a_offs, const int16_t* b, const int64_t* b_offs,
+                   int32_t P, int32_t band, int64_t* cost);
+/* The same three on host pointers, in plain C++ (`compare --cpu`; also the definition the GPU must equal bit for bit): records /
+ * pairs are dealt out over `threads` >= 1 host threads; the DTW sweeps rows with two rolling rows.  S2S_ERR_ARG as above, and for a
+ * record or a pair member longer than S2S_DTW_MAX_SAMPLES or offsets that decrease. */
+int s2s_signal_median_mad_host(const int16_t* samples, const int64_t* offs, int32_t R, int32_t* med, int32_t* mad, int32_t threads);
+int s2s_signal_normalise_host(const int16_t* samples, const int64_t* offs, int32_t R, const int32_t* med, const int32_t* mad,
+                              int32_t scale, int16_t* out, int32_t threads);
+int s2s_dtw_banded_host(const int16_t* a, const int64_t* a_offs, const int16_t* b, const int64_t* b_offs, int32_t P, int32_t band,
+                        int64_t* cost, int32_t threads);
+
 /* ---- host-side helper (no GPU work, no handle): replays the DRAWS of the reference's read sampler (utils.py:415-479
  * `sampling`, with the read-length law of utils.py:325-331 `draw_expon_dis`) without building a read, so that a rank of a sharded
  * run finds the generator state of its first read in microseconds per thousand reads instead of replaying them in the

@@ -31,7 +31,9 @@ EXPORTS = ("s2s_blob_floats", "s2s_create", "s2s_destroy", "s2s_last_error", "s2
            "s2s_fasta_count", "s2s_fasta_clean", "s2s_fastq_clean", "s2s_copy_ranges", "s2s_blow5_scan", "s2s_blow5_scan_upto", "s2s_attention_redo_threshold", "s2s_evaluate_chunks",
            "s2s_align_chunks", "s2s_paf_format", "s2s_paf_format_bound", "s2s_event_stats", "s2s_events_format", "s2s_events_format_bound",
            "s2s_kmer_table_rows", "s2s_kmer_table_accumulate", "s2s_kmer_table_format", "s2s_kmer_table_format_bound",
-           "s2s_event_fixed", "s2s_kmer_model_accumulate", "s2s_kmer_model_format", "s2s_kmer_model_format_bound")
+           "s2s_event_fixed", "s2s_kmer_model_accumulate", "s2s_kmer_model_format", "s2s_kmer_model_format_bound",
+           "s2s_dtw_max_band", "s2s_signal_median_mad", "s2s_signal_normalise", "s2s_dtw_banded",
+           "s2s_signal_median_mad_host", "s2s_signal_normalise_host", "s2s_dtw_banded_host")
 
 
 def lib():
@@ -102,5 +104,12 @@ def lib():
     bind("s2s_kmer_model_accumulate", i32, [vp, vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, vp])
     bind("s2s_kmer_model_format_bound", i64, [vp, i32, f32, f32, f32, i32])
     bind("s2s_kmer_model_format", i64, [vp, i32, f32, f32, f32, i32, vp, i64])
+    bind("s2s_dtw_max_band", i32, [])
+    bind("s2s_signal_median_mad", i32, [i32, vp, vp, vp, i32, vp, vp])
+    bind("s2s_signal_normalise", i32, [i32, vp, vp, vp, i32, vp, vp, i32, vp])
+    bind("s2s_dtw_banded", i32, [i32, vp, vp, vp, vp, vp, i32, i32, vp])
+    bind("s2s_signal_median_mad_host", i32, [vp, vp, i32, vp, vp, i32])
+    bind("s2s_signal_normalise_host", i32, [vp, vp, i32, vp, vp, i32, vp, i32])
+    bind("s2s_dtw_banded_host", i32, [vp, vp, vp, vp, i32, i32, vp, i32])
     _lib = L
     return L

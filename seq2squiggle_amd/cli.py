@@ -524,5 +524,45 @@ def evaluate(data_dir, models, compute_mode, max_chunks, batch_size, per_chunk, 
     if per_chunk:
         np.savez(per_chunk, models=np.array([str(m) for m in models]), **arrays)
 
+
+@main.command()
+@click.argument("a", type=click.Path(dir_okay=False))
+@click.argument("b", type=click.Path(dir_okay=False))
+@click.option("-o", "--out", required=True, type=click.Path(dir_okay=False), help="Output table (.tsv), one row per pair of records.")
+@click.option("--band", default=512, type=int, show_default=True,
+              help="Half width of the DTW band in samples of the shorter signal.  The default is a choice, not a measurement: the dwell "
+                   "drift over a 5 kb read is a few hundred samples.")
+@click.option("--normalise", "normalise", default="mad", type=click.Choice(["mad", "none"]), show_default=True,
+              help="mad: (x - median) / MAD per record, in integer steps of 1/64 MAD; none: the stored samples as they are.")
+@click.option("--by-order", is_flag=True, help="Pair the k-th record of A with the k-th of B instead of pairing by read id.")
+@click.option("--max-samples", default=1 << 27, type=int, show_default=True, help="Samples of both files per batch.")
+@click.option("--cpu", is_flag=True, help="Compute on host threads instead of the GPU (the same integers).")
+@click.option("--json", "as_json", is_flag=True, help="Print the summary as one JSON object.")
+def compare(a, b, out, band, normalise, by_order, max_samples, cpu, as_json):
+    """Banded dynamic-time-warping distance between the signals of two .blow5 / .slow5 files, record against record (paired by read
+    id, in A's order): OUT gets read_id, n_a, n_b, med_a, mad_a, med_b, mad_b, band, dtw, dtw_per_sample.  Everything is computed in
+    integers on the stored int16 samples; dtw_per_sample = dtw / (n_a + n_b) / 64, in MADs per step with --normalise mad."""
+    for p in (a, b):
+        if str(p).endswith(".pod5"):
+            raise click.UsageError(f"{p}: compare reads .blow5 and .slow5 files; reading POD5 is not supported")
+        if not str(p).endswith((".blow5", ".slow5")):
+            raise click.UsageError(f"{p}: compare reads .blow5 and .slow5 files")
+    if max_samples < 1:
+        raise click.BadParameter("must be >= 1", param_hint="--max-samples")
+    import json
+    if not cpu:
+        import torch  # noqa: F401  (before the library: see engine.py)
+    from . import compare as C
+    if not 1 <= band <= C.max_band():
+        raise click.BadParameter(f"must be 1..{C.max_band()}", param_hint="--band")
+    s = C.compare_files(a, b, out, band=band, normalise=normalise, by_order=by_order, max_samples=max_samples, cpu=cpu)
+    if as_json:
+        click.echo(json.dumps(s))
+    else:
+        fmt = lambda v: "nan" if v is None else f"{v:.6f}"      # noqa: E731
+        click.echo(f"{s['pairs']} pairs -> {out}  [band {band}, normalise {normalise}; unpaired: {s['unpaired_a']} of {s['records_a']} in "
+                   f"{a}, {s['unpaired_b']} of {s['records_b']} in {b}]  dtw_per_sample mean {fmt(s['mean_dtw_per_sample'])}  "
+                   f"median {fmt(s['median_dtw_per_sample'])}")
+
 if __name__ == "__main__":
     main()

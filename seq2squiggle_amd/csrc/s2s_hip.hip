@@ -14,6 +14,8 @@
 #include "s2s_generic_h.h"
 #include "../../include/s2s_hip.h"
 #include "s2s_event_fixed.h"
+#define S2S_DTW_KERNELS
+#include "s2s_dtw.h"
 
 #include <cctype>
 #include <cstdio>
@@ -2560,6 +2562,50 @@ int s2s_diag_read(s2s_handle* h, uint64_t* out48) {
     HIP_TRY(h, hipDeviceSynchronize());
     HIP_TRY(h, hipMemcpy(out48, h->d_diag, 8 * 48 * sizeof(uint64_t), hipMemcpyDeviceToHost));
     HIP_TRY(h, hipMemset(h->d_diag, 0, 8 * 48 * sizeof(uint64_t)));
+    return S2S_OK;
+}
+
+// ---- compare (s2s_dtw.h): handle-free, stream-ordered
+int32_t s2s_dtw_max_band(void) { return S2S_DTW_MAX_BAND; }
+
+int s2s_signal_median_mad(int device, void* stream_, const int16_t* samples, const int64_t* offs, int32_t R, int32_t* med, int32_t* mad) {
+    if (R < 0 || !offs || (R > 0 && (!samples || !med || !mad))) return fail(nullptr, S2S_ERR_ARG, "s2s_signal_median_mad: bad argument");
+    if (R == 0) return S2S_OK;
+    DeviceGuard guard(device);
+    if (!guard.ok) return fail(nullptr, S2S_ERR_HIP, "hipSetDevice failed");
+    hipLaunchKernelGGL(s2s_median_mad_kernel, dim3(R), dim3(S2S_DTW_SELECT_THREADS), 0, static_cast<hipStream_t>(stream_), samples,
+                       reinterpret_cast<const long long*>(offs), med, mad);
+    HIP_TRY(nullptr, hipGetLastError());
+    return S2S_OK;
+}
+
+int s2s_signal_normalise(int device, void* stream_, const int16_t* samples, const int64_t* offs, int32_t R, const int32_t* med,
+                         const int32_t* mad, int32_t scale, int16_t* out) {
+    if (R < 0 || !offs || scale < 1 || scale > S2S_DTW_MAX_SCALE || (R > 0 && (!samples || !med || !mad || !out)))
+        return fail(nullptr, S2S_ERR_ARG, "s2s_signal_normalise: bad argument (scale must be 1..8192)");
+    if (R == 0) return S2S_OK;
+    DeviceGuard guard(device);
+    if (!guard.ok) return fail(nullptr, S2S_ERR_HIP, "hipSetDevice failed");
+    hipLaunchKernelGGL(s2s_normalise_kernel, dim3(R, S2S_DTW_NORM_SLICES), dim3(256), 0, static_cast<hipStream_t>(stream_), samples,
+                       reinterpret_cast<const long long*>(offs), med, mad, scale, out);
+    HIP_TRY(nullptr, hipGetLastError());
+    return S2S_OK;
+}
+
+int s2s_dtw_banded(int device, void* stream_, const int16_t* a, const int64_t* a_offs, const int16_t* b, const int64_t* b_offs,
+                   int32_t P, int32_t band, int64_t* cost) {
+    if (P < 0 || band < 1 || band > S2S_DTW_MAX_BAND || !a_offs || !b_offs || (P > 0 && (!a || !b || !cost)))
+        return fail(nullptr, S2S_ERR_ARG, "s2s_dtw_banded: bad argument (band must be 1..S2S_DTW_MAX_BAND)");
+    if (P == 0) return S2S_OK;
+    DeviceGuard guard(device);
+    if (!guard.ok) return fail(nullptr, S2S_ERR_HIP, "hipSetDevice failed");
+    // a diagonal holds at most 2 band + 1 cells: one wave while two strides cover it, else four
+    const int threads = 2 * band + 1 <= 128 ? 64 : 256;
+    const size_t lds = S2S_DTW_LDS_BYTES(band);      // 58,416 B at S2S_DTW_MAX_BAND
+    hipLaunchKernelGGL(s2s_dtw_kernel, dim3(P), dim3(threads), lds, static_cast<hipStream_t>(stream_), a,
+                       reinterpret_cast<const long long*>(a_offs), b, reinterpret_cast<const long long*>(b_offs), band,
+                       reinterpret_cast<long long*>(cost));
+    HIP_TRY(nullptr, hipGetLastError());
     return S2S_OK;
 }
 

@@ -1505,3 +1505,103 @@ extern "C" int64_t s2s_blow5_scan_upto(int32_t fd, int64_t begin, int64_t limit,
     return n;
 }
 
+
+// ================================================================================ compare: median / MAD, normalise, banded DTW on the host
+// The plain-C++ twins of the three kernels of s2s_dtw.h (include/s2s_hip.h states the definitions): `compare --cpu`, and what the
+// kernels must equal bit for bit.  Records / pairs are dealt out over host threads; nothing is shared between them.
+#include "s2s_dtw.h"
+
+namespace {
+
+template <class F>
+void dtw_for_each(int32_t n, int32_t threads, F fn) {
+    std::atomic<int32_t> next{0};
+    auto work = [&]() {
+        for (int32_t i; (i = next.fetch_add(1)) < n;) fn(i);
+    };
+    const int extra = std::min<int32_t>(threads, n) - 1;
+    std::vector<std::thread> pool;
+    for (int t = 0; t < extra; ++t) pool.emplace_back(work);
+    work();
+    for (auto& t : pool) t.join();
+}
+
+bool dtw_offsets_ok(const int64_t* offs, int32_t n) {
+    for (int32_t i = 0; i < n; ++i) {
+        const int64_t len = offs[i + 1] - offs[i];
+        if (len < 0 || len > S2S_DTW_MAX_SAMPLES) return false;
+    }
+    return true;
+}
+
+inline int64_t dtw_floor_div(int64_t a, int64_t b) {       // b > 0
+    int64_t q = a / b;
+    return a - q * b < 0 ? q - 1 : q;
+}
+
+// Row sweep: row i holds the columns jlo(i) .. jhi(i) = ceil((i m - T) / n) .. floor((i m + T) / n) clipped to the matrix; two rolling
+// rows indexed by j - jlo of their own row; a predecessor outside its row's range is +infinity.
+int64_t dtw_pair(const int16_t* a, int64_t n, const int16_t* b, int64_t m, int64_t R) {
+    if (n <= 0 || m <= 0) return S2S_DTW_COST_EMPTY;
+    const int64_t T = R * std::max(n, m);
+    const int64_t width = std::min<int64_t>(m, 2 * (T / n) + 3);
+    std::vector<int64_t> rows(2 * (size_t)width);
+    int64_t* prev = rows.data();
+    int64_t* cur = prev + width;
+    int64_t plo = 0, phi = -1;
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t jlo = std::max<int64_t>(0, -dtw_floor_div(T - i * m, n)), jhi = std::min(m - 1, dtw_floor_div(i * m + T, n));
+        for (int64_t j = jlo; j <= jhi; ++j) {
+            int64_t best = (i == 0 && j == 0) ? 0 : S2S_DTW_UNREACHED;
+            if (j >= plo && j <= phi) best = std::min(best, prev[j - plo]);                  // (i - 1, j)
+            if (j - 1 >= plo && j - 1 <= phi) best = std::min(best, prev[j - 1 - plo]);      // (i - 1, j - 1)
+            if (j - 1 >= jlo) best = std::min(best, cur[j - 1 - jlo]);                       // (i, j - 1)
+            const int64_t c = std::abs((int64_t)a[i] - (int64_t)b[j]);
+            cur[j - jlo] = best >= S2S_DTW_UNREACHED ? S2S_DTW_UNREACHED : best + c;
+        }
+        std::swap(prev, cur);
+        plo = jlo; phi = jhi;
+    }
+    return (m - 1 >= plo && m - 1 <= phi) ? prev[m - 1 - plo] : S2S_DTW_UNREACHED;
+}
+
+}  // namespace
+
+extern "C" int s2s_signal_median_mad_host(const int16_t* samples, const int64_t* offs, int32_t R, int32_t* med, int32_t* mad, int32_t threads) {
+    if (R < 0 || threads < 1 || !offs || (R > 0 && (!samples || !med || !mad)) || !dtw_offsets_ok(offs, R)) return S2S_ERR_ARG;
+    dtw_for_each(R, threads, [&](int32_t r) {
+        const int64_t n = offs[r + 1] - offs[r];
+        if (n == 0) { med[r] = 0; mad[r] = 0; return; }
+        const int16_t* p = samples + offs[r];
+        const int64_t k = (n - 1) / 2;
+        std::vector<int32_t> v(p, p + n);
+        std::nth_element(v.begin(), v.begin() + k, v.end());
+        const int32_t md = v[k];
+        for (int64_t i = 0; i < n; ++i) v[i] = std::abs((int32_t)p[i] - md);
+        std::nth_element(v.begin(), v.begin() + k, v.end());
+        med[r] = md; mad[r] = v[k];
+    });
+    return S2S_OK;
+}
+
+extern "C" int s2s_signal_normalise_host(const int16_t* samples, const int64_t* offs, int32_t R, const int32_t* med, const int32_t* mad,
+                                         int32_t scale, int16_t* out, int32_t threads) {
+    if (R < 0 || threads < 1 || !offs || scale < 1 || scale > S2S_DTW_MAX_SCALE || (R > 0 && (!samples || !med || !mad || !out)) ||
+        !dtw_offsets_ok(offs, R))
+        return S2S_ERR_ARG;
+    dtw_for_each(R, threads, [&](int32_t r) {
+        for (int64_t i = offs[r]; i < offs[r + 1]; ++i) out[i] = s2s_dtw_normalise_one(samples[i], med[r], mad[r], scale);
+    });
+    return S2S_OK;
+}
+
+extern "C" int s2s_dtw_banded_host(const int16_t* a, const int64_t* a_offs, const int16_t* b, const int64_t* b_offs, int32_t P, int32_t band,
+                                   int64_t* cost, int32_t threads) {
+    if (P < 0 || threads < 1 || band < 1 || band > S2S_DTW_MAX_BAND || !a_offs || !b_offs || (P > 0 && (!a || !b || !cost)) ||
+        !dtw_offsets_ok(a_offs, P) || !dtw_offsets_ok(b_offs, P))
+        return S2S_ERR_ARG;
+    dtw_for_each(P, threads, [&](int32_t p) {
+        cost[p] = dtw_pair(a + a_offs[p], a_offs[p + 1] - a_offs[p], b + b_offs[p], b_offs[p + 1] - b_offs[p], band);
+    });
+    return S2S_OK;
+}

@@ -1,0 +1,103 @@
+#!/usr/bin/env python
+"""What `compare` computes per second (GPU box).
+    python tools/compare_rate.py [--pairs P] [--len N] [--band R ...] [--host-threads T] [--reps K]
+P pairs of signal-like int16 records (levels of 8 samples plus noise; B's lengths N +- 2 %, so the band is sloped) are generated on the
+device; per band: HIP-event milliseconds of s2s_dtw_banded on the normalised samples -> pairs/s and cell updates/s (the cells inside
+the band, counted per pair in closed form on the host), and of the median and normalise kernels on the same records.
+--host-threads T > 0 also times s2s_dtw_banded_host on T threads on the same inputs (the baseline) and checks that the costs are
+equal.  One JSON line per measurement; the device clock is read with amd-smi after the runs."""
+import argparse, json, os, subprocess, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def clock():
+    try:
+        r = subprocess.run(["amd-smi", "metric", "-g", "0", "-c", "--json"], capture_output=True, text=True, timeout=20)
+        return r.stdout.strip()[:400] if r.returncode == 0 else None
+    except (OSError, subprocess.SubprocessError):
+        return None
+
+
+def band_cells(n, m, R):
+    """Cells (i, j) with |i m - j n| <= R max(n, m), row by row in closed form."""
+    import numpy as np
+    i = np.arange(n, dtype=np.int64)
+    T = R * max(n, m)
+    jlo = np.maximum(0, -((T - i * m) // n))
+    jhi = np.minimum(m - 1, (i * m + T) // n)
+    return int((jhi - jlo + 1).sum())
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--pairs", type=int, default=1000)
+    ap.add_argument("--len", type=int, default=50000)
+    ap.add_argument("--band", type=int, nargs="+", default=[512, 64])
+    ap.add_argument("--host-threads", type=int, default=0)
+    ap.add_argument("--reps", type=int, default=3)
+    a = ap.parse_args()
+    import ctypes as C
+    import numpy as np, torch
+    from seq2squiggle_amd._lib import lib
+    L = lib()
+    P, N = a.pairs, a.len
+    rng = np.random.default_rng(0)
+    na = np.full(P, N, np.int64)
+    nb = np.maximum(1, N + rng.integers(-N // 50, N // 50 + 1, P)) if N >= 50 else na.copy()
+    nb = np.minimum(nb, 1 << 22)
+    offs = np.concatenate([[0], np.cumsum(np.concatenate([na, nb]))]).astype(np.int64)
+    total = int(offs[-1])
+    g = torch.Generator(device="cuda").manual_seed(1)
+    levels = torch.randint(-150, 150, (total // 8 + 1,), device="cuda", generator=g, dtype=torch.int32)
+    x = (400 + levels.repeat_interleave(8)[:total] + torch.randint(-12, 13, (total,), device="cuda", generator=g, dtype=torch.int32)).to(torch.int16)
+    del levels
+    offs_d = torch.from_numpy(offs).cuda()
+    med = torch.empty(2 * P, dtype=torch.int32, device="cuda")
+    mad = torch.empty(2 * P, dtype=torch.int32, device="cuda")
+    q = torch.empty(total, dtype=torch.int16, device="cuda")
+    cost = torch.empty(P, dtype=torch.int64, device="cuda")
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def timed(fn, reps):
+        fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / reps
+
+    def check(rc):
+        assert rc == 0, (rc, L.s2s_last_error(None))
+    base = dict(pairs=P, len_a=N, len_b_min=int(nb.min()), len_b_max=int(nb.max()), samples=total)
+    ms = timed(lambda: check(L.s2s_signal_median_mad(0, stream, x.data_ptr(), offs_d.data_ptr(), 2 * P, med.data_ptr(), mad.data_ptr())), a.reps)
+    print(json.dumps(dict(base, kernel="median_mad", ms=round(ms, 4), records_per_s=round(2 * P / ms * 1e3), samples_per_s=round(total / ms * 1e3))), flush=True)
+    ms = timed(lambda: check(L.s2s_signal_normalise(0, stream, x.data_ptr(), offs_d.data_ptr(), 2 * P, med.data_ptr(), mad.data_ptr(), 64,
+                                                    q.data_ptr())), a.reps)
+    print(json.dumps(dict(base, kernel="normalise", ms=round(ms, 4), samples_per_s=round(total / ms * 1e3))), flush=True)
+    q_h = q.cpu().numpy() if a.host_threads > 0 else None
+    for R in a.band:
+        cells = sum(band_cells(int(n), int(m), R) for n, m in zip(na, nb))
+        run = lambda: check(L.s2s_dtw_banded(0, stream, q.data_ptr(), offs_d.data_ptr(), q.data_ptr(), offs_d.data_ptr() + 8 * P, P, R,  # noqa: E731
+                                             cost.data_ptr()))
+        ms = timed(run, a.reps)
+        got = cost.cpu().numpy()
+        print(json.dumps(dict(base, kernel="dtw_banded", band=R, ms=round(ms, 3), pairs_per_s=round(P / ms * 1e3, 2), cells=cells,
+                              cell_updates_per_s=round(cells / ms * 1e3), mean_dtw_per_sample=float((got / (na + nb) / 64).mean()))), flush=True)
+        if a.host_threads > 0:
+            host = np.zeros(P, np.int64)
+            t0 = time.perf_counter()
+            check(L.s2s_dtw_banded_host(q_h.ctypes.data, offs.ctypes.data, q_h.ctypes.data, offs.ctypes.data + 8 * P, P, R, host.ctypes.data,
+                                        a.host_threads))
+            s = time.perf_counter() - t0
+            print(json.dumps(dict(base, kernel="dtw_banded_host", threads=a.host_threads, band=R, ms=round(s * 1e3, 1),
+                                  pairs_per_s=round(P / s, 2), cell_updates_per_s=round(cells / s), equal_to_gpu=bool(np.array_equal(host, got)),
+                                  gpu_over_host=round(s * 1e3 / ms, 2))), flush=True)
+    print(json.dumps({"clock_after": clock()}), flush=True)
+
+
+if __name__ == "__main__":
+    main()

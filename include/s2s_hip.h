@@ -569,9 +569,22 @@ int64_t s2s_kmer_model_format(const int64_t* table, int32_t k, float digitisatio
  *   i m - j n <= 0, else j);
  *   cost(i, j) = |a[i] - b[j]|;  D(i, j) = cost(i, j) + min(D(i - 1, j), D(i, j - 1), D(i - 1, j - 1)) over the predecessors inside
  *   the band and the matrix, D(0, 0) = cost(0, 0);
- *   the result is D(n - 1, m - 1), an int64 (70,000 samples of opposite extremes pass 2^32).  No path is traced back.  The
- *   per-sample figure of `compare` is D / (n + m) / S, formed on the host in double.
+ *   the result is D(n - 1, m - 1), an int64 (70,000 samples of opposite extremes pass 2^32).  The per-sample figure of `compare`
+ *   is D / (n + m) / S, formed on the host in double.
  *   n = 0 or m = 0: S2S_DTW_COST_EMPTY (-1).
+ * Warping path of a pair (s2s_dtw_path; D, the band and the cell cost as above): the walk back from (n - 1, m - 1) to (0, 0) that
+ *   steps from (i, j) to the predecessor with the smallest D among (i - 1, j - 1), (i - 1, j), (i, j - 1); a predecessor outside the
+ *   matrix, outside the band or unreached does not count; on equal D the preference is (i - 1, j - 1), then (i - 1, j), then
+ *   (i, j - 1).  D is unique, so the path is.  The tie rule governs the path only (the cost's `min` does not care).  Written
+ *   forward from (0, 0) the path is a string of ops, one byte each:
+ *     S2S_DTW_OP_M 0  to (i + 1, j + 1);   S2S_DTW_OP_A 1  to (i + 1, j): one more sample of a on the same sample of b;
+ *     S2S_DTW_OP_B 2  to (i, j + 1)        (S2S_DTW_OP_NONE 3 is the code of (0, 0) and of unreached cells in the scratch only).
+ *   steps = the number of ops: max(n, m) - 1 <= steps <= n + m - 2, #M + #A = n - 1, #M + #B = m - 1; every visited cell is in the
+ *   band and the costs of the visited cells, (0, 0) included, sum to D(n - 1, m - 1).  A pair with an empty or too long member or
+ *   an unreached corner has steps = 0; its cost is what s2s_dtw_banded gives.
+ *   Boundary map g of a path (formed on the host: compare.boundary_map): g(0) = 0, g(n) = m, for 0 < i < n g(i) = the smallest j
+ *   with (i, j) on the path; g never decreases, and the samples [s, e) of a map to [g(s), g(e)) of b: abutting intervals stay
+ *   abutting, a sample of b shared by several of a belongs to the last of them, an interval may come out empty.
  * Limits: 1 <= band <= S2S_DTW_MAX_BAND (s2s_dtw_max_band() returns it); n, m <= S2S_DTW_MAX_SAMPLES = 2^22; 0 <= R, P.  A band or
  * a count outside them is S2S_ERR_ARG and nothing is launched.  The lengths of the device entries lie in device memory, which a
  * stream-ordered call cannot read: a pair with a member longer than the limit costs no work and gets S2S_DTW_COST_TOO_LONG (-2);
@@ -584,8 +597,23 @@ int64_t s2s_kmer_model_format(const int64_t* table, int32_t k, float digitisatio
  *  s2s_dtw_banded          pair p = a[a_offs[p] .. a_offs[p+1]) against b[b_offs[p] .. b_offs[p+1]); cost [P] out.  One workgroup
  *                 per pair sweeps the anti-diagonals with three rolling diagonals of int64 in LDS (3 (2 band + 2) 8 bytes) and two
  *                 windows of the samples of the next 256 diagonals (2 (2 band + 256) 2 bytes): 58,416 B at S2S_DTW_MAX_BAND; no
- *                 atomics, no traffic between workgroups. */
+ *                 atomics, no traffic between workgroups.
+ *  s2s_dtw_path   the same pairs; cost [P] out, identical to s2s_dtw_banded's.  ops: one byte per op; pair p owns
+ *                 ops[path_offs[p] .. path_offs[p+1]) (int64 [P + 1], at least n + m - 2 bytes for a pair with two non-empty members)
+ *                 and its path comes out RIGHT-ALIGNED there, in forward order: ops[path_offs[p+1] - steps[p] .. path_offs[p+1]);
+ *                 steps int64 [P] out.  scratch: device memory for the decisions, 16-byte aligned; pair p owns the bytes
+ *                 scratch[scratch_offs[p] .. scratch_offs[p+1]) (int64 [P + 1], every offset a multiple of 16), at least
+ *                 s2s_dtw_path_scratch_bytes(n, m, band) = (n + m - 1) * ceil((floor(2 band max(n, m) / (n + m)) + 1) / 64) * 16 of
+ *                 them (0 for a pair without path; a host function, S2S_ERR_ARG for a band outside the limits): per diagonal i + j
+ *                 a fixed number of 16-byte word pairs, 2 bits per in-band cell.  Two kernels: the sweep of s2s_dtw_banded in an
+ *                 instance that also stores the decisions (two wave ballots and one 16-byte store per 64 cells), then one wave per
+ *                 pair that walks back.  A pair whose slots are too small or misaligned gets its cost and steps = 0, and nothing
+ *                 is written outside a slot; the walk is bounded by n + m - 2 steps whatever the scratch holds. */
 #define S2S_DTW_SCALE 64
+#define S2S_DTW_OP_M 0
+#define S2S_DTW_OP_A 1
+#define S2S_DTW_OP_B 2
+#define S2S_DTW_OP_NONE 3
 #define S2S_DTW_MAX_BAND 1024
 #define S2S_DTW_MAX_SAMPLES (1 << 22)
 #define S2S_DTW_COST_EMPTY (-1)
@@ -596,6 +624,10 @@ int s2s_signal_normalise(int device, void* stream, const int16_t* samples, const
                          const int32_t* mad, int32_t scale, int16_t* out);
 int s2s_dtw_banded(int device, void* stream, const int16_t* a, const int64_t* a_offs, const int16_t* b, const int64_t* b_offs,
                    int32_t P, int32_t band, int64_t* cost);
+int64_t s2s_dtw_path_scratch_bytes(int64_t n, int64_t m, int32_t band);
+int s2s_dtw_path(int device, void* stream, const int16_t* a, const int64_t* a_offs, const int16_t* b, const int64_t* b_offs, int32_t P,
+                 int32_t band, int64_t* cost, uint8_t* scratch, const int64_t* scratch_offs, uint8_t* ops, const int64_t* path_offs,
+                 int64_t* steps);
 /* The same three on host pointers, in plain C++ (`compare --cpu`; also the definition the GPU must equal bit for bit): records /
  * pairs are dealt out over `threads` >= 1 host threads; the DTW sweeps rows with two rolling rows.  S2S_ERR_ARG as above, and for a
  * record or a pair member longer than S2S_DTW_MAX_SAMPLES or offsets that decrease. */
@@ -604,6 +636,11 @@ int s2s_signal_normalise_host(const int16_t* samples, const int64_t* offs, int32
                               int32_t scale, int16_t* out, int32_t threads);
 int s2s_dtw_banded_host(const int16_t* a, const int64_t* a_offs, const int16_t* b, const int64_t* b_offs, int32_t P, int32_t band,
                         int64_t* cost, int32_t threads);
+/* s2s_dtw_path on host pointers (`compare --cpu --path`): a row sweep that keeps 2 bits per in-band cell (n rows of
+ * ceil(min(m, 2 floor(band max(n, m) / n) + 3) / 32) 64-bit words per pair in flight), then the walk back; the same cost, ops and
+ * steps bit for bit.  No scratch argument.  S2S_ERR_ARG also for a slot of ops shorter than n + m - 2. */
+int s2s_dtw_path_host(const int16_t* a, const int64_t* a_offs, const int16_t* b, const int64_t* b_offs, int32_t P, int32_t band,
+                      int64_t* cost, uint8_t* ops, const int64_t* path_offs, int64_t* steps, int32_t threads);
 
 /* ---- host-side helper (no GPU work, no handle): replays the DRAWS of the reference's read sampler (utils.py:415-479
  * `sampling`, with the read-length law of utils.py:325-331 `draw_expon_dis`) without building a read, so that a rank of a sharded

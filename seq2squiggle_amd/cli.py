@@ -538,7 +538,17 @@ def evaluate(data_dir, models, compute_mode, max_chunks, batch_size, per_chunk, 
 @click.option("--max-samples", default=1 << 27, type=int, show_default=True, help="Samples of both files per batch.")
 @click.option("--cpu", is_flag=True, help="Compute on host threads instead of the GPU (the same integers).")
 @click.option("--json", "as_json", is_flag=True, help="Print the summary as one JSON object.")
-def compare(a, b, out, band, normalise, by_order, max_samples, cpu, as_json):
+@click.option("--path", "path_out", default=None, type=click.Path(dir_okay=False),
+              help="Also trace the warping path of every pair and write it here (.paths.tsv): read_id, n_a, n_b, band, dtw, steps, path; "
+                   "path is run-length encoded (12M3A1M2B: M both signals step, A only A's, B only B's; * for no steps).")
+@click.option("--events-a", default=None, type=click.Path(dir_okay=False, exists=True),
+              help="The event table `predict --events` wrote for file A; needs --events-out.")
+@click.option("--events-out", default=None, type=click.Path(dir_okay=False),
+              help="Write A's events carried through the warping path onto B's samples: start_idx / end_idx in B, level and deviation "
+                   "of B's stored samples with the offset, range and digitisation of B's record; events that map to no sample are dropped.")
+@click.option("--path-memory", default=8 << 30, type=int, show_default=True,
+              help="Bytes of decision scratch per batch with --path / --events-out; a pair that needs more is refused.")
+def compare(a, b, out, band, normalise, by_order, max_samples, cpu, as_json, path_out, events_a, events_out, path_memory):
     """Banded dynamic-time-warping distance between the signals of two .blow5 / .slow5 files, record against record (paired by read
     id, in A's order): OUT gets read_id, n_a, n_b, med_a, mad_a, med_b, mad_b, band, dtw, dtw_per_sample.  Everything is computed in
     integers on the stored int16 samples; dtw_per_sample = dtw / (n_a + n_b) / 64, in MADs per step with --normalise mad."""
@@ -549,16 +559,24 @@ def compare(a, b, out, band, normalise, by_order, max_samples, cpu, as_json):
             raise click.UsageError(f"{p}: compare reads .blow5 and .slow5 files")
     if max_samples < 1:
         raise click.BadParameter("must be >= 1", param_hint="--max-samples")
+    if path_memory < 1:
+        raise click.BadParameter("must be >= 1", param_hint="--path-memory")
+    if (events_a is None) != (events_out is None):
+        raise click.UsageError("--events-a and --events-out go together")
     import json
     if not cpu:
         import torch  # noqa: F401  (before the library: see engine.py)
     from . import compare as C
     if not 1 <= band <= C.max_band():
         raise click.BadParameter(f"must be 1..{C.max_band()}", param_hint="--band")
-    s = C.compare_files(a, b, out, band=band, normalise=normalise, by_order=by_order, max_samples=max_samples, cpu=cpu)
+    s = C.compare_files(a, b, out, band=band, normalise=normalise, by_order=by_order, max_samples=max_samples, cpu=cpu,
+                        path_out=path_out, events_a=events_a, events_out=events_out, path_memory=path_memory)
     if as_json:
         click.echo(json.dumps(s))
     else:
+        if events_out is not None:
+            click.echo(f"{s['events_written']} events -> {events_out}  [{s['events_dropped']} dropped: no sample of B; "
+                       f"{s['events_unpaired']} of reads without a pair]")
         fmt = lambda v: "nan" if v is None else f"{v:.6f}"      # noqa: E731
         click.echo(f"{s['pairs']} pairs -> {out}  [band {band}, normalise {normalise}; unpaired: {s['unpaired_a']} of {s['records_a']} in "
                    f"{a}, {s['unpaired_b']} of {s['records_b']} in {b}]  dtw_per_sample mean {fmt(s['mean_dtw_per_sample'])}  "

@@ -4,8 +4,14 @@ s2s_dtw_banded, states the definitions; tests/_dtw_ref.py restates them): the GP
 (`--cpu`) and any batching give the same bytes.  Per batch of pairs: one host-to-device copy (offsets and samples of both
 sides), the three kernels, one device-to-host copy (cost, med, mad).  The reference has no such command and no DTW tool was
 at hand to compare against: what is pinned is that every number is the stated integer function of exactly the int16 samples the
-two files store -- DESIGN.md section 6."""
+two files store -- DESIGN.md section 6.
+
+`--path` adds the warping path behind every distance (s2s_dtw_path: the sweep in an instance that stores one 2-bit decision per
+in-band cell into a device scratch, then a walk back), written run-length encoded, and `--events-a / --events-out` carry the
+k-mer boundaries of an event table of file A (`predict --events`) through the path onto B's samples (`boundary_map`,
+`transfer_events`: plain numpy on the host)."""
 import logging
+import math
 import os
 from typing import Iterable, Sequence
 
@@ -19,6 +25,10 @@ MAX_SAMPLES = 1 << 22            # S2S_DTW_MAX_SAMPLES per record
 DEFAULT_BAND = 512
 DEFAULT_MAX_SAMPLES = 1 << 27    # samples of both sides per batch: 256 MiB of int16 on the device, twice with the normalised copy
 COLUMNS = ("read_id", "n_a", "n_b", "med_a", "mad_a", "med_b", "mad_b", "band", "dtw", "dtw_per_sample")
+DEFAULT_PATH_MEMORY = 8 << 30    # bytes of decision scratch per batch with --path
+PATH_COLUMNS = ("read_id", "n_a", "n_b", "band", "dtw", "steps", "path")
+EVENT_COLUMNS = ("read_name", "position", "model_kmer", "start_idx", "end_idx", "event_level_mean", "event_stdv")
+OPS = "MAB"                      # S2S_DTW_OP_M, _A, _B
 
 
 def max_band() -> int:
@@ -139,12 +149,36 @@ def normalise(records: Sequence[np.ndarray], med=None, mad=None, scale: int = SC
     return [out[offs[i]:offs[i + 1]] for i in range(n)]
 
 
-def _run_batch(a_list, b_list, band: int, norm: bool, cpu: bool, device: int = 0, threads: int = None):
-    """One batch of pairs -> (cost int64 [P], med int32 [2 P], mad int32 [2 P]); records 0..P-1 are A's, P..2P-1 B's."""
+def path_scratch_bytes(n: int, m: int, band: int) -> int:
+    """Bytes of decision scratch s2s_dtw_path needs for a pair of n against m samples (0 for a pair without path)."""
+    from ._lib import lib
+    r = int(lib().s2s_dtw_path_scratch_bytes(int(n), int(m), int(band)))
+    if r < 0:
+        raise ValueError(f"band must be 1..{max_band()}")
+    return r
+
+
+def _path_slots(offs: np.ndarray, P: int):
+    """-> int64 [P + 1] offsets of the pairs' slots of ops: n + m - 2 bytes for a pair with two non-empty members, else none."""
+    n, m = np.diff(offs[:P + 1]), np.diff(offs[P:])
+    return np.concatenate([[0], np.cumsum(np.where((n > 0) & (m > 0), n + m - 2, 0))]).astype(np.int64)
+
+
+def _split_ops(ops: np.ndarray, path_offs: np.ndarray, steps: np.ndarray):
+    """The right-aligned paths of a batch -> one uint8 array per pair."""
+    return [ops[int(e) - int(k):int(e)].copy() for e, k in zip(path_offs[1:], steps)]
+
+
+def _run_batch(a_list, b_list, band: int, norm: bool, cpu: bool, device: int = 0, threads: int = None, path: bool = False):
+    """One batch of pairs -> (cost int64 [P], med int32 [2 P], mad int32 [2 P]); records 0..P-1 are A's, P..2P-1 B's.  path=True:
+    s2s_dtw_path instead of s2s_dtw_banded, and a fourth result: the ops of every pair (uint8 arrays, empty without a path)."""
     from ._lib import lib
     L = lib()
     P = len(a_list)
     flat, offs = _pack(list(a_list) + list(b_list))
+    if path:
+        path_offs = _path_slots(offs, P)
+        n_ops = max(int(path_offs[-1]), 1)
     if cpu:
         threads = threads or _host_threads()
         med, mad, cost = np.zeros(2 * P, np.int32), np.zeros(2 * P, np.int32), np.zeros(P, np.int64)
@@ -155,6 +189,11 @@ def _run_batch(a_list, b_list, band: int, norm: bool, cpu: bool, device: int = 0
             q = np.empty(len(flat), np.int16)
             _check(L.s2s_signal_normalise_host(flat.ctypes.data, offs.ctypes.data, 2 * P, med.ctypes.data, mad.ctypes.data, SCALE,
                                                q.ctypes.data, threads), "s2s_signal_normalise_host")
+        if path:
+            ops, steps = np.zeros(n_ops, np.uint8), np.zeros(P, np.int64)
+            _check(L.s2s_dtw_path_host(q.ctypes.data, offs.ctypes.data, q.ctypes.data, offs.ctypes.data + 8 * P, P, band, cost.ctypes.data,
+                                       ops.ctypes.data, path_offs.ctypes.data, steps.ctypes.data, threads), "s2s_dtw_path_host")
+            return cost, med, mad, _split_ops(ops, path_offs, steps)
         _check(L.s2s_dtw_banded_host(q.ctypes.data, offs.ctypes.data, q.ctypes.data, offs.ctypes.data + 8 * P, P, band,
                                      cost.ctypes.data, threads), "s2s_dtw_banded_host")
         return cost, med, mad
@@ -167,6 +206,18 @@ def _run_batch(a_list, b_list, band: int, norm: bool, cpu: bool, device: int = 0
         q_ptr = q.data_ptr()
         _check(L.s2s_signal_normalise(dev.device, dev.stream, dev.samples_ptr, dev.offs_ptr, 2 * P, med_p, mad_p, SCALE, q_ptr),
                "s2s_signal_normalise")
+    if path:
+        torch, where = dev.torch, f"cuda:{dev.device}"
+        lens = np.diff(offs)
+        need = np.array([path_scratch_bytes(lens[i], lens[P + i], band) for i in range(P)], np.int64)
+        slots = np.concatenate([[0], np.cumsum(need), path_offs]).astype(np.int64)        # scratch_offs [P + 1], then path_offs [P + 1]
+        slots_d = torch.from_numpy(slots).to(where)
+        scratch = torch.empty(max(int(slots[P]), 16), dtype=torch.uint8, device=where)
+        out = torch.empty(8 * P + n_ops, dtype=torch.uint8, device=where)                # steps int64 [P], then the ops
+        _check(L.s2s_dtw_path(dev.device, dev.stream, q_ptr, dev.offs_ptr, q_ptr, dev.offs_ptr + 8 * P, P, band, cost_p, scratch.data_ptr(),
+                              slots_d.data_ptr(), out.data_ptr() + 8 * P, slots_d.data_ptr() + 8 * (P + 1), out.data_ptr()), "s2s_dtw_path")
+        raw = out.cpu().numpy()
+        return (*_split_down(t.cpu().numpy(), P, 2 * P), _split_ops(raw[8 * P:], path_offs, raw[:8 * P].view(np.int64)))
     _check(L.s2s_dtw_banded(dev.device, dev.stream, q_ptr, dev.offs_ptr, q_ptr, dev.offs_ptr + 8 * P, P, band, cost_p), "s2s_dtw_banded")
     return _split_down(t.cpu().numpy(), P, 2 * P)
 
@@ -182,6 +233,114 @@ def dtw_banded(a_list: Sequence[np.ndarray], b_list: Sequence[np.ndarray], band:
     if not len(a_list):
         return np.zeros(0, np.int64)
     return _run_batch(a_list, b_list, band, False, cpu, device)[0]
+
+
+def _check_path_memory(path_memory: int) -> int:
+    if int(path_memory) < 1:
+        raise ValueError("path_memory must be >= 1")
+    return int(path_memory)
+
+
+def dtw_path(a_list: Sequence[np.ndarray], b_list: Sequence[np.ndarray], band: int, cpu: bool = False, device: int = 0,
+             path_memory: int = DEFAULT_PATH_MEMORY):
+    """dtw_banded with the warping path: -> (cost int64 [P], [ops uint8 array per pair]); ops[k] = 0 (M: both signals step), 1 (A:
+    a steps) or 2 (B: b steps), forward from (0, 0); empty for a pair without path (an empty member, or n = m = 1).  The pairs
+    run in batches whose decision scratch stays within path_memory bytes; a single pair beyond it is a ValueError."""
+    if len(a_list) != len(b_list):
+        raise ValueError("a_list and b_list must pair up")
+    band = _check_band(band)
+    path_memory = _check_path_memory(path_memory)
+    if not cpu:
+        import torch  # noqa: F401
+    need = [path_scratch_bytes(np.size(a), np.size(b), band) for a, b in zip(a_list, b_list)]
+    for p, nb in enumerate(need):
+        if nb > path_memory:
+            raise ValueError(f"pair {p}: the path needs {nb} bytes of decision scratch, more than path_memory = {path_memory}")
+    cost, ops, start, held = [np.zeros(0, np.int64)], [], 0, 0
+    for p in range(len(need) + 1):
+        if p == len(need) or (p > start and held + need[p] > path_memory):
+            if p > start:
+                c, _, _, o = _run_batch(a_list[start:p], b_list[start:p], band, False, cpu, device, path=True)
+                cost.append(c)
+                ops += o
+            start, held = p, 0
+        if p < len(need):
+            held += need[p]
+    return np.concatenate(cost), ops
+
+
+def path_cells(ops):
+    """-> (i, j), int64 arrays of length len(ops) + 1: the cells a path visits, from (0, 0)."""
+    ops = np.asarray(ops, np.uint8).reshape(-1)
+    if ops.size and int(ops.max()) > 2:
+        raise ValueError("ops must be 0 (M), 1 (A) or 2 (B)")
+    i = np.concatenate([[0], np.cumsum(ops != 2)]).astype(np.int64)
+    j = np.concatenate([[0], np.cumsum(ops != 1)]).astype(np.int64)
+    return i, j
+
+
+def boundary_map(ops, n: int, m: int) -> np.ndarray:
+    """-> g, int64 [n + 1]: g[0] = 0, g[n] = m, else the smallest j with (i, j) on the path; the samples [s, e) of a map to
+    [g[s], g[e]) of b."""
+    i, j = path_cells(ops)
+    n, m = int(n), int(m)
+    if n < 1 or m < 1 or int(i[-1]) != n - 1 or int(j[-1]) != m - 1:
+        raise ValueError("ops is not a path from (0, 0) to (n - 1, m - 1)")
+    g = np.empty(n + 1, np.int64)
+    g[0], g[n] = 0, m
+    g[1:n] = j[1:][np.asarray(ops).reshape(-1) != 2]           # the cell a step of i arrives at is the first of its row
+    return g
+
+
+def path_string(ops) -> str:
+    """Run-length encoded ops, e.g. 12M3A1M2B; * for no ops."""
+    ops = np.asarray(ops, np.uint8).reshape(-1)
+    if not ops.size:
+        return "*"
+    cut = np.concatenate([[0], np.flatnonzero(np.diff(ops)) + 1, [ops.size]])
+    return "".join(f"{int(e - s)}{OPS[int(ops[s])]}" for s, e in zip(cut[:-1], cut[1:]))
+
+
+def read_events(path: str) -> dict:
+    """An event table of `predict --events` -> {read_name: [(position, model_kmer, start_idx, end_idx)]} in the table's order; a
+    `samples` column is ignored."""
+    table = {}
+    with open(path) as f:
+        head = f.readline().rstrip("\n").split("\t")
+        if head[:len(EVENT_COLUMNS)] != list(EVENT_COLUMNS):
+            raise click.ClickException(f"{path}: not an event table of predict --events (header {head[:len(EVENT_COLUMNS)]})")
+        for no, line in enumerate(f, 2):
+            v = line.rstrip("\n").split("\t")
+            try:
+                row = (v[1], v[2], int(v[3]), int(v[4]))
+            except (IndexError, ValueError):
+                raise click.ClickException(f"{path}: line {no} is not a row of an event table")
+            table.setdefault(v[0], []).append(row)
+    return table
+
+
+def transfer_events(rid: str, rows, g: np.ndarray, b: np.ndarray, digitisation: float, offset: float, signal_range: float):
+    """The rows of read `rid` (read_events) with [start_idx, end_idx) mapped through g onto b's stored int16 samples and the level
+    and deviation of the event table (include/s2s_hip.h, s2s_events_format) formed from them with b's record calibration ->
+    (text, dropped): rows that come out empty are dropped."""
+    x = np.asarray(b, np.int64)
+    cs = np.concatenate([[0], np.cumsum(x)])
+    cq = np.concatenate([[0], np.cumsum(x * x)])
+    n_a = len(g) - 1
+    out, dropped = [], 0
+    for pos, kmer, s, e in rows:
+        if not 0 <= s <= e <= n_a:
+            raise click.ClickException(f"read {rid}: event [{s}, {e}) lies outside its {n_a} samples")
+        s2, e2 = int(g[s]), int(g[e])
+        n = e2 - s2
+        if n <= 0:
+            dropped += 1
+            continue
+        S, Q = int(cs[e2] - cs[s2]), int(cq[e2] - cq[s2])
+        mean = (float(S) / n + offset) * signal_range / digitisation
+        stdv = math.sqrt(float(max(n * Q - S * S, 0))) / n * signal_range / digitisation
+        out.append(f"{rid}\t{pos}\t{kmer}\t{s2}\t{e2}\t{'%.4f' % mean}\t{'%.4f' % stdv}\n")
+    return "".join(out), dropped
 
 
 # ------------------------------------------------------------------ files
@@ -224,10 +383,14 @@ def _open_records(path: str) -> Iterable[dict]:
 
 
 def _pairs(a_path: str, b_path: str, by_order: bool):
-    """-> generator of (read_id, signal a, signal b), counters {"unpaired_a", "unpaired_b", "records_a", "records_b"} (filled while
-    the generator runs).  By id: B is held in memory by read id, A streams; A's order."""
+    """-> generator of (read_id, signal a, signal b, (digitisation, offset, range) of b's record), counters {"unpaired_a",
+    "unpaired_b", "records_a", "records_b"} (filled while the generator runs).  By id: B is held in memory by read id, A streams;
+    A's order."""
     counts = dict(records_a=0, records_b=0, unpaired_a=0, unpaired_b=0)
     ia, ib = _open_records(a_path), _open_records(b_path)
+
+    def cal(r):
+        return float(r["digitisation"]), float(r["offset"]), float(r["range"])
 
     def gen():
         if by_order:
@@ -240,12 +403,12 @@ def _pairs(a_path: str, b_path: str, by_order: bool):
                 if ra is None or rb is None:
                     counts["unpaired_a" if rb is None else "unpaired_b"] += 1
                     continue
-                yield ra["read_id"], np.asarray(ra["signal"], np.int16), np.asarray(rb["signal"], np.int16)
+                yield ra["read_id"], np.asarray(ra["signal"], np.int16), np.asarray(rb["signal"], np.int16), cal(rb)
         else:
             b = {}
             for r in ib:
                 counts["records_b"] += 1
-                b.setdefault(r["read_id"], np.array(r["signal"], np.int16))
+                b.setdefault(r["read_id"], (np.array(r["signal"], np.int16), cal(r)))
             used = set()
             for r in ia:
                 counts["records_a"] += 1
@@ -254,7 +417,7 @@ def _pairs(a_path: str, b_path: str, by_order: bool):
                     counts["unpaired_a"] += 1
                     continue
                 used.add(rid)
-                yield rid, np.asarray(r["signal"], np.int16), b[rid]
+                yield rid, np.asarray(r["signal"], np.int16), *b[rid]
             counts["unpaired_b"] = counts["records_b"] - len(used)
     return gen(), counts
 
@@ -265,11 +428,21 @@ def _row(rid, n_a, n_b, med_a, mad_a, med_b, mad_b, band, cost) -> str:
 
 
 def compare_files(a_path, b_path, out, band: int = DEFAULT_BAND, normalise: str = "mad", by_order: bool = False,
-                  max_samples: int = DEFAULT_MAX_SAMPLES, cpu: bool = False, device: int = 0) -> dict:
+                  max_samples: int = DEFAULT_MAX_SAMPLES, cpu: bool = False, device: int = 0, path_out=None, events_a=None,
+                  events_out=None, path_memory: int = DEFAULT_PATH_MEMORY) -> dict:
     """Write OUT.tsv (COLUMNS; one row per pair, A's order) and return the summary: pairs, records and unpaired records per file,
     mean and median of dtw_per_sample over the pairs that have one.  `normalise` = "mad" | "none" (`none`: the stored samples as they
     are, in units of 1 / 64 ADC count per sample in the last column).  A batch holds pairs until the samples of both sides pass
-    max_samples (at least one pair)."""
+    max_samples (at least one pair).
+    path_out: also write PATH_COLUMNS, one row per pair: the warping path of the pair, run-length encoded (path_string).  events_a
+    with events_out: carry the rows of A's event table (read_events) through the path onto B (transfer_events) and write
+    EVENT_COLUMNS; the summary then counts events_written, events_dropped (mapped to no sample of B) and events_unpaired (rows of
+    reads without a pair).  With either, a batch also ends before its decision scratch would pass path_memory bytes, and a pair
+    that needs more on its own is refused by its read id in a first pass over the lengths, before anything is computed."""
+    if (events_a is None) != (events_out is None):
+        raise ValueError("events_a and events_out go together")
+    want_path = path_out is not None or events_out is not None
+    path_memory = _check_path_memory(path_memory)
     if normalise not in ("mad", "none"):
         raise ValueError("normalise must be 'mad' or 'none'")
     if int(max_samples) < 1:
@@ -277,30 +450,57 @@ def compare_files(a_path, b_path, out, band: int = DEFAULT_BAND, normalise: str 
     if not cpu:
         import torch  # noqa: F401  (before the library: see engine.py)
     band = _check_band(band)
+    events = read_events(str(events_a)) if events_a is not None else None
+    if want_path:
+        for rid, a, b, _ in _pairs(str(a_path), str(b_path), by_order)[0]:
+            if len(a) <= MAX_SAMPLES and len(b) <= MAX_SAMPLES and path_scratch_bytes(len(a), len(b), band) > path_memory:
+                raise click.ClickException(f"read {rid}: the path of {len(a)} against {len(b)} samples at band {band} needs "
+                                           f"{path_scratch_bytes(len(a), len(b), band)} bytes of decision scratch, more than "
+                                           f"--path-memory {path_memory}")
     pairs, counts = _pairs(str(a_path), str(b_path), by_order)
     per_sample = []
     n_pairs = 0
-    with open(out, "w") as f:
+    ev = dict(written=0, dropped=0, paired=0)
+    with open(out, "w") as f, open(path_out or os.devnull, "w") as fp, open(events_out or os.devnull, "w") as fe:
         f.write("\t".join(COLUMNS) + "\n")
+        fp.write("\t".join(PATH_COLUMNS) + "\n")
+        fe.write("\t".join(EVENT_COLUMNS) + "\n")
 
         def flush(batch):
             P = len(batch)
-            cost, med, mad = _run_batch([p[1] for p in batch], [p[2] for p in batch], band, normalise == "mad", cpu, device)
-            for i, (rid, a, b) in enumerate(batch):
+            cost, med, mad, *ops = _run_batch([p[1] for p in batch], [p[2] for p in batch], band, normalise == "mad", cpu, device,
+                                              path=want_path)
+            for i, (rid, a, b, cal) in enumerate(batch):
                 c = int(cost[i])
                 f.write(_row(rid, len(a), len(b), int(med[i]), int(mad[i]), int(med[P + i]), int(mad[P + i]), band, c))
                 if c >= 0:
                     per_sample.append(float(c) / float(len(a) + len(b)) / float(SCALE))
+                if not want_path:
+                    continue
+                o = ops[0][i]
+                fp.write(f"{rid}\t{len(a)}\t{len(b)}\t{band}\t{c if c >= 0 else 'nan'}\t{len(o)}\t{path_string(o)}\n")
+                if events is not None and rid in events:
+                    rows = events[rid]
+                    ev["paired"] += len(rows)
+                    if len(o) == 0 and (len(a) != 1 or len(b) != 1):                 # no path (an empty record): nothing to map through
+                        ev["dropped"] += len(rows)
+                        continue
+                    text, dropped = transfer_events(rid, rows, boundary_map(o, len(a), len(b)), b, *cal)
+                    fe.write(text)
+                    ev["dropped"] += dropped
+                    ev["written"] += len(rows) - dropped
 
-        batch, held = [], 0
-        for rid, a, b in pairs:
+        batch, held, held_path = [], 0, 0
+        for rid, a, b, cal in pairs:
             if len(a) > MAX_SAMPLES or len(b) > MAX_SAMPLES:
                 raise click.ClickException(f"read {rid}: more than {MAX_SAMPLES} samples")
-            if batch and held + len(a) + len(b) > max_samples:
+            need = path_scratch_bytes(len(a), len(b), band) if want_path else 0
+            if batch and (held + len(a) + len(b) > max_samples or held_path + need > path_memory):
                 flush(batch)
-                batch, held = [], 0
-            batch.append((rid, a, b))
+                batch, held, held_path = [], 0, 0
+            batch.append((rid, a, b, cal))
             held += len(a) + len(b)
+            held_path += need
             n_pairs += 1
         if batch:
             flush(batch)
@@ -309,6 +509,13 @@ def compare_files(a_path, b_path, out, band: int = DEFAULT_BAND, normalise: str 
                    unpaired_b=counts["unpaired_b"],
                    mean_dtw_per_sample=float(np.mean(per_sample)) if per_sample else None,
                    median_dtw_per_sample=float(np.median(per_sample)) if per_sample else None)
+    if path_out is not None:
+        summary["path_out"] = str(path_out)
+    if events is not None:
+        unpaired = sum(len(r) for r in events.values()) - ev["paired"]
+        summary.update(events_out=str(events_out), events_written=ev["written"], events_dropped=ev["dropped"], events_unpaired=unpaired)
+        logger.info("compare: %d event(s) carried onto %s, %d dropped (no sample of B), %d of reads without a pair", ev["written"],
+                    b_path, ev["dropped"], unpaired)
     if counts["unpaired_a"] or counts["unpaired_b"]:
         logger.warning("compare: %d record(s) of %s and %d of %s have no partner", counts["unpaired_a"], a_path, counts["unpaired_b"], b_path)
     return summary

@@ -26,6 +26,18 @@ S2S_DTW_HD inline int16_t s2s_dtw_normalise_one(int32_t x, int32_t med, int32_t 
     return (int16_t)(q < -32767 ? -32767 : q > 32767 ? 32767 : q);
 }
 
+// The decision scratch of a pair's warping path (s2s_dtw_path): diagonal d = i + j holds at most floor(2 T / (n + m)) + 1 in-band
+// cells, T = R max(n, m) (the rows i with |i (n + m) - d n| <= T), packed 64 cells to a 16-byte word pair (bit 0 of the 64 codes,
+// then bit 1), cell i at bit (i - lo(d)) of pair (i - lo(d)) / 64: a fixed number of pairs per diagonal, n + m - 1 diagonals.
+S2S_DTW_HD inline int32_t s2s_dtw_path_chunks(int64_t n, int64_t m, int64_t R) {
+    const int64_t T = R * (n > m ? n : m);
+    return (int32_t)((2 * T / (n + m) + 1 + 63) / 64);
+}
+S2S_DTW_HD inline int64_t s2s_dtw_path_bytes(int64_t n, int64_t m, int64_t R) {
+    if (n <= 0 || m <= 0 || n > S2S_DTW_MAX_SAMPLES || m > S2S_DTW_MAX_SAMPLES) return 0;
+    return (n + m - 1) * s2s_dtw_path_chunks(n, m, R) * 16;
+}
+
 #if defined(S2S_DTW_KERNELS)           // s2s_hip.hip alone defines it: s2s_host.cpp passes through the same compiler
 #include <hip/hip_runtime.h>
 
@@ -121,9 +133,18 @@ __global__ __launch_bounds__(256) void s2s_normalise_kernel(const int16_t* __res
 // most 1 per diagonal, so the rows of the next S2S_DTW_WINDOW diagonals lie in lo(d0) .. lo(d0) + 2 R + S2S_DTW_WINDOW - 1 and their
 // columns in d0 - hi(d0) .. d0 - hi(d0) + 2 R + S2S_DTW_WINDOW - 1.  n, m, R and the two offsets are the only inputs of every loop bound and of
 // every branch around a barrier: the control flow is uniform over the workgroup.  Any number of threads gives the same integers.
+//   PATH = true (s2s_dtw_path) also records, per in-band cell, which predecessor its D came from -- S2S_DTW_OP_M / _A / _B for
+// (i - 1, j - 1) / (i - 1, j) / (i, j - 1), the smallest D, on equal D in this order; S2S_DTW_OP_NONE for (0, 0) and for a cell no
+// reached predecessor leads to -- as 2 bits in the pair's slot of `scratch` (layout: s2s_dtw_path_chunks above).  A wave's lanes
+// hold 64 consecutive rows of the diagonal: two ballots and one 16-byte store by lane 0.  The strides are walked per wave here
+// (the ballots need all 64 lanes in the same step); lanes past hi(d) repeat row hi(d), store nothing and vote NONE.  A slot that is
+// misaligned or smaller than s2s_dtw_path_bytes gets no store at all (s2s_dtw_trace_kernel applies the same test and reports no
+// path).  PATH = false is the cost-only kernel of s2s_dtw_banded, statement for statement what it was before the flag.
+template <bool PATH>
 __global__ __launch_bounds__(256) void s2s_dtw_kernel(const int16_t* __restrict__ a, const long long* __restrict__ a_offs,
                                                       const int16_t* __restrict__ b, const long long* __restrict__ b_offs, int R,
-                                                      long long* __restrict__ cost) {
+                                                      long long* __restrict__ cost, unsigned char* __restrict__ scratch,
+                                                      const long long* __restrict__ scratch_offs) {
     extern __shared__ long long s2s_dtw_ring[];     // [3][W] int64, then the two sample windows [2][2 R + S2S_DTW_WINDOW] int16
     const int p = blockIdx.x;
     const long long ao = a_offs[p], bo = b_offs[p];
@@ -152,6 +173,13 @@ __global__ __launch_bounds__(256) void s2s_dtw_kernel(const int16_t* __restrict_
     int16_t* wa = reinterpret_cast<int16_t*>(s2s_dtw_ring + 3 * W);
     int16_t* wb = wa + win;
     int a0 = 0, b0 = 0;                             // first row / column of the windows
+    int chunks = 0;                                 // (PATH) word pairs per diagonal, and the pair's slot (nullptr: record nothing)
+    ulonglong2* dec = nullptr;
+    if constexpr (PATH) {
+        chunks = s2s_dtw_path_chunks(n, m, R);
+        const long long so = scratch_offs[p], sz = scratch_offs[p + 1] - so;
+        if (so >= 0 && (so & 15) == 0 && sz >= (long long)(nm - 1) * chunks * 16) dec = reinterpret_cast<ulonglong2*>(scratch + so);
+    }
     for (int d = 0; d <= last; ++d) {
         int lo = d - (m - 1);
         lo = lo < 0 ? 0 : lo;
@@ -159,6 +187,7 @@ __global__ __launch_bounds__(256) void s2s_dtw_kernel(const int16_t* __restrict_
         int hi = d < n - 1 ? d : n - 1;
         hi = hi > qh ? qh : hi;
         hi = hi > lo + 2 * R ? lo + 2 * R : hi;      // (never binds: hi - lo <= 2 T / nm < 2 R; keeps every slot inside the ring whatever happens)
+        if constexpr (PATH) hi = hi > lo + 64 * chunks - 1 ? lo + 64 * chunks - 1 : hi;   // (never binds either: keeps every store inside the slot)
         slo += lo - lo1;                            // lo never decreases and grows by at most 1
         while (slo >= W) slo -= W;
         if ((d & (S2S_DTW_WINDOW - 1)) == 0) {      // (uniform: d is) the samples of the next S2S_DTW_WINDOW diagonals, once
@@ -174,7 +203,7 @@ __global__ __launch_bounds__(256) void s2s_dtw_kernel(const int16_t* __restrict_
         // issue back to back), then the stores; the rest of the diagonal one cell per thread and step.  The three predecessors are
         // read whatever they hold (every slot lies inside the ring) and chosen by their row ranges.
         const long long first = d == 0 ? 0 : S2S_DTW_UNREACHED;
-        auto cell = [&](int i, int& slot) -> long long {
+        auto cell = [&](int i, int& slot, unsigned& code) -> long long {
             int s = slo + (i - lo);
             s = s >= W ? s - W : s;
             const int sm = s == 0 ? W - 1 : s - 1;       // slot of row i - 1
@@ -184,27 +213,63 @@ __global__ __launch_bounds__(256) void s2s_dtw_kernel(const int16_t* __restrict_
             const bool has_up = (unsigned)(i - 1 - lo1) < cnt1;         // (i - 1, j)
             const bool has_left = (unsigned)(i - lo1) < cnt1;           // (i, j - 1)
             const bool has_diag = (unsigned)(i - 1 - lo2) < cnt2;       // (i - 1, j - 1)
+            slot = s;
+            if constexpr (PATH) {                   // the tie rule of the path: diagonal, then up, then left ('<' keeps the earlier one)
+                long long best = S2S_DTW_UNREACHED;
+                code = S2S_DTW_OP_NONE;
+                if (has_diag && diag < best) { best = diag; code = S2S_DTW_OP_M; }
+                if (has_up && up < best) { best = up; code = S2S_DTW_OP_A; }
+                if (has_left && left < best) { best = left; code = S2S_DTW_OP_B; }
+                best = d == 0 ? 0 : best;           // (0, 0) has no predecessor: NONE
+                return best >= S2S_DTW_UNREACHED ? S2S_DTW_UNREACHED : best + c;
+            }
             long long best = first;
             best = has_up && up < best ? up : best;
             best = has_left && left < best ? left : best;
             best = has_diag && diag < best ? diag : best;
-            slot = s;
             return best >= S2S_DTW_UNREACHED ? S2S_DTW_UNREACHED : best + c;
         };
         const int bd = (int)blockDim.x;
-        int i0 = lo + (int)threadIdx.x;
-        for (; i0 + (S2S_DTW_CELLS - 1) * bd <= hi; i0 += S2S_DTW_CELLS * bd) {
-            long long v[S2S_DTW_CELLS];
-            int slot[S2S_DTW_CELLS];
+        if constexpr (PATH) {
+            const int lane = (int)threadIdx.x & 63;
+            for (int base = lo + (int)threadIdx.x - lane; base <= hi; base += S2S_DTW_CELLS * bd) {      // (base: the same for a wave's lanes)
+                long long v[S2S_DTW_CELLS];
+                int slot[S2S_DTW_CELLS];
+                unsigned code[S2S_DTW_CELLS];
 #pragma unroll
-            for (int u = 0; u < S2S_DTW_CELLS; ++u) v[u] = cell(i0 + u * bd, slot[u]);
+                for (int u = 0; u < S2S_DTW_CELLS; ++u) {
+                    const int i = base + u * bd + lane;
+                    v[u] = cell(i <= hi ? i : hi, slot[u], code[u]);
+                    code[u] = i <= hi ? code[u] : (unsigned)S2S_DTW_OP_NONE;
+                }
 #pragma unroll
-            for (int u = 0; u < S2S_DTW_CELLS; ++u) s2s_dtw_ring[oc + slot[u]] = v[u];
-        }
-        for (; i0 <= hi; i0 += bd) {
-            int slot;
-            const long long v = cell(i0, slot);
-            s2s_dtw_ring[oc + slot] = v;
+                for (int u = 0; u < S2S_DTW_CELLS; ++u)
+                    if (base + u * bd + lane <= hi) s2s_dtw_ring[oc + slot[u]] = v[u];
+#pragma unroll
+                for (int u = 0; u < S2S_DTW_CELLS; ++u) {
+                    if (base + u * bd <= hi) {
+                        const unsigned long long b0 = __ballot(code[u] & 1u), b1 = __ballot(code[u] & 2u);
+                        if (lane == 0 && dec) dec[(long long)d * chunks + ((base + u * bd - lo) >> 6)] = make_ulonglong2(b0, b1);
+                    }
+                }
+            }
+        } else {
+            int i0 = lo + (int)threadIdx.x;
+            for (; i0 + (S2S_DTW_CELLS - 1) * bd <= hi; i0 += S2S_DTW_CELLS * bd) {
+                long long v[S2S_DTW_CELLS];
+                int slot[S2S_DTW_CELLS];
+                unsigned code;
+#pragma unroll
+                for (int u = 0; u < S2S_DTW_CELLS; ++u) v[u] = cell(i0 + u * bd, slot[u], code);
+#pragma unroll
+                for (int u = 0; u < S2S_DTW_CELLS; ++u) s2s_dtw_ring[oc + slot[u]] = v[u];
+            }
+            for (; i0 <= hi; i0 += bd) {
+                int slot;
+                unsigned code;
+                const long long v = cell(i0, slot, code);
+                s2s_dtw_ring[oc + slot] = v;
+            }
         }
         __syncthreads();
         const int o = o2; o2 = o1; o1 = oc; oc = o;
@@ -218,5 +283,64 @@ __global__ __launch_bounds__(256) void s2s_dtw_kernel(const int16_t* __restrict_
         s = s >= W ? s - W : s;
         cost[p] = (unsigned)(n - 1 - lo1) < cnt1 ? s2s_dtw_ring[o1 + s] : S2S_DTW_UNREACHED;
     }
+}
+
+// The walk back through the decisions of s2s_dtw_kernel<true>: one wave per pair, from (n - 1, m - 1) on diagonal n + m - 2.  Every
+// lane runs the same walk on the same values (the loads are wave-uniform); lane k mod 64 keeps the k-th op and the wave stores 64
+// of them at a time, right-aligned in the pair's slot of `ops`: the k-th op of the walk is byte path_offs[p + 1] - 1 - k.  lo(d) is
+// carried downwards the way the sweep carries it upwards (one 64-bit division in front of the loop).  The walk ends at (0, 0), on
+// a NONE code, on a step that would leave the matrix, or after n + m - 2 steps, and the cell index is clamped to the diagonal's
+// words: whatever the scratch holds, the loop is bounded and every address lies inside the pair's slots.  steps[p] = the ops
+// written if the walk arrived at (0, 0), else 0 (also for a pair without cost, or whose slots are too small).
+__global__ __launch_bounds__(64) void s2s_dtw_trace_kernel(const long long* __restrict__ a_offs, const long long* __restrict__ b_offs, int R,
+                                                           const long long* __restrict__ cost, const unsigned char* __restrict__ scratch,
+                                                           const long long* __restrict__ scratch_offs, unsigned char* __restrict__ ops,
+                                                           const long long* __restrict__ path_offs, long long* __restrict__ steps) {
+    const int p = blockIdx.x;
+    const int lane = (int)threadIdx.x;
+    const long long n64 = a_offs[p + 1] - a_offs[p], m64 = b_offs[p + 1] - b_offs[p];
+    const long long so = scratch_offs[p], sz = scratch_offs[p + 1] - so;
+    const long long pend = path_offs[p + 1], cap = pend - path_offs[p];
+    const long long c = cost[p];
+    bool ok = n64 > 0 && m64 > 0 && n64 <= S2S_DTW_MAX_SAMPLES && m64 <= S2S_DTW_MAX_SAMPLES && c >= 0 && c < S2S_DTW_UNREACHED;
+    const int n = ok ? (int)n64 : 1, m = ok ? (int)m64 : 1, nm = n + m;
+    const int chunks = s2s_dtw_path_chunks(n, m, R);
+    const int bound = nm - 2;
+    ok = ok && so >= 0 && (so & 15) == 0 && sz >= (long long)(nm - 1) * chunks * 16 && path_offs[p] >= 0 && cap >= bound;
+    if (!ok) {
+        if (lane == 0) steps[p] = 0;
+        return;
+    }
+    const ulonglong2* dec = reinterpret_cast<const ulonglong2*>(scratch + so);
+    const long long T = (long long)R * (n > m ? n : m);
+    int i = n - 1, j = m - 1, d = nm - 2;
+    const long long numl = nm - 1 - T + (long long)d * n;        // ceil((d n - T) / nm) = floor(numl / nm)
+    long long ql64 = numl / nm;
+    if (numl - ql64 * nm < 0) ql64 -= 1;
+    int ql = (int)ql64, rl = (int)(numl - ql64 * nm);
+    int k = 0;
+    unsigned mine = 0;
+    while ((i | j) != 0 && k < bound) {
+        int lo = d - (m - 1);
+        lo = lo < 0 ? 0 : lo;
+        lo = lo < ql ? ql : lo;
+        int x = i - lo;
+        x = x < 0 ? 0 : x > 64 * chunks - 1 ? 64 * chunks - 1 : x;
+        const ulonglong2 w = dec[(long long)d * chunks + (x >> 6)];
+        const unsigned code = (unsigned)((w.x >> (x & 63)) & 1ull) | ((unsigned)((w.y >> (x & 63)) & 1ull) << 1);
+        const int di = code != S2S_DTW_OP_B, dj = code != S2S_DTW_OP_A;
+        if (code == S2S_DTW_OP_NONE || i < di || j < dj) break;
+        mine = (k & 63) == lane ? code : mine;
+        ++k;
+        if ((k & 63) == 0) ops[pend - 1 - (k - 64 + lane)] = (unsigned char)mine;
+        i -= di;
+        j -= dj;
+        for (int s = di + dj; s > 0; --s) {          // one or two diagonals down
+            --d;
+            rl -= n; if (rl < 0) { rl += nm; ql -= 1; }
+        }
+    }
+    if (lane < (k & 63)) ops[pend - 1 - ((k & ~63) + lane)] = (unsigned char)mine;
+    if (lane == 0) steps[p] = (i | j) == 0 ? k : 0;
 }
 #endif  // S2S_DTW_KERNELS

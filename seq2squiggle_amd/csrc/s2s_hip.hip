@@ -2602,9 +2602,37 @@ int s2s_dtw_banded(int device, void* stream_, const int16_t* a, const int64_t* a
     // a diagonal holds at most 2 band + 1 cells: one wave while two strides cover it, else four
     const int threads = 2 * band + 1 <= 128 ? 64 : 256;
     const size_t lds = S2S_DTW_LDS_BYTES(band);      // 58,416 B at S2S_DTW_MAX_BAND
-    hipLaunchKernelGGL(s2s_dtw_kernel, dim3(P), dim3(threads), lds, static_cast<hipStream_t>(stream_), a,
+    hipLaunchKernelGGL(s2s_dtw_kernel<false>, dim3(P), dim3(threads), lds, static_cast<hipStream_t>(stream_), a,
                        reinterpret_cast<const long long*>(a_offs), b, reinterpret_cast<const long long*>(b_offs), band,
-                       reinterpret_cast<long long*>(cost));
+                       reinterpret_cast<long long*>(cost), static_cast<unsigned char*>(nullptr), static_cast<const long long*>(nullptr));
+    HIP_TRY(nullptr, hipGetLastError());
+    return S2S_OK;
+}
+
+int64_t s2s_dtw_path_scratch_bytes(int64_t n, int64_t m, int32_t band) {
+    if (band < 1 || band > S2S_DTW_MAX_BAND) return S2S_ERR_ARG;
+    return s2s_dtw_path_bytes(n, m, band);
+}
+
+int s2s_dtw_path(int device, void* stream_, const int16_t* a, const int64_t* a_offs, const int16_t* b, const int64_t* b_offs, int32_t P,
+                 int32_t band, int64_t* cost, uint8_t* scratch, const int64_t* scratch_offs, uint8_t* ops, const int64_t* path_offs,
+                 int64_t* steps) {
+    if (P < 0 || band < 1 || band > S2S_DTW_MAX_BAND || !a_offs || !b_offs || !scratch_offs || !path_offs ||
+        (P > 0 && (!a || !b || !cost || !scratch || !ops || !steps)) || (reinterpret_cast<uintptr_t>(scratch) & 15u))
+        return fail(nullptr, S2S_ERR_ARG, "s2s_dtw_path: bad argument (band must be 1..S2S_DTW_MAX_BAND, scratch 16-byte aligned)");
+    if (P == 0) return S2S_OK;
+    DeviceGuard guard(device);
+    if (!guard.ok) return fail(nullptr, S2S_ERR_HIP, "hipSetDevice failed");
+    const int threads = 2 * band + 1 <= 128 ? 64 : 256;          // as s2s_dtw_banded
+    const size_t lds = S2S_DTW_LDS_BYTES(band);
+    hipLaunchKernelGGL(s2s_dtw_kernel<true>, dim3(P), dim3(threads), lds, static_cast<hipStream_t>(stream_), a,
+                       reinterpret_cast<const long long*>(a_offs), b, reinterpret_cast<const long long*>(b_offs), band,
+                       reinterpret_cast<long long*>(cost), scratch, reinterpret_cast<const long long*>(scratch_offs));
+    HIP_TRY(nullptr, hipGetLastError());
+    hipLaunchKernelGGL(s2s_dtw_trace_kernel, dim3(P), dim3(64), 0, static_cast<hipStream_t>(stream_),
+                       reinterpret_cast<const long long*>(a_offs), reinterpret_cast<const long long*>(b_offs), band,
+                       reinterpret_cast<const long long*>(cost), scratch, reinterpret_cast<const long long*>(scratch_offs), ops,
+                       reinterpret_cast<const long long*>(path_offs), reinterpret_cast<long long*>(steps));
     HIP_TRY(nullptr, hipGetLastError());
     return S2S_OK;
 }

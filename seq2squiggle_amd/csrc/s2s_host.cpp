@@ -1565,6 +1565,55 @@ int64_t dtw_pair(const int16_t* a, int64_t n, const int16_t* b, int64_t m, int64
     return (m - 1 >= plo && m - 1 <= phi) ? prev[m - 1 - plo] : S2S_DTW_UNREACHED;
 }
 
+// dtw_pair with the path: the same sweep, the predecessors taken in the order of the tie rule (diagonal, up, left; '<' keeps the
+// earlier one), 2 bits per cell in `stride` 64-bit words per row (cell j of row i at bit pair j - jlo(i)), then the walk back from
+// (n - 1, m - 1).  The k-th op of the walk is ops_end[-1 - k]; -> the cost, *steps = the ops written.
+int64_t dtw_pair_path(const int16_t* a, int64_t n, const int16_t* b, int64_t m, int64_t R, uint8_t* ops_end, int64_t* steps) {
+    *steps = 0;
+    if (n <= 0 || m <= 0) return S2S_DTW_COST_EMPTY;
+    const int64_t T = R * std::max(n, m);
+    const int64_t width = std::min<int64_t>(m, 2 * (T / n) + 3), stride = (width + 31) / 32;
+    std::vector<int64_t> rows(2 * (size_t)width);
+    std::vector<uint64_t> dec((size_t)n * (size_t)stride, 0);
+    int64_t* prev = rows.data();
+    int64_t* cur = prev + width;
+    int64_t plo = 0, phi = -1;
+    auto row_lo = [&](int64_t i) { return std::max<int64_t>(0, -dtw_floor_div(T - i * m, n)); };
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t jlo = row_lo(i), jhi = std::min(m - 1, dtw_floor_div(i * m + T, n));
+        uint64_t* drow = dec.data() + (size_t)i * (size_t)stride;
+        for (int64_t j = jlo; j <= jhi; ++j) {
+            int64_t best = S2S_DTW_UNREACHED;
+            uint64_t code = S2S_DTW_OP_NONE;
+            if (j - 1 >= plo && j - 1 <= phi && prev[j - 1 - plo] < best) { best = prev[j - 1 - plo]; code = S2S_DTW_OP_M; }
+            if (j >= plo && j <= phi && prev[j - plo] < best) { best = prev[j - plo]; code = S2S_DTW_OP_A; }
+            if (j - 1 >= jlo && cur[j - 1 - jlo] < best) { best = cur[j - 1 - jlo]; code = S2S_DTW_OP_B; }
+            if (i == 0 && j == 0) best = 0;
+            const int64_t c = std::abs((int64_t)a[i] - (int64_t)b[j]);
+            cur[j - jlo] = best >= S2S_DTW_UNREACHED ? S2S_DTW_UNREACHED : best + c;
+            drow[(j - jlo) >> 5] |= code << (2 * ((j - jlo) & 31));
+        }
+        std::swap(prev, cur);
+        plo = jlo; phi = jhi;
+    }
+    const int64_t cost = (m - 1 >= plo && m - 1 <= phi) ? prev[m - 1 - plo] : S2S_DTW_UNREACHED;
+    if (cost >= S2S_DTW_UNREACHED) return cost;
+    int64_t i = n - 1, j = m - 1, k = 0;
+    while ((i | j) != 0 && k < n + m - 2) {
+        const int64_t x = j - row_lo(i);
+        if (x < 0 || x >= width) break;
+        const unsigned code = (unsigned)(dec[(size_t)i * (size_t)stride + (size_t)(x >> 5)] >> (2 * (x & 31))) & 3u;
+        const int64_t di = code != S2S_DTW_OP_B, dj = code != S2S_DTW_OP_A;
+        if (code == S2S_DTW_OP_NONE || i < di || j < dj) break;
+        ops_end[-1 - k] = (uint8_t)code;
+        ++k;
+        i -= di;
+        j -= dj;
+    }
+    *steps = (i | j) == 0 ? k : 0;
+    return cost;
+}
+
 }  // namespace
 
 extern "C" int s2s_signal_median_mad_host(const int16_t* samples, const int64_t* offs, int32_t R, int32_t* med, int32_t* mad, int32_t threads) {
@@ -1602,6 +1651,22 @@ extern "C" int s2s_dtw_banded_host(const int16_t* a, const int64_t* a_offs, cons
         return S2S_ERR_ARG;
     dtw_for_each(P, threads, [&](int32_t p) {
         cost[p] = dtw_pair(a + a_offs[p], a_offs[p + 1] - a_offs[p], b + b_offs[p], b_offs[p + 1] - b_offs[p], band);
+    });
+    return S2S_OK;
+}
+
+extern "C" int s2s_dtw_path_host(const int16_t* a, const int64_t* a_offs, const int16_t* b, const int64_t* b_offs, int32_t P, int32_t band,
+                                 int64_t* cost, uint8_t* ops, const int64_t* path_offs, int64_t* steps, int32_t threads) {
+    if (P < 0 || threads < 1 || band < 1 || band > S2S_DTW_MAX_BAND || !a_offs || !b_offs || !path_offs ||
+        (P > 0 && (!a || !b || !cost || !ops || !steps)) || !dtw_offsets_ok(a_offs, P) || !dtw_offsets_ok(b_offs, P))
+        return S2S_ERR_ARG;
+    for (int32_t p = 0; p < P; ++p) {               // every pair's slot holds its longest path
+        const int64_t n = a_offs[p + 1] - a_offs[p], m = b_offs[p + 1] - b_offs[p];
+        if (path_offs[p] < 0 || path_offs[p + 1] - path_offs[p] < (n > 0 && m > 0 ? n + m - 2 : 0)) return S2S_ERR_ARG;
+    }
+    dtw_for_each(P, threads, [&](int32_t p) {
+        cost[p] = dtw_pair_path(a + a_offs[p], a_offs[p + 1] - a_offs[p], b + b_offs[p], b_offs[p + 1] - b_offs[p], band,
+                                ops + path_offs[p + 1], &steps[p]);
     });
     return S2S_OK;
 }

@@ -5,7 +5,11 @@ P pairs of signal-like int16 records (levels of 8 samples plus noise; B's length
 device; per band: HIP-event milliseconds of s2s_dtw_banded on the normalised samples -> pairs/s and cell updates/s (the cells inside
 the band, counted per pair in closed form on the host), and of the median and normalise kernels on the same records.
 --host-threads T > 0 also times s2s_dtw_banded_host on T threads on the same inputs (the baseline) and checks that the costs are
-equal.  One JSON line per measurement; the device clock is read with amd-smi after the runs."""
+equal.  --path adds the warping path per band: s2s_dtw_path whole (the recording sweep and the walk back), the recording sweep
+alone (the same call with empty slots for the ops: the trace kernel then returns at once), their difference as the walk back, the
+bytes of decision scratch, and with --host-threads s2s_dtw_path_host with an equality check of cost, steps and ops.  --parent-lib
+LIB also times s2s_dtw_banded of another build of the library (the parent commit's) in the same process, on the same inputs.
+One JSON line per measurement; the device clock is read with amd-smi after the runs."""
 import argparse, json, os, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -36,6 +40,8 @@ def main():
     ap.add_argument("--band", type=int, nargs="+", default=[512, 64])
     ap.add_argument("--host-threads", type=int, default=0)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--path", action="store_true")
+    ap.add_argument("--parent-lib", default=None)
     a = ap.parse_args()
     import ctypes as C
     import numpy as np, torch
@@ -79,6 +85,11 @@ def main():
                                                     q.data_ptr())), a.reps)
     print(json.dumps(dict(base, kernel="normalise", ms=round(ms, 4), samples_per_s=round(total / ms * 1e3))), flush=True)
     q_h = q.cpu().numpy() if a.host_threads > 0 else None
+    parent = None
+    if a.parent_lib:
+        parent = C.CDLL(os.path.abspath(a.parent_lib))
+        parent.s2s_dtw_banded.restype = C.c_int32
+        parent.s2s_dtw_banded.argtypes = [C.c_int32] + [C.c_void_p] * 5 + [C.c_int32, C.c_int32, C.c_void_p]
     for R in a.band:
         cells = sum(band_cells(int(n), int(m), R) for n, m in zip(na, nb))
         run = lambda: check(L.s2s_dtw_banded(0, stream, q.data_ptr(), offs_d.data_ptr(), q.data_ptr(), offs_d.data_ptr() + 8 * P, P, R,  # noqa: E731
@@ -96,6 +107,47 @@ def main():
             print(json.dumps(dict(base, kernel="dtw_banded_host", threads=a.host_threads, band=R, ms=round(s * 1e3, 1),
                                   pairs_per_s=round(P / s, 2), cell_updates_per_s=round(cells / s), equal_to_gpu=bool(np.array_equal(host, got)),
                                   gpu_over_host=round(s * 1e3 / ms, 2))), flush=True)
+        if parent is not None:
+            pcost = torch.empty(P, dtype=torch.int64, device="cuda")
+            pms = timed(lambda: check(parent.s2s_dtw_banded(0, stream, q.data_ptr(), offs_d.data_ptr(), q.data_ptr(), offs_d.data_ptr() + 8 * P, P, R,
+                                                            pcost.data_ptr())), a.reps)
+            print(json.dumps(dict(base, kernel="dtw_banded_parent", band=R, ms=round(pms, 3), this_over_parent=round(ms / pms, 4),
+                                  equal_to_this=bool(np.array_equal(pcost.cpu().numpy(), got)))), flush=True)
+        if a.path:
+            need = np.array([L.s2s_dtw_path_scratch_bytes(int(n), int(m), R) for n, m in zip(na, nb)], np.int64)
+            slots = np.concatenate([[0], np.cumsum(need), [0], np.cumsum(na + nb - 2), np.zeros(P + 1, np.int64)]).astype(np.int64)
+            slots_d = torch.from_numpy(slots).cuda()       # scratch_offs, path_offs, and path_offs of empty slots
+            scratch = torch.empty(int(slots[P]), dtype=torch.uint8, device="cuda")
+            n_ops = int(slots[2 * P + 1])
+            ops = torch.empty(max(n_ops, 1), dtype=torch.uint8, device="cuda")
+            steps = torch.empty(P, dtype=torch.int64, device="cuda")
+            pcost = torch.empty(P, dtype=torch.int64, device="cuda")
+
+            def run_path(path_offs_at):
+                return lambda: check(L.s2s_dtw_path(0, stream, q.data_ptr(), offs_d.data_ptr(), q.data_ptr(), offs_d.data_ptr() + 8 * P, P, R,
+                                                    pcost.data_ptr(), scratch.data_ptr(), slots_d.data_ptr(), ops.data_ptr(),
+                                                    slots_d.data_ptr() + 8 * path_offs_at, steps.data_ptr()))
+            sweep_ms = timed(run_path(2 * P + 2), a.reps)
+            assert int(steps.abs().sum()) == 0
+            path_ms = timed(run_path(P + 1), a.reps)
+            st = steps.cpu().numpy()
+            print(json.dumps(dict(base, kernel="dtw_path", band=R, ms=round(path_ms, 3), sweep_ms=round(sweep_ms, 3),
+                                  trace_ms=round(path_ms - sweep_ms, 3), sweep_over_cost_only=round(sweep_ms / ms, 4),
+                                  scratch_bytes=int(slots[P]), ops_bytes=n_ops, mean_steps=float(st.mean()),
+                                  cost_equal=bool(np.array_equal(pcost.cpu().numpy(), got)), pairs_per_s=round(P / path_ms * 1e3, 2))), flush=True)
+            if a.host_threads > 0:
+                hcost, hsteps, hops = np.zeros(P, np.int64), np.zeros(P, np.int64), np.zeros(max(n_ops, 1), np.uint8)
+                po = slots[P + 1:2 * P + 2].copy()
+                t0 = time.perf_counter()
+                check(L.s2s_dtw_path_host(q_h.ctypes.data, offs.ctypes.data, q_h.ctypes.data, offs.ctypes.data + 8 * P, P, R, hcost.ctypes.data,
+                                          hops.ctypes.data, po.ctypes.data, hsteps.ctypes.data, a.host_threads))
+                s = time.perf_counter() - t0
+                g_ops = ops.cpu().numpy()
+                same_ops = all(np.array_equal(g_ops[e - k:e], hops[e - k:e]) for e, k in zip(po[1:], hsteps))
+                print(json.dumps(dict(base, kernel="dtw_path_host", threads=a.host_threads, band=R, ms=round(s * 1e3, 1),
+                                      equal_to_gpu=bool(np.array_equal(hcost, got) and np.array_equal(hsteps, st) and same_ops),
+                                      gpu_over_host=round(s * 1e3 / path_ms, 2))), flush=True)
+            del scratch, ops
     print(json.dumps({"clock_after": clock()}), flush=True)
 
 

@@ -642,6 +642,47 @@ int s2s_dtw_banded_host(const int16_t* a, const int64_t* a_offs, const int16_t* 
 int s2s_dtw_path_host(const int16_t* a, const int64_t* a_offs, const int16_t* b, const int64_t* b_offs, int32_t P, int32_t band,
                       int64_t* cost, uint8_t* ops, const int64_t* path_offs, int64_t* steps, int32_t threads);
 
+/* ---- `compare --open-ends`: where a short query sits inside a target -- subsequence DTW (free start, free end), in integers like
+ * the entries above and with their conventions (no handle, stream-ordered, S2S_OK / S2S_ERR_ARG / S2S_ERR_HIP).  `compare` runs it
+ * on the first and on the last samples of record A against the head and the tail of record B and then hands the interval of B
+ * between the two anchors to s2s_dtw_banded / s2s_dtw_path.
+ *
+ * Subsequence DTW of a query q (L samples) inside a target t (H samples), both int16:
+ *   cost(i, j) = |q[i] - t[j]|;
+ *   row 0 starts anywhere and has NO horizontal predecessor: E(0, j) = cost(0, j), S(0, j) = j;
+ *   for i > 0: E(i, j) = cost(i, j) + min over the predecessors (i - 1, j - 1), (i - 1, j), (i, j - 1) that lie inside the matrix
+ *   (column 0 has (i - 1, 0) only), and S(i, j) = S of the predecessor with the smallest E; on equal E the preference is
+ *   (i - 1, j - 1), then (i - 1, j), then (i, j - 1) -- the order of s2s_dtw_path.  Ties follow the predecessor order, never the
+ *   smaller S;
+ *   the result: j* = the SMALLEST j that minimises E(L - 1, j); cost = E(L - 1, j*), start = S(L - 1, j*), end = j* + 1: the query
+ *   matched t[start .. end).
+ *   reverse != 0 solves the same problem on q and t read back to front (q'[i] = q[L - 1 - i], t'[j] = t[H - 1 - j]; no reversed
+ *   copy is made) and reports the interval in forward coordinates of t: start = H - end', end = H - start'.
+ *   E fits int32: the vertical path in column j is always available, so E(i, j) <= (i + 1) 65,535 < 2^28 for L <= 2048.  cost leaves
+ *   as int64 like the other entries.
+ *   L = 0 or H = 0: cost = S2S_DTW_COST_EMPTY, start = end = 0.
+ * Limits: L <= S2S_SDTW_MAX_QUERY = 2048 (s2s_sdtw_max_query() returns it), H <= S2S_DTW_MAX_SAMPLES, 0 <= P.  The device entry
+ * cannot see the lengths: a problem with L or H beyond the limit, or with a negative begin or len, costs no work and gets
+ * cost = S2S_DTW_COST_TOO_LONG, start = end = 0; the host twin returns S2S_ERR_ARG for it before it computes anything.
+ *
+ *  s2s_sdtw       problem p = q[q_begin[p] .. q_begin[p] + q_len[p]) inside t[t_begin[p] .. t_begin[p] + t_len[p]); q and t may be
+ *                 the same pool and the ranges of different problems may overlap (the head and the tail anchor of one pair read
+ *                 the same two records); reverse uint8 [P]; cost, start, end int64 [P] out.  P = 0 launches nothing.  One
+ *                 workgroup of 1024 threads per problem sweeps the anti-diagonals i + j, one barrier each, with three rolling
+ *                 diagonals of (int32 E, int32 S) in LDS (3 (2048 + 2) 8 bytes), the query whole (2048 2 bytes) and a window of
+ *                 the target samples of the next 256 diagonals ((2048 + 256) 2 bytes): 57,904 B of static LDS whatever L is;
+ *                 a thread keeps the rows i = its index mod 1024, so the running (min E, smallest j, S) of row L - 1 lives in the
+ *                 registers of one thread; no atomics, no traffic between workgroups; L + H - 1 diagonals whatever memory holds.
+ *  s2s_sdtw_host  the same on host pointers, in plain C++ (`compare --open-ends --cpu`; the definition the kernel must equal bit
+ *                 for bit): a row sweep with two rolling rows of (E, S), problems dealt out over `threads` >= 1 host threads. */
+#define S2S_SDTW_MAX_QUERY 2048
+int32_t s2s_sdtw_max_query(void);
+int s2s_sdtw(int device, void* stream, const int16_t* q, const int64_t* q_begin, const int64_t* q_len, const int16_t* t,
+             const int64_t* t_begin, const int64_t* t_len, const uint8_t* reverse, int32_t P, int64_t* cost, int64_t* start,
+             int64_t* end);
+int s2s_sdtw_host(const int16_t* q, const int64_t* q_begin, const int64_t* q_len, const int16_t* t, const int64_t* t_begin,
+                  const int64_t* t_len, const uint8_t* reverse, int32_t P, int64_t* cost, int64_t* start, int64_t* end, int32_t threads);
+
 /* ---- host-side helper (no GPU work, no handle): replays the DRAWS of the reference's read sampler (utils.py:415-479
  * `sampling`, with the read-length law of utils.py:325-331 `draw_expon_dis`) without building a read, so that a rank of a sharded
  * run finds the generator state of its first read in microseconds per thousand reads instead of replaying them in the

@@ -34,7 +34,8 @@ EXPORTS = ("s2s_blob_floats", "s2s_create", "s2s_destroy", "s2s_last_error", "s2
            "s2s_event_fixed", "s2s_kmer_model_accumulate", "s2s_kmer_model_format", "s2s_kmer_model_format_bound",
            "s2s_dtw_max_band", "s2s_signal_median_mad", "s2s_signal_normalise", "s2s_dtw_banded",
            "s2s_signal_median_mad_host", "s2s_signal_normalise_host", "s2s_dtw_banded_host",
-           "s2s_dtw_path_scratch_bytes", "s2s_dtw_path", "s2s_dtw_path_host")
+           "s2s_dtw_path_scratch_bytes", "s2s_dtw_path", "s2s_dtw_path_host",
+           "s2s_sdtw_max_query", "s2s_sdtw", "s2s_sdtw_host")
 
 
 def lib():
@@ -115,5 +116,8 @@ def lib():
     bind("s2s_dtw_path_scratch_bytes", i64, [i64, i64, i32])
     bind("s2s_dtw_path", i32, [i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp])
     bind("s2s_dtw_path_host", i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32])
+    bind("s2s_sdtw_max_query", i32, [])
+    bind("s2s_sdtw", i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp])
+    bind("s2s_sdtw_host", i32, [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32])
     _lib = L
     return L

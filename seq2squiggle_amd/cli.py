@@ -547,11 +547,26 @@ def evaluate(data_dir, models, compute_mode, max_chunks, batch_size, per_chunk, 
               help="Write A's events carried through the warping path onto B's samples: start_idx / end_idx in B, level and deviation "
                    "of B's stored samples with the offset, range and digitisation of B's record; events that map to no sample are dropped.")
 @click.option("--path-memory", default=8 << 30, type=int, show_default=True,
-              help="Bytes of decision scratch per batch with --path / --events-out; a pair that needs more is refused.")
-def compare(a, b, out, band, normalise, by_order, max_samples, cpu, as_json, path_out, events_a, events_out, path_memory):
+              help="Bytes of decision scratch per batch with --path / --events-out; a pair that needs more is refused.  With "
+                   "--open-ends a pair is refused when its interval of B is known, in front of its batch: the rows of earlier batches "
+                   "are already written then.")
+@click.option("--open-ends", is_flag=True,
+              help="B may carry samples in front of and behind what A holds (adapter, stall, open pore, trailing samples): locate the "
+                   "first and the last --anchor samples of A inside the first and the last --anchor-window samples of B by subsequence "
+                   "DTW and compare A with that interval of B only.  OUT gains b_start, b_end, head_cost, tail_cost, the path rows "
+                   "b_start, b_end; carried events come out in B's own coordinates.  To trim A instead, swap the files.")
+@click.option("--anchor", default=None, type=int,
+              help="Samples of A's head and tail that are located in B (--open-ends).  [default: 1024]  A choice, not a measurement: "
+                   "long enough to be unmistakable, short enough to sit inside one window.")
+@click.option("--anchor-window", default=None, type=int,
+              help="Samples of B's head and tail the anchors are searched in (--open-ends).  [default: 16384]  A choice, not a "
+                   "measurement: a DNA adapter is on the order of a thousand samples, and the window must cover the adapter plus the anchor.")
+def compare(a, b, out, band, normalise, by_order, max_samples, cpu, as_json, path_out, events_a, events_out, path_memory, open_ends,
+            anchor, anchor_window):
     """Banded dynamic-time-warping distance between the signals of two .blow5 / .slow5 files, record against record (paired by read
     id, in A's order): OUT gets read_id, n_a, n_b, med_a, mad_a, med_b, mad_b, band, dtw, dtw_per_sample.  Everything is computed in
-    integers on the stored int16 samples; dtw_per_sample = dtw / (n_a + n_b) / 64, in MADs per step with --normalise mad."""
+    integers on the stored int16 samples; dtw_per_sample = dtw / (n_a + n_b) / 64, in MADs per step with --normalise mad.
+    The alignment is global: a record of B that carries samples A lacks (a real read against a simulated one) needs --open-ends."""
     for p in (a, b):
         if str(p).endswith(".pod5"):
             raise click.UsageError(f"{p}: compare reads .blow5 and .slow5 files; reading POD5 is not supported")
@@ -563,14 +578,25 @@ def compare(a, b, out, band, normalise, by_order, max_samples, cpu, as_json, pat
         raise click.BadParameter("must be >= 1", param_hint="--path-memory")
     if (events_a is None) != (events_out is None):
         raise click.UsageError("--events-a and --events-out go together")
+    if not open_ends and (anchor is not None or anchor_window is not None):
+        raise click.UsageError("--anchor and --anchor-window need --open-ends")
     import json
     if not cpu:
         import torch  # noqa: F401  (before the library: see engine.py)
     from . import compare as C
     if not 1 <= band <= C.max_band():
         raise click.BadParameter(f"must be 1..{C.max_band()}", param_hint="--band")
+    open_kw = {}
+    if open_ends:
+        anchor = C.DEFAULT_ANCHOR if anchor is None else anchor
+        anchor_window = C.DEFAULT_ANCHOR_WINDOW if anchor_window is None else anchor_window
+        if not 1 <= anchor <= C.max_query():
+            raise click.BadParameter(f"must be 1..{C.max_query()}", param_hint="--anchor")
+        if not 1 <= anchor_window <= C.MAX_SAMPLES:
+            raise click.BadParameter(f"must be 1..{C.MAX_SAMPLES}", param_hint="--anchor-window")
+        open_kw = dict(open_ends=True, anchor=anchor, anchor_window=anchor_window)
     s = C.compare_files(a, b, out, band=band, normalise=normalise, by_order=by_order, max_samples=max_samples, cpu=cpu,
-                        path_out=path_out, events_a=events_a, events_out=events_out, path_memory=path_memory)
+                        path_out=path_out, events_a=events_a, events_out=events_out, path_memory=path_memory, **open_kw)
     if as_json:
         click.echo(json.dumps(s))
     else:
@@ -578,6 +604,9 @@ def compare(a, b, out, band, normalise, by_order, max_samples, cpu, as_json, pat
             click.echo(f"{s['events_written']} events -> {events_out}  [{s['events_dropped']} dropped: no sample of B; "
                        f"{s['events_unpaired']} of reads without a pair]")
         fmt = lambda v: "nan" if v is None else f"{v:.6f}"      # noqa: E731
+        if open_ends:
+            click.echo(f"open ends: anchor {anchor} in windows of {anchor_window}; {s['anchors_crossed']} pair(s) with crossed anchors "
+                       f"compared against all of B")
         click.echo(f"{s['pairs']} pairs -> {out}  [band {band}, normalise {normalise}; unpaired: {s['unpaired_a']} of {s['records_a']} in "
                    f"{a}, {s['unpaired_b']} of {s['records_b']} in {b}]  dtw_per_sample mean {fmt(s['mean_dtw_per_sample'])}  "
                    f"median {fmt(s['median_dtw_per_sample'])}")

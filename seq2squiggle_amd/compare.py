@@ -9,7 +9,11 @@ two files store -- DESIGN.md section 6.
 `--path` adds the warping path behind every distance (s2s_dtw_path: the sweep in an instance that stores one 2-bit decision per
 in-band cell into a device scratch, then a walk back), written run-length encoded, and `--events-a / --events-out` carry the
 k-mer boundaries of an event table of file A (`predict --events`) through the path onto B's samples (`boundary_map`,
-`transfer_events`: plain numpy on the host)."""
+`transfer_events`: plain numpy on the host).
+
+`--open-ends` is for a B that carries samples A lacks in front and behind (a real read against a simulated one): per batch the
+first and the last samples of A are located in the head and the tail of B by subsequence DTW (s2s_sdtw, csrc/s2s_sdtw.h: free
+start, free end, exact integers like the rest; `sdtw`, `_anchors`), and the batch path above then runs on that interval of B."""
 import logging
 import math
 import os
@@ -29,6 +33,9 @@ DEFAULT_PATH_MEMORY = 8 << 30    # bytes of decision scratch per batch with --pa
 PATH_COLUMNS = ("read_id", "n_a", "n_b", "band", "dtw", "steps", "path")
 EVENT_COLUMNS = ("read_name", "position", "model_kmer", "start_idx", "end_idx", "event_level_mean", "event_stdv")
 OPS = "MAB"                      # S2S_DTW_OP_M, _A, _B
+DEFAULT_ANCHOR = 1024            # --open-ends: samples of A's head and tail that are located in B (a choice, not a measurement)
+DEFAULT_ANCHOR_WINDOW = 16384    # ... inside this many samples of B's head and tail (a choice as well)
+OPEN_COLUMNS = ("b_start", "b_end", "head_cost", "tail_cost")
 
 
 def max_band() -> int:
@@ -70,16 +77,21 @@ def _check_band(band: int) -> int:
 class _Device:
     """One batch on the GPU: a single uint8 buffer up (offsets, then samples) and a single one down (cost, med, mad)."""
 
-    def __init__(self, flat: np.ndarray, offs: np.ndarray, device: int = 0):
+    def __init__(self, flat: np.ndarray, offs: np.ndarray, device: int = 0, extra: np.ndarray = None):
         import torch
         self.torch, self.device = torch, int(device)
         self.n_rec, self.total = len(offs) - 1, int(offs[-1])
-        host = np.empty(offs.nbytes + flat.nbytes, np.uint8)
+        extra = np.zeros(0, np.uint8) if extra is None else extra           # further int64 tables behind the offsets (extra_ptr)
+        assert extra.dtype == np.uint8 and extra.nbytes % 8 == 0
+        head = offs.nbytes + extra.nbytes
+        host = np.empty(head + flat.nbytes, np.uint8)
         host[:offs.nbytes] = offs.view(np.uint8)
-        host[offs.nbytes:] = flat.view(np.uint8)
+        host[offs.nbytes:head] = extra
+        host[head:] = flat.view(np.uint8)
         self.up = torch.from_numpy(host).to(f"cuda:{self.device}")
         self.offs_ptr = self.up.data_ptr()
-        self.samples_ptr = self.offs_ptr + offs.nbytes                       # (8-byte aligned: behind int64s)
+        self.extra_ptr = self.offs_ptr + offs.nbytes
+        self.samples_ptr = self.offs_ptr + head                              # (8-byte aligned: behind int64s)
         self.stream = torch.cuda.current_stream(self.device).cuda_stream
 
     def down(self, n_pairs: int):
@@ -233,6 +245,113 @@ def dtw_banded(a_list: Sequence[np.ndarray], b_list: Sequence[np.ndarray], band:
     if not len(a_list):
         return np.zeros(0, np.int64)
     return _run_batch(a_list, b_list, band, False, cpu, device)[0]
+
+
+# ------------------------------------------------------------------ open ends: subsequence DTW anchors
+def max_query() -> int:
+    from ._lib import lib
+    return int(lib().s2s_sdtw_max_query())
+
+
+def _check_anchor(anchor: int, anchor_window: int):
+    anchor, anchor_window = int(anchor), int(anchor_window)
+    if not 1 <= anchor <= max_query():
+        raise ValueError(f"anchor must be 1..{max_query()}")
+    if not 1 <= anchor_window <= MAX_SAMPLES:
+        raise ValueError(f"anchor_window must be 1..{MAX_SAMPLES}")
+    return anchor, anchor_window
+
+
+def _problem_table(q_begin, q_len, t_begin, t_len, reverse) -> np.ndarray:
+    """The problems of one s2s_sdtw call as one uint8 buffer: int64 q_begin, q_len, t_begin, t_len [N] each, then reverse uint8 [N]
+    (padded to a multiple of 8 bytes)."""
+    N = len(q_begin)
+    tab = np.zeros(32 * N + (N + 7) // 8 * 8, np.uint8)
+    tab[:32 * N] = np.concatenate([q_begin, q_len, t_begin, t_len]).astype(np.int64).view(np.uint8)
+    tab[32 * N:33 * N] = np.asarray(reverse, np.uint8)
+    return tab
+
+
+def _sdtw_host(q: np.ndarray, t: np.ndarray, tab: np.ndarray, N: int, threads: int):
+    from ._lib import lib
+    out = np.zeros(3 * max(N, 1), np.int64)
+    p, o = tab.ctypes.data, out.ctypes.data
+    _check(lib().s2s_sdtw_host(q.ctypes.data, p, p + 8 * N, t.ctypes.data, p + 16 * N, p + 24 * N, p + 32 * N, N, o, o + 8 * N, o + 16 * N,
+                               threads), "s2s_sdtw_host")
+    return out[:N], out[N:2 * N], out[2 * N:3 * N]
+
+
+def _sdtw_device(dev: _Device, q_ptr: int, t_ptr: int, N: int):
+    """s2s_sdtw on the problem table behind dev's offsets (dev.extra_ptr), then the one device-to-host copy of its results."""
+    from ._lib import lib
+    out = dev.torch.empty(3 * max(N, 1), dtype=dev.torch.int64, device=f"cuda:{dev.device}")
+    p, o = dev.extra_ptr, out.data_ptr()
+    _check(lib().s2s_sdtw(dev.device, dev.stream, q_ptr, p, p + 8 * N, t_ptr, p + 16 * N, p + 24 * N, p + 32 * N, N, o, o + 8 * N, o + 16 * N),
+           "s2s_sdtw")
+    out = out.cpu().numpy()
+    return out[:N], out[N:2 * N], out[2 * N:3 * N]
+
+
+def sdtw(queries: Sequence[np.ndarray], targets: Sequence[np.ndarray], reverse=False, cpu: bool = False, device: int = 0):
+    """Subsequence DTW (include/s2s_hip.h, next to s2s_sdtw) of the int16 record queries[p] inside targets[p] AS THEY ARE (no
+    normalisation) -> (cost, start, end), int64 [P] each: the query matched targets[p][start:end]; cost -1, start = end = 0 for an
+    empty member.  `reverse`: a bool, or one per problem -- the same problem on both records read back to front, the interval in
+    forward coordinates."""
+    if len(queries) != len(targets):
+        raise ValueError("queries and targets must pair up")
+    P = len(queries)
+    rev = np.broadcast_to(np.asarray(reverse, bool), (P,)) if np.ndim(reverse) == 0 else np.asarray(reverse, bool)
+    if rev.shape != (P,):
+        raise ValueError("reverse must be a bool or hold one per problem")
+    if any(np.size(x) > max_query() for x in queries):
+        raise ValueError(f"a query holds more than {max_query()} samples")
+    if not cpu:
+        import torch  # noqa: F401
+    if not P:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.int64)
+    flat, offs = _pack(list(queries) + list(targets))
+    lens = np.diff(offs)
+    tab = _problem_table(offs[:P], lens[:P], offs[P:2 * P], lens[P:], rev)
+    if cpu:
+        return _sdtw_host(flat, flat, tab, P, _host_threads())
+    dev = _Device(flat, offs, device, extra=tab)
+    return _sdtw_device(dev, dev.samples_ptr, dev.samples_ptr, P)
+
+
+def _anchors(a_list, b_list, norm: bool, cpu: bool, device: int, anchor: int, anchor_window: int, threads: int = None):
+    """Stage 1 of `--open-ends` for one batch of pairs: pack and normalise A and B as _run_batch does (whole-record median / MAD),
+    then ONE s2s_sdtw call of 2 P problems on the normalised pool -- problem p: the first La = min(anchor, n_a) samples of A inside
+    the first Hb = min(anchor_window, n_b) of B; problem P + p: the last La of A inside the last Hb of B, reversed -- and one
+    device-to-host copy.  -> (cost, start, end) int64 [2 P], start / end relative to the target's window, and Hb [P]."""
+    from ._lib import lib
+    L = lib()
+    P = len(a_list)
+    flat, offs = _pack(list(a_list) + list(b_list))
+    lens = np.diff(offs)
+    na, nb = lens[:P], lens[P:]
+    la, hb = np.minimum(anchor, na), np.minimum(anchor_window, nb)
+    tab = _problem_table(np.concatenate([offs[:P], offs[:P] + na - la]), np.concatenate([la, la]),
+                         np.concatenate([offs[P:2 * P], offs[P:2 * P] + nb - hb]), np.concatenate([hb, hb]), [0] * P + [1] * P)
+    if cpu:
+        threads = threads or _host_threads()
+        q = flat
+        if norm:
+            med, mad, q = np.zeros(2 * P, np.int32), np.zeros(2 * P, np.int32), np.empty(len(flat), np.int16)
+            _check(L.s2s_signal_median_mad_host(flat.ctypes.data, offs.ctypes.data, 2 * P, med.ctypes.data, mad.ctypes.data, threads),
+                   "s2s_signal_median_mad_host")
+            _check(L.s2s_signal_normalise_host(flat.ctypes.data, offs.ctypes.data, 2 * P, med.ctypes.data, mad.ctypes.data, SCALE,
+                                               q.ctypes.data, threads), "s2s_signal_normalise_host")
+        return (*_sdtw_host(q, q, tab, 2 * P, threads), hb)
+    dev = _Device(flat, offs, device, extra=tab)
+    q_ptr = dev.samples_ptr
+    if norm:
+        t, _, med_p, mad_p = dev.down(0)
+        q = dev.scratch()
+        q_ptr = q.data_ptr()
+        _check(L.s2s_signal_median_mad(dev.device, dev.stream, dev.samples_ptr, dev.offs_ptr, 2 * P, med_p, mad_p), "s2s_signal_median_mad")
+        _check(L.s2s_signal_normalise(dev.device, dev.stream, dev.samples_ptr, dev.offs_ptr, 2 * P, med_p, mad_p, SCALE, q_ptr),
+               "s2s_signal_normalise")
+    return (*_sdtw_device(dev, q_ptr, q_ptr, 2 * P), hb)
 
 
 def _check_path_memory(path_memory: int) -> int:
@@ -422,14 +541,16 @@ def _pairs(a_path: str, b_path: str, by_order: bool):
     return gen(), counts
 
 
-def _row(rid, n_a, n_b, med_a, mad_a, med_b, mad_b, band, cost) -> str:
-    per = "nan" if cost < 0 else "%.6f" % (float(cost) / float(n_a + n_b) / float(SCALE))
-    return f"{rid}\t{n_a}\t{n_b}\t{med_a}\t{mad_a}\t{med_b}\t{mad_b}\t{band}\t{cost if cost >= 0 else 'nan'}\t{per}\n"
+def _row(rid, n_a, n_b, med_a, mad_a, med_b, mad_b, band, cost, tail: str = "", m: int = None) -> str:
+    """One row of OUT; `tail`: further columns (with their tabs), m: the samples of B the distance spans (default: all n_b)."""
+    per = "nan" if cost < 0 else "%.6f" % (float(cost) / float(n_a + (n_b if m is None else m)) / float(SCALE))
+    return f"{rid}\t{n_a}\t{n_b}\t{med_a}\t{mad_a}\t{med_b}\t{mad_b}\t{band}\t{cost if cost >= 0 else 'nan'}\t{per}{tail}\n"
 
 
 def compare_files(a_path, b_path, out, band: int = DEFAULT_BAND, normalise: str = "mad", by_order: bool = False,
                   max_samples: int = DEFAULT_MAX_SAMPLES, cpu: bool = False, device: int = 0, path_out=None, events_a=None,
-                  events_out=None, path_memory: int = DEFAULT_PATH_MEMORY) -> dict:
+                  events_out=None, path_memory: int = DEFAULT_PATH_MEMORY, open_ends: bool = False, anchor: int = DEFAULT_ANCHOR,
+                  anchor_window: int = DEFAULT_ANCHOR_WINDOW) -> dict:
     """Write OUT.tsv (COLUMNS; one row per pair, A's order) and return the summary: pairs, records and unpaired records per file,
     mean and median of dtw_per_sample over the pairs that have one.  `normalise` = "mad" | "none" (`none`: the stored samples as they
     are, in units of 1 / 64 ADC count per sample in the last column).  A batch holds pairs until the samples of both sides pass
@@ -438,7 +559,16 @@ def compare_files(a_path, b_path, out, band: int = DEFAULT_BAND, normalise: str 
     with events_out: carry the rows of A's event table (read_events) through the path onto B (transfer_events) and write
     EVENT_COLUMNS; the summary then counts events_written, events_dropped (mapped to no sample of B) and events_unpaired (rows of
     reads without a pair).  With either, a batch also ends before its decision scratch would pass path_memory bytes, and a pair
-    that needs more on its own is refused by its read id in a first pass over the lengths, before anything is computed."""
+    that needs more on its own is refused by its read id in a first pass over the lengths, before anything is computed.
+    open_ends: B may carry samples in front of and behind what A holds (adapter, stall, open pore, trailing samples).  Per batch,
+    stage 1 (_anchors) locates the first and the last min(anchor, n_a) samples of A inside the first and the last
+    min(anchor_window, n_b) of B by subsequence DTW on the records normalised as a whole: b_start = the head anchor's start, b_end
+    = the tail anchor's end; anchors that cross (b_end - b_start < 1) fall back to all of B and are counted in anchors_crossed, a
+    pair with an empty record gets no anchors.  Stage 2 is the batch path above on A against B[b_start:b_end) (median / MAD of that
+    interval).  OUT gains OPEN_COLUMNS (n_b stays the stored length, dtw_per_sample = dtw / (n_a + b_end - b_start) / 64), the path
+    rows gain b_start and b_end, and the carried events come out in B's own coordinates.  The trimmed lengths are known only after
+    stage 1, so no first pass runs: a pair whose path needs more than path_memory is refused by its read id in front of its
+    batch's stage 2, when earlier batches' rows are already written."""
     if (events_a is None) != (events_out is None):
         raise ValueError("events_a and events_out go together")
     want_path = path_out is not None or events_out is not None
@@ -450,8 +580,10 @@ def compare_files(a_path, b_path, out, band: int = DEFAULT_BAND, normalise: str 
     if not cpu:
         import torch  # noqa: F401  (before the library: see engine.py)
     band = _check_band(band)
+    if open_ends:
+        anchor, anchor_window = _check_anchor(anchor, anchor_window)
     events = read_events(str(events_a)) if events_a is not None else None
-    if want_path:
+    if want_path and not open_ends:
         for rid, a, b, _ in _pairs(str(a_path), str(b_path), by_order)[0]:
             if len(a) <= MAX_SAMPLES and len(b) <= MAX_SAMPLES and path_scratch_bytes(len(a), len(b), band) > path_memory:
                 raise click.ClickException(f"read {rid}: the path of {len(a)} against {len(b)} samples at band {band} needs "
@@ -461,31 +593,76 @@ def compare_files(a_path, b_path, out, band: int = DEFAULT_BAND, normalise: str 
     per_sample = []
     n_pairs = 0
     ev = dict(written=0, dropped=0, paired=0)
+    crossed = [0]
     with open(out, "w") as f, open(path_out or os.devnull, "w") as fp, open(events_out or os.devnull, "w") as fe:
-        f.write("\t".join(COLUMNS) + "\n")
-        fp.write("\t".join(PATH_COLUMNS) + "\n")
+        f.write("\t".join(COLUMNS + (OPEN_COLUMNS if open_ends else ())) + "\n")
+        fp.write("\t".join(PATH_COLUMNS + (OPEN_COLUMNS[:2] if open_ends else ())) + "\n")
         fe.write("\t".join(EVENT_COLUMNS) + "\n")
+
+        def stage2(al, bl):
+            """_run_batch; with open ends and a path, in runs of pairs whose decision scratch stays within path_memory (the batches
+            were formed before the trimmed lengths were known)."""
+            if not (open_ends and want_path):
+                return _run_batch(al, bl, band, normalise == "mad", cpu, device, path=want_path)
+            P = len(al)
+            need = [path_scratch_bytes(len(x), len(y), band) for x, y in zip(al, bl)]
+            cost, med, mad, ops = np.zeros(P, np.int64), np.zeros(2 * P, np.int32), np.zeros(2 * P, np.int32), []
+            s, held = 0, 0
+            for p in range(P + 1):
+                if p == P or (p > s and held + need[p] > path_memory):
+                    c, md, dv, o = _run_batch(al[s:p], bl[s:p], band, normalise == "mad", cpu, device, path=True)
+                    cost[s:p], ops = c, ops + o
+                    med[s:p], med[P + s:P + p], mad[s:p], mad[P + s:P + p] = md[:p - s], md[p - s:], dv[:p - s], dv[p - s:]
+                    s, held = p, 0
+                if p < P:
+                    held += need[p]
+            return cost, med, mad, ops
 
         def flush(batch):
             P = len(batch)
-            cost, med, mad, *ops = _run_batch([p[1] for p in batch], [p[2] for p in batch], band, normalise == "mad", cpu, device,
-                                              path=want_path)
+            al, bl = [p[1] for p in batch], [p[2] for p in batch]
+            iv = None                                   # per pair (b_start, b_end, head_cost, tail_cost)
+            if open_ends:
+                c1, s1, e1, hb = _anchors(al, bl, normalise == "mad", cpu, device, anchor, anchor_window)
+                iv = []
+                for i, (a, b) in enumerate(zip(al, bl)):
+                    if not len(a) or not len(b):        # an empty record: no anchors
+                        iv.append((0, len(b), "nan", "nan"))
+                        continue
+                    bs, be = int(s1[i]), len(b) - int(hb[i]) + int(e1[P + i])
+                    if be - bs < 1:                     # the anchors crossed: all of B
+                        bs, be = 0, len(b)
+                        crossed[0] += 1
+                    iv.append((bs, be, int(c1[i]), int(c1[P + i])))
+                bl = [b[v[0]:v[1]] for b, v in zip(bl, iv)]
+                if want_path:
+                    for (rid, a, _, _), b in zip(batch, bl):
+                        if path_scratch_bytes(len(a), len(b), band) > path_memory:
+                            raise click.ClickException(f"read {rid}: the path of {len(a)} against {len(b)} samples at band {band} needs "
+                                                       f"{path_scratch_bytes(len(a), len(b), band)} bytes of decision scratch, more than "
+                                                       f"--path-memory {path_memory}")
+            cost, med, mad, *ops = stage2(al, bl)
             for i, (rid, a, b, cal) in enumerate(batch):
-                c = int(cost[i])
-                f.write(_row(rid, len(a), len(b), int(med[i]), int(mad[i]), int(med[P + i]), int(mad[P + i]), band, c))
+                c, m = int(cost[i]), len(bl[i])         # m: the samples of B the distance spans (n_b without open ends)
+                tail = "" if iv is None else "\t%d\t%d\t%s\t%s" % iv[i]
+                f.write(_row(rid, len(a), len(b), int(med[i]), int(mad[i]), int(med[P + i]), int(mad[P + i]), band, c, tail, m))
                 if c >= 0:
-                    per_sample.append(float(c) / float(len(a) + len(b)) / float(SCALE))
+                    per_sample.append(float(c) / float(len(a) + m) / float(SCALE))
                 if not want_path:
                     continue
                 o = ops[0][i]
-                fp.write(f"{rid}\t{len(a)}\t{len(b)}\t{band}\t{c if c >= 0 else 'nan'}\t{len(o)}\t{path_string(o)}\n")
+                ptail = "" if iv is None else "\t%d\t%d" % iv[i][:2]
+                fp.write(f"{rid}\t{len(a)}\t{len(b)}\t{band}\t{c if c >= 0 else 'nan'}\t{len(o)}\t{path_string(o)}{ptail}\n")
                 if events is not None and rid in events:
                     rows = events[rid]
                     ev["paired"] += len(rows)
-                    if len(o) == 0 and (len(a) != 1 or len(b) != 1):                 # no path (an empty record): nothing to map through
+                    if len(o) == 0 and (len(a) != 1 or m != 1):                      # no path (an empty record): nothing to map through
                         ev["dropped"] += len(rows)
                         continue
-                    text, dropped = transfer_events(rid, rows, boundary_map(o, len(a), len(b)), b, *cal)
+                    g = boundary_map(o, len(a), m)
+                    if iv is not None:
+                        g = g + iv[i][0]                # B's own coordinates
+                    text, dropped = transfer_events(rid, rows, g, b, *cal)
                     fe.write(text)
                     ev["dropped"] += dropped
                     ev["written"] += len(rows) - dropped
@@ -494,7 +671,7 @@ def compare_files(a_path, b_path, out, band: int = DEFAULT_BAND, normalise: str 
         for rid, a, b, cal in pairs:
             if len(a) > MAX_SAMPLES or len(b) > MAX_SAMPLES:
                 raise click.ClickException(f"read {rid}: more than {MAX_SAMPLES} samples")
-            need = path_scratch_bytes(len(a), len(b), band) if want_path else 0
+            need = path_scratch_bytes(len(a), len(b), band) if want_path and not open_ends else 0
             if batch and (held + len(a) + len(b) > max_samples or held_path + need > path_memory):
                 flush(batch)
                 batch, held, held_path = [], 0, 0
@@ -509,6 +686,8 @@ def compare_files(a_path, b_path, out, band: int = DEFAULT_BAND, normalise: str 
                    unpaired_b=counts["unpaired_b"],
                    mean_dtw_per_sample=float(np.mean(per_sample)) if per_sample else None,
                    median_dtw_per_sample=float(np.median(per_sample)) if per_sample else None)
+    if open_ends:
+        summary.update(open_ends=True, anchor=anchor, anchor_window=anchor_window, anchors_crossed=crossed[0])
     if path_out is not None:
         summary["path_out"] = str(path_out)
     if events is not None:

@@ -16,6 +16,7 @@
 #include "s2s_event_fixed.h"
 #define S2S_DTW_KERNELS
 #include "s2s_dtw.h"
+#include "s2s_sdtw.h"
 
 #include <cctype>
 #include <cstdio>
@@ -2633,6 +2634,26 @@ int s2s_dtw_path(int device, void* stream_, const int16_t* a, const int64_t* a_o
                        reinterpret_cast<const long long*>(a_offs), reinterpret_cast<const long long*>(b_offs), band,
                        reinterpret_cast<const long long*>(cost), scratch, reinterpret_cast<const long long*>(scratch_offs), ops,
                        reinterpret_cast<const long long*>(path_offs), reinterpret_cast<long long*>(steps));
+    HIP_TRY(nullptr, hipGetLastError());
+    return S2S_OK;
+}
+
+// ---- compare --open-ends (s2s_sdtw.h)
+int32_t s2s_sdtw_max_query(void) { return S2S_SDTW_MAX_QUERY; }
+
+int s2s_sdtw(int device, void* stream_, const int16_t* q, const int64_t* q_begin, const int64_t* q_len, const int16_t* t,
+             const int64_t* t_begin, const int64_t* t_len, const uint8_t* reverse, int32_t P, int64_t* cost, int64_t* start,
+             int64_t* end) {
+    if (P < 0 || (P > 0 && (!q || !q_begin || !q_len || !t || !t_begin || !t_len || !reverse || !cost || !start || !end)))
+        return fail(nullptr, S2S_ERR_ARG, "s2s_sdtw: bad argument");
+    if (P == 0) return S2S_OK;
+    DeviceGuard guard(device);
+    if (!guard.ok) return fail(nullptr, S2S_ERR_HIP, "hipSetDevice failed");
+    static_assert(S2S_SDTW_LDS_BYTES == 57904, "include/s2s_hip.h states the LDS bytes of s2s_sdtw");
+    hipLaunchKernelGGL(s2s_sdtw_kernel, dim3(P), dim3(S2S_SDTW_THREADS), 0, static_cast<hipStream_t>(stream_), q,
+                       reinterpret_cast<const long long*>(q_begin), reinterpret_cast<const long long*>(q_len), t,
+                       reinterpret_cast<const long long*>(t_begin), reinterpret_cast<const long long*>(t_len), reverse,
+                       reinterpret_cast<long long*>(cost), reinterpret_cast<long long*>(start), reinterpret_cast<long long*>(end));
     HIP_TRY(nullptr, hipGetLastError());
     return S2S_OK;
 }

@@ -1670,3 +1670,55 @@ extern "C" int s2s_dtw_path_host(const int16_t* a, const int64_t* a_offs, const 
     });
     return S2S_OK;
 }
+
+// ================================================================================ compare --open-ends: subsequence DTW on the host
+// The definition of include/s2s_hip.h (next to s2s_sdtw) as a row sweep with two rolling rows of (E, S); reverse reads q and t back
+// to front through the index, no copy.  What the kernel of s2s_sdtw.h must equal bit for bit.
+namespace {
+
+void sdtw_one(const int16_t* q, int64_t L, const int16_t* t, int64_t H, bool rev, int64_t* cost, int64_t* start, int64_t* end) {
+    *start = 0;
+    *end = 0;
+    if (L <= 0 || H <= 0) { *cost = S2S_DTW_COST_EMPTY; return; }
+    struct Cell { int32_t e, s; };
+    std::vector<Cell> rows(2 * (size_t)H);
+    Cell* prev = rows.data();
+    Cell* cur = prev + H;
+    auto qa = [&](int64_t i) { return (int32_t)(rev ? q[L - 1 - i] : q[i]); };
+    auto ta = [&](int64_t j) { return (int32_t)(rev ? t[H - 1 - j] : t[j]); };
+    for (int64_t j = 0; j < H; ++j) cur[j] = Cell{std::abs(qa(0) - ta(j)), (int32_t)j};
+    for (int64_t i = 1; i < L; ++i) {
+        std::swap(prev, cur);
+        const int32_t x = qa(i);
+        cur[0] = Cell{prev[0].e + std::abs(x - ta(0)), prev[0].s};
+        for (int64_t j = 1; j < H; ++j) {
+            Cell b = prev[j - 1];                                   // (i - 1, j - 1), then (i - 1, j), then (i, j - 1): '<' keeps the earlier
+            if (prev[j].e < b.e) b = prev[j];
+            if (cur[j - 1].e < b.e) b = cur[j - 1];
+            cur[j] = Cell{b.e + std::abs(x - ta(j)), b.s};
+        }
+    }
+    int64_t js = 0;
+    for (int64_t j = 1; j < H; ++j)
+        if (cur[j].e < cur[js].e) js = j;
+    *cost = cur[js].e;
+    *start = rev ? H - (js + 1) : cur[js].s;
+    *end = rev ? H - cur[js].s : js + 1;
+}
+
+}  // namespace
+
+extern "C" int s2s_sdtw_host(const int16_t* q, const int64_t* q_begin, const int64_t* q_len, const int16_t* t, const int64_t* t_begin,
+                             const int64_t* t_len, const uint8_t* reverse, int32_t P, int64_t* cost, int64_t* start, int64_t* end,
+                             int32_t threads) {
+    if (P < 0 || threads < 1 || (P > 0 && (!q || !q_begin || !q_len || !t || !t_begin || !t_len || !reverse || !cost || !start || !end)))
+        return S2S_ERR_ARG;
+    for (int32_t p = 0; p < P; ++p)
+        if (q_begin[p] < 0 || t_begin[p] < 0 || q_len[p] < 0 || t_len[p] < 0 || q_len[p] > S2S_SDTW_MAX_QUERY ||
+            t_len[p] > S2S_DTW_MAX_SAMPLES)
+            return S2S_ERR_ARG;
+    dtw_for_each(P, threads, [&](int32_t p) {
+        sdtw_one(q + q_begin[p], q_len[p], t + t_begin[p], t_len[p], reverse[p] != 0, &cost[p], &start[p], &end[p]);
+    });
+    return S2S_OK;
+}

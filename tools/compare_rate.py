@@ -9,6 +9,11 @@ equal.  --path adds the warping path per band: s2s_dtw_path whole (the recording
 alone (the same call with empty slots for the ops: the trace kernel then returns at once), their difference as the walk back, the
 bytes of decision scratch, and with --host-threads s2s_dtw_path_host with an equality check of cost, steps and ops.  --parent-lib
 LIB also times s2s_dtw_banded of another build of the library (the parent commit's) in the same process, on the same inputs.
+--open-ends adds the anchor search of `compare --open-ends`: every B gets --pad further signal-like samples in front, the padded
+records are normalised, and s2s_sdtw is timed on the 2 P anchors (--anchor samples of A's head and tail inside --anchor-window
+samples of B's head and tail) -> anchors/s and cell updates/s (L H cells per anchor); with --host-threads s2s_sdtw_host on the same
+problems with an equality check; then one batch through compare's own two stages (_anchors, then _run_batch on the trimmed B, at
+the first --band) on the wall clock, host-to-device copies included: the share of stage 1 in the call.
 One JSON line per measurement; the device clock is read with amd-smi after the runs."""
 import argparse, json, os, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -42,6 +47,10 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--path", action="store_true")
     ap.add_argument("--parent-lib", default=None)
+    ap.add_argument("--open-ends", action="store_true")
+    ap.add_argument("--pad", type=int, default=3000)
+    ap.add_argument("--anchor", type=int, default=1024)
+    ap.add_argument("--anchor-window", type=int, default=16384)
     a = ap.parse_args()
     import ctypes as C
     import numpy as np, torch
@@ -148,6 +157,65 @@ def main():
                                       equal_to_gpu=bool(np.array_equal(hcost, got) and np.array_equal(hsteps, st) and same_ops),
                                       gpu_over_host=round(s * 1e3 / path_ms, 2))), flush=True)
             del scratch, ops
+    if a.open_ends:
+        from seq2squiggle_amd import compare as CMP
+        pad = a.pad
+        nb2 = nb + pad
+        offs2 = np.concatenate([[0], np.cumsum(np.concatenate([na, nb2]))]).astype(np.int64)
+        total2 = int(offs2[-1])
+        x2 = torch.empty(total2, dtype=torch.int16, device="cuda")
+        x2[:int(offs[P])] = x[:int(offs[P])]
+        lev = torch.randint(-150, 150, (P * pad // 8 + 1,), device="cuda", generator=g, dtype=torch.int32)
+        junk = (400 + lev.repeat_interleave(8)[:P * pad] + torch.randint(-12, 13, (P * pad,), device="cuda", generator=g, dtype=torch.int32)).to(torch.int16)
+        for p in range(P):                             # B' = pad fresh samples, then B
+            o = int(offs2[P + p])
+            x2[o:o + pad] = junk[p * pad:(p + 1) * pad]
+            x2[o + pad:o + pad + int(nb[p])] = x[int(offs[P + p]):int(offs[P + p + 1])]
+        offs2_d = torch.from_numpy(offs2).cuda()
+        q2 = torch.empty(total2, dtype=torch.int16, device="cuda")
+        check(L.s2s_signal_median_mad(0, stream, x2.data_ptr(), offs2_d.data_ptr(), 2 * P, med.data_ptr(), mad.data_ptr()))
+        check(L.s2s_signal_normalise(0, stream, x2.data_ptr(), offs2_d.data_ptr(), 2 * P, med.data_ptr(), mad.data_ptr(), 64, q2.data_ptr()))
+        la, hb = np.minimum(a.anchor, na), np.minimum(a.anchor_window, nb2)
+        tab = np.concatenate([offs2[:P], offs2[:P] + na - la, la, la, offs2[P:2 * P], offs2[P:2 * P] + nb2 - hb, hb, hb]).astype(np.int64)
+        rev = np.concatenate([np.zeros(P, np.uint8), np.ones(P, np.uint8)])
+        tab_d, rev_d = torch.from_numpy(tab).cuda(), torch.from_numpy(rev).cuda()
+        res = torch.empty(6 * P, dtype=torch.int64, device="cuda")
+        N2 = 2 * P
+        tp, rp = tab_d.data_ptr(), res.data_ptr()
+        ms = timed(lambda: check(L.s2s_sdtw(0, stream, q2.data_ptr(), tp, tp + 8 * N2, q2.data_ptr(), tp + 16 * N2, tp + 24 * N2,
+                                            rev_d.data_ptr(), N2, rp, rp + 8 * N2, rp + 16 * N2)), a.reps)
+        got = res.cpu().numpy()
+        cells = int(2 * (la * hb).sum())
+        print(json.dumps(dict(base, kernel="sdtw", pad=pad, anchor=a.anchor, anchor_window=a.anchor_window, anchors=N2, ms=round(ms, 3),
+                              anchors_per_s=round(N2 / ms * 1e3, 1), cells=cells, cell_updates_per_s=round(cells / ms * 1e3),
+                              mean_b_start=float(got[N2:N2 + P].mean()))), flush=True)
+        if a.host_threads > 0:
+            q2_h, hres = q2.cpu().numpy(), np.zeros(6 * P, np.int64)
+            hp, ho = tab.ctypes.data, hres.ctypes.data
+            t0 = time.perf_counter()
+            check(L.s2s_sdtw_host(q2_h.ctypes.data, hp, hp + 8 * N2, q2_h.ctypes.data, hp + 16 * N2, hp + 24 * N2, rev.ctypes.data, N2,
+                                  ho, ho + 8 * N2, ho + 16 * N2, a.host_threads))
+            sec = time.perf_counter() - t0
+            print(json.dumps(dict(base, kernel="sdtw_host", threads=a.host_threads, ms=round(sec * 1e3, 1), cell_updates_per_s=round(cells / sec),
+                                  equal_to_gpu=bool(np.array_equal(hres, got)), gpu_over_host=round(sec * 1e3 / ms, 2))), flush=True)
+        # compare's own two stages on one batch, wall clock (copies included)
+        x2_h = x2.cpu().numpy()
+        al = [x2_h[offs2[p]:offs2[p + 1]] for p in range(P)]
+        bl = [x2_h[offs2[P + p]:offs2[P + p + 1]] for p in range(P)]
+        R = a.band[0]
+        for rep in range(2):                           # the second pass is the measurement
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            c1, s1, e1, hb1 = CMP._anchors(al, bl, True, False, 0, a.anchor, a.anchor_window)
+            t1 = time.perf_counter()
+            cut = [(int(s1[p]), len(bl[p]) - int(hb1[p]) + int(e1[P + p])) for p in range(P)]
+            cut = [(s_, e_) if e_ - s_ >= 1 else (0, len(bl[p])) for p, (s_, e_) in enumerate(cut)]
+            t2 = time.perf_counter()
+            CMP._run_batch(al, [b_[s_:e_] for b_, (s_, e_) in zip(bl, cut)], R, True, False, 0)
+            t3 = time.perf_counter()
+        print(json.dumps(dict(base, kernel="open_ends_call", band=R, stage1_ms=round((t1 - t0) * 1e3, 1), stage2_ms=round((t3 - t2) * 1e3, 1),
+                              stage1_share=round((t1 - t0) / ((t1 - t0) + (t3 - t2)), 4), sdtw_kernel_ms=round(ms, 3),
+                              mean_trimmed=float(np.mean([e_ - s_ for s_, e_ in cut])))), flush=True)
     print(json.dumps({"clock_after": clock()}), flush=True)
 
 

@@ -683,6 +683,71 @@ int s2s_sdtw(int device, void* stream, const int16_t* q, const int64_t* q_begin,
 int s2s_sdtw_host(const int16_t* q, const int64_t* q_begin, const int64_t* q_len, const int16_t* t, const int64_t* t_begin,
                   const int64_t* t_len, const uint8_t* reverse, int32_t P, int64_t* cost, int64_t* start, int64_t* end, int32_t threads);
 
+/* ---- `resquiggle`: which samples of a stored signal belong to which k-mer of its sequence, given the level a pore model expects
+ * for every k-mer -- a dynamic programme over (sample, k-mer) in integers, with the conventions of the `compare` entries above (no
+ * handle, `device` and `stream`, stream-ordered, device pointers, int64 offs, S2S_OK / S2S_ERR_ARG / S2S_ERR_HIP).  The reference
+ * has no such command (its event tables come from uncalled4).  Unvalidated against f5c / uncalled4.
+ *
+ * Per read: q[0 .. n) the normalised int16 samples, l[0 .. K) the normalised int16 levels of its k-mers (s2s_signal_normalise clamps
+ * to +-32767, so S2S_RSQ_UNKNOWN = -32768 is free: it marks a k-mer without a level).  Parameters: band R, 1 .. S2S_DTW_MAX_BAND;
+ * skip_penalty, 0 .. S2S_RSQ_MAX_SKIP_PENALTY = 2^20; unknown_cost, 0 .. S2S_RSQ_MAX_UNKNOWN_COST = 65,535.
+ *   cost(i, j) = |q[i] - l[j]|, or unknown_cost when l[j] == S2S_RSQ_UNKNOWN;
+ *   cell (i, j) is inside the band iff |i K - j n| <= R n (in int64): +-R k-mers around the diagonal, at most 2 R + 1 cells per row;
+ *   D(0, 0) = cost(0, 0); no other cell of row 0 is reached (both ends are pinned: sample 0 belongs to k-mer 0, sample n - 1 to
+ *   k-mer K - 1);
+ *   for i > 0: D(i, j) = cost(i, j) + min(D(i - 1, j - 1), D(i - 1, j), D(i - 1, j - 2) + skip_penalty) over the predecessors that lie
+ *   inside the matrix and the band and are themselves reached; a cell without such a predecessor is unreached.  Every sample belongs
+ *   to exactly one k-mer and the k-mer index never falls; a cell depends on the previous row only;
+ *   the result is D(n - 1, K - 1), an int64 (70,000 samples at the opposite extreme of their levels pass 2^32).
+ * Path: the walk back from (n - 1, K - 1) that steps to the predecessor with the smallest term of the minimum; on equal terms the
+ *   preference is advance (i - 1, j - 1), then stay (i - 1, j), then skip (i - 1, j - 2).  K-mer j owns the samples
+ *   [ev_start[j], ev_start[j] + ev_len[j]) of the rows the path spends in column j; a skipped k-mer gets ev_start = -1, ev_len = 0.
+ * Result codes (in cost):
+ *   n = 0 or K = 0: S2S_DTW_COST_EMPTY;
+ *   n or K above S2S_DTW_MAX_SAMPLES: S2S_DTW_COST_TOO_LONG -- the device does no work for it and leaves its ev_start / ev_len
+ *   untouched; the host twin, which sees the lengths, returns S2S_ERR_ARG before it computes anything;
+ *   K > 2 n (no work: so a row's window moves by at most two columns per row), or the corner unreached (it is never outside the band
+ *   for K <= 2 n): S2S_RSQ_UNREACHED (-3).
+ *   A read without a solution that is not too long gets ev_start = -1, ev_len = 0 for every k-mer.
+ * A solved read: the ev_len sum to n; ev_start[0] = 0; the starts of the unskipped k-mers ascend and abut; k-mers 0 and K - 1 are never
+ *   skipped, nor two neighbours; the costs of the visited cells plus skip_penalty x (number of skipped k-mers) equal the result.
+ *
+ *  s2s_resquiggle  read p = q[q_offs[p] .. q_offs[p+1]) against l[l_offs[p] .. l_offs[p+1]); cost int64 [P] out; ev_start, ev_len
+ *                 int32 out, k-mer j of read p at l_offs[p] + j.  scratch: device memory for the decisions, 16-byte aligned; read p
+ *                 owns scratch[scratch_offs[p] .. scratch_offs[p+1]) (int64 [P + 1], every offset a multiple of 16), at least
+ *                 s2s_resquiggle_scratch_bytes(n, K, band) = n * ceil((2 band + 1) / 64) * 16 of them (0 for a read without a
+ *                 solution by its lengths; a host function, S2S_ERR_ARG for a band outside the limits): per row ceil((2 band + 1) /
+ *                 64) 16-byte word pairs, 2 bits per slot, cell (i, j) in slot j mod (64 ceil((2 band + 1) / 64)).  A read whose slot
+ *                 is too small or misaligned gets its cost and no events (-1 / 0), and nothing is written outside a slot.  Two
+ *                 kernels (csrc/s2s_resquiggle.h): one workgroup per read sweeps the sample rows, one barrier each, D of the last
+ *                 two rows in LDS rings addressed by j mod ring (nothing is shifted when the window slides), the own column's D in
+ *                 a register, two wave ballots and one 16-byte store per 64 cells; then one wave per read walks back, at most n
+ *                 steps whatever the scratch holds.  Dynamic LDS: 1024 c + 2 (64 c + 128) bytes, c = ceil((2 band + 1) / 64):
+ *                 38,272 B at S2S_DTW_MAX_BAND, 19,840 B at band 512.
+ *  s2s_event_sums per k-mer S = sum x and Q = sum x^2 (int64) over the samples [ev_start, ev_start + ev_len) of the read's record in
+ *                 `samples` (the RAW stored int16, record p = samples[s_offs[p] .. s_offs[p+1])); S, Q int64 out at l_offs[p] + j.
+ *                 A skipped k-mer, and an interval that does not lie inside the record, give 0, 0.  No atomics: 16 lanes share a
+ *                 k-mer whatever its length (a stalled k-mer of 30,000 samples is 1,875 strides of its 16 lanes) and add up by
+ *                 shuffles.
+ *  s2s_resquiggle_host, s2s_event_sums_host   the same on host pointers, in plain C++ (`resquiggle --cpu`; the definition the
+ *                 kernels must equal bit for bit): a row sweep with two rolling rows that keeps 2 bits per in-band cell, then the
+ *                 walk back; reads dealt out over `threads` >= 1 host threads; no scratch argument.  S2S_ERR_ARG as above, and for a
+ *                 read longer than the limits or offsets that decrease. */
+#define S2S_RSQ_UNKNOWN (-32768)
+#define S2S_RSQ_UNREACHED (-3)
+#define S2S_RSQ_MAX_SKIP_PENALTY (1 << 20)
+#define S2S_RSQ_MAX_UNKNOWN_COST 65535
+int64_t s2s_resquiggle_scratch_bytes(int64_t n, int64_t K, int32_t band);
+int s2s_resquiggle(int device, void* stream, const int16_t* q, const int64_t* q_offs, const int16_t* l, const int64_t* l_offs, int32_t P,
+                   int32_t band, int32_t skip_penalty, int32_t unknown_cost, int64_t* cost, uint8_t* scratch, const int64_t* scratch_offs,
+                   int32_t* ev_start, int32_t* ev_len);
+int s2s_event_sums(int device, void* stream, const int16_t* samples, const int64_t* s_offs, const int32_t* ev_start, const int32_t* ev_len,
+                   const int64_t* l_offs, int32_t P, int64_t* S, int64_t* Q);
+int s2s_resquiggle_host(const int16_t* q, const int64_t* q_offs, const int16_t* l, const int64_t* l_offs, int32_t P, int32_t band,
+                        int32_t skip_penalty, int32_t unknown_cost, int64_t* cost, int32_t* ev_start, int32_t* ev_len, int32_t threads);
+int s2s_event_sums_host(const int16_t* samples, const int64_t* s_offs, const int32_t* ev_start, const int32_t* ev_len,
+                        const int64_t* l_offs, int32_t P, int64_t* S, int64_t* Q, int32_t threads);
+
 /* ---- host-side helper (no GPU work, no handle): replays the DRAWS of the reference's read sampler (utils.py:415-479
  * `sampling`, with the read-length law of utils.py:325-331 `draw_expon_dis`) without building a read, so that a rank of a sharded
  * run finds the generator state of its first read in microseconds per thousand reads instead of replaying them in the

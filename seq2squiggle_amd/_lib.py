@@ -35,7 +35,8 @@ EXPORTS = ("s2s_blob_floats", "s2s_create", "s2s_destroy", "s2s_last_error", "s2
            "s2s_dtw_max_band", "s2s_signal_median_mad", "s2s_signal_normalise", "s2s_dtw_banded",
            "s2s_signal_median_mad_host", "s2s_signal_normalise_host", "s2s_dtw_banded_host",
            "s2s_dtw_path_scratch_bytes", "s2s_dtw_path", "s2s_dtw_path_host",
-           "s2s_sdtw_max_query", "s2s_sdtw", "s2s_sdtw_host")
+           "s2s_sdtw_max_query", "s2s_sdtw", "s2s_sdtw_host",
+           "s2s_resquiggle_scratch_bytes", "s2s_resquiggle", "s2s_event_sums", "s2s_resquiggle_host", "s2s_event_sums_host")
 
 
 def lib():
@@ -119,5 +120,10 @@ def lib():
     bind("s2s_sdtw_max_query", i32, [])
     bind("s2s_sdtw", i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp])
     bind("s2s_sdtw_host", i32, [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32])
+    bind("s2s_resquiggle_scratch_bytes", i64, [i64, i64, i32])
+    bind("s2s_resquiggle", i32, [i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp])
+    bind("s2s_event_sums", i32, [i32, vp, vp, vp, vp, vp, vp, i32, vp, vp])
+    bind("s2s_resquiggle_host", i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, i32])
+    bind("s2s_event_sums_host", i32, [vp, vp, vp, vp, vp, i32, vp, vp, i32])
     _lib = L
     return L

@@ -611,5 +611,68 @@ def compare(a, b, out, band, normalise, by_order, max_samples, cpu, as_json, pat
                    f"{a}, {s['unpaired_b']} of {s['records_b']} in {b}]  dtw_per_sample mean {fmt(s['mean_dtw_per_sample'])}  "
                    f"median {fmt(s['median_dtw_per_sample'])}")
 
+@main.command()
+@click.argument("seqs", type=click.Path(dir_okay=False, exists=True))
+@click.argument("signals", type=click.Path(dir_okay=False))
+@click.option("--kmer-model", "model", required=True, type=click.Path(dir_okay=False, exists=True),
+              help="Pore model: the file `predict --kmer-model` writes, or a nanopolish-style table with the columns kmer and level_mean.")
+@click.option("-o", "--out", required=True, type=click.Path(dir_okay=False), help="Output event table (.events.tsv).")
+@click.option("--samples", "with_samples", is_flag=True, help="Add the `samples` column: every event's samples in pA.")
+@click.option("--band", default=512, type=int, show_default=True,
+              help="Half width of the band in k-mers around the diagonal.  A choice, not a measurement.")
+@click.option("--skip-penalty", default=128, type=int, show_default=True,
+              help="Cost of a k-mer that gets no sample, in 1/64 MAD.  The default, two MADs, is a choice, not a measurement.")
+@click.option("--unknown-cost", default=64, type=int, show_default=True,
+              help="Cost per sample on a k-mer the model has no level for (or with a letter outside ACGT), in 1/64 MAD.  The default, "
+                   "one MAD, is a choice, not a measurement.")
+@click.option("--rna", is_flag=True, help="The stored signal is reversed (RNA profiles): read the levels back to front; position stays in "
+                                          "read coordinates and start_idx falls as it rises, as in predict --events.")
+@click.option("--intervals", default=None, type=click.Path(dir_okay=False, exists=True),
+              help="A table of compare --open-ends: restrict every record to its [b_start, b_end) (an untrimmed real read); rows come out "
+                   "in the record's own coordinates.")
+@click.option("--cpu", is_flag=True, help="Compute on host threads instead of the GPU (the same bytes).")
+@click.option("--json", "as_json", is_flag=True, help="Print the summary as one JSON object.")
+@click.option("--summary", "summary_out", default=None, type=click.Path(dir_okay=False), help="Also write one row per read here (.tsv).")
+@click.option("--max-samples", default=1 << 27, type=int, show_default=True, help="Samples per batch.")
+@click.option("--trace-memory", default=8 << 30, type=int, show_default=True,
+              help="Bytes of decision scratch per batch; a read that needs more on its own is refused by its id.")
+def resquiggle(seqs, signals, model, out, with_samples, band, skip_penalty, unknown_cost, rna, intervals, cpu, as_json, summary_out,
+               max_samples, trace_memory):
+    """Align every record of a .blow5 / .slow5 file to the levels a pore model expects for the k-mers of its sequence (SEQS: FASTA or
+    FASTQ, record names = read ids) and write the event table predict --events writes: read_name, position, model_kmer, start_idx,
+    end_idx, event_level_mean, event_stdv.  Both ends are pinned: the first sample belongs to the first k-mer, the last to the last.
+    Exact integers on median / MAD normalised samples and levels; unvalidated against f5c / uncalled4."""
+    if str(signals).endswith(".pod5"):
+        raise click.UsageError(f"{signals}: resquiggle reads .blow5 and .slow5 files; reading POD5 is not supported")
+    if not str(signals).endswith((".blow5", ".slow5")):
+        raise click.UsageError(f"{signals}: resquiggle reads .blow5 and .slow5 files")
+    if max_samples < 1:
+        raise click.BadParameter("must be >= 1", param_hint="--max-samples")
+    if trace_memory < 1:
+        raise click.BadParameter("must be >= 1", param_hint="--trace-memory")
+    import json
+    if not cpu:
+        import torch  # noqa: F401  (before the library: see engine.py)
+    from . import compare as C
+    from . import resquiggle as R
+    if not 1 <= band <= C.max_band():
+        raise click.BadParameter(f"must be 1..{C.max_band()}", param_hint="--band")
+    if not 0 <= skip_penalty <= R.MAX_SKIP_PENALTY:
+        raise click.BadParameter(f"must be 0..{R.MAX_SKIP_PENALTY}", param_hint="--skip-penalty")
+    if not 0 <= unknown_cost <= R.MAX_UNKNOWN_COST:
+        raise click.BadParameter(f"must be 0..{R.MAX_UNKNOWN_COST}", param_hint="--unknown-cost")
+    s = R.resquiggle_files(seqs, signals, model, out, band=band, skip_penalty=skip_penalty, unknown_cost=unknown_cost, rna=rna,
+                           intervals=intervals, with_samples=with_samples, cpu=cpu, summary_out=summary_out, max_samples=max_samples,
+                           trace_memory=trace_memory)
+    if as_json:
+        click.echo(json.dumps(s))
+    else:
+        per = "nan" if s["mean_cost_per_sample"] is None else f"{s['mean_cost_per_sample']:.4f}"
+        click.echo(f"{s['events']} events of {s['solved']} reads -> {out}  [k {s['k']}, band {band}, skip penalty {skip_penalty}, unknown "
+                   f"cost {unknown_cost}; of {s['records']} records {s['unreached']} unreached, {s['refused']} refused, "
+                   f"{s['no_sequence']} without a sequence, {s['no_known_level']} without a known level; {s['skipped_kmers']} skipped "
+                   f"k-mers]  mean cost per sample {per} MAD")
+
+
 if __name__ == "__main__":
     main()

@@ -17,6 +17,7 @@
 #define S2S_DTW_KERNELS
 #include "s2s_dtw.h"
 #include "s2s_sdtw.h"
+#include "s2s_resquiggle.h"
 
 #include <cctype>
 #include <cstdio>
@@ -2654,6 +2655,51 @@ int s2s_sdtw(int device, void* stream_, const int16_t* q, const int64_t* q_begin
                        reinterpret_cast<const long long*>(q_begin), reinterpret_cast<const long long*>(q_len), t,
                        reinterpret_cast<const long long*>(t_begin), reinterpret_cast<const long long*>(t_len), reverse,
                        reinterpret_cast<long long*>(cost), reinterpret_cast<long long*>(start), reinterpret_cast<long long*>(end));
+    HIP_TRY(nullptr, hipGetLastError());
+    return S2S_OK;
+}
+
+// ---- resquiggle (s2s_resquiggle.h)
+int64_t s2s_resquiggle_scratch_bytes(int64_t n, int64_t K, int32_t band) {
+    if (band < 1 || band > S2S_DTW_MAX_BAND) return S2S_ERR_ARG;
+    return s2s_rsq_bytes(n, K, band);
+}
+
+int s2s_resquiggle(int device, void* stream_, const int16_t* q, const int64_t* q_offs, const int16_t* l, const int64_t* l_offs, int32_t P,
+                   int32_t band, int32_t skip_penalty, int32_t unknown_cost, int64_t* cost, uint8_t* scratch, const int64_t* scratch_offs,
+                   int32_t* ev_start, int32_t* ev_len) {
+    if (P < 0 || band < 1 || band > S2S_DTW_MAX_BAND || skip_penalty < 0 || skip_penalty > S2S_RSQ_MAX_SKIP_PENALTY || unknown_cost < 0 ||
+        unknown_cost > S2S_RSQ_MAX_UNKNOWN_COST || !q_offs || !l_offs || !scratch_offs ||
+        (P > 0 && (!q || !l || !cost || !scratch || !ev_start || !ev_len)) || (reinterpret_cast<uintptr_t>(scratch) & 15u))
+        return fail(nullptr, S2S_ERR_ARG, "s2s_resquiggle: bad argument (band must be 1..S2S_DTW_MAX_BAND, skip_penalty 0..2^20, "
+                                          "unknown_cost 0..65535, scratch 16-byte aligned)");
+    if (P == 0) return S2S_OK;
+    DeviceGuard guard(device);
+    if (!guard.ok) return fail(nullptr, S2S_ERR_HIP, "hipSetDevice failed");
+    static_assert(S2S_RSQ_LDS_BYTES(S2S_DTW_MAX_BAND) == 38272 && S2S_RSQ_LDS_BYTES(512) == 19840,
+                  "include/s2s_hip.h states the LDS bytes of s2s_resquiggle");
+    hipLaunchKernelGGL(s2s_resquiggle_kernel, dim3(P), dim3(64 * s2s_rsq_waves(band)), S2S_RSQ_LDS_BYTES(band),
+                       static_cast<hipStream_t>(stream_), q, reinterpret_cast<const long long*>(q_offs), l,
+                       reinterpret_cast<const long long*>(l_offs), band, skip_penalty, unknown_cost, reinterpret_cast<long long*>(cost),
+                       scratch, reinterpret_cast<const long long*>(scratch_offs));
+    HIP_TRY(nullptr, hipGetLastError());
+    hipLaunchKernelGGL(s2s_resquiggle_trace_kernel, dim3(P), dim3(64), 0, static_cast<hipStream_t>(stream_),
+                       reinterpret_cast<const long long*>(q_offs), reinterpret_cast<const long long*>(l_offs), band,
+                       reinterpret_cast<const long long*>(cost), scratch, reinterpret_cast<const long long*>(scratch_offs), ev_start, ev_len);
+    HIP_TRY(nullptr, hipGetLastError());
+    return S2S_OK;
+}
+
+int s2s_event_sums(int device, void* stream_, const int16_t* samples, const int64_t* s_offs, const int32_t* ev_start, const int32_t* ev_len,
+                   const int64_t* l_offs, int32_t P, int64_t* S, int64_t* Q) {
+    if (P < 0 || !s_offs || !l_offs || (P > 0 && (!samples || !ev_start || !ev_len || !S || !Q)))
+        return fail(nullptr, S2S_ERR_ARG, "s2s_event_sums: bad argument");
+    if (P == 0) return S2S_OK;
+    DeviceGuard guard(device);
+    if (!guard.ok) return fail(nullptr, S2S_ERR_HIP, "hipSetDevice failed");
+    hipLaunchKernelGGL(s2s_event_sums_kernel, dim3(P, S2S_RSQ_SUM_SLICES), dim3(256), 0, static_cast<hipStream_t>(stream_), samples,
+                       reinterpret_cast<const long long*>(s_offs), ev_start, ev_len, reinterpret_cast<const long long*>(l_offs),
+                       reinterpret_cast<long long*>(S), reinterpret_cast<long long*>(Q));
     HIP_TRY(nullptr, hipGetLastError());
     return S2S_OK;
 }

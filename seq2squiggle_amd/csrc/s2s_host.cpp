@@ -1722,3 +1722,110 @@ extern "C" int s2s_sdtw_host(const int16_t* q, const int64_t* q_begin, const int
     });
     return S2S_OK;
 }
+
+// ================================================================================ resquiggle: signal against k-mer levels on the host
+// The definition of include/s2s_hip.h (next to s2s_resquiggle) as a row sweep: row i holds the columns jlo(i) .. jhi(i) =
+// max(0, ceil(i K / n) - R) .. min(K - 1, floor(i K / n) + R); two rolling rows indexed by j - jlo of their own row; 2 bits per
+// in-band cell; then the walk back.  What the kernels of s2s_resquiggle.h must equal bit for bit.
+#include "s2s_resquiggle.h"
+
+namespace {
+
+int64_t rsq_one(const int16_t* q, int64_t n, const int16_t* l, int64_t K, int64_t R, int64_t skip, int64_t unknown, int32_t* start,
+                int32_t* len) {
+    for (int64_t j = 0; j < K; ++j) { start[j] = -1; len[j] = 0; }
+    if (n <= 0 || K <= 0) return S2S_DTW_COST_EMPTY;
+    if (K > 2 * n) return S2S_RSQ_UNREACHED;
+    const int64_t width = std::min<int64_t>(K, 2 * R + 1), stride = (width + 31) / 32;
+    std::vector<int64_t> rows(2 * (size_t)width, S2S_DTW_UNREACHED);
+    std::vector<uint64_t> dec((size_t)n * (size_t)stride, 0);
+    int64_t* prev = rows.data();
+    int64_t* cur = prev + width;
+    int64_t plo = 0, phi = -1;
+    auto row_lo = [&](int64_t i) { return std::max<int64_t>(0, (i * K + n - 1) / n - R); };
+    auto at = [&](int64_t j) { return j >= plo && j <= phi ? prev[j - plo] : S2S_DTW_UNREACHED; };
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t jlo = row_lo(i), jhi = std::min(K - 1, i * K / n + R);
+        uint64_t* drow = dec.data() + (size_t)i * (size_t)stride;
+        for (int64_t j = jlo; j <= jhi; ++j) {
+            int64_t best = S2S_DTW_UNREACHED;
+            uint64_t code = S2S_RSQ_NONE;
+            if (at(j - 1) < best) { best = at(j - 1); code = S2S_RSQ_ADV; }
+            if (at(j) < best) { best = at(j); code = S2S_RSQ_STAY; }
+            const int64_t t2 = at(j - 2) >= S2S_DTW_UNREACHED ? S2S_DTW_UNREACHED : at(j - 2) + skip;
+            if (t2 < best) { best = t2; code = S2S_RSQ_SKIP; }
+            if (i == 0) { best = j == 0 ? 0 : S2S_DTW_UNREACHED; code = S2S_RSQ_NONE; }
+            const int64_t c = l[j] == S2S_RSQ_UNKNOWN ? unknown : std::abs((int64_t)q[i] - (int64_t)l[j]);
+            cur[j - jlo] = best >= S2S_DTW_UNREACHED ? S2S_DTW_UNREACHED : best + c;
+            drow[(j - jlo) >> 5] |= (best >= S2S_DTW_UNREACHED ? (uint64_t)S2S_RSQ_NONE : code) << (2 * ((j - jlo) & 31));
+        }
+        std::swap(prev, cur);
+        plo = jlo; phi = jhi;
+    }
+    const int64_t cost = at(K - 1);
+    if (cost >= S2S_DTW_UNREACHED) return S2S_RSQ_UNREACHED;
+    int64_t i = n - 1, j = K - 1, run = 0;
+    bool arrived = false;
+    for (;;) {
+        ++run;
+        if (i == 0) {
+            arrived = j == 0;
+            if (arrived) { start[0] = 0; len[0] = (int32_t)run; }
+            break;
+        }
+        const int64_t x = j - row_lo(i);
+        if (x < 0 || x >= width) break;
+        const unsigned code = (unsigned)(dec[(size_t)i * (size_t)stride + (size_t)(x >> 5)] >> (2 * (x & 31))) & 3u;
+        if (code == S2S_RSQ_NONE) break;
+        if (code != S2S_RSQ_STAY) {
+            const int64_t dj = code == S2S_RSQ_ADV ? 1 : 2;
+            if (j < dj) break;
+            start[j] = (int32_t)i; len[j] = (int32_t)run;
+            run = 0;
+            j -= dj;
+        }
+        --i;
+    }
+    if (!arrived)                                   // (never: a reached corner has a path)
+        for (int64_t t = 0; t < K; ++t) { start[t] = -1; len[t] = 0; }
+    return cost;
+}
+
+}  // namespace
+
+extern "C" int s2s_resquiggle_host(const int16_t* q, const int64_t* q_offs, const int16_t* l, const int64_t* l_offs, int32_t P, int32_t band,
+                                   int32_t skip_penalty, int32_t unknown_cost, int64_t* cost, int32_t* ev_start, int32_t* ev_len,
+                                   int32_t threads) {
+    if (P < 0 || threads < 1 || band < 1 || band > S2S_DTW_MAX_BAND || skip_penalty < 0 || skip_penalty > S2S_RSQ_MAX_SKIP_PENALTY ||
+        unknown_cost < 0 || unknown_cost > S2S_RSQ_MAX_UNKNOWN_COST || !q_offs || !l_offs ||
+        (P > 0 && (!q || !l || !cost || !ev_start || !ev_len)) || !dtw_offsets_ok(q_offs, P) || !dtw_offsets_ok(l_offs, P) ||
+        (P > 0 && l_offs[0] < 0))
+        return S2S_ERR_ARG;
+    dtw_for_each(P, threads, [&](int32_t p) {
+        cost[p] = rsq_one(q + q_offs[p], q_offs[p + 1] - q_offs[p], l + l_offs[p], l_offs[p + 1] - l_offs[p], band, skip_penalty,
+                          unknown_cost, ev_start + l_offs[p], ev_len + l_offs[p]);
+    });
+    return S2S_OK;
+}
+
+extern "C" int s2s_event_sums_host(const int16_t* samples, const int64_t* s_offs, const int32_t* ev_start, const int32_t* ev_len,
+                                   const int64_t* l_offs, int32_t P, int64_t* S, int64_t* Q, int32_t threads) {
+    if (P < 0 || threads < 1 || !s_offs || !l_offs || (P > 0 && (!samples || !ev_start || !ev_len || !S || !Q))) return S2S_ERR_ARG;
+    for (int32_t p = 0; p < P; ++p)
+        if (s_offs[p + 1] < s_offs[p] || l_offs[p + 1] < l_offs[p] || l_offs[0] < 0) return S2S_ERR_ARG;
+    dtw_for_each(P, threads, [&](int32_t p) {
+        const int64_t n = s_offs[p + 1] - s_offs[p];
+        for (int64_t j = l_offs[p]; j < l_offs[p + 1]; ++j) {
+            const int64_t b = ev_start[j], len = ev_len[j];
+            int64_t s1 = 0, s2 = 0;
+            if (b >= 0 && len > 0 && b + len <= n)
+                for (int64_t t = 0; t < len; ++t) {
+                    const int64_t x = samples[s_offs[p] + b + t];
+                    s1 += x;
+                    s2 += x * x;
+                }
+            S[j] = s1; Q[j] = s2;
+        }
+    });
+    return S2S_OK;
+}

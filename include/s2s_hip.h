@@ -748,6 +748,92 @@ int s2s_resquiggle_host(const int16_t* q, const int64_t* q_offs, const int16_t* 
 int s2s_event_sums_host(const int16_t* samples, const int64_t* s_offs, const int32_t* ev_start, const int32_t* ev_len,
                         const int64_t* l_offs, int32_t P, int64_t* S, int64_t* Q, int32_t threads);
 
+/* ---- `segment`: event detection -- a stored record cut into runs of constant level without its sequence, by two windowed
+ * t-statistics in integers, with the conventions of the entries above (no handle, `device` and `stream`, stream-ordered, device
+ * pointers, int64 offs, S2S_OK / S2S_ERR_ARG / S2S_ERR_HIP).  The reference has no such command.  This is NOT scrappie's detector
+ * (there is no peak-height state machine), and it is unvalidated against scrappie / f5c / uncalled4.
+ *
+ * Per record x[0 .. n) (the raw stored int16).  A detector is a window w and an integer threshold T.
+ * Score: for w <= i <= n - w let L = [i - w, i), R = [i, i + w), S and Q the sum and the sum of squares of a window,
+ *     d = S_R - S_L,   V = w (Q_L + Q_R) - S_L^2 - S_R^2   (w^2 times the sum of the two population variances: never negative),
+ *     score_w(i) = floor(256 w d^2 / max(V, 1))   as int64: 256 times Welch's t^2 between the windows (t^2 = d^2 w / V);
+ *   every other i has score 0 -- all i of a record with n < 2 w among them.  With w <= S2S_SEG_MAX_WINDOW = 32: |d| <= 32 * 65,535 <
+ *   2^21, so the numerator 256 w d^2 stays below 2^8 2^5 2^42 = 2^55 < 2^56, and V <= w (Q_L + Q_R) <= 32 * 64 * 2^30 = 2^41 < 2^42.
+ * Peak: i is a peak of the detector iff score(i) >= T, score(i) > score(i') for every i - w <= i' < i, and score(i) >= score(i')
+ *   for every i < i' <= i + w; neighbours outside [0, n] do not count.  On equal scores the leftmost wins, and two peaks of one
+ *   detector are more than w apart.  (T >= 1 puts a peak at w <= i <= n - w: all its neighbours lie in [0, n].)
+ * Two detectors run together: short (w_s, T_s) and long (w_l, T_l), 1 <= w_s <= w_l <= S2S_SEG_MAX_WINDOW, 1 <= T <=
+ *   S2S_SEG_MAX_THRESHOLD = 2^40.
+ * Boundaries: every short peak, and every long peak without a short peak at distance <= w_s.  The rule is local: nothing is
+ *   greedy, nothing is ordered left to right.
+ * Events: with the boundaries b_1 < ... < b_m the events are [0, b_1), [b_1, b_2), ..., [b_m, n); a record with n >= 1 and no
+ *   boundary is one event, a record with n = 0 has none.  The events abut and sum to n; the first and the last hold at least w_s
+ *   samples and every other at least w_s + 1; so a record has at most s2s_segment_capacity(n, w_s) = max(1, floor(n / w_s)) events
+ *   (0 for n = 0).
+ * `segment` takes t on its command line: T = floor(256.0 * t * t) in double (segment.threshold_int, the one place).
+ *
+ *  s2s_segment_capacity       host function: the bound above; S2S_ERR_ARG for n < 0 or w_short outside 1 .. S2S_SEG_MAX_WINDOW.
+ *  s2s_segment_scratch_bytes  host function: the bytes of `scratch` s2s_segment needs for `total` pooled samples: per tile of
+ *                 S2S_SEG_TILE = 2048 positions 32 flag words of 64 bits and 32 int32 ranks of the words inside the tile, and
+ *                 tiles + 1 int64 ranks of the tiles (R does not enter today); S2S_ERR_ARG for total < 0 or R < 0.
+ *  s2s_segment    samples: the records back to back, record r = samples[offs[r] .. offs[r+1]); `total` is the caller's offs[R], by
+ *                 value: the entry cannot read device memory before the launch and the grid depends on it.  No pooled position
+ *                 >= total is ever read, whatever offs holds.  Record r owns the slots [ev_offs[r], ev_offs[r+1]) of ev_start /
+ *                 ev_len (int32; event k of the record at ev_offs[r] + k: start in the record, samples) -- the layout
+ *                 s2s_event_sums reads through its l_offs, so the two chain on the device without a copy.  n_events int32 [R]: the
+ *                 record's events; -(events) for a record whose slot is smaller than that (nothing is written to its slot then);
+ *                 S2S_DTW_COST_TOO_LONG for a record of more than S2S_DTW_MAX_SAMPLES samples (no work is done for it and its
+ *                 samples are not read).  A record with offs[r] < 0, offs[r+1] < offs[r] or offs[r+1] > total counts as empty: 0
+ *                 events.  Nothing is ever written outside a slot.  scratch: 16-byte aligned; it needs no initialisation and may be
+ *                 reused by the next call on the stream.  R = 0 or total = 0 launches nothing (and writes nothing: with total = 0
+ *                 every record is empty, which the caller knows).  -(events) and S2S_DTW_COST_TOO_LONG can coincide at -2; the
+ *                 caller, who knows the lengths, tells them apart.  Windows or thresholds outside the limits: S2S_ERR_ARG, nothing is launched.
+ *                 Three launches (csrc/s2s_segment.h), nothing spins or waits between workgroups, no atomics: the work is split over
+ *                 the POOLED positions, not over records -- workgroup t owns the positions [2048 t, 2048 (t + 1)) and reads a halo
+ *                 of max(2 w_l, 3 w_s) <= 96 on each side; a thread finds its record by a search in offs; a record's edges zero
+ *                 the scores, so nothing crosses from one record into the next.  (1) flags: the samples and, per position, its
+ *                 distance to its record's two ends (clamped bytes) go to LDS, both detectors' scores come from direct window
+ *                 sums (the two 64-bit divisions per position are skipped where d = 0), then the peak and the merge rule; one bit
+ *                 per position by wave ballots -- the first sample of every record that is neither empty nor too long is flagged
+ *                 too, so the events are exactly the flagged positions -- and one count per tile.  Static LDS: S2S_SEG_LDS_BYTES
+ *                 = 47,296 B.  (2) one workgroup scans the tile counts.  (3) compact: a flagged position with global rank g in
+ *                 record r writes slot ev_offs[r] + (g - rank(offs[r])); its length runs to the next flagged position, found by
+ *                 rank (a search in the tile ranks, never a walk over samples), or to the record's end; n_events from the ranks at
+ *                 the record's two ends.  1,000 records of 50,000 samples and one record of 2^22 load the device alike.
+ *  s2s_segment_host   the same on host pointers, in plain C++ (`segment --cpu`; the definition the kernels must equal bit for
+ *                 bit): records dealt out over `threads` >= 1 host threads, window sums from prefix sums; no scratch argument.
+ *                 S2S_ERR_ARG for what the device can only mark: a record longer than S2S_DTW_MAX_SAMPLES or offsets that decrease
+ *                 or are negative (before anything is computed), and a slot smaller than its record's events (that record gets
+ *                 n_events = -(events) and an untouched slot, the others are complete).
+ *  s2s_segment_format_bound, s2s_segment_format   host helpers: the event table of `segment` as text, rows formatted on `threads`
+ *                 host threads.  Tab separated, "\n" ended; the header is
+ *                      read_name  event_index  start_idx  end_idx  event_level_mean  event_stdv
+ *                 and record r gives one row per event k < n_events[r] (a record with n_events <= 0 gives none), records in order:
+ *                 its id (ids[id_offs[r] .. id_offs[r+1])), k, ev_start, ev_start + ev_len, and with n = ev_len, S, Q the sums of
+ *                 s2s_event_sums in the slot and (digitisation, offset, range) = cal[3 r .. 3 r + 3) the RECORD's own calibration
+ *                 (double), the two expressions of s2s_events_format, in double and exactly as written there:
+ *                      event_level_mean = ((double)S / n + offset) * range / digitisation
+ *                      event_stdv       = sqrt((double)max(n*Q - S*S, 0)) / n * range / digitisation
+ *                 both "%.4f" (the population deviation); n*Q - S*S is formed exactly (an event may hold 2^22 samples, so in 128
+ *                 bits) and rounded to double once.  Returns the bytes written, or S2S_ERR_ARG: a NULL pointer, a record with
+ *                 rows whose calibration is not finite or has digitisation or range 0, an event with ev_len < 1, a slot smaller
+ *                 than n_events, or capacity below the bound function's value for the same arguments (nothing is written then). */
+#define S2S_SEG_MAX_WINDOW 32
+#define S2S_SEG_MAX_THRESHOLD ((int64_t)1 << 40)
+#define S2S_SEG_TILE 2048
+int64_t s2s_segment_capacity(int64_t n, int32_t w_short);
+int64_t s2s_segment_scratch_bytes(int64_t total, int32_t R);
+int s2s_segment(int device, void* stream, const int16_t* samples, const int64_t* offs, int32_t R, int64_t total, int32_t w_short,
+                int32_t w_long, int64_t thr_short, int64_t thr_long, uint8_t* scratch, const int64_t* ev_offs, int32_t* ev_start,
+                int32_t* ev_len, int32_t* n_events);
+int s2s_segment_host(const int16_t* samples, const int64_t* offs, int32_t R, int64_t total, int32_t w_short, int32_t w_long,
+                     int64_t thr_short, int64_t thr_long, const int64_t* ev_offs, int32_t* ev_start, int32_t* ev_len, int32_t* n_events,
+                     int32_t threads);
+int64_t s2s_segment_format_bound(const int32_t* n_events, int32_t R, const int64_t* id_offs, const double* cal, int32_t with_header);
+int64_t s2s_segment_format(const int32_t* ev_start, const int32_t* ev_len, const int64_t* S, const int64_t* Q, const int64_t* ev_offs,
+                           const int32_t* n_events, int32_t R, const uint8_t* ids, const int64_t* id_offs, const double* cal,
+                           int32_t with_header, int32_t threads, uint8_t* out, int64_t capacity);
+
 /* ---- host-side helper (no GPU work, no handle): replays the DRAWS of the reference's read sampler (utils.py:415-479
  * `sampling`, with the read-length law of utils.py:325-331 `draw_expon_dis`) without building a read, so that a rank of a sharded
  * run finds the generator state of its first read in microseconds per thousand reads instead of replaying them in the

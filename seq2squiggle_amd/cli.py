@@ -674,5 +674,52 @@ def resquiggle(seqs, signals, model, out, with_samples, band, skip_penalty, unkn
                    f"k-mers]  mean cost per sample {per} MAD")
 
 
+@main.command()
+@click.argument("signals", type=click.Path(dir_okay=False))
+@click.option("-o", "--out", required=True, type=click.Path(dir_okay=False), help="Output event table (.events.tsv).")
+@click.option("--window-short", default=3, type=int, show_default=True, help="Window of the short detector in samples (1..32).")
+@click.option("--window-long", default=6, type=int, show_default=True, help="Window of the long detector in samples (short..32).")
+@click.option("--threshold-short", default=1.4, type=float, show_default=True,
+              help="Threshold t of the short detector on Welch's t between the two windows.  A choice, not a measurement.")
+@click.option("--threshold-long", default=9.0, type=float, show_default=True,
+              help="Threshold t of the long detector.  A choice, not a measurement.")
+@click.option("--cpu", is_flag=True, help="Compute on host threads instead of the GPU (the same bytes).")
+@click.option("--json", "as_json", is_flag=True, help="Print the summary as one JSON object.")
+@click.option("--summary", "summary_out", default=None, type=click.Path(dir_okay=False), help="Also write one row per read here (.tsv).")
+@click.option("--max-samples", default=1 << 27, type=int, show_default=True, help="Samples per batch.")
+def segment(signals, out, window_short, window_long, threshold_short, threshold_long, cpu, as_json, summary_out, max_samples):
+    """Cut every record of a .blow5 / .slow5 file into events -- runs of constant level -- without its sequence, and write one row per
+    event: read_name, event_index, start_idx, end_idx, event_level_mean, event_stdv.  A boundary is a peak of a windowed t-statistic,
+    short window or long; exact integers.  Not scrappie's detector; unvalidated against scrappie / f5c / uncalled4."""
+    if str(signals).endswith(".pod5"):
+        raise click.UsageError(f"{signals}: segment reads .blow5 and .slow5 files; reading POD5 is not supported")
+    if not str(signals).endswith((".blow5", ".slow5")):
+        raise click.UsageError(f"{signals}: segment reads .blow5 and .slow5 files")
+    if max_samples < 1:
+        raise click.BadParameter("must be >= 1", param_hint="--max-samples")
+    import json
+    if not cpu:
+        import torch  # noqa: F401  (before the library: see engine.py)
+    from . import segment as SEG
+    if not 1 <= window_short <= SEG.MAX_WINDOW:
+        raise click.BadParameter(f"must be 1..{SEG.MAX_WINDOW}", param_hint="--window-short")
+    if not window_short <= window_long <= SEG.MAX_WINDOW:
+        raise click.BadParameter(f"must be --window-short..{SEG.MAX_WINDOW}", param_hint="--window-long")
+    for hint, t in (("--threshold-short", threshold_short), ("--threshold-long", threshold_long)):
+        try:
+            SEG.threshold_int(t)
+        except ValueError as e:
+            raise click.BadParameter(str(e), param_hint=hint)
+    s = SEG.segment_files(signals, out, window_short=window_short, window_long=window_long, threshold_short=threshold_short,
+                          threshold_long=threshold_long, cpu=cpu, summary_out=summary_out, max_samples=max_samples)
+    if as_json:
+        click.echo(json.dumps(s))
+    else:
+        per = "nan" if s["mean_samples_per_event"] is None else f"{s['mean_samples_per_event']:.3f}"
+        click.echo(f"{s['events']} events of {s['records'] - s['refused']} records -> {out}  [windows {window_short} / {window_long}, "
+                   f"thresholds {threshold_short} / {threshold_long}; {s['samples']} samples, {s['refused']} record(s) refused: too long]  "
+                   f"mean samples per event {per}")
+
+
 if __name__ == "__main__":
     main()

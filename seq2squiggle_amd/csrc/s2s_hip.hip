@@ -18,6 +18,7 @@
 #include "s2s_dtw.h"
 #include "s2s_sdtw.h"
 #include "s2s_resquiggle.h"
+#include "s2s_segment.h"
 
 #include <cctype>
 #include <cstdio>
@@ -2700,6 +2701,40 @@ int s2s_event_sums(int device, void* stream_, const int16_t* samples, const int6
     hipLaunchKernelGGL(s2s_event_sums_kernel, dim3(P, S2S_RSQ_SUM_SLICES), dim3(256), 0, static_cast<hipStream_t>(stream_), samples,
                        reinterpret_cast<const long long*>(s_offs), ev_start, ev_len, reinterpret_cast<const long long*>(l_offs),
                        reinterpret_cast<long long*>(S), reinterpret_cast<long long*>(Q));
+    HIP_TRY(nullptr, hipGetLastError());
+    return S2S_OK;
+}
+
+// ---- segment (s2s_segment.h)
+int64_t s2s_segment_scratch_bytes(int64_t total, int32_t R) {
+    if (total < 0 || total > S2S_SEG_MAX_TOTAL || R < 0) return S2S_ERR_ARG;
+    return s2s_seg_scratch(total);
+}
+
+int s2s_segment(int device, void* stream_, const int16_t* samples, const int64_t* offs, int32_t R, int64_t total, int32_t w_short,
+                int32_t w_long, int64_t thr_short, int64_t thr_long, uint8_t* scratch, const int64_t* ev_offs, int32_t* ev_start,
+                int32_t* ev_len, int32_t* n_events) {
+    if (R < 0 || total < 0 || total > S2S_SEG_MAX_TOTAL || !s2s_seg_params_ok(w_short, w_long, thr_short, thr_long) || !offs || !ev_offs ||
+        (R > 0 && total > 0 && (!samples || !scratch || !ev_start || !ev_len || !n_events)) || (reinterpret_cast<uintptr_t>(scratch) & 15u))
+        return fail(nullptr, S2S_ERR_ARG, "s2s_segment: bad argument (windows 1 <= short <= long <= 32, thresholds 1..2^40, total 0..2^40, "
+                                          "scratch 16-byte aligned)");
+    if (R == 0 || total == 0) return S2S_OK;
+    DeviceGuard guard(device);
+    if (!guard.ok) return fail(nullptr, S2S_ERR_HIP, "hipSetDevice failed");
+    const int64_t tiles = s2s_seg_tiles(total);
+    unsigned long long* words = reinterpret_cast<unsigned long long*>(scratch);
+    int* wrank = reinterpret_cast<int*>(scratch + tiles * S2S_SEG_WORDS * 8);
+    long long* trank = reinterpret_cast<long long*>(scratch + tiles * S2S_SEG_WORDS * 12);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    hipLaunchKernelGGL(s2s_segment_flags_kernel, dim3((unsigned)tiles), dim3(S2S_SEG_THREADS), 0, stream, samples,
+                       reinterpret_cast<const long long*>(offs), R, (long long)total, w_short, w_long, (long long)thr_short,
+                       (long long)thr_long, words, wrank, trank);
+    HIP_TRY(nullptr, hipGetLastError());
+    hipLaunchKernelGGL(s2s_segment_scan_kernel, dim3(1), dim3(1024), 0, stream, trank, (long long)tiles);
+    HIP_TRY(nullptr, hipGetLastError());
+    hipLaunchKernelGGL(s2s_segment_compact_kernel, dim3((unsigned)tiles), dim3(S2S_SEG_THREADS), 0, stream,
+                       reinterpret_cast<const long long*>(offs), R, (long long)total, (long long)tiles, words, wrank, trank,
+                       reinterpret_cast<const long long*>(ev_offs), ev_start, ev_len, n_events);
     HIP_TRY(nullptr, hipGetLastError());
     return S2S_OK;
 }

@@ -1829,3 +1829,193 @@ extern "C" int s2s_event_sums_host(const int16_t* samples, const int64_t* s_offs
     });
     return S2S_OK;
 }
+
+// ================================================================================ segment: event detection on the host
+// The definition of include/s2s_hip.h (next to s2s_segment) record by record: the window sums from prefix sums, the two detectors'
+// scores over [0, n], the peaks, the merge rule, the events.  What the kernels of s2s_segment.h must equal bit for bit.
+#include "s2s_segment.h"
+
+namespace {
+
+// score_w(i) for i = 0 .. n into sc [n + 1]; ps / pq [n + 1]: prefix sums of x and x^2
+void seg_scores(const std::vector<int64_t>& ps, const std::vector<int64_t>& pq, int64_t n, int32_t w, std::vector<int64_t>& sc) {
+    std::fill(sc.begin(), sc.begin() + n + 1, 0);
+    for (int64_t i = w; i + w <= n; ++i)
+        sc[i] = s2s_seg_score((int32_t)(ps[i] - ps[i - w]), (int32_t)(ps[i + w] - ps[i]), pq[i + w] - pq[i - w], w);
+}
+
+// peaks of one detector into pk [n + 1]
+void seg_peaks(const std::vector<int64_t>& sc, int64_t n, int32_t w, int64_t thr, std::vector<uint8_t>& pk) {
+    std::fill(pk.begin(), pk.begin() + n + 1, 0);
+    for (int64_t i = 0; i <= n; ++i) {
+        const int64_t v = sc[i];
+        if (v < thr) continue;
+        bool p = true;
+        for (int64_t j = std::max<int64_t>(0, i - w); j < i && p; ++j) p = v > sc[j];
+        for (int64_t j = i + 1; j <= std::min(n, i + w) && p; ++j) p = v >= sc[j];
+        pk[i] = p;
+    }
+}
+
+struct SegWork {
+    std::vector<int64_t> ps, pq, sc;
+    std::vector<uint8_t> pk_s, pk_l;
+    std::vector<int32_t> bounds;
+};
+
+// -> the record's boundaries (ascending) in wk.bounds
+void seg_one(const int16_t* x, int64_t n, int32_t w_s, int32_t w_l, int64_t t_s, int64_t t_l, SegWork& wk) {
+    wk.bounds.clear();
+    if (n < 2 * w_s) return;                         // no position has a score
+    const size_t m = (size_t)n + 1;
+    if (wk.ps.size() < m) { wk.ps.resize(m); wk.pq.resize(m); wk.sc.resize(m); wk.pk_s.resize(m); wk.pk_l.resize(m); }
+    wk.ps[0] = wk.pq[0] = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t v = x[i];
+        wk.ps[i + 1] = wk.ps[i] + v;
+        wk.pq[i + 1] = wk.pq[i] + v * v;
+    }
+    seg_scores(wk.ps, wk.pq, n, w_s, wk.sc);
+    seg_peaks(wk.sc, n, w_s, t_s, wk.pk_s);
+    seg_scores(wk.ps, wk.pq, n, w_l, wk.sc);
+    seg_peaks(wk.sc, n, w_l, t_l, wk.pk_l);
+    for (int64_t i = 0; i <= n; ++i) {
+        bool b = wk.pk_s[i];
+        if (!b && wk.pk_l[i]) {
+            b = true;
+            for (int64_t j = std::max<int64_t>(0, i - w_s); j <= std::min(n, i + w_s) && b; ++j) b = !wk.pk_s[j];
+        }
+        if (b) wk.bounds.push_back((int32_t)i);
+    }
+}
+
+}  // namespace
+
+extern "C" int64_t s2s_segment_capacity(int64_t n, int32_t w_short) {
+    if (n < 0 || w_short < 1 || w_short > S2S_SEG_MAX_WINDOW) return S2S_ERR_ARG;
+    return n == 0 ? 0 : std::max<int64_t>(1, n / w_short);
+}
+
+extern "C" int s2s_segment_host(const int16_t* samples, const int64_t* offs, int32_t R, int64_t total, int32_t w_short, int32_t w_long,
+                                int64_t thr_short, int64_t thr_long, const int64_t* ev_offs, int32_t* ev_start, int32_t* ev_len,
+                                int32_t* n_events, int32_t threads) {
+    if (R < 0 || total < 0 || threads < 1 || !s2s_seg_params_ok(w_short, w_long, thr_short, thr_long) || !offs || !ev_offs ||
+        (R > 0 && (!n_events || (total > 0 && (!samples || !ev_start || !ev_len)))) || !dtw_offsets_ok(offs, R) ||
+        (R > 0 && (offs[0] < 0 || offs[R] > total)))
+        return S2S_ERR_ARG;
+    std::atomic<int32_t> next{0}, small{0};
+    auto work = [&]() {
+        SegWork wk;
+        for (int32_t r; (r = next.fetch_add(1)) < R;) {
+            const int64_t n = offs[r + 1] - offs[r];
+            if (n == 0) { n_events[r] = 0; continue; }
+            seg_one(samples + offs[r], n, w_short, w_long, thr_short, thr_long, wk);
+            const int64_t cnt = (int64_t)wk.bounds.size() + 1, eo = ev_offs[r], cap = ev_offs[r + 1] - eo;
+            if (eo < 0 || cnt > cap) { n_events[r] = (int32_t)-cnt; small = 1; continue; }
+            int64_t at = 0;
+            for (int64_t k = 0; k < cnt; ++k) {
+                const int64_t end = k + 1 < cnt ? wk.bounds[k] : n;
+                ev_start[eo + k] = (int32_t)at;
+                ev_len[eo + k] = (int32_t)(end - at);
+                at = end;
+            }
+            n_events[r] = (int32_t)cnt;
+        }
+    };
+    const int extra = std::min<int32_t>(threads, R) - 1;
+    std::vector<std::thread> pool;
+    for (int t = 0; t < extra; ++t) pool.emplace_back(work);
+    work();
+    for (auto& t : pool) t.join();
+    return small ? S2S_ERR_ARG : S2S_OK;
+}
+
+namespace {
+
+constexpr char kSegmentHeader[] = "read_name\tevent_index\tstart_idx\tend_idx\tevent_level_mean\tevent_stdv\n";
+constexpr int64_t kSegmentBlock = 4096;             // rows of one unit of formatting work
+
+// bytes one row of record r may take, or -1 for a calibration that is refused
+inline int64_t segment_row_bound(int64_t id_len, const double* cal) {
+    if (!std::isfinite(cal[0]) || !std::isfinite(cal[1]) || !std::isfinite(cal[2])) return -1;
+    const EventWidths w = event_widths(cal[0], cal[2], cal[1]);
+    if (!w.ok) return -1;
+    return id_len + 3 * 10 + 2 * (int64_t)w.level + 6;     // three int32 numbers, two levels, five tabs and the line end
+}
+
+}  // namespace
+
+extern "C" int64_t s2s_segment_format_bound(const int32_t* n_events, int32_t R, const int64_t* id_offs, const double* cal,
+                                            int32_t with_header) {
+    if (R < 0 || (R > 0 && (!n_events || !id_offs || !cal))) return S2S_ERR_ARG;
+    int64_t total = with_header ? (int64_t)sizeof kSegmentHeader - 1 : 0;
+    for (int32_t r = 0; r < R; ++r) {
+        if (id_offs[r + 1] < id_offs[r]) return S2S_ERR_ARG;
+        if (n_events[r] <= 0) continue;
+        const int64_t row = segment_row_bound(id_offs[r + 1] - id_offs[r], cal + 3 * (int64_t)r);
+        if (row < 0) return S2S_ERR_ARG;
+        total += row * n_events[r];
+    }
+    return total;
+}
+
+extern "C" int64_t s2s_segment_format(const int32_t* ev_start, const int32_t* ev_len, const int64_t* S, const int64_t* Q,
+                                      const int64_t* ev_offs, const int32_t* n_events, int32_t R, const uint8_t* ids, const int64_t* id_offs,
+                                      const double* cal, int32_t with_header, int32_t threads, uint8_t* out, int64_t capacity) {
+    if (threads < 1 || !out || capacity < 0) return S2S_ERR_ARG;
+    const int64_t bound = s2s_segment_format_bound(n_events, R, id_offs, cal, with_header);
+    if (bound < 0 || capacity < bound) return S2S_ERR_ARG;
+    struct Unit { int32_t r; int64_t k0, k1, at, size; };
+    std::vector<Unit> units;
+    int64_t head = with_header ? (int64_t)sizeof kSegmentHeader - 1 : 0, at = head;
+    std::vector<int64_t> row(R > 0 ? R : 0, 0);
+    for (int32_t r = 0; r < R; ++r) {
+        if (n_events[r] <= 0) continue;
+        if (!ev_start || !ev_len || !S || !Q || !ev_offs || !ids || ev_offs[r] < 0 || ev_offs[r + 1] - ev_offs[r] < n_events[r])
+            return S2S_ERR_ARG;
+        row[r] = segment_row_bound(id_offs[r + 1] - id_offs[r], cal + 3 * (int64_t)r);
+        for (int64_t k0 = 0; k0 < n_events[r]; k0 += kSegmentBlock) {
+            const int64_t k1 = std::min<int64_t>(n_events[r], k0 + kSegmentBlock);
+            units.push_back(Unit{r, k0, k1, at, 0});
+            at += (k1 - k0) * row[r];
+        }
+    }
+    std::atomic<int> failed{0};
+    dtw_for_each((int32_t)units.size(), threads, [&](int32_t u) {
+        Unit& un = units[u];
+        const int32_t r = un.r;
+        const double dig = cal[3 * (int64_t)r], offset = cal[3 * (int64_t)r + 1], range = cal[3 * (int64_t)r + 2];
+        const uint8_t* id = ids + id_offs[r];
+        const int64_t id_len = id_offs[r + 1] - id_offs[r];
+        uint8_t* p = out + un.at;
+        uint8_t* const end = p + (un.k1 - un.k0) * row[r];
+        for (int64_t k = un.k0; k < un.k1; ++k) {
+            const int64_t j = ev_offs[r] + k, n = ev_len[j], start = ev_start[j], s = S[j], q = Q[j];
+            if (n < 1 || start < 0 || end - p < row[r]) { failed = 1; return; }
+            // an event may hold 2^22 samples: n Q passes 2^63, so the difference is formed in 128 bits and rounded once
+            const __int128 var = std::max<__int128>((__int128)n * q - (__int128)s * s, 0);
+            const double mean = ((double)s / (double)n + offset) * range / dig;
+            const double stdv = std::sqrt((double)var) / (double)n * range / dig;
+            std::memcpy(p, id, id_len); p += id_len; *p++ = '\t';
+            p = put_u64(p, (uint64_t)k); *p++ = '\t';
+            p = put_u64(p, (uint64_t)start); *p++ = '\t';
+            p = put_u64(p, (uint64_t)(start + n)); *p++ = '\t';
+            char tmp[400];
+            int c = std::snprintf(tmp, sizeof tmp, "%.4f", mean);
+            if (c < 0 || end - p < c + 1) { failed = 1; return; }
+            std::memcpy(p, tmp, c); p += c; *p++ = '\t';
+            c = std::snprintf(tmp, sizeof tmp, "%.4f", stdv);
+            if (c < 0 || end - p < c + 1) { failed = 1; return; }
+            std::memcpy(p, tmp, c); p += c; *p++ = '\n';
+        }
+        un.size = p - (out + un.at);
+    });
+    if (failed) return S2S_ERR_ARG;
+    if (with_header) std::memcpy(out, kSegmentHeader, head);
+    int64_t pos = head;
+    for (const Unit& un : units) {                                   // close the gaps, in order
+        if (un.size && pos != un.at) std::memmove(out + pos, out + un.at, un.size);
+        pos += un.size;
+    }
+    return pos;
+}

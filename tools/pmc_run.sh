@@ -18,6 +18,8 @@ for grp in "FETCH_SIZE" "WRITE_SIZE" \
   # (eight SQ counters are what one pass can hold: a ninth makes rocprofv3 abort with "exceeds the capabilities of the hardware" and
   #  then sit in its signal handler -- hence the wall limit on every pass)
   timeout -k 10 300 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $OUT -o pmc$i -- python3 $R/bench.py $ARGS > $OUT/pmc$i.log 2>&1
-  echo "pass $i ($grp): rc=$?"
+  rc=$?
+  echo "pass $i ($grp): rc=$rc"
+  [ $rc -eq 0 ] || exit $rc      # a pass that failed or ran into its limit ends the run: nothing more is started on that GPU
 done
 ls $OUT

@@ -525,6 +525,15 @@ def evaluate(data_dir, models, compute_mode, max_chunks, batch_size, per_chunk, 
         np.savez(per_chunk, models=np.array([str(m) for m in models]), **arrays)
 
 
+def _signal_files(command: str, *paths) -> None:
+    """The signal-analysis commands read .blow5 / .slow5 only: refuse anything else by its name, before any work."""
+    for p in paths:
+        if str(p).endswith(".pod5"):
+            raise click.UsageError(f"{p}: {command} reads .blow5 and .slow5 files; reading POD5 is not supported")
+        if not str(p).endswith((".blow5", ".slow5")):
+            raise click.UsageError(f"{p}: {command} reads .blow5 and .slow5 files")
+
+
 @main.command()
 @click.argument("a", type=click.Path(dir_okay=False))
 @click.argument("b", type=click.Path(dir_okay=False))
@@ -567,11 +576,7 @@ def compare(a, b, out, band, normalise, by_order, max_samples, cpu, as_json, pat
     id, in A's order): OUT gets read_id, n_a, n_b, med_a, mad_a, med_b, mad_b, band, dtw, dtw_per_sample.  Everything is computed in
     integers on the stored int16 samples; dtw_per_sample = dtw / (n_a + n_b) / 64, in MADs per step with --normalise mad.
     The alignment is global: a record of B that carries samples A lacks (a real read against a simulated one) needs --open-ends."""
-    for p in (a, b):
-        if str(p).endswith(".pod5"):
-            raise click.UsageError(f"{p}: compare reads .blow5 and .slow5 files; reading POD5 is not supported")
-        if not str(p).endswith((".blow5", ".slow5")):
-            raise click.UsageError(f"{p}: compare reads .blow5 and .slow5 files")
+    _signal_files("compare", a, b)
     if max_samples < 1:
         raise click.BadParameter("must be >= 1", param_hint="--max-samples")
     if path_memory < 1:
@@ -583,17 +588,17 @@ def compare(a, b, out, band, normalise, by_order, max_samples, cpu, as_json, pat
     import json
     if not cpu:
         import torch  # noqa: F401  (before the library: see engine.py)
-    from . import compare as C
-    if not 1 <= band <= C.max_band():
-        raise click.BadParameter(f"must be 1..{C.max_band()}", param_hint="--band")
+    from . import compare as C, signal_batch as SB
+    if not 1 <= band <= SB.max_band():
+        raise click.BadParameter(f"must be 1..{SB.max_band()}", param_hint="--band")
     open_kw = {}
     if open_ends:
         anchor = C.DEFAULT_ANCHOR if anchor is None else anchor
         anchor_window = C.DEFAULT_ANCHOR_WINDOW if anchor_window is None else anchor_window
         if not 1 <= anchor <= C.max_query():
             raise click.BadParameter(f"must be 1..{C.max_query()}", param_hint="--anchor")
-        if not 1 <= anchor_window <= C.MAX_SAMPLES:
-            raise click.BadParameter(f"must be 1..{C.MAX_SAMPLES}", param_hint="--anchor-window")
+        if not 1 <= anchor_window <= SB.MAX_SAMPLES:
+            raise click.BadParameter(f"must be 1..{SB.MAX_SAMPLES}", param_hint="--anchor-window")
         open_kw = dict(open_ends=True, anchor=anchor, anchor_window=anchor_window)
     s = C.compare_files(a, b, out, band=band, normalise=normalise, by_order=by_order, max_samples=max_samples, cpu=cpu,
                         path_out=path_out, events_a=events_a, events_out=events_out, path_memory=path_memory, **open_kw)
@@ -642,10 +647,7 @@ def resquiggle(seqs, signals, model, out, with_samples, band, skip_penalty, unkn
     FASTQ, record names = read ids) and write the event table predict --events writes: read_name, position, model_kmer, start_idx,
     end_idx, event_level_mean, event_stdv.  Both ends are pinned: the first sample belongs to the first k-mer, the last to the last.
     Exact integers on median / MAD normalised samples and levels; unvalidated against f5c / uncalled4."""
-    if str(signals).endswith(".pod5"):
-        raise click.UsageError(f"{signals}: resquiggle reads .blow5 and .slow5 files; reading POD5 is not supported")
-    if not str(signals).endswith((".blow5", ".slow5")):
-        raise click.UsageError(f"{signals}: resquiggle reads .blow5 and .slow5 files")
+    _signal_files("resquiggle", signals)
     if max_samples < 1:
         raise click.BadParameter("must be >= 1", param_hint="--max-samples")
     if trace_memory < 1:
@@ -653,10 +655,9 @@ def resquiggle(seqs, signals, model, out, with_samples, band, skip_penalty, unkn
     import json
     if not cpu:
         import torch  # noqa: F401  (before the library: see engine.py)
-    from . import compare as C
-    from . import resquiggle as R
-    if not 1 <= band <= C.max_band():
-        raise click.BadParameter(f"must be 1..{C.max_band()}", param_hint="--band")
+    from . import resquiggle as R, signal_batch as SB
+    if not 1 <= band <= SB.max_band():
+        raise click.BadParameter(f"must be 1..{SB.max_band()}", param_hint="--band")
     if not 0 <= skip_penalty <= R.MAX_SKIP_PENALTY:
         raise click.BadParameter(f"must be 0..{R.MAX_SKIP_PENALTY}", param_hint="--skip-penalty")
     if not 0 <= unknown_cost <= R.MAX_UNKNOWN_COST:
@@ -691,10 +692,7 @@ def segment(signals, out, window_short, window_long, threshold_short, threshold_
     """Cut every record of a .blow5 / .slow5 file into events -- runs of constant level -- without its sequence, and write one row per
     event: read_name, event_index, start_idx, end_idx, event_level_mean, event_stdv.  A boundary is a peak of a windowed t-statistic,
     short window or long; exact integers.  Not scrappie's detector; unvalidated against scrappie / f5c / uncalled4."""
-    if str(signals).endswith(".pod5"):
-        raise click.UsageError(f"{signals}: segment reads .blow5 and .slow5 files; reading POD5 is not supported")
-    if not str(signals).endswith((".blow5", ".slow5")):
-        raise click.UsageError(f"{signals}: segment reads .blow5 and .slow5 files")
+    _signal_files("segment", signals)
     if max_samples < 1:
         raise click.BadParameter("must be >= 1", param_hint="--max-samples")
     import json

@@ -1,10 +1,10 @@
 """`compare A B -o OUT.tsv`: how far the signals of two files are apart -- per pair of records the banded dynamic-time-warping (DTW)
 distance between their median / MAD normalised int16 samples.  Everything is defined in integers (include/s2s_hip.h, next to
 s2s_dtw_banded, states the definitions; tests/_dtw_ref.py restates them): the GPU kernels (csrc/s2s_dtw.h), their host twins
-(`--cpu`) and any batching give the same bytes.  Per batch of pairs: one host-to-device copy (offsets and samples of both
-sides), the three kernels, one device-to-host copy (cost, med, mad).  The reference has no such command and no DTW tool was
-at hand to compare against: what is pinned is that every number is the stated integer function of exactly the int16 samples the
-two files store -- DESIGN.md section 6.
+(`--cpu`) and any batching give the same bytes.  Per batch of pairs (signal_batch.Batch): one host-to-device copy (offsets, tables
+and samples of both sides), the three kernels, one device-to-host copy (cost, med, mad; with --path steps and ops as well).  The
+reference has no such command and no DTW tool was at hand to compare against: what is pinned is that every number is the stated
+integer function of exactly the int16 samples the two files store -- DESIGN.md section 6.
 
 `--path` adds the warping path behind every distance (s2s_dtw_path: the sweep in an instance that stores one 2-bit decision per
 in-band cell into a device scratch, then a walk back), written run-length encoded, and `--events-a / --events-out` carry the
@@ -15,17 +15,17 @@ k-mer boundaries of an event table of file A (`predict --events`) through the pa
 first and the last samples of A are located in the head and the tail of B by subsequence DTW (s2s_sdtw, csrc/s2s_sdtw.h: free
 start, free end, exact integers like the rest; `sdtw`, `_anchors`), and the batch path above then runs on that interval of B."""
 import logging
-import math
 import os
-from typing import Iterable, Sequence
+from typing import Sequence
 
 import click
 import numpy as np
 
+from .signal_batch import (MAX_SAMPLES, SCALE, Batch, batches, calibration, check_band, device_only, event_level, max_band,
+                           open_records, slots)
+
 logger = logging.getLogger("seq2squiggle")
 
-SCALE = 64                       # S2S_DTW_SCALE: one MAD is 64 units
-MAX_SAMPLES = 1 << 22            # S2S_DTW_MAX_SAMPLES per record
 DEFAULT_BAND = 512
 DEFAULT_MAX_SAMPLES = 1 << 27    # samples of both sides per batch: 256 MiB of int16 on the device, twice with the normalised copy
 COLUMNS = ("read_id", "n_a", "n_b", "med_a", "mad_a", "med_b", "mad_b", "band", "dtw", "dtw_per_sample")
@@ -38,97 +38,15 @@ DEFAULT_ANCHOR_WINDOW = 16384    # ... inside this many samples of B's head and 
 OPEN_COLUMNS = ("b_start", "b_end", "head_cost", "tail_cost")
 
 
-def max_band() -> int:
-    from ._lib import lib
-    return int(lib().s2s_dtw_max_band())
-
-
-def _host_threads() -> int:
-    from .signal_io import cpu_share
-    return cpu_share()
-
-
-def _check(rc: int, what: str) -> None:
-    if rc != 0:
-        from ._lib import lib
-        raise RuntimeError(f"{what} failed ({rc}): {lib().s2s_last_error(None).decode()}")
-
-
-def _pack(records: Sequence[np.ndarray]):
-    """int16 records -> (flat int16, int64 offsets [len + 1]); a record longer than the kernels' limit is refused here, where the
-    lengths are known (the device entries cannot see them)."""
-    recs = [np.ascontiguousarray(r, dtype=np.int16).reshape(-1) for r in records]
-    offs = np.zeros(len(recs) + 1, np.int64)
-    if recs:
-        np.cumsum([len(r) for r in recs], out=offs[1:])
-        if max(len(r) for r in recs) > MAX_SAMPLES:
-            raise ValueError(f"a record holds more than {MAX_SAMPLES} samples")
-    flat = np.concatenate(recs) if recs else np.zeros(0, np.int16)
-    return flat, offs
-
-
-def _check_band(band: int) -> int:
-    band = int(band)
-    if not 1 <= band <= max_band():
-        raise ValueError(f"band must be 1..{max_band()}")
-    return band
-
-
-class _Device:
-    """One batch on the GPU: a single uint8 buffer up (offsets, then samples) and a single one down (cost, med, mad)."""
-
-    def __init__(self, flat: np.ndarray, offs: np.ndarray, device: int = 0, extra: np.ndarray = None):
-        import torch
-        self.torch, self.device = torch, int(device)
-        self.n_rec, self.total = len(offs) - 1, int(offs[-1])
-        extra = np.zeros(0, np.uint8) if extra is None else extra           # further int64 tables behind the offsets (extra_ptr)
-        assert extra.dtype == np.uint8 and extra.nbytes % 8 == 0
-        head = offs.nbytes + extra.nbytes
-        host = np.empty(head + flat.nbytes, np.uint8)
-        host[:offs.nbytes] = offs.view(np.uint8)
-        host[offs.nbytes:head] = extra
-        host[head:] = flat.view(np.uint8)
-        self.up = torch.from_numpy(host).to(f"cuda:{self.device}")
-        self.offs_ptr = self.up.data_ptr()
-        self.extra_ptr = self.offs_ptr + offs.nbytes
-        self.samples_ptr = self.offs_ptr + head                              # (8-byte aligned: behind int64s)
-        self.stream = torch.cuda.current_stream(self.device).cuda_stream
-
-    def down(self, n_pairs: int):
-        """The result buffer: [cost int64 x n_pairs][med int32 x n_rec][mad int32 x n_rec] -> (tensor, cost ptr, med ptr, mad ptr)."""
-        t = self.torch.empty(8 * n_pairs + 8 * self.n_rec + 8, dtype=self.torch.uint8, device=f"cuda:{self.device}")
-        p = t.data_ptr()
-        return t, p, p + 8 * n_pairs, p + 8 * n_pairs + 4 * self.n_rec
-
-    def scratch(self):
-        return self.torch.empty(max(self.total, 1), dtype=self.torch.int16, device=f"cuda:{self.device}")
-
-
-def _split_down(raw: np.ndarray, n_pairs: int, n_rec: int):
-    cost = raw[:8 * n_pairs].view(np.int64).copy()
-    med = raw[8 * n_pairs:8 * n_pairs + 4 * n_rec].view(np.int32).copy()
-    mad = raw[8 * n_pairs + 4 * n_rec:8 * n_pairs + 8 * n_rec].view(np.int32).copy()
-    return cost, med, mad
-
-
 def median_mad(records: Sequence[np.ndarray], cpu: bool = False, device: int = 0):
     """-> (med int32 [n], mad int32 [n]): the lower median of every int16 record and the lower median of its |x - med|."""
     if not cpu:
         import torch  # noqa: F401  (before the library: see engine.py)
-    from ._lib import lib
-    L = lib()
-    flat, offs = _pack(records)
-    n = len(offs) - 1
-    if cpu:
-        med, mad = np.zeros(n, np.int32), np.zeros(n, np.int32)
-        _check(L.s2s_signal_median_mad_host(flat.ctypes.data, offs.ctypes.data, n, med.ctypes.data, mad.ctypes.data, _host_threads()),
-               "s2s_signal_median_mad_host")
-        return med, mad
-    dev = _Device(flat, offs, device)
-    t, _, med_p, mad_p = dev.down(0)
-    _check(L.s2s_signal_median_mad(dev.device, dev.stream, dev.samples_ptr, dev.offs_ptr, n, med_p, mad_p), "s2s_signal_median_mad")
-    _, med, mad = _split_down(t.cpu().numpy(), 0, n)
-    return med, mad
+    B = Batch(records, cpu=cpu, device=device)
+    res = B.alloc(med=(np.int32, B.n_rec), mad=(np.int32, B.n_rec))
+    B.measure(res.ptr("med"), res.ptr("mad"))
+    r = res.fetch()
+    return r["med"], r["mad"]
 
 
 def normalise(records: Sequence[np.ndarray], med=None, mad=None, scale: int = SCALE, cpu: bool = False, device: int = 0):
@@ -136,29 +54,18 @@ def normalise(records: Sequence[np.ndarray], med=None, mad=None, scale: int = SC
     to the records' own (median_mad)."""
     if not cpu:
         import torch  # noqa: F401
-    from ._lib import lib
-    L = lib()
-    flat, offs = _pack(records)
-    n = len(offs) - 1
     if med is None or mad is None:
         med, mad = median_mad(records, cpu=cpu, device=device)
-    med = np.ascontiguousarray(med, dtype=np.int32)
-    mad = np.ascontiguousarray(mad, dtype=np.int32)
-    if med.shape != (n,) or mad.shape != (n,):
-        raise ValueError("med and mad must hold one value per record")
-    if cpu:
-        out = np.empty(len(flat), np.int16)
-        _check(L.s2s_signal_normalise_host(flat.ctypes.data, offs.ctypes.data, n, med.ctypes.data, mad.ctypes.data, int(scale),
-                                           out.ctypes.data, _host_threads()), "s2s_signal_normalise_host")
-    else:
-        import torch
-        dev = _Device(flat, offs, device)
-        mm = torch.from_numpy(np.concatenate([med, mad])).to(f"cuda:{dev.device}")
-        q = dev.scratch()
-        _check(L.s2s_signal_normalise(dev.device, dev.stream, dev.samples_ptr, dev.offs_ptr, n, mm.data_ptr(), mm.data_ptr() + 4 * n,
-                                      int(scale), q.data_ptr()), "s2s_signal_normalise")
-        out = q.cpu().numpy()[:len(flat)]
-    return [out[offs[i]:offs[i + 1]] for i in range(n)]
+
+    def given(offs):                                    # med, mad travel with the samples as two int32 tables
+        tab = np.ascontiguousarray(med, dtype=np.int32), np.ascontiguousarray(mad, dtype=np.int32)
+        if tab[0].shape != (len(offs) - 1,) or tab[1].shape != (len(offs) - 1,):
+            raise ValueError("med and mad must hold one value per record")
+        return tab
+    B = Batch(records, given, cpu=cpu, device=device)
+    B.normalised(B.table(0), B.table(1), given=True, scale=scale)
+    out, offs = B.pool(), B.host_offs
+    return [out[offs[i]:offs[i + 1]] for i in range(B.n_rec)]
 
 
 def path_scratch_bytes(n: int, m: int, band: int) -> int:
@@ -170,12 +77,6 @@ def path_scratch_bytes(n: int, m: int, band: int) -> int:
     return r
 
 
-def _path_slots(offs: np.ndarray, P: int):
-    """-> int64 [P + 1] offsets of the pairs' slots of ops: n + m - 2 bytes for a pair with two non-empty members, else none."""
-    n, m = np.diff(offs[:P + 1]), np.diff(offs[P:])
-    return np.concatenate([[0], np.cumsum(np.where((n > 0) & (m > 0), n + m - 2, 0))]).astype(np.int64)
-
-
 def _split_ops(ops: np.ndarray, path_offs: np.ndarray, steps: np.ndarray):
     """The right-aligned paths of a batch -> one uint8 array per pair."""
     return [ops[int(e) - int(k):int(e)].copy() for e, k in zip(path_offs[1:], steps)]
@@ -184,54 +85,32 @@ def _split_ops(ops: np.ndarray, path_offs: np.ndarray, steps: np.ndarray):
 def _run_batch(a_list, b_list, band: int, norm: bool, cpu: bool, device: int = 0, threads: int = None, path: bool = False):
     """One batch of pairs -> (cost int64 [P], med int32 [2 P], mad int32 [2 P]); records 0..P-1 are A's, P..2P-1 B's.  path=True:
     s2s_dtw_path instead of s2s_dtw_banded, and a fourth result: the ops of every pair (uint8 arrays, empty without a path)."""
-    from ._lib import lib
-    L = lib()
     P = len(a_list)
-    flat, offs = _pack(list(a_list) + list(b_list))
+
+    def path_tables(offs):
+        """-> path_offs int64 [P + 1]: the pairs' slots of ops, n + m - 2 bytes for a pair with two non-empty members, else none;
+        scratch_offs int64 [P + 1]: their slots of decision scratch, formed for the device only."""
+        n, m = np.diff(offs[:P + 1]), np.diff(offs[P:])
+        return (slots(np.where((n > 0) & (m > 0), n + m - 2, 0)),
+                device_only(lambda: slots([path_scratch_bytes(n[i], m[i], band) for i in range(P)])))
+    B = Batch(list(a_list) + list(b_list), path_tables if path else (), cpu, device, threads)
+    fields = dict(cost=(np.int64, P), med=(np.int32, 2 * P), mad=(np.int32, 2 * P))
     if path:
-        path_offs = _path_slots(offs, P)
-        n_ops = max(int(path_offs[-1]), 1)
-    if cpu:
-        threads = threads or _host_threads()
-        med, mad, cost = np.zeros(2 * P, np.int32), np.zeros(2 * P, np.int32), np.zeros(P, np.int64)
-        _check(L.s2s_signal_median_mad_host(flat.ctypes.data, offs.ctypes.data, 2 * P, med.ctypes.data, mad.ctypes.data, threads),
-               "s2s_signal_median_mad_host")
-        q = flat
-        if norm:
-            q = np.empty(len(flat), np.int16)
-            _check(L.s2s_signal_normalise_host(flat.ctypes.data, offs.ctypes.data, 2 * P, med.ctypes.data, mad.ctypes.data, SCALE,
-                                               q.ctypes.data, threads), "s2s_signal_normalise_host")
-        if path:
-            ops, steps = np.zeros(n_ops, np.uint8), np.zeros(P, np.int64)
-            _check(L.s2s_dtw_path_host(q.ctypes.data, offs.ctypes.data, q.ctypes.data, offs.ctypes.data + 8 * P, P, band, cost.ctypes.data,
-                                       ops.ctypes.data, path_offs.ctypes.data, steps.ctypes.data, threads), "s2s_dtw_path_host")
-            return cost, med, mad, _split_ops(ops, path_offs, steps)
-        _check(L.s2s_dtw_banded_host(q.ctypes.data, offs.ctypes.data, q.ctypes.data, offs.ctypes.data + 8 * P, P, band,
-                                     cost.ctypes.data, threads), "s2s_dtw_banded_host")
-        return cost, med, mad
-    dev = _Device(flat, offs, device)
-    t, cost_p, med_p, mad_p = dev.down(P)
-    _check(L.s2s_signal_median_mad(dev.device, dev.stream, dev.samples_ptr, dev.offs_ptr, 2 * P, med_p, mad_p), "s2s_signal_median_mad")
-    q_ptr = dev.samples_ptr
-    if norm:
-        q = dev.scratch()
-        q_ptr = q.data_ptr()
-        _check(L.s2s_signal_normalise(dev.device, dev.stream, dev.samples_ptr, dev.offs_ptr, 2 * P, med_p, mad_p, SCALE, q_ptr),
-               "s2s_signal_normalise")
+        path_offs = B.tables[0]
+        fields.update(steps=(np.int64, P), ops=(np.uint8, path_offs[-1]))
+    res = B.alloc(**fields)
+    q = B.normalised(res.ptr("med"), res.ptr("mad"), norm)
+    if not norm:
+        B.measure(res.ptr("med"), res.ptr("mad"))       # (med / mad are results either way)
     if path:
-        torch, where = dev.torch, f"cuda:{dev.device}"
-        lens = np.diff(offs)
-        need = np.array([path_scratch_bytes(lens[i], lens[P + i], band) for i in range(P)], np.int64)
-        slots = np.concatenate([[0], np.cumsum(need), path_offs]).astype(np.int64)        # scratch_offs [P + 1], then path_offs [P + 1]
-        slots_d = torch.from_numpy(slots).to(where)
-        scratch = torch.empty(max(int(slots[P]), 16), dtype=torch.uint8, device=where)
-        out = torch.empty(8 * P + n_ops, dtype=torch.uint8, device=where)                # steps int64 [P], then the ops
-        _check(L.s2s_dtw_path(dev.device, dev.stream, q_ptr, dev.offs_ptr, q_ptr, dev.offs_ptr + 8 * P, P, band, cost_p, scratch.data_ptr(),
-                              slots_d.data_ptr(), out.data_ptr() + 8 * P, slots_d.data_ptr() + 8 * (P + 1), out.data_ptr()), "s2s_dtw_path")
-        raw = out.cpu().numpy()
-        return (*_split_down(t.cpu().numpy(), P, 2 * P), _split_ops(raw[8 * P:], path_offs, raw[:8 * P].view(np.int64)))
-    _check(L.s2s_dtw_banded(dev.device, dev.stream, q_ptr, dev.offs_ptr, q_ptr, dev.offs_ptr + 8 * P, P, band, cost_p), "s2s_dtw_banded")
-    return _split_down(t.cpu().numpy(), P, 2 * P)
+        B.call("dtw_path", q, B.offs(), q, B.offs(P), P, band, res.ptr("cost"), B.scratch(lambda: B.tables[1][-1]), B.table(1),
+               res.ptr("ops"), B.table(0), res.ptr("steps"))
+    else:
+        B.call("dtw_banded", q, B.offs(), q, B.offs(P), P, band, res.ptr("cost"))
+    r = res.fetch()
+    if path:
+        return r["cost"], r["med"], r["mad"], _split_ops(r["ops"], path_offs, r["steps"])
+    return r["cost"], r["med"], r["mad"]
 
 
 def dtw_banded(a_list: Sequence[np.ndarray], b_list: Sequence[np.ndarray], band: int, cpu: bool = False, device: int = 0) -> np.ndarray:
@@ -239,7 +118,7 @@ def dtw_banded(a_list: Sequence[np.ndarray], b_list: Sequence[np.ndarray], band:
     pair with an empty member."""
     if len(a_list) != len(b_list):
         raise ValueError("a_list and b_list must pair up")
-    band = _check_band(band)
+    band = check_band(band)
     if not cpu:
         import torch  # noqa: F401
     if not len(a_list):
@@ -262,34 +141,20 @@ def _check_anchor(anchor: int, anchor_window: int):
     return anchor, anchor_window
 
 
-def _problem_table(q_begin, q_len, t_begin, t_len, reverse) -> np.ndarray:
-    """The problems of one s2s_sdtw call as one uint8 buffer: int64 q_begin, q_len, t_begin, t_len [N] each, then reverse uint8 [N]
-    (padded to a multiple of 8 bytes)."""
-    N = len(q_begin)
-    tab = np.zeros(32 * N + (N + 7) // 8 * 8, np.uint8)
-    tab[:32 * N] = np.concatenate([q_begin, q_len, t_begin, t_len]).astype(np.int64).view(np.uint8)
-    tab[32 * N:33 * N] = np.asarray(reverse, np.uint8)
-    return tab
+def _problem_tables(q_begin, q_len, t_begin, t_len, reverse):
+    """The problems of one s2s_sdtw call as the five tables of a Batch: int64 q_begin, q_len, t_begin, t_len [N], reverse uint8 [N]."""
+    return (*(np.asarray(x, np.int64) for x in (q_begin, q_len, t_begin, t_len)), np.asarray(reverse, np.uint8))
 
 
-def _sdtw_host(q: np.ndarray, t: np.ndarray, tab: np.ndarray, N: int, threads: int):
-    from ._lib import lib
-    out = np.zeros(3 * max(N, 1), np.int64)
-    p, o = tab.ctypes.data, out.ctypes.data
-    _check(lib().s2s_sdtw_host(q.ctypes.data, p, p + 8 * N, t.ctypes.data, p + 16 * N, p + 24 * N, p + 32 * N, N, o, o + 8 * N, o + 16 * N,
-                               threads), "s2s_sdtw_host")
-    return out[:N], out[N:2 * N], out[2 * N:3 * N]
-
-
-def _sdtw_device(dev: _Device, q_ptr: int, t_ptr: int, N: int):
-    """s2s_sdtw on the problem table behind dev's offsets (dev.extra_ptr), then the one device-to-host copy of its results."""
-    from ._lib import lib
-    out = dev.torch.empty(3 * max(N, 1), dtype=dev.torch.int64, device=f"cuda:{dev.device}")
-    p, o = dev.extra_ptr, out.data_ptr()
-    _check(lib().s2s_sdtw(dev.device, dev.stream, q_ptr, p, p + 8 * N, t_ptr, p + 16 * N, p + 24 * N, p + 32 * N, N, o, o + 8 * N, o + 16 * N),
-           "s2s_sdtw")
-    out = out.cpu().numpy()
-    return out[:N], out[N:2 * N], out[2 * N:3 * N]
+def _sdtw(B: Batch, N: int, norm: bool = False):
+    """s2s_sdtw of the N problems in B's tables on B's samples, with `norm` on their normalised copy (whole-record median / MAD), then
+    the one copy of its results -> (cost, start, end) int64 [N]."""
+    n_stat = B.n_rec if norm else 0
+    res = B.alloc(cost=(np.int64, N), start=(np.int64, N), end=(np.int64, N), med=(np.int32, n_stat), mad=(np.int32, n_stat))
+    q = B.normalised(res.ptr("med"), res.ptr("mad"), norm)
+    B.call("sdtw", q, B.table(0), B.table(1), q, B.table(2), B.table(3), B.table(4), N, res.ptr("cost"), res.ptr("start"), res.ptr("end"))
+    r = res.fetch()
+    return r["cost"], r["start"], r["end"]
 
 
 def sdtw(queries: Sequence[np.ndarray], targets: Sequence[np.ndarray], reverse=False, cpu: bool = False, device: int = 0):
@@ -309,13 +174,9 @@ def sdtw(queries: Sequence[np.ndarray], targets: Sequence[np.ndarray], reverse=F
         import torch  # noqa: F401
     if not P:
         return np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.int64)
-    flat, offs = _pack(list(queries) + list(targets))
-    lens = np.diff(offs)
-    tab = _problem_table(offs[:P], lens[:P], offs[P:2 * P], lens[P:], rev)
-    if cpu:
-        return _sdtw_host(flat, flat, tab, P, _host_threads())
-    dev = _Device(flat, offs, device, extra=tab)
-    return _sdtw_device(dev, dev.samples_ptr, dev.samples_ptr, P)
+    B = Batch(list(queries) + list(targets), lambda offs: _problem_tables(offs[:P], np.diff(offs)[:P], offs[P:2 * P], np.diff(offs)[P:], rev),
+              cpu, device)
+    return _sdtw(B, P)
 
 
 def _anchors(a_list, b_list, norm: bool, cpu: bool, device: int, anchor: int, anchor_window: int, threads: int = None):
@@ -323,35 +184,15 @@ def _anchors(a_list, b_list, norm: bool, cpu: bool, device: int, anchor: int, an
     then ONE s2s_sdtw call of 2 P problems on the normalised pool -- problem p: the first La = min(anchor, n_a) samples of A inside
     the first Hb = min(anchor_window, n_b) of B; problem P + p: the last La of A inside the last Hb of B, reversed -- and one
     device-to-host copy.  -> (cost, start, end) int64 [2 P], start / end relative to the target's window, and Hb [P]."""
-    from ._lib import lib
-    L = lib()
     P = len(a_list)
-    flat, offs = _pack(list(a_list) + list(b_list))
-    lens = np.diff(offs)
-    na, nb = lens[:P], lens[P:]
-    la, hb = np.minimum(anchor, na), np.minimum(anchor_window, nb)
-    tab = _problem_table(np.concatenate([offs[:P], offs[:P] + na - la]), np.concatenate([la, la]),
-                         np.concatenate([offs[P:2 * P], offs[P:2 * P] + nb - hb]), np.concatenate([hb, hb]), [0] * P + [1] * P)
-    if cpu:
-        threads = threads or _host_threads()
-        q = flat
-        if norm:
-            med, mad, q = np.zeros(2 * P, np.int32), np.zeros(2 * P, np.int32), np.empty(len(flat), np.int16)
-            _check(L.s2s_signal_median_mad_host(flat.ctypes.data, offs.ctypes.data, 2 * P, med.ctypes.data, mad.ctypes.data, threads),
-                   "s2s_signal_median_mad_host")
-            _check(L.s2s_signal_normalise_host(flat.ctypes.data, offs.ctypes.data, 2 * P, med.ctypes.data, mad.ctypes.data, SCALE,
-                                               q.ctypes.data, threads), "s2s_signal_normalise_host")
-        return (*_sdtw_host(q, q, tab, 2 * P, threads), hb)
-    dev = _Device(flat, offs, device, extra=tab)
-    q_ptr = dev.samples_ptr
-    if norm:
-        t, _, med_p, mad_p = dev.down(0)
-        q = dev.scratch()
-        q_ptr = q.data_ptr()
-        _check(L.s2s_signal_median_mad(dev.device, dev.stream, dev.samples_ptr, dev.offs_ptr, 2 * P, med_p, mad_p), "s2s_signal_median_mad")
-        _check(L.s2s_signal_normalise(dev.device, dev.stream, dev.samples_ptr, dev.offs_ptr, 2 * P, med_p, mad_p, SCALE, q_ptr),
-               "s2s_signal_normalise")
-    return (*_sdtw_device(dev, q_ptr, q_ptr, 2 * P), hb)
+
+    def problems(offs):
+        na, nb = np.diff(offs)[:P], np.diff(offs)[P:]
+        la, hb = np.minimum(anchor, na), np.minimum(anchor_window, nb)
+        return _problem_tables(np.concatenate([offs[:P], offs[:P] + na - la]), np.concatenate([la, la]),
+                               np.concatenate([offs[P:2 * P], offs[P:2 * P] + nb - hb]), np.concatenate([hb, hb]), [0] * P + [1] * P)
+    B = Batch(list(a_list) + list(b_list), problems, cpu, device, threads)
+    return (*_sdtw(B, 2 * P, norm), B.tables[3][:P])        # (t_len of the head problems is Hb)
 
 
 def _check_path_memory(path_memory: int) -> int:
@@ -367,7 +208,7 @@ def dtw_path(a_list: Sequence[np.ndarray], b_list: Sequence[np.ndarray], band: i
     run in batches whose decision scratch stays within path_memory bytes; a single pair beyond it is a ValueError."""
     if len(a_list) != len(b_list):
         raise ValueError("a_list and b_list must pair up")
-    band = _check_band(band)
+    band = check_band(band)
     path_memory = _check_path_memory(path_memory)
     if not cpu:
         import torch  # noqa: F401
@@ -375,16 +216,11 @@ def dtw_path(a_list: Sequence[np.ndarray], b_list: Sequence[np.ndarray], band: i
     for p, nb in enumerate(need):
         if nb > path_memory:
             raise ValueError(f"pair {p}: the path needs {nb} bytes of decision scratch, more than path_memory = {path_memory}")
-    cost, ops, start, held = [np.zeros(0, np.int64)], [], 0, 0
-    for p in range(len(need) + 1):
-        if p == len(need) or (p > start and held + need[p] > path_memory):
-            if p > start:
-                c, _, _, o = _run_batch(a_list[start:p], b_list[start:p], band, False, cpu, device, path=True)
-                cost.append(c)
-                ops += o
-            start, held = p, 0
-        if p < len(need):
-            held += need[p]
+    cost, ops = [np.zeros(0, np.int64)], []
+    for run in batches(range(len(need)), lambda p: (need[p],), (path_memory,)):
+        c, _, _, o = _run_batch(a_list[run[0]:run[-1] + 1], b_list[run[0]:run[-1] + 1], band, False, cpu, device, path=True)
+        cost.append(c)
+        ops += o
     return np.concatenate(cost), ops
 
 
@@ -456,60 +292,18 @@ def transfer_events(rid: str, rows, g: np.ndarray, b: np.ndarray, digitisation: 
             dropped += 1
             continue
         S, Q = int(cs[e2] - cs[s2]), int(cq[e2] - cq[s2])
-        mean = (float(S) / n + offset) * signal_range / digitisation
-        stdv = math.sqrt(float(max(n * Q - S * S, 0))) / n * signal_range / digitisation
+        mean, stdv = event_level(S, Q, n, (digitisation, offset, signal_range))
         out.append(f"{rid}\t{pos}\t{kmer}\t{s2}\t{e2}\t{'%.4f' % mean}\t{'%.4f' % stdv}\n")
     return "".join(out), dropped
 
 
 # ------------------------------------------------------------------ files
-def _open_records(path: str) -> Iterable[dict]:
-    """-> iterator over the records of a .blow5 / .slow5 file of ours; anything else is a ClickException that names the file (the
-    file's extension, magic number and end marker are checked here, before anything is written)."""
-    from . import signal_io
-    path = str(path)
-    if path.endswith(".pod5"):
-        raise click.UsageError(f"{path}: compare reads .blow5 and .slow5 files; reading POD5 is not supported")
-    if not path.endswith((".blow5", ".slow5")):
-        raise click.UsageError(f"{path}: compare reads .blow5 and .slow5 files")
-    if not os.path.isfile(path):
-        raise click.ClickException(f"{path}: no such file")
-    if path.endswith(".slow5"):
-        try:
-            return iter(signal_io.read_slow5(path)[1])
-        except (ValueError, IndexError, UnicodeDecodeError) as e:
-            raise click.ClickException(f"{path}: not a SLOW5 file this project writes ({type(e).__name__}: {e})")
-    size = os.path.getsize(path)
-    with open(path, "rb") as f:
-        head = f.read(68)
-        f.seek(max(size - 5, 0))
-        tail = f.read(5)
-    if len(head) < 68 or head[:6] != b"BLOW5\x01":
-        raise click.ClickException(f"{path}: not a BLOW5 file (no BLOW5 magic number)")
-    if tail != signal_io.BLOW5Writer._EOF:
-        raise click.ClickException(f"{path}: truncated BLOW5 file (no end-of-file marker)")
-    if head[9] not in (0, 1, 2) or head[14] not in (0, 1):
-        raise click.ClickException(f"{path}: BLOW5 record / signal compression {head[9]} / {head[14]} is not one this project reads")
-
-    def records():
-        it = signal_io.iter_blow5(path)
-        try:
-            next(it)                                # the header text
-            yield from it
-        except Exception as e:                      # a damaged record: struct / zlib / codec errors, asserts of the reader
-            raise click.ClickException(f"{path}: damaged BLOW5 record ({type(e).__name__}: {e})")
-    return records()
-
-
 def _pairs(a_path: str, b_path: str, by_order: bool):
     """-> generator of (read_id, signal a, signal b, (digitisation, offset, range) of b's record), counters {"unpaired_a",
     "unpaired_b", "records_a", "records_b"} (filled while the generator runs).  By id: B is held in memory by read id, A streams;
     A's order."""
     counts = dict(records_a=0, records_b=0, unpaired_a=0, unpaired_b=0)
-    ia, ib = _open_records(a_path), _open_records(b_path)
-
-    def cal(r):
-        return float(r["digitisation"]), float(r["offset"]), float(r["range"])
+    ia, ib = open_records(a_path), open_records(b_path)
 
     def gen():
         if by_order:
@@ -522,12 +316,12 @@ def _pairs(a_path: str, b_path: str, by_order: bool):
                 if ra is None or rb is None:
                     counts["unpaired_a" if rb is None else "unpaired_b"] += 1
                     continue
-                yield ra["read_id"], np.asarray(ra["signal"], np.int16), np.asarray(rb["signal"], np.int16), cal(rb)
+                yield ra["read_id"], np.asarray(ra["signal"], np.int16), np.asarray(rb["signal"], np.int16), calibration(rb)
         else:
             b = {}
             for r in ib:
                 counts["records_b"] += 1
-                b.setdefault(r["read_id"], (np.array(r["signal"], np.int16), cal(r)))
+                b.setdefault(r["read_id"], (np.array(r["signal"], np.int16), calibration(r)))
             used = set()
             for r in ia:
                 counts["records_a"] += 1
@@ -579,7 +373,7 @@ def compare_files(a_path, b_path, out, band: int = DEFAULT_BAND, normalise: str 
         raise ValueError("max_samples must be >= 1")
     if not cpu:
         import torch  # noqa: F401  (before the library: see engine.py)
-    band = _check_band(band)
+    band = check_band(band)
     if open_ends:
         anchor, anchor_window = _check_anchor(anchor, anchor_window)
     events = read_events(str(events_a)) if events_a is not None else None
@@ -607,15 +401,11 @@ def compare_files(a_path, b_path, out, band: int = DEFAULT_BAND, normalise: str 
             P = len(al)
             need = [path_scratch_bytes(len(x), len(y), band) for x, y in zip(al, bl)]
             cost, med, mad, ops = np.zeros(P, np.int64), np.zeros(2 * P, np.int32), np.zeros(2 * P, np.int32), []
-            s, held = 0, 0
-            for p in range(P + 1):
-                if p == P or (p > s and held + need[p] > path_memory):
-                    c, md, dv, o = _run_batch(al[s:p], bl[s:p], band, normalise == "mad", cpu, device, path=True)
-                    cost[s:p], ops = c, ops + o
-                    med[s:p], med[P + s:P + p], mad[s:p], mad[P + s:P + p] = md[:p - s], md[p - s:], dv[:p - s], dv[p - s:]
-                    s, held = p, 0
-                if p < P:
-                    held += need[p]
+            for run in batches(range(P), lambda p: (need[p],), (path_memory,)):
+                s, p = run[0], run[-1] + 1
+                c, md, dv, o = _run_batch(al[s:p], bl[s:p], band, normalise == "mad", cpu, device, path=True)
+                cost[s:p], ops = c, ops + o
+                med[s:p], med[P + s:P + p], mad[s:p], mad[P + s:P + p] = md[:p - s], md[p - s:], dv[:p - s], dv[p - s:]
             return cost, med, mad, ops
 
         def flush(batch):
@@ -667,20 +457,15 @@ def compare_files(a_path, b_path, out, band: int = DEFAULT_BAND, normalise: str 
                     ev["dropped"] += dropped
                     ev["written"] += len(rows) - dropped
 
-        batch, held, held_path = [], 0, 0
-        for rid, a, b, cal in pairs:
+        def cost(pair):
+            rid, a, b, _ = pair
             if len(a) > MAX_SAMPLES or len(b) > MAX_SAMPLES:
                 raise click.ClickException(f"read {rid}: more than {MAX_SAMPLES} samples")
-            need = path_scratch_bytes(len(a), len(b), band) if want_path and not open_ends else 0
-            if batch and (held + len(a) + len(b) > max_samples or held_path + need > path_memory):
-                flush(batch)
-                batch, held, held_path = [], 0, 0
-            batch.append((rid, a, b, cal))
-            held += len(a) + len(b)
-            held_path += need
-            n_pairs += 1
-        if batch:
+            return len(a) + len(b), path_scratch_bytes(len(a), len(b), band) if want_path and not open_ends else 0
+
+        for batch in batches(pairs, cost, (max_samples, path_memory)):
             flush(batch)
+            n_pairs += len(batch)
     summary = dict(a=str(a_path), b=str(b_path), out=str(out), band=band, normalise=normalise, pairs=n_pairs,
                    records_a=counts["records_a"], records_b=counts["records_b"], unpaired_a=counts["unpaired_a"],
                    unpaired_b=counts["unpaired_b"],

@@ -4,11 +4,10 @@ written as the event table `predict --events` writes.  Everything that decides a
 include/s2s_hip.h next to s2s_resquiggle (tests/_resquiggle_ref.py restates it): samples and levels are median / MAD normalised by the
 entries `compare` uses, the alignment is the dynamic programme of csrc/s2s_resquiggle.h (one workgroup per read, then a walk back),
 the per-event sums are s2s_event_sums; `--cpu` runs the host twins of the same entries and gives the same bytes, as does any batching.
-Per batch of reads: one host-to-device copy (offsets, samples, levels), the kernels, two device-to-host copies (int64 and int32
-results); the rows are formatted on the host in Python.  The reference has no such command, and no f5c / uncalled4 was at hand: the
-output is unvalidated against them -- DESIGN.md section 6."""
+Per batch of reads (signal_batch.Batch): one host-to-device copy (offsets, slot tables, samples, levels) and the mask of k-mers
+without a level, the kernels, one device-to-host copy of all results; the rows are formatted on the host in Python.  The reference
+has no such command, and no f5c / uncalled4 was at hand: the output is unvalidated against them -- DESIGN.md section 6."""
 import logging
-import math
 import os
 import time
 from typing import Sequence
@@ -16,7 +15,9 @@ from typing import Sequence
 import click
 import numpy as np
 
-from . import compare as C
+from .compare import EVENT_COLUMNS
+from .signal_batch import (MAX_SAMPLES, SCALE, Batch, batches, calibration, check_band, device_only, event_level, max_band,
+                           open_records, sample_at, slots)
 
 logger = logging.getLogger("seq2squiggle")
 
@@ -30,7 +31,6 @@ MAX_UNKNOWN_COST = 65535
 DEFAULT_MAX_SAMPLES = 1 << 27    # samples per batch
 DEFAULT_TRACE_MEMORY = 8 << 30   # bytes of decision scratch per batch
 LEVEL_SCALE = 64                 # levels enter as integers of 1/64 pA
-EVENT_COLUMNS = C.EVENT_COLUMNS
 SUMMARY_COLUMNS = ("read_id", "n_samples", "n_kmers", "status", "cost", "cost_per_sample", "events", "skipped", "med", "mad",
                    "level_med", "level_mad", "start", "end")
 _CODE = np.full(256, -1, np.int64)
@@ -129,7 +129,7 @@ def read_intervals(path: str) -> dict:
 
 # ------------------------------------------------------------------ the solver
 def _check_params(band: int, skip_penalty: int, unknown_cost: int):
-    band, skip_penalty, unknown_cost = C._check_band(band), int(skip_penalty), int(unknown_cost)
+    band, skip_penalty, unknown_cost = check_band(band), int(skip_penalty), int(unknown_cost)
     if not 0 <= skip_penalty <= MAX_SKIP_PENALTY:
         raise ValueError(f"skip_penalty must be 0..{MAX_SKIP_PENALTY}")
     if not 0 <= unknown_cost <= MAX_UNKNOWN_COST:
@@ -142,12 +142,8 @@ def scratch_bytes(n: int, K: int, band: int) -> int:
     from ._lib import lib
     r = int(lib().s2s_resquiggle_scratch_bytes(int(n), int(K), int(band)))
     if r < 0:
-        raise ValueError(f"band must be 1..{C.max_band()}")
+        raise ValueError(f"band must be 1..{max_band()}")
     return r
-
-
-def _slots(need) -> np.ndarray:
-    return np.concatenate([[0], np.cumsum(need)]).astype(np.int64)
 
 
 def _run_batch(sig_list, lev_list, known_list, band: int, skip_penalty: int, unknown_cost: int, norm: bool, cpu: bool, device: int = 0,
@@ -156,74 +152,30 @@ def _run_batch(sig_list, lev_list, known_list, band: int, skip_penalty: int, unk
     norm: samples are normalised by their own median / MAD and the levels by the median / MAD of the read's KNOWN levels, both by
     s2s_signal_median_mad / s2s_signal_normalise at scale 64 (else both enter as they are); k-mers without a level get S2S_RSQ_UNKNOWN.
     -> dict(cost int64 [P], start / len int32 per read, S / Q int64 per read (raw samples), med / mad int32 [2 P]: samples, then levels)."""
-    from ._lib import lib
-    L = lib()
     P = len(sig_list)
     known_recs = [np.asarray(l, np.int16)[np.asarray(kn, bool)] for l, kn in zip(lev_list, known_list)]
     full_recs = [np.where(np.asarray(kn, bool), np.asarray(l, np.int16), np.int16(0)).astype(np.int16) for l, kn in zip(lev_list, known_list)]
-    flat, offs = C._pack(list(sig_list) + known_recs + full_recs)
-    lens = np.diff(offs)
-    n, K = lens[:P], lens[2 * P:]
-    l_offs = (offs[2 * P:] - offs[2 * P]).astype(np.int64)
-    KT, l0 = int(l_offs[-1]), int(offs[2 * P])
     unknown = ~np.concatenate([np.asarray(kn, bool).reshape(-1) for kn in known_list] + [np.zeros(0, bool)])
-    need = np.array([scratch_bytes(n[p], K[p], band) for p in range(P)], np.int64)
-    s_offs = _slots(need)
-    out64 = np.zeros(P + 2 * max(KT, 1), np.int64)                  # cost, S, Q
-    out32 = np.zeros(2 * max(KT, 1) + 4 * P, np.int32)              # start, len, med [2 P], mad [2 P]
-    kt = max(KT, 1)
-    if cpu:
-        threads = threads or C._host_threads()
-        med, mad = out32[2 * kt:2 * kt + 2 * P], out32[2 * kt + 2 * P:]
-        q = flat
-        if norm:
-            C._check(L.s2s_signal_median_mad_host(flat.ctypes.data, offs.ctypes.data, 2 * P, med.ctypes.data, mad.ctypes.data, threads),
-                     "s2s_signal_median_mad_host")
-            q = np.zeros(len(flat), np.int16)
-            C._check(L.s2s_signal_normalise_host(flat.ctypes.data, offs.ctypes.data, P, med.ctypes.data, mad.ctypes.data, C.SCALE,
-                                                 q.ctypes.data, threads), "s2s_signal_normalise_host")
-            C._check(L.s2s_signal_normalise_host(flat.ctypes.data, offs.ctypes.data + 16 * P, P, med.ctypes.data + 4 * P,
-                                                 mad.ctypes.data + 4 * P, C.SCALE, q.ctypes.data, threads), "s2s_signal_normalise_host")
-        else:
-            q = flat.copy()
-        q[l0:][unknown] = UNKNOWN
-        C._check(L.s2s_resquiggle_host(q.ctypes.data, offs.ctypes.data, q.ctypes.data + 2 * l0, l_offs.ctypes.data, P, band, skip_penalty,
-                                       unknown_cost, out64.ctypes.data, out32.ctypes.data, out32.ctypes.data + 4 * kt, threads),
-                 "s2s_resquiggle_host")
-        if sums:
-            C._check(L.s2s_event_sums_host(flat.ctypes.data, offs.ctypes.data, out32.ctypes.data, out32.ctypes.data + 4 * kt,
-                                           l_offs.ctypes.data, P, out64.ctypes.data + 8 * P, out64.ctypes.data + 8 * (P + kt), threads),
-                     "s2s_event_sums_host")
-    else:
-        extra = np.concatenate([l_offs, s_offs]).astype(np.int64).view(np.uint8)
-        dev = C._Device(flat, offs, device, extra=extra)
-        torch, where = dev.torch, f"cuda:{dev.device}"
-        d64 = torch.zeros(len(out64), dtype=torch.int64, device=where)
-        d32 = torch.zeros(len(out32), dtype=torch.int32, device=where)
-        p64, p32 = d64.data_ptr(), d32.data_ptr()
-        med_p, mad_p = p32 + 8 * kt, p32 + 8 * kt + 8 * P
-        if norm:
-            C._check(L.s2s_signal_median_mad(dev.device, dev.stream, dev.samples_ptr, dev.offs_ptr, 2 * P, med_p, mad_p), "s2s_signal_median_mad")
-            q = torch.zeros(max(dev.total, 1), dtype=torch.int16, device=where)
-            C._check(L.s2s_signal_normalise(dev.device, dev.stream, dev.samples_ptr, dev.offs_ptr, P, med_p, mad_p, C.SCALE, q.data_ptr()),
-                     "s2s_signal_normalise")
-            C._check(L.s2s_signal_normalise(dev.device, dev.stream, dev.samples_ptr, dev.offs_ptr + 16 * P, P, med_p + 4 * P, mad_p + 4 * P,
-                                            C.SCALE, q.data_ptr()), "s2s_signal_normalise")
-        else:
-            q = dev.up[dev.samples_ptr - dev.offs_ptr:].view(torch.int16).clone() if dev.total else torch.zeros(1, dtype=torch.int16, device=where)
-        if KT:                                          # the marker of a k-mer without a level (a fill, no arithmetic)
-            q[l0:l0 + KT].masked_fill_(torch.from_numpy(unknown).to(where), UNKNOWN)
-        scratch = torch.empty(max(int(s_offs[-1]), 16), dtype=torch.uint8, device=where)
-        q_ptr = q.data_ptr()
-        C._check(L.s2s_resquiggle(dev.device, dev.stream, q_ptr, dev.offs_ptr, q_ptr + 2 * l0, dev.extra_ptr, P, band, skip_penalty,
-                                  unknown_cost, p64, scratch.data_ptr(), dev.extra_ptr + 8 * (P + 1), p32, p32 + 4 * kt), "s2s_resquiggle")
-        if sums:
-            C._check(L.s2s_event_sums(dev.device, dev.stream, dev.samples_ptr, dev.offs_ptr, p32, p32 + 4 * kt, dev.extra_ptr, P,
-                                      p64 + 8 * P, p64 + 8 * (P + kt)), "s2s_event_sums")
-        out64, out32 = d64.cpu().numpy(), d32.cpu().numpy()
+
+    def tables(offs):
+        """The pool is 3 P records: samples, known levels, all levels -> l_offs int64 [P + 1]: the reads' slots of k-mers (the offsets
+        of the third part from its start); s_offs int64 [P + 1]: their slots of decision scratch (device only)."""
+        lens = np.diff(offs)
+        return (offs[2 * P:] - offs[2 * P]).astype(np.int64), slots([scratch_bytes(lens[p], lens[2 * P + p], band) for p in range(P)])
+    B = Batch(list(sig_list) + known_recs + full_recs, tables, cpu, device, threads)
+    l_offs, s_offs = B.tables
+    KT, l0 = int(l_offs[-1]), int(B.host_offs[2 * P])
+    res = B.alloc(cost=(np.int64, P), S=(np.int64, KT), Q=(np.int64, KT), start=(np.int32, KT), len=(np.int32, KT),
+                  med=(np.int32, 2 * P), mad=(np.int32, 2 * P))
+    q = B.normalised(res.ptr("med"), res.ptr("mad"), norm, halves=P)
+    q = B.marked(q, l0, unknown, UNKNOWN)               # the marker of a k-mer without a level
+    B.call("resquiggle", q, B.offs(), sample_at(q, l0), B.table(0), P, band, skip_penalty, unknown_cost, res.ptr("cost"),
+           B.scratch(s_offs[-1]), device_only(B.table(1)), res.ptr("start"), res.ptr("len"))
+    if sums:
+        B.call("event_sums", B.samples, B.offs(), res.ptr("start"), res.ptr("len"), B.table(0), P, res.ptr("S"), res.ptr("Q"))
+    r = res.fetch()
     cut = lambda a: [a[l_offs[p]:l_offs[p + 1]] for p in range(P)]      # noqa: E731
-    return dict(cost=out64[:P], start=cut(out32[:kt]), len=cut(out32[kt:2 * kt]), S=cut(out64[P:P + kt]), Q=cut(out64[P + kt:]),
-                med=out32[2 * kt:2 * kt + 2 * P], mad=out32[2 * kt + 2 * P:2 * kt + 4 * P])
+    return dict(cost=r["cost"], start=cut(r["start"]), len=cut(r["len"]), S=cut(r["S"]), Q=cut(r["Q"]), med=r["med"], mad=r["mad"])
 
 
 def resquiggle(samples: Sequence[np.ndarray], levels: Sequence[np.ndarray], band: int = DEFAULT_BAND,
@@ -241,61 +193,44 @@ def resquiggle(samples: Sequence[np.ndarray], levels: Sequence[np.ndarray], band
         raise ValueError("trace_memory must be >= 1")
     if not cpu:
         import torch  # noqa: F401  (before the library: see engine.py)
-    if any(np.size(l) > C.MAX_SAMPLES for l in levels):
-        raise ValueError(f"a read holds more than {C.MAX_SAMPLES} k-mers")
-    need = [scratch_bytes(min(np.size(s), C.MAX_SAMPLES), np.size(l), band) for s, l in zip(samples, levels)]
+    if any(np.size(l) > MAX_SAMPLES for l in levels):
+        raise ValueError(f"a read holds more than {MAX_SAMPLES} k-mers")
+    need = [scratch_bytes(min(np.size(s), MAX_SAMPLES), np.size(l), band) for s, l in zip(samples, levels)]
     for p, nb in enumerate(need):
         if nb > trace_memory:
             raise ValueError(f"read {p}: the walk back needs {nb} bytes of decision scratch, more than trace_memory = {trace_memory}")
-    cost, start, length, s0, held = [np.zeros(0, np.int64)], [], [], 0, 0
-    for p in range(len(need) + 1):
-        if p == len(need) or (p > s0 and held + need[p] > trace_memory):
-            if p > s0:
-                lev = [np.asarray(l, np.int16).reshape(-1) for l in levels[s0:p]]
-                r = _run_batch(samples[s0:p], lev, [l != UNKNOWN for l in lev], band, skip_penalty, unknown_cost, False, cpu, device, sums=False)
-                cost.append(r["cost"])
-                start += r["start"]
-                length += r["len"]
-            s0, held = p, 0
-        if p < len(need):
-            held += need[p]
+    cost, start, length = [np.zeros(0, np.int64)], [], []
+    for run in batches(range(len(need)), lambda p: (need[p],), (trace_memory,)):
+        lev = [np.asarray(l, np.int16).reshape(-1) for l in levels[run[0]:run[-1] + 1]]
+        r = _run_batch(samples[run[0]:run[-1] + 1], lev, [l != UNKNOWN for l in lev], band, skip_penalty, unknown_cost, False, cpu, device,
+                       sums=False)
+        cost.append(r["cost"])
+        start += r["start"]
+        length += r["len"]
     return np.concatenate(cost), start, length
 
 
 def event_sums(samples: Sequence[np.ndarray], start: Sequence[np.ndarray], length: Sequence[np.ndarray], cpu: bool = False, device: int = 0):
     """-> ([S int64 per read], [Q int64 per read]): sum and sum of squares of samples[p][start[j] : start[j] + length[j]) per k-mer
     (s2s_event_sums); 0, 0 for a skipped k-mer or an interval outside the record."""
-    from ._lib import lib
-    L = lib()
     P = len(samples)
-    flat, offs = C._pack(samples)
     st = [np.ascontiguousarray(x, np.int32).reshape(-1) for x in start]
     ln = [np.ascontiguousarray(x, np.int32).reshape(-1) for x in length]
-    l_offs = _slots([len(x) for x in st])
-    kt = max(int(l_offs[-1]), 1)
-    ev = np.zeros(2 * kt, np.int32)
-    ev[:l_offs[-1]] = np.concatenate(st + [np.zeros(0, np.int32)])
-    ev[kt:kt + l_offs[-1]] = np.concatenate(ln + [np.zeros(0, np.int32)])
-    out = np.zeros(2 * kt, np.int64)
-    if cpu:
-        C._check(L.s2s_event_sums_host(flat.ctypes.data, offs.ctypes.data, ev.ctypes.data, ev.ctypes.data + 4 * kt, l_offs.ctypes.data, P,
-                                       out.ctypes.data, out.ctypes.data + 8 * kt, C._host_threads()), "s2s_event_sums_host")
-    else:
-        import torch
-        dev = C._Device(flat, offs, device, extra=np.concatenate([l_offs, ev.view(np.int64)]).view(np.uint8))
-        d = torch.zeros(2 * kt, dtype=torch.int64, device=f"cuda:{dev.device}")
-        ev_p = dev.extra_ptr + 8 * (P + 1)
-        C._check(L.s2s_event_sums(dev.device, dev.stream, dev.samples_ptr, dev.offs_ptr, ev_p, ev_p + 4 * kt, dev.extra_ptr, P, d.data_ptr(),
-                                  d.data_ptr() + 8 * kt), "s2s_event_sums")
-        out = d.cpu().numpy()
-    return [out[l_offs[p]:l_offs[p + 1]] for p in range(P)], [out[kt + l_offs[p]:kt + l_offs[p + 1]] for p in range(P)]
+    l_offs = slots([len(x) for x in st])
+    ev = np.zeros((2, int(l_offs[-1])), np.int32)       # (as many lengths as starts, or a ValueError)
+    ev[0], ev[1] = np.concatenate(st + [np.zeros(0, np.int32)]), np.concatenate(ln + [np.zeros(0, np.int32)])
+    B = Batch(samples, (l_offs, ev[0], ev[1]), cpu, device)
+    res = B.alloc(S=(np.int64, l_offs[-1]), Q=(np.int64, l_offs[-1]))
+    B.call("event_sums", B.samples, B.offs(), B.table(1), B.table(2), B.table(0), P, res.ptr("S"), res.ptr("Q"))
+    r = res.fetch()
+    return [r["S"][l_offs[p]:l_offs[p + 1]] for p in range(P)], [r["Q"][l_offs[p]:l_offs[p + 1]] for p in range(P)]
 
 
 # ------------------------------------------------------------------ files
 def format_rows(rid: str, clean: str, k: int, start, length, S, Q, signal: np.ndarray, cal, rna: bool, shift: int, with_samples: bool) -> str:
     """The rows of one solved read, by position: one per k-mer with samples.  start / length / S / Q are in the order the solver saw the
     levels (back to front for RNA); `shift` is added to start_idx / end_idx (the record's own coordinates with --intervals).  Level and
-    deviation by the formulas of compare.transfer_events (include/s2s_hip.h, s2s_events_format), in double."""
+    deviation by signal_batch.event_level (include/s2s_hip.h, s2s_events_format), in double."""
     digitisation, offset, signal_range = cal
     K = len(start)
     order = range(K - 1, -1, -1) if rna else range(K)
@@ -306,8 +241,7 @@ def format_rows(rid: str, clean: str, k: int, start, length, S, Q, signal: np.nd
             continue
         pos = K - 1 - j if rna else j
         s, Sj, Qj = int(start[j]), int(S[j]), int(Q[j])
-        mean = (float(Sj) / n + offset) * signal_range / digitisation
-        stdv = math.sqrt(float(max(n * Qj - Sj * Sj, 0))) / n * signal_range / digitisation
+        mean, stdv = event_level(Sj, Qj, n, cal)
         row = f"{rid}\t{pos}\t{clean[pos:pos + k]}\t{s + shift}\t{s + n + shift}\t{'%.4f' % mean}\t{'%.4f' % stdv}"
         if with_samples:
             row += "\t" + ",".join("%.3f" % ((float(x) + offset) * signal_range / digitisation) for x in signal[s:s + n])
@@ -357,7 +291,7 @@ def resquiggle_files(seqs, signals, model, out, band: int = DEFAULT_BAND, skip_p
                            cpu, device)
             t1 = time.perf_counter()
             P = len(batch)
-            for p, (rid, clean, sig, _, _, cal, b0, b1, no) in enumerate(batch):
+            for p, (rid, clean, sig, _, _, cal, b0, b1, no, _) in enumerate(batch):
                 c, ln = int(r["cost"][p]), r["len"][p]
                 mm = (int(r["med"][p]), int(r["mad"][p]), int(r["med"][P + p]), int(r["mad"][P + p]))
                 if c < 0:
@@ -371,53 +305,50 @@ def resquiggle_files(seqs, signals, model, out, band: int = DEFAULT_BAND, skip_p
                 tot["cost"] += c
                 tot["samples"] += len(sig)
                 f.write(format_rows(rid, clean, k, r["start"][p], ln, r["S"][p], r["Q"][p], sig, cal, rna, b0, with_samples))
-                note(no, rid, len(sig), len(ln), "solved", b0, b1, c, "%.6f" % (c / len(sig) / C.SCALE), events, len(ln) - events, mm)
+                note(no, rid, len(sig), len(ln), "solved", b0, b1, c, "%.6f" % (c / len(sig) / SCALE), events, len(ln) - events, mm)
             tot["solve_s"] += t1 - t0
             tot["format_s"] += time.perf_counter() - t1
 
-        batch, held, held_scratch = [], 0, 0
-        for rec in C._open_records(str(signals)):
-            no = cnt["records"]
-            cnt["records"] += 1
-            rid, sig = rec["read_id"], np.asarray(rec["signal"], np.int16)
-            cal = (float(rec["digitisation"]), float(rec["offset"]), float(rec["range"]))
-            b0, b1 = 0, len(sig)
-            if iv is not None and rid in iv:
-                b0, b1 = max(0, min(iv[rid][0], len(sig))), max(0, min(iv[rid][1], len(sig)))
-                b1 = max(b0, b1)
-                sig = sig[b0:b1]
-            clean = sequences.get(rid)
-            codes = kmer_codes(clean, k) if clean is not None else np.zeros(0, np.int64)
-            if not len(codes):
-                cnt["no_sequence"] += 1
-                note(no, rid, len(sig), 0, "no_sequence", b0, b1)
-                continue
-            known = (codes >= 0) & has[np.maximum(codes, 0)]
-            lev = table[np.maximum(codes, 0)]
-            if rna:
-                known, lev = known[::-1], lev[::-1]
-            if not known.any():
-                cnt["no_known_level"] += 1
-                note(no, rid, len(sig), len(codes), "no_known_level", b0, b1)
-                continue
-            need = 0 if len(sig) > C.MAX_SAMPLES or len(codes) > C.MAX_SAMPLES else scratch_bytes(len(sig), len(codes), band)
-            if len(sig) > C.MAX_SAMPLES or len(codes) > C.MAX_SAMPLES or need > trace_memory:
-                cnt["refused"] += 1
-                logger.warning("resquiggle: read %s refused: %d samples against %d k-mers at band %d (limit %d each; %d bytes of decision "
-                               "scratch against --trace-memory %d)", rid, len(sig), len(codes), band, C.MAX_SAMPLES, need, trace_memory)
-                note(no, rid, len(sig), len(codes), "refused", b0, b1)
-                continue
-            if batch and (held + len(sig) > max_samples or held_scratch + need > trace_memory):
-                flush(batch)
-                batch, held, held_scratch = [], 0, 0
-            batch.append((rid, clean, sig, lev, known, cal, b0, b1, no))
-            held += len(sig)
-            held_scratch += need
-        if batch:
+        def reads():
+            """The records that go to the solver, as flush takes them; the others are counted and noted here."""
+            for rec in open_records(str(signals)):
+                no = cnt["records"]
+                cnt["records"] += 1
+                rid, sig = rec["read_id"], np.asarray(rec["signal"], np.int16)
+                cal = calibration(rec)
+                b0, b1 = 0, len(sig)
+                if iv is not None and rid in iv:
+                    b0, b1 = max(0, min(iv[rid][0], len(sig))), max(0, min(iv[rid][1], len(sig)))
+                    b1 = max(b0, b1)
+                    sig = sig[b0:b1]
+                clean = sequences.get(rid)
+                codes = kmer_codes(clean, k) if clean is not None else np.zeros(0, np.int64)
+                if not len(codes):
+                    cnt["no_sequence"] += 1
+                    note(no, rid, len(sig), 0, "no_sequence", b0, b1)
+                    continue
+                known = (codes >= 0) & has[np.maximum(codes, 0)]
+                lev = table[np.maximum(codes, 0)]
+                if rna:
+                    known, lev = known[::-1], lev[::-1]
+                if not known.any():
+                    cnt["no_known_level"] += 1
+                    note(no, rid, len(sig), len(codes), "no_known_level", b0, b1)
+                    continue
+                need = 0 if len(sig) > MAX_SAMPLES or len(codes) > MAX_SAMPLES else scratch_bytes(len(sig), len(codes), band)
+                if len(sig) > MAX_SAMPLES or len(codes) > MAX_SAMPLES or need > trace_memory:
+                    cnt["refused"] += 1
+                    logger.warning("resquiggle: read %s refused: %d samples against %d k-mers at band %d (limit %d each; %d bytes of decision "
+                                   "scratch against --trace-memory %d)", rid, len(sig), len(codes), band, MAX_SAMPLES, need, trace_memory)
+                    note(no, rid, len(sig), len(codes), "refused", b0, b1)
+                    continue
+                yield rid, clean, sig, lev, known, cal, b0, b1, no, need
+
+        for batch in batches(reads(), lambda b: (len(b[2]), b[9]), (max_samples, trace_memory)):
             flush(batch)
     s = dict(seqs=str(seqs), signals=str(signals), model=str(model), out=str(out), k=k, band=band, skip_penalty=skip_penalty,
              unknown_cost=unknown_cost, rna=bool(rna), **cnt,
-             mean_cost_per_sample=(tot["cost"] / tot["samples"] / C.SCALE) if tot["samples"] else None,
+             mean_cost_per_sample=(tot["cost"] / tot["samples"] / SCALE) if tot["samples"] else None,
              solve_seconds=tot["solve_s"], format_seconds=tot["format_s"])
     if summary_out is not None:
         s["summary_out"] = str(summary_out)

@@ -1,9 +1,9 @@
 """`segment SIGNALS -o OUT.events.tsv`: event detection -- every stored record cut into runs of constant level without its sequence, by
 two windowed t-statistics (a short and a long window) whose peaks are the event boundaries.  Everything that decides an output byte is
 an integer function stated in include/s2s_hip.h next to s2s_segment (tests/_segment_ref.py restates it); `--cpu` runs the host twin and
-gives the same bytes, as does any batching.  Per batch of records: one host-to-device copy (offsets, slots, samples), s2s_segment and
-s2s_event_sums on the same device buffers, one device-to-host copy; the rows are formatted by native host threads
-(s2s_segment_format).  The defaults 3 / 6 / 1.4 / 9.0 are the figures commonly quoted for scrappie's R9.4 DNA detector; here they are
+gives the same bytes, as does any batching.  Per batch of records (signal_batch.Batch): one host-to-device copy (offsets, slots,
+samples), s2s_segment and s2s_event_sums on the same device buffers, one device-to-host copy; the rows are formatted by native host
+threads (s2s_segment_format).  The defaults 3 / 6 / 1.4 / 9.0 are the figures commonly quoted for scrappie's R9.4 DNA detector; here they are
 choices, not measurements, and this detector is not scrappie's (no peak-height state machine).  Unvalidated against scrappie / f5c /
 uncalled4."""
 import logging
@@ -15,7 +15,7 @@ from typing import Sequence
 import click
 import numpy as np
 
-from . import compare as C
+from .signal_batch import MAX_SAMPLES, Batch, batches, calibration, host_threads, open_records, slots
 
 logger = logging.getLogger("seq2squiggle")
 
@@ -62,40 +62,22 @@ def _run_batch(sig_list, w_short: int, w_long: int, T_short: int, T_long: int, c
     """One batch of records -> dict(n_events int32 [R], ev_offs int64 [R + 1], start / len int32 [slots], S / Q int64 [slots]): record
     r's events in the slots ev_offs[r] .. ev_offs[r] + n_events[r]."""
     from ._lib import lib
-    L = lib()
     R = len(sig_list)
-    flat, offs = C._pack(sig_list)
-    total = int(offs[-1])
-    ev_offs = np.concatenate([[0], np.cumsum(capacity(np.diff(offs), w_short))]).astype(np.int64)
-    kt = max(int(ev_offs[-1]), 1)
-    nbytes = 24 * kt + 4 * max(R, 1)                      # S, Q int64 [kt]; start, len int32 [kt]; n_events int32 [R]
-    if cpu:
-        down = np.zeros(nbytes, np.uint8)
-        p = down.ctypes.data
-        rc = L.s2s_segment_host(flat.ctypes.data, offs.ctypes.data, R, total, w_short, w_long, T_short, T_long, ev_offs.ctypes.data,
-                                p + 16 * kt, p + 20 * kt, p + 24 * kt, threads or C._host_threads())
-        C._check(rc, "s2s_segment_host")
-        if sums:
-            C._check(L.s2s_event_sums_host(flat.ctypes.data, offs.ctypes.data, p + 16 * kt, p + 20 * kt, ev_offs.ctypes.data, R, p, p + 8 * kt,
-                                           threads or C._host_threads()), "s2s_event_sums_host")
-    else:
-        dev = C._Device(flat, offs, device, extra=ev_offs.view(np.uint8))
-        torch, where = dev.torch, f"cuda:{dev.device}"
-        d = torch.zeros(nbytes, dtype=torch.uint8, device=where)
-        need = int(L.s2s_segment_scratch_bytes(total, R))
+    B = Batch(sig_list, lambda offs: (slots(capacity(np.diff(offs), w_short)),), cpu, device, threads)
+    ev_offs = B.tables[0]
+    KT = int(ev_offs[-1])
+    res = B.alloc(S=(np.int64, KT), Q=(np.int64, KT), start=(np.int32, KT), len=(np.int32, KT), n_events=(np.int32, R))
+
+    def scratch_bytes():
+        need = int(lib().s2s_segment_scratch_bytes(B.total, R))
         if need < 0:
             raise ValueError("a batch holds more samples than s2s_segment takes")
-        scratch = torch.empty(max(need, 16), dtype=torch.uint8, device=where)
-        p = d.data_ptr()
-        C._check(L.s2s_segment(dev.device, dev.stream, dev.samples_ptr, dev.offs_ptr, R, total, w_short, w_long, T_short, T_long,
-                               scratch.data_ptr(), dev.extra_ptr, p + 16 * kt, p + 20 * kt, p + 24 * kt), "s2s_segment")
-        if sums:
-            C._check(L.s2s_event_sums(dev.device, dev.stream, dev.samples_ptr, dev.offs_ptr, p + 16 * kt, p + 20 * kt, dev.extra_ptr, R, p,
-                                      p + 8 * kt), "s2s_event_sums")
-        down = d.cpu().numpy()
-    return dict(ev_offs=ev_offs, S=down[:8 * kt].view(np.int64), Q=down[8 * kt:16 * kt].view(np.int64),
-                start=down[16 * kt:20 * kt].view(np.int32), len=down[20 * kt:24 * kt].view(np.int32),
-                n_events=down[24 * kt:24 * kt + 4 * R].view(np.int32))
+        return need
+    B.call("segment", B.samples, B.offs(), R, B.total, w_short, w_long, T_short, T_long, B.scratch(scratch_bytes), B.table(0),
+           res.ptr("start"), res.ptr("len"), res.ptr("n_events"))
+    if sums:
+        B.call("event_sums", B.samples, B.offs(), res.ptr("start"), res.ptr("len"), B.table(0), R, res.ptr("S"), res.ptr("Q"))
+    return dict(ev_offs=ev_offs, **res.fetch())
 
 
 def segment(samples: Sequence[np.ndarray], window_short: int = DEFAULT_WINDOW_SHORT, window_long: int = DEFAULT_WINDOW_LONG,
@@ -147,7 +129,7 @@ def segment_files(signals, out, window_short: int = DEFAULT_WINDOW_SHORT, window
         raise ValueError("max_samples must be >= 1")
     if not cpu:
         import torch  # noqa: F401  (before the library: see engine.py)
-    threads = C._host_threads()
+    threads = host_threads()
     cnt = dict(records=0, samples=0, events=0, refused=0, batches=0)
     tot = dict(solve_s=0.0, format_s=0.0)
     with open(out, "wb") as f, open(summary_out or os.devnull, "w") as fs:
@@ -172,23 +154,20 @@ def segment_files(signals, out, window_short: int = DEFAULT_WINDOW_SHORT, window
             tot["solve_s"] += t1 - t0
             tot["format_s"] += time.perf_counter() - t1
 
-        batch, held = [], 0
-        for rec in C._open_records(str(signals)):
-            cnt["records"] += 1
-            rid, sig = rec["read_id"], np.asarray(rec["signal"], np.int16)
-            cal = (float(rec["digitisation"]), float(rec["offset"]), float(rec["range"]))
-            if len(sig) > C.MAX_SAMPLES:
-                cnt["refused"] += 1
-                logger.warning("segment: record %s refused: %d samples (limit %d)", rid, len(sig), C.MAX_SAMPLES)
-                batch.append((rid, None, cal, len(sig)))
-                continue
-            if held and held + len(sig) > max_samples:
-                flush(batch)
-                batch, held = [], 0
-            batch.append((rid, sig, cal, len(sig)))
-            held += len(sig)
-            cnt["samples"] += len(sig)
-        if batch:
+        def records():
+            """(read id, samples or None for a refused record, calibration, stored length) of every record."""
+            for rec in open_records(str(signals)):
+                cnt["records"] += 1
+                rid, sig = rec["read_id"], np.asarray(rec["signal"], np.int16)
+                if len(sig) > MAX_SAMPLES:
+                    cnt["refused"] += 1
+                    logger.warning("segment: record %s refused: %d samples (limit %d)", rid, len(sig), MAX_SAMPLES)
+                    yield rid, None, calibration(rec), len(sig)
+                    continue
+                cnt["samples"] += len(sig)
+                yield rid, sig, calibration(rec), len(sig)
+
+        for batch in batches(records(), lambda b: (0 if b[1] is None else b[3],), (max_samples,)):    # (a refused record costs nothing)
             flush(batch)
     s = dict(signals=str(signals), out=str(out), window_short=w_s, window_long=w_l, threshold_short=float(threshold_short),
              threshold_long=float(threshold_long), T_short=T_s, T_long=T_l, **cnt,

@@ -1,15 +1,29 @@
-"""Build-time guard: every PRODUCTION instance of the predict kernel (s2s_fused_kernel<MODE, TEST = false, EXACT>)
-must compile without scratch memory or spilled vector registers -- round 4's key interleave pushed the exact instance to 32 B of
-scratch per lane and 7 spills without anybody noticing until a review ran the compiler with remarks on.  hipcc cross-compiles
-for gfx950 without a GPU (about 35 s)."""
+"""Build-time guards on the compiler's kernel-resource-usage remarks, one test per family of kernels; the library is compiled ONCE for
+all of them (the module-scoped `usage`): hipcc cross-compiles for gfx950 without a GPU (about 35 s).
+- The predict kernel: every PRODUCTION instance (s2s_fused_kernel<MODE, TEST = false, EXACT>) must compile without
+  scratch memory or spilled vector registers -- round 4's key interleave pushed the exact instance to 32 B of scratch per lane and 7
+  spills without anybody noticing until a review ran the compiler with remarks on.
+- The kernel of `compare --open-ends` (s2s_sdtw_kernel, csrc/s2s_sdtw.h): no scratch memory, no spilled registers, and the static LDS
+  include/s2s_hip.h states -- 57,904 B, so that two workgroups share a CU's 160 KB.
+- The kernels of `resquiggle` (csrc/s2s_resquiggle.h): no scratch memory, no spilled registers, and the LDS include/s2s_hip.h states --
+  none of it static: the sweep's LDS is dynamic, 1024 c + 2 (64 c + 128) bytes for c = ceil((2 band + 1) / 64) word pairs per row,
+  which the header gives for bands 512 and 1024 and the host entry pins with a static_assert.
+- The kernels of `segment` (csrc/s2s_segment.h): no scratch memory, no spilled registers, and the LDS include/s2s_hip.h states for the
+  flag pass -- static, pinned by a static_assert next to the kernel."""
 import os
 import re
+
+import pytest
 
 from seq2squiggle_amd import _build
 
 
-def test_production_kernel_instances_have_no_scratch(tmp_path):
-    usage = _build.compile_to(str(tmp_path / "libcheck.so"), report=True)
+@pytest.fixture(scope="module")
+def usage(tmp_path_factory):
+    return _build.compile_to(str(tmp_path_factory.mktemp("build_resources") / "libcheck.so"), report=True)
+
+
+def test_production_kernel_instances_have_no_scratch(usage):
     fused = {k: v for k, v in usage.items() if "s2s_fused_kernel" in k}
     # _Z16s2s_fused_kernelILi<MODE>ELb<TEST>ELb<EXACT>EE...
     inst = {}
@@ -28,3 +42,60 @@ def test_production_kernel_instances_have_no_scratch(tmp_path):
     for name, u in usage.items():
         if "s2s_fused_kernel" not in name:
             assert u["ScratchSize [bytes/lane]"] == 0 and u["VGPRs Spill"] == 0, (name, u)
+
+
+def test_sdtw_kernel_has_no_scratch_and_the_stated_lds(usage):
+    mine = {k: v for k, v in usage.items() if "s2s_sdtw_kernel" in k}
+    assert len(mine) == 1, sorted(usage)
+    (u,) = mine.values()
+    assert u["ScratchSize [bytes/lane]"] == 0 and u["VGPRs Spill"] == 0 and u["SGPRs Spill"] == 0, u
+    assert u["LDS Size [bytes/block]"] == 3 * (2048 + 2) * 8 + 2048 * 2 + (2048 + 256) * 2 == 57904, u
+    assert u["VGPRs"] <= 64, u                      # 1024 threads are four waves per SIMD; the LDS admits two such workgroups per CU:
+                                                    # eight waves per SIMD share its 512 registers
+
+
+def test_resquiggle_kernels_have_no_scratch_and_the_stated_lds(usage):
+    KERNELS = ("s2s_resquiggle_kernel", "s2s_resquiggle_trace_kernel", "s2s_event_sums_kernel")
+
+    def lds_bytes(band):
+        c = -(-(2 * band + 1) // 64)
+        return 2 * 64 * c * 8 + (64 * c + 128) * 2
+
+    for name in KERNELS:
+        mine = {k: v for k, v in usage.items() if name in k}
+        assert len(mine) == 1, (name, sorted(usage))
+        (u,) = mine.values()
+        assert u["ScratchSize [bytes/lane]"] == 0 and u["VGPRs Spill"] == 0 and u["SGPRs Spill"] == 0, (name, u)
+        assert u["LDS Size [bytes/block]"] == 0, (name, u)          # no static LDS: the sweep asks for S2S_RSQ_LDS_BYTES(band) at launch
+    sweep = next(v for k, v in usage.items() if KERNELS[0] in k)
+    assert sweep["VGPRs"] <= 128, sweep                             # 1024 threads are four waves per SIMD: 512 / 4 registers each
+    header = open(os.path.join(os.path.dirname(_build.HERE), "include", "s2s_hip.h")).read()
+    hip = open(_build.SRC).read()
+    assert lds_bytes(1024) == 38272 and lds_bytes(512) == 19840
+    assert "38,272 B at S2S_DTW_MAX_BAND, 19,840 B at band 512" in header
+    assert re.search(r"static_assert\(S2S_RSQ_LDS_BYTES\(S2S_DTW_MAX_BAND\) == 38272 && S2S_RSQ_LDS_BYTES\(512\) == 19840", hip)
+    assert lds_bytes(1024) <= 65536                                 # what one workgroup may ask for
+
+
+def test_segment_kernels_have_no_scratch_and_the_stated_lds(usage):
+    KERNELS = ("s2s_segment_flags_kernel", "s2s_segment_scan_kernel", "s2s_segment_compact_kernel")
+    TILE, MAX_WINDOW = 2048, 32
+
+    def lds_bytes():
+        ext = TILE + 2 * 3 * MAX_WINDOW                  # the tile and a halo of max(2 w_l, 3 w_s) on each side
+        return 2 * ext * 8 + (TILE // 64) * 8 + ext * (2 + 1 + 1 + 1)
+
+    lds = {}
+    for name in KERNELS:
+        mine = {k: v for k, v in usage.items() if name in k}
+        assert len(mine) == 1, (name, sorted(usage))
+        (u,) = mine.values()
+        assert u["ScratchSize [bytes/lane]"] == 0 and u["VGPRs Spill"] == 0 and u["SGPRs Spill"] == 0, (name, u)
+        lds[name] = u["LDS Size [bytes/block]"]
+    assert lds_bytes() == 47296 <= 65536              # what one workgroup may ask for
+    assert lds[KERNELS[0]] == lds_bytes() and lds[KERNELS[1]] == 16 * 8 and lds[KERNELS[2]] == 0, lds
+    header = open(os.path.join(os.path.dirname(_build.HERE), "include", "s2s_hip.h")).read()
+    seg = open(os.path.join(_build.HERE, "csrc", "s2s_segment.h")).read()
+    assert "S2S_SEG_LDS_BYTES\n *                 = 47,296 B" in header and "#define S2S_SEG_TILE 2048" in header
+    assert re.search(r"#define S2S_SEG_LDS_BYTES 47296", seg)
+    assert re.search(r"static_assert\(sizeof\(S2SSegLds\) == S2S_SEG_LDS_BYTES && S2S_SEG_LDS_BYTES <= 65536", seg)

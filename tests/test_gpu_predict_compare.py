@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from seq2squiggle_amd import compare as CMP
+from seq2squiggle_amd import signal_batch as SB
 from seq2squiggle_amd import utils as U
 from _events_ref import parse_events
 from test_gpu_events import _run
@@ -45,7 +46,7 @@ def test_compare_of_a_predicted_file_with_itself(run, other):
         outs[mode] = tuple(open(n, "rb").read() for n in names)
     assert outs["gpu"] == outs["cpu"]
     s = sums["gpu"]
-    recs_a, recs_b = list(CMP._open_records(a)), {r["read_id"]: r for r in CMP._open_records(b)}
+    recs_a, recs_b = list(SB.open_records(a)), {r["read_id"]: r for r in SB.open_records(b)}
     assert s["pairs"] == len(recs_a) == len(recs_b) >= 10 and (s["unpaired_a"], s["unpaired_b"]) == (0, 0)
     assert s["events_dropped"] == 0 == s["events_unpaired"] and s["events_written"] > 100
     assert all(np.array_equal(r["signal"], recs_b[r["read_id"]]["signal"]) for r in recs_a)            # the same samples thrice

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from seq2squiggle_amd import compare as CMP
+from seq2squiggle_amd import signal_batch as SB
 from seq2squiggle_amd import resquiggle as RSQ
 from seq2squiggle_amd import utils as U
 from test_gpu_kmer_model import CKPT, LAMBDA, PROFILE, SEED
@@ -48,7 +49,7 @@ def test_gpu_bytes_equal_cpu_bytes(run):
 def test_rows_match_the_fasta_and_partition_each_record(run):
     d, gpu, _ = run
     seqs = {name: RSQ.clean_sequence(seq) for seq, name in U.read_fasta(str(d / "reads.fasta"))}
-    lengths = {r["read_id"]: len(r["signal"]) for r in CMP._open_records(str(d / "p.blow5"))}
+    lengths = {r["read_id"]: len(r["signal"]) for r in SB.open_records(str(d / "p.blow5"))}
     table = CMP.read_events(str(d / "gpu.tsv"))
     assert len(table) == gpu["solved"] and sum(len(v) for v in table.values()) == gpu["events"]
     for rid, rows in table.items():
@@ -65,7 +66,7 @@ def test_measure_the_share_of_samples_on_their_true_kmer(run):
     d, gpu, _ = run
     truth, got = CMP.read_events(str(d / "truth.tsv")), CMP.read_events(str(d / "gpu.tsv"))
     seqs = {name: seq for seq, name in U.read_fasta(str(d / "reads.fasta"))}
-    lengths = {r["read_id"]: len(r["signal"]) for r in CMP._open_records(str(d / "p.blow5"))}
+    lengths = {r["read_id"]: len(r["signal"]) for r in SB.open_records(str(d / "p.blow5"))}
     total = hit = ruler = 0
     for rid, rows in truth.items():
         if rid not in got:

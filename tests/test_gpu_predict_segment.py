@@ -10,6 +10,7 @@ import pytest
 
 import _segment_ref as REF
 from seq2squiggle_amd import compare as CMP
+from seq2squiggle_amd import signal_batch as SB
 from seq2squiggle_amd import segment as SEG
 from seq2squiggle_amd import utils as U
 from test_gpu_kmer_model import CKPT, LAMBDA, PROFILE, SEED
@@ -32,7 +33,7 @@ def run(tmp_path_factory):
                   min_noise=0.0, min_duration=3, min_read_len=30, preserve_read_ids=True, seed=SEED, events=str(d / "truth.tsv"),
                   events_samples=False, kmer_table=None, kmer_model=None)
     records = [(r["read_id"], np.asarray(r["signal"], np.int16), (float(r["digitisation"]), float(r["offset"]), float(r["range"])))
-               for r in CMP._open_records(str(d / "p.blow5"))]
+               for r in SB.open_records(str(d / "p.blow5"))]
     lens = [len(x) for _, x, _ in records]
 
     def batches(m):                                  # the batching rule of segment_files

@@ -13,6 +13,7 @@ from _dtw_ref import ref_median_mad, ref_normalise
 from _events_ref import parse_events
 from seq2squiggle_amd import _lib, cli, kmer_model
 from seq2squiggle_amd import compare as CMP
+from seq2squiggle_amd import signal_batch as SB
 from seq2squiggle_amd import resquiggle as RSQ
 from test_compare_cpu import write_file
 
@@ -203,7 +204,7 @@ def files(tmp_path_factory):
     sigs = [reads[i][1] for i in reads] + [np.arange(50, dtype=np.int16)]
     blow5 = write_file(d / "s.blow5", ids, sigs, record_compression="zlib")
     slow5 = write_file(d / "s.slow5", ids, sigs)
-    rec = next(iter(CMP._open_records(blow5)))
+    rec = next(iter(SB.open_records(blow5)))
     cal = (float(rec["digitisation"]), float(rec["offset"]), float(rec["range"]))
     (d / "m.model").write_bytes(bytes(kmer_model.format_model(model_counts(adc), K3, cal[0], cal[2], cal[1])))
     (d / "r.fasta").write_text("".join(f">{i} comment\n{reads[i][0][:30]}\n{reads[i][0][30:]}\n" for i in reads))

@@ -210,10 +210,10 @@ def run(*args):
 
 
 def test_cli_cpu_writes_the_restatements_bytes_whatever_the_batching(files):
-    from seq2squiggle_amd import compare as CMP
+    from seq2squiggle_amd import signal_batch as SB
     d, ids, sigs, paths = files
     for path in paths:
-        recs = list(CMP._open_records(path))
+        recs = list(SB.open_records(path))
         assert [r["read_id"] for r in recs] == ids
         records = [(r["read_id"], np.asarray(r["signal"], np.int16), (float(r["digitisation"]), float(r["offset"]), float(r["range"])))
                    for r in recs]
@@ -254,3 +254,26 @@ def test_every_new_symbol_resolves_with_the_stated_signature():
         assert name in _lib.EXPORTS
         fn = getattr(L, name)
         assert fn.restype is res and list(fn.argtypes) == args, name
+
+
+def test_refused_record_behind_a_lone_record_beyond_max_samples(tmp_path, monkeypatch):
+    """The budget loop's corner: a record beyond --max-samples on its own, then a refused one, then two that share a batch.  The refused
+    record costs nothing and ends no batch with a sample in it: rows and counters are those of one batch for everything -- but for
+    `batches`, 2: the lone record's, then the rest."""
+    monkeypatch.setattr(SEG, "MAX_SAMPLES", 1000)                   # (a refused record never reaches the solver, whose limit stays)
+    sigs = [noisy(50, 900), noisy(51, 1001), noisy(52, 300), noisy(53, 300)]
+    ids = [f"read_{i}" for i in range(len(sigs))]
+    path = write_file(tmp_path / "s.blow5", ids, sigs)
+    got = {}
+    for max_samples in (1 << 27, 700):
+        d = tmp_path / str(max_samples)
+        d.mkdir()
+        got[max_samples] = (SEG.segment_files(path, d / "o.tsv", cpu=True, summary_out=d / "s.tsv", max_samples=max_samples),
+                            (d / "o.tsv").read_bytes(), (d / "s.tsv").read_text())
+    (one, rows1, sum1), (split, rows2, sum2) = got[1 << 27], got[700]
+    assert rows1 == rows2 and sum1 == sum2 and b"read_1\t" not in rows1 and b"read_0\t" in rows1 and b"read_3\t" in rows1
+    assert sum1.splitlines()[2] == "read_1\t1001\t0"
+    assert (one["batches"], split["batches"]) == (1, 2)
+    for key in ("records", "samples", "events", "refused", "mean_samples_per_event"):
+        assert one[key] == split[key], key
+    assert one["records"] == 4 and one["refused"] == 1 and one["samples"] == 1500

@@ -81,11 +81,75 @@ def check_invariants(q, l, R, skip_penalty, unknown_cost, cost, start, length):
 
 SMALL = [(1, 1, 1), (5, 1, 1), (1, 2, 1), (2, 3, 2), (3, 7, 4), (7, 7, 1), (64, 64, 1), (65, 9, 1), (300, 40, 1), (300, 40, 3),
          (300, 290, 8), (200, 260, 16), (129, 64, 31), (129, 64, 32), (500, 70, 32), (1000, 200, 96),
-         (100, 199, 31), (150, 299, 63)]     # K = 2 n - 1 past a ring of exactly 2 R + 2 slots: a slot's old column is active a row before its new one
+         (100, 199, 31), (150, 299, 63)]     # K = 2 n - 1 past a ring of exactly 2 R + 2 slots: a slot's old column is active TWO rows before its new one (one row: K = 2 n, band_shapes)
 LARGE = [(5000, 3, 1), (5000, 600, 31), (5000, 600, 32), (4097, 2100, 512), (3000, 2900, 1024), (2500, 4000, 1024), (20000, 1, 1024)]
 EXTREME = (70000, 6000, 64)                             # samples 32767 against levels -32767: the cost passes 2^32
 KINDS = ("planted", "noisy", "zeros", "unknown")
 SKIP, UNK = 128, 64
+
+
+MAX_WAVES = 16
+
+
+def chunks(R):
+    """Word pairs of a decision row (csrc/s2s_resquiggle.h): 64 slots each, ring = 64 chunks > 2 R + 1."""
+    return (2 * R + 1 + 63) // 64
+
+
+def per_wave(R):
+    """The chunks are dealt out evenly over at most 16 waves: ceil(chunks / 16) to a wave."""
+    return -(-chunks(R) // MAX_WAVES)
+
+
+def waves(R):
+    return -(-chunks(R) // per_wave(R))
+
+
+# the smallest and the largest band of every chunk count 1 .. 33; the largest one has the tightest ring, 64 c == 2 R + 2
+BANDS_BY_CHUNKS = [1, 31] + [R for c in range(2, 33) for R in (32 * (c - 1), 32 * c - 1)] + [1024]
+
+
+def band_shapes(R):
+    """-> [(n, K, kind)] of a band.  K = ring + 200 < n: the level window and the slots both wrap.  K = 2 n - 1 past the ring: the row's
+    window moves by two columns, a slot's old column is active one row before its new one -- `zeros` as well: there every row but the
+    first must skip and a skip is the only cost.  K = 2 n: i K mod n is 0 in every row, so a row holds all 2 R + 1 columns and its
+    window moves by two -- with ring == 2 R + 2 the only case in which a slot's old column, jlo(i - 1), is active one row before its
+    new one, jhi(i) = jlo(i - 1) + ring (at K = 2 n - 1 a row holds 2 R columns and the two are never a row apart).  No path covers
+    2 n columns in n rows, so the answer is `unreached`; a value left over from the old column would make it a cost."""
+    ring = 64 * chunks(R)
+    K1, n2 = ring + 200, ring // 2 + 120
+    return [(K1 + 150, K1, "planted"), (K1 + 150, K1, "noisy"), (n2, 2 * n2 - 1, "noisy"), (n2, 2 * n2 - 1, "unknown"),
+            (n2, 2 * n2 - 1, "zeros"), (n2, 2 * n2, "noisy"), (n2, 2 * n2, "zeros")]
+
+
+# (n, K, R) at which pressed() is solved along both edges of the band (tests/test_resquiggle_cpu.py asserts it on the host twin)
+PRESSED_SMALL = [(7, 7, 1), (64, 64, 1), (65, 9, 1), (300, 40, 1), (300, 40, 3), (300, 290, 8), (200, 260, 16)]     # held to solve()
+PRESSED = PRESSED_SMALL + [(5000, 600, 31), (5000, 600, 32), (4097, 2100, 512), (2600, 2400, 480), (2600, 2400, 511),
+                           (4400, 4200, 992), (4400, 4200, 1023), (4400, 4200, 1024)]
+
+
+def pressed(n, K, R):
+    """-> (q, l) whose optimum is pressed against both edges of the band: noisy levels and samples, but the first third of the samples
+    is exactly the first level and the last third exactly the last one, both far from every other level.  The path stays on k-mer 0 as
+    long as the band lets it (the cells with jlo = ceil(i K / n) - R) and reaches k-mer K - 1 as soon as the band lets it (jhi =
+    floor(i K / n) + R, then the clamp at K - 1).  Not one of KINDS: case() seeds by KINDS.index."""
+    rng = np.random.default_rng([n, K, R, len(KINDS)])
+    lev = rng.integers(-300, 300, K).astype(np.int16)
+    lev[0], lev[K - 1] = 3000, -3000
+    j = np.minimum(np.arange(n) * K // n, K - 1)
+    q = (lev[j].astype(np.int64) + rng.integers(-40, 41, n)).astype(np.int16)
+    q[:n // 3], q[n - n // 3:] = lev[0], lev[K - 1]
+    return q, lev
+
+
+def edge_contact(n, K, R, start, length):
+    """-> (lower, upper): has the path a cell with i K - j n > (R - 1) n (no room for one more row on column j: the lower edge), and
+    one with i K - j n < -(R - 1) n (the upper edge)?"""
+    length = np.asarray(length, np.int64)
+    j = np.repeat(np.arange(K, dtype=np.int64), length)
+    d = np.arange(n, dtype=np.int64) * K - j * n
+    assert len(j) == n
+    return bool((d > (R - 1) * n).any()), bool((d < -(R - 1) * n).any())
 
 
 def planted(n, K, R, rng):

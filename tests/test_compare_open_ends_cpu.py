@@ -71,6 +71,19 @@ def test_host_equals_the_restatement(kind, L, H):
         assert 0 <= s < e <= H and 0 <= cost <= L * 65535
 
 
+@pytest.mark.parametrize("kind", KINDS)
+def test_host_equals_the_restatement_at_1025_by_300(kind):
+    """The smallest query that gives some threads of s2s_sdtw_kernel two rows and the others one, against a target shorter than the
+    workgroup is wide (the restatement takes 0.2 s per direction here); tests/test_gpu_compare_open_ends.py holds the kernel to this."""
+    L, H = 1025, 300
+    q, t = make(kind, L, H)
+    for rev in (False, True):
+        want = ref_of(kind, L, H, rev)
+        assert host(q, t, rev) == want, rev
+        cost, s, e = want
+        assert 0 <= s < e <= H and 0 <= cost <= L * 65535
+
+
 def test_known_answers():
     # all-zero inputs: the first column forward, the last one reversed
     for L, H in ((1, 1), (5, 9), (64, 300)):

@@ -15,6 +15,10 @@ pytestmark = pytest.mark.gpu
 
 # held to the host twin only: one stride per thread and more, the largest query, a one-sample target, many window refills
 LARGE = [(256, 256), (257, 1000), (1024, 3000), (2048, 2500), (2048, 1), (16, 70000)]
+# between one and two rows per thread (1,024 threads): some threads own two rows (the unrolled pair loop) and the others one (the tail
+# cell) -- a query of 1,025 and of 2,047 samples, the middle -- against targets of one sample, shorter than the workgroup is wide (r
+# rotates), around a multiple of 256 and of several window refills
+BETWEEN = [(1025, 300), (1025, 3000), (1536, 255), (1536, 257), (2047, 1), (2047, 1023), (2047, 2500)]
 
 
 def triple(r):
@@ -42,6 +46,7 @@ def problems():
     """[(q, t, reverse)]: every small shape and kind in both directions, the large shapes in one direction per kind."""
     probs = [(*make(k, L, H), rev) for k in KINDS for L, H in SHAPES for rev in (False, True)]
     probs += [(*make(k, L, H), bool((i + n) % 2)) for i, k in enumerate(KINDS) for n, (L, H) in enumerate(LARGE)]
+    probs += [(*make(k, L, H), bool((i + n) % 2)) for i, k in enumerate(KINDS) for n, (L, H) in enumerate(BETWEEN)]
     host = CMP.sdtw([p[0] for p in probs], [p[1] for p in probs], reverse=[p[2] for p in probs], cpu=True)
     return probs, triple(host)
 
@@ -62,11 +67,20 @@ def test_every_shape_alone(problems):
 
 
 def test_large_shapes_in_the_other_direction():
-    for i, k in enumerate(KINDS):
-        for n, (L, H) in enumerate(LARGE):
-            q, t = make(k, L, H)
-            rev = not bool((i + n) % 2)
-            assert triple(CMP.sdtw([q], [t], reverse=rev)) == triple(CMP.sdtw([q], [t], reverse=rev, cpu=True)), (k, L, H)
+    for shapes in (LARGE, BETWEEN):
+        for i, k in enumerate(KINDS):
+            for n, (L, H) in enumerate(shapes):
+                q, t = make(k, L, H)
+                rev = not bool((i + n) % 2)
+                assert triple(CMP.sdtw([q], [t], reverse=rev)) == triple(CMP.sdtw([q], [t], reverse=rev, cpu=True)), (k, L, H)
+
+
+def test_a_query_of_1025_samples_against_the_restatement():
+    """(1025, 300) in both directions against the restatement itself (tests/test_compare_open_ends_cpu.py holds the host entry to it)."""
+    for k in KINDS:
+        q, t = make(k, 1025, 300)
+        for rev in (False, True):
+            assert triple(CMP.sdtw([q], [t], reverse=rev)) == [ref_of(k, 1025, 300, rev)], (k, rev)
 
 
 def test_known_answers():

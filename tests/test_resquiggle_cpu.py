@@ -134,6 +134,109 @@ def test_python_entry_and_event_sums():
             assert S[p][j] == (x[s:s + n].sum() if ok else 0) and Q[p][j] == ((x[s:s + n] ** 2).sum() if ok else 0)
 
 
+# ------------------------------------------------------------------ every dealing of chunks to waves, both band edges
+def test_bands_by_chunks_cover_every_dealing_of_chunks_to_waves():
+    """The restatement of s2s_rsq_chunks / s2s_rsq_waves (the header's comment, no C): the 65 listed bands produce every (chunks, chunks
+    per wave, waves) that the bands 1 .. 1024 produce, the 16-wave workgroups at one and at two chunks per wave among them."""
+    R = REF.BANDS_BY_CHUNKS
+    assert R == sorted(set(R)) and len(R) == 65 and R[:4] == [1, 31, 32, 63] and R[-3:] == [992, 1023, 1024]
+    deal = lambda band: (REF.chunks(band), REF.per_wave(band), REF.waves(band))      # noqa: E731
+    every = {deal(band) for band in range(1, 1025)}
+    assert {deal(band) for band in R} == every and len(every) == 33
+    assert {(16, 1, 16), (32, 2, 16), (33, 3, 11), (17, 2, 9), (4, 1, 4)} <= every
+    assert sorted({d[0] for d in every}) == list(range(1, 34))                       # every chunk count 1 .. 33
+    assert [band for band in range(1, 1025) if deal(band)[2] == 16] == list(range(480, 512)) + list(range(960, 1024))
+    for c in range(1, 33):                           # the largest band of a count has the tightest ring: 64 c == 2 R + 2
+        assert 64 * REF.chunks(32 * c - 1) == 2 * (32 * c - 1) + 2 and REF.chunks(32 * c) == c + 1
+    L = _lib.lib()                                   # what the library states of the layout: 16 bytes per chunk and sample
+    assert [L.s2s_resquiggle_scratch_bytes(10, 5, band) for band in R] == [10 * 16 * REF.chunks(band) for band in R]
+
+
+@pytest.mark.parametrize("R", REF.BANDS_BY_CHUNKS)
+def test_host_twin_at_the_bands_of_every_chunk_count(R):
+    """The shapes of REF.band_shapes in their kinds: the invariants of a solved read at every band, the planted path exactly, `unreached`
+    at K = 2 n, and the full-matrix restatement up to three chunks (measured: up to 2 s for a band of three chunks, and more for
+    each band beyond)."""
+    for n, K, kind in REF.band_shapes(R):
+        q, l, plant = REF.case(n, K, R, kind)
+        rc, c, st, ln = host([(q, l)], R)
+        if K == 2 * n:                               # 2 n columns in n rows: no path, whatever the band
+            assert rc == 0 and int(c[0]) == REF.UNREACHED and set(st[0].tolist()) == {-1} and set(ln[0].tolist()) == {0}
+            assert REF.chunks(R) > 3 or REF.solve(q, l, R, REF.SKIP, REF.UNK)[0] == REF.UNREACHED
+            continue
+        assert rc == 0 and int(c[0]) >= 0
+        REF.check_invariants(q, l, R, REF.SKIP, REF.UNK, int(c[0]), st[0], ln[0])
+        if kind == "planted":
+            assert plant is not None and int(c[0]) == 0 and (st[0] == plant[0]).all() and (ln[0] == plant[1]).all()
+        if K > n:
+            assert (ln[0] == 0).sum() >= K - n       # K = 2 n - 1: all but one column in two is skipped
+        if kind == "zeros":
+            assert K == 2 * n - 1 and int(c[0]) == (n - 1) * REF.SKIP      # every row but the first skips, and nothing else costs
+        if REF.chunks(R) <= 3:
+            assert (int(c[0]), st[0].tolist(), ln[0].tolist()) == REF.solve(q, l, R, REF.SKIP, REF.UNK)
+
+
+@pytest.mark.parametrize("n,K,R", REF.PRESSED)
+def test_pressed_path_runs_along_both_edges_of_the_band(n, K, R):
+    q, l = REF.pressed(n, K, R)
+    rc, c, st, ln = host([(q, l)], R)
+    assert rc == 0 and int(c[0]) >= 0
+    REF.check_invariants(q, l, R, REF.SKIP, REF.UNK, int(c[0]), st[0], ln[0])
+    assert REF.edge_contact(n, K, R, st[0], ln[0]) == (True, True)      # a condition of the case: a shape without it is not listed
+    if (n, K, R) in REF.PRESSED_SMALL:
+        assert (int(c[0]), st[0].tolist(), ln[0].tolist()) == REF.solve(q, l, R, REF.SKIP, REF.UNK)
+
+
+def test_pressed_needs_a_band_narrower_than_a_third_of_the_kmers():
+    """Where K < 3 R or so the band holds the lag of a third of the samples and no edge is touched: why PRESSED has K >= 4 R."""
+    for n, K, R in ((129, 64, 31), (1000, 200, 96), (3000, 2900, 1024)):
+        rc, c, st, ln = host([REF.pressed(n, K, R)], R)
+        assert rc == 0 and REF.edge_contact(n, K, R, st[0], ln[0]) == (False, False)
+    assert all(K >= 4 * R for _, K, R in REF.PRESSED)
+
+
+def event_sum_case():
+    """-> (records, start, length, want): reads of 127, 128, 129, 1,025 and 0 k-mers and one of 131 whose samples are all -32768 -- past
+    one stride of 128 k-mers of s2s_event_sums_kernel, with odd offsets of the samples and of the k-mers.  The lengths cycle through
+    1, 15, 16, 17, 31, 32, 33 and 4,097 (one stride of a quarter wave, one less, one more, two, many); some intervals at indices >= 128
+    are skipped k-mers or lie outside their record.  want: (S, Q) per k-mer in numpy int64, (0, 0) for what counts as empty."""
+    rng = np.random.default_rng(12)
+    cycle = np.array([1, 15, 16, 17, 31, 32, 33, 4097], np.int32)
+    recs, start, length = [], [], []
+    for p, K in enumerate((127, 128, 129, 1025, 0)):
+        ln = cycle[(np.arange(K) + p) % 8]
+        st = np.concatenate([[0], np.cumsum(ln)[:-1]]).astype(np.int32) if K else np.zeros(0, np.int32)
+        n = int(ln.sum()) + 1 + p
+        recs.append(rng.integers(-32768, 32768, n).astype(np.int16))
+        st, ln = st.copy(), ln.copy()
+        if K > 128:
+            st[128], ln[128] = -1, 0                # a skipped k-mer in the second trip
+        if K > 200:
+            st[130], ln[130] = n - 5, 6             # one sample past the record's end
+            st[200], ln[200] = -3, 4                # begins in front of it
+            st[640], ln[640] = 7, 0
+            st[1024], ln[1024] = n - 4097, 4097     # the record's last samples, exactly
+        start.append(st)
+        length.append(ln)
+    assert (np.cumsum([len(x) for x in recs]) % 2 == 1).sum() >= 2      # reads that begin at an odd offset of the pool
+    recs.append(np.full(40_001, -32768, np.int16))   # |S| = 30,000 * 2^15, Q = 30,000 * 2^30 > 2^44
+    start.append(np.concatenate([np.arange(129) * 50, [6450, 36_450]]).astype(np.int32))
+    length.append(np.concatenate([np.full(129, 50), [30_000, 3_551]]).astype(np.int32))
+    want = []
+    for x, st, ln in zip(recs, start, length):
+        x = x.astype(np.int64)
+        ok = (st >= 0) & (ln > 0) & (st.astype(np.int64) + ln <= len(x))
+        want.append([(int(x[s:s + n].sum()), int((x[s:s + n] ** 2).sum())) if o else (0, 0) for s, n, o in zip(st.tolist(), ln.tolist(), ok)])
+    assert want[5][129] == (-32768 * 30_000, 30_000 << 30) and want[3][130] == (0, 0) and want[3][1024] != (0, 0)
+    return recs, start, length, want
+
+
+def test_event_sums_host_past_128_kmers_against_numpy():
+    recs, start, length, want = event_sum_case()
+    S, Q = RSQ.event_sums(recs, start, length, cpu=True)
+    assert [list(zip(s.tolist(), q.tolist())) for s, q in zip(S, Q)] == want
+
+
 # ------------------------------------------------------------------ the model reader
 K3 = 3
 

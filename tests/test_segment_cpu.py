@@ -171,6 +171,76 @@ def test_one_and_sixteen_threads_agree():
     assert [s.tolist() for s in st] == a[2] and [l.tolist() for l in ln] == a[3]
 
 
+# ------------------------------------------------------------------ pools of more than 1,024 tiles (s2s_segment_scan_kernel's step)
+TILE, SCAN_STEP = 2048, 1024
+
+
+def three_step_pool():
+    """2,051 tiles, boundaries in every tile of the long record: three steps of the scan, every wave's count and the carry non-zero."""
+    return [noisy(1, 1 << 22), noisy(2, 5000)]
+
+
+def tiled_pool(total, seed=60):
+    """`total` pooled samples: noisy records of 3,001 samples and one that makes up the remainder; every record but the first begins
+    off a tile border (3,001 is odd, 2,048 a power of two: k * 3,001 is no multiple of 2,048 for 0 < k < 2,048)."""
+    m = total // 3001
+    recs = squiggles(seed, [3001] * m + [total - 3001 * m])
+    assert m < TILE and sum(len(r) for r in recs) == total
+    return recs
+
+
+def silent_pool(variant):
+    """Noisy records up to tile 1,000, one record of 100 * 2,048 + 5 samples across the tiles 1,000 .. 1,100, noisy records to past tile
+    1,100.  `one`: the record is constant -- one event, no flag in the tiles around 1,024.  `cut`: the constant record cut in two at the
+    pooled offset 1,024 * 2,048 exactly.  `step`: constant but for one step of 3,000 in tile 1,030 -- the search for the next flag crosses
+    thirty empty tiles and the border of the scan's step.  -> (records, the index of the (first) silent record)."""
+    m = -(-1000 * TILE // 3001)
+    front, back = squiggles(61, [3001] * m), squiggles(62, [3001] * 20)
+    at, n = 3001 * m, 100 * TILE + 5
+    assert at // TILE == 1000 and (at + n - 1) // TILE == 1100 and at % TILE
+    flat = np.full(n, -7, np.int16)
+    if variant == "cut":
+        mid = [flat[:SCAN_STEP * TILE - at], flat[SCAN_STEP * TILE - at:]]
+    elif variant == "step":
+        flat[1030 * TILE + 77 - at:] = 2993
+        mid = [flat]
+    else:
+        mid = [flat]
+    return front + mid + back, m
+
+
+def test_three_scan_steps_host_reference_has_boundaries_in_every_tile():
+    recs = three_step_pool()
+    assert -(-sum(len(r) for r in recs) // TILE) == 2051
+    a, b = host(recs, 3, 6, *T_DEFAULT, threads=1), host(recs, 3, 6, *T_DEFAULT, threads=16)
+    assert a[0] == b[0] == 0 and a[1:4] == b[1:4]
+    per_tile = np.bincount(np.asarray(a[2][0][1:]) // TILE, minlength=2048)           # (without the record's start)
+    assert len(per_tile) == 2048 and per_tile.min() >= 1      # what makes the case meaningful (measured: 261 .. 299 a tile)
+    for r, x in enumerate(recs):
+        REF.check_consequences(len(x), a[2][r], a[3][r], 3)
+    es, el = REF.events(recs[1], 3, 6, *T_DEFAULT)
+    assert (a[2][1], a[3][1]) == (es, el)
+
+
+@pytest.mark.parametrize("variant", ("one", "cut", "step"))
+def test_silent_stretch_across_tile_1024_keeps_the_consequences(variant):
+    recs, k = silent_pool(variant)
+    rc, ne, st, ln, _, _ = host(recs, 3, 6, *T_DEFAULT, threads=16)
+    assert rc == 0 and -(-sum(len(r) for r in recs) // TILE) > 1100
+    for r, x in enumerate(recs):
+        REF.check_consequences(len(x), st[r], ln[r], 3)
+    if variant == "one":
+        assert (st[k], ln[k]) == ([0], [100 * TILE + 5])
+    elif variant == "cut":
+        assert (st[k], ln[k], st[k + 1]) == ([0], [len(recs[k])], [0]) and ln[k + 1] == [len(recs[k + 1])]
+        assert sum(len(r) for r in recs[:k + 1]) == SCAN_STEP * TILE and len(recs[k]) + len(recs[k + 1]) == 100 * TILE + 5
+    else:
+        at = 1030 * TILE + 77 - 3001 * k
+        assert st[k] == [0, at] and ln[k] == [at, 100 * TILE + 5 - at]
+    for r in (0, k - 1, k + 1 if variant != "cut" else k + 2, len(recs) - 1):       # the restatement on the neighbours
+        assert (st[r], ln[r]) == REF.events(recs[r], 3, 6, *T_DEFAULT)
+
+
 def test_formatter_rounds_a_huge_event_once_and_refuses_what_it_must():
     L = _lib.lib()
     n = 300000

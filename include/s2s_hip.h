@@ -834,6 +834,94 @@ int64_t s2s_segment_format(const int32_t* ev_start, const int32_t* ev_len, const
                            const int32_t* n_events, int32_t R, const uint8_t* ids, const int64_t* id_offs, const double* cal,
                            int32_t with_header, int32_t threads, uint8_t* out, int64_t capacity);
 
+/* ---- `eventalign`: which detected events of an UNTRIMMED stored signal belong to which k-mer of its sequence -- the events of
+ * s2s_segment, their means normalised by the entries of `compare`, aligned to the normalised levels inside a narrow band that follows
+ * the path (the adaptive band of Suzuki and Kasahara, as nanopolish and f5c use it), with free ends that cost a trim penalty per
+ * event.  In integers, with the conventions of the entries above (no handle, `device` and `stream`, stream-ordered, device pointers,
+ * int64 offs, S2S_OK / S2S_ERR_ARG / S2S_ERR_HIP).  The reference has no such command.  Unvalidated against f5c / nanopolish /
+ * uncalled4.
+ *
+ * Event means: event e of record r, with S_e the sum of s2s_event_sums and n_e = ev_len, has the mean
+ *   x_e = round-half-even(S_e / n_e) as int16 (a sum of n int16 values divided by n fits; any other S is clamped to int16, and an
+ *   event with n_e < 1 has mean 0).  Record r contributes c_r = n_events[r] means when 0 < n_events[r] <= ev_offs[r+1] - ev_offs[r]
+ *   and ev_offs[r] >= 0, else none (n_events 0, -k and S2S_DTW_COST_TOO_LONG give none).  The means lie back to back, events in
+ *   order: m_offs[0] = 0, m_offs[r+1] = m_offs[r] + c_r, mean e of record r at m_offs[r] + e -- the layout s2s_signal_median_mad
+ *   and s2s_signal_normalise take.
+ *
+ * Alignment, per read: m[0 .. E) the normalised int16 event means, l[0 .. K) the normalised int16 levels (S2S_RSQ_UNKNOWN marks a
+ * k-mer without a level, as for s2s_resquiggle), the events' (ev_start, ev_len) in the slot layout of s2s_segment.  Parameters: band
+ * width W, a multiple of 64 in 64 .. S2S_EVA_MAX_WIDTH = 1024; skip_penalty 0 .. S2S_RSQ_MAX_SKIP_PENALTY and trim_penalty 0 ..
+ * S2S_EVA_MAX_TRIM_PENALTY, both 2^20; unknown_cost 0 .. S2S_RSQ_MAX_UNKNOWN_COST; E, K <= S2S_DTW_MAX_SAMPLES.
+ *   cost(e, j) = |m[e] - l[j]|, or unknown_cost when l[j] == S2S_RSQ_UNKNOWN.
+ *   D(e, j): the best cost of a path that has consumed the events up to e and the k-mers up to j.  Event e belongs to k-mer j iff
+ *   the path enters (e, j) by diag, stay or start.  The candidates, tried in this order, strict '<' keeps the earlier one:
+ *     diag   D(e - 1, j - 1) + cost(e, j)      j >= 1
+ *     stay   D(e - 1, j) + cost(e, j)
+ *     skip   D(e, j - 1) + skip_penalty        j >= 1; no cell cost: k-mer j gets no event from this move
+ *     start  e trim_penalty + cost(e, j)       j = 0 only: the events 0 .. e - 1 are trimmed
+ *   Only predecessors that were inside their own band and are reached count; a cell without a candidate is unreached.
+ *   The band: band b, b = 0 .. E + K - 2, holds the W cells o = 0 .. W - 1 with k-mer j = lk(b) + o and event e = b - j; cells
+ *   outside the matrix are unreached.  lk(0) = -W / 2, so (0, 0) is cell W / 2 of band 0.  For b >= 1 let ll = D of cell 0 and ur = D
+ *   of cell W - 1 of band b - 1, unreached counting as +infinity: if both are unreached the band moves right iff b is odd, else it
+ *   moves right iff ll > ur (a tie between reached cells moves down).  Right: lk(b) = lk(b - 1) + 1, r_b = 1; down: lk(b) = lk(b - 1),
+ *   r_b = 0.  Seen from cell o of band b, stay is cell o + r_b and skip cell o + r_b - 1 of band b - 1, diag cell o + r_b + r_(b-1) - 1
+ *   of band b - 2: three rolling bands suffice and every shift is the same for the whole band.
+ *   Result: over all reached cells (e, K - 1) that lie in their band, the smallest D(e, K - 1) + (E - 1 - e) trim_penalty, on a tie
+ *   the smallest e; cost is int64.  E = 0 or K = 0: S2S_DTW_COST_EMPTY.  E or K above S2S_DTW_MAX_SAMPLES: S2S_DTW_COST_TOO_LONG --
+ *   the device does no work for it and leaves its outputs but cost untouched; the host twin returns S2S_ERR_ARG before it computes
+ *   anything.  No such reached cell: S2S_RSQ_UNREACHED.
+ *   Walk back: from that cell along the stored 2-bit decisions until a start; at most E + K steps whatever the scratch holds.
+ *   Outputs: first_event and end_event per read (0, 0 without a path); per event, at m_offs[p] + e, its k-mer, or -1 when trimmed;
+ *   per k-mer, at l_offs[p] + j: k_start = ev_start of its first event, k_len = ev_start + ev_len of its last event - k_start (the
+ *   samples of its events: the events of s2s_segment are consecutive and abut), k_events = how many events it got.  A skipped k-mer
+ *   gets -1 / 0 / 0, and so does every k-mer of an unsolved read, whose events all get -1.
+ * A solved read: the events first_event .. end_event - 1 are all assigned and no other is; the assigned k-mer indices never fall;
+ *   the first assigned event is on k-mer 0; the unskipped k-mers' intervals abut; cost = the sum of cost(e, kmer(e)) +
+ *   skip_penalty (K - distinct assigned k-mers) + trim_penalty (first_event + E - end_event).  (A k-mer entered by skip never gets
+ *   an event: stay out of such a cell would have to beat diag out of the same predecessor, which is tried first and costs no more.)
+ *
+ *  s2s_event_means  S, ev_len, ev_offs, n_events as s2s_segment and s2s_event_sums leave them; m_offs int64 [R + 1] and means int16
+ *                 out.  capacity: the int16 values `means` holds, by value; the sum of the slots, ev_offs[R] - ev_offs[0], always
+ *                 suffices; a record whose means would end beyond it writes none (the host twin: S2S_ERR_ARG).  Two launches
+ *                 (csrc/s2s_eventalign.h): one workgroup scans the counts, in strides of 1,024 with a carry when R exceeds the
+ *                 workgroup; then a fill, record r to the workgroups (r, 0 .. 7).  No atomics, nothing waits between workgroups.
+ *                 R = 0 writes m_offs[0] = 0.
+ *  s2s_eventalign_scratch_bytes  host function: (E + K - 1) (16 W / 64 + 4) rounded up to 16 -- per band W / 64 16-byte word pairs
+ *                 (2 bits per cell: bit 0 of 64 codes, then bit 1) and, behind all of them, one int32 lk; 0 for a read without a
+ *                 solution by its lengths; S2S_ERR_ARG for a width outside the limits.  It grows with E, so a slot sized by
+ *                 s2s_segment_capacity holds whatever s2s_segment finds.
+ *  s2s_eventalign read p = m[m_offs[p] .. m_offs[p+1]) against l[l_offs[p] .. l_offs[p+1]), its events in the slots from ev_offs[p]
+ *                 on; cost int64 [P], first_event, end_event int32 [P], ev_kmer int32 at m_offs[p] + e, k_start, k_len, k_events
+ *                 int32 at l_offs[p] + j out.  scratch: 16-byte aligned; read p owns scratch[scratch_offs[p] .. scratch_offs[p+1])
+ *                 (int64 [P + 1], every offset a multiple of 16).  A read whose slot is too small or misaligned, or whose slot of
+ *                 events is smaller than E, gets its cost and no path, and nothing is ever written outside a slot.  Two kernels:
+ *                 one workgroup of W threads per read sweeps the bands, one barrier each, with three rolling bands of int64 in LDS;
+ *                 a thread keeps its own m[e] and l[j] and reads only the one that changed, from windows staged every 256 bands;
+ *                 per 64 cells two wave ballots and one 16-byte store, per band one int32 lk; every thread keeps its best final
+ *                 candidate and one reduction picks the result.  Then one wave per read walks back.  Every loop bound is a function
+ *                 of E, K and W; no atomics, nothing spins or waits between workgroups.  Width or penalties outside the limits:
+ *                 S2S_ERR_ARG, nothing is launched.  Dynamic LDS: 3 (W + 2) 8 + 2 (W + 256) 2 bytes: 29,744 B at W = 1024, 4,656 B
+ *                 at W = 128.
+ *  s2s_event_means_host, s2s_eventalign_host   the same on host pointers, in plain C++ (`eventalign --cpu`; the definition the
+ *                 kernels must equal bit for bit): records / reads dealt out over `threads` >= 1 host threads; no scratch
+ *                 argument.  S2S_ERR_ARG as above, and for a read longer than the limits, offsets that decrease or are negative,
+ *                 and a slot of events smaller than E. */
+#define S2S_EVA_MAX_WIDTH 1024
+#define S2S_EVA_MAX_TRIM_PENALTY (1 << 20)
+int64_t s2s_eventalign_scratch_bytes(int64_t E, int64_t K, int32_t width);
+int s2s_event_means(int device, void* stream, const int64_t* S, const int32_t* ev_len, const int64_t* ev_offs, const int32_t* n_events,
+                    int32_t R, int64_t capacity, int64_t* m_offs, int16_t* means);
+int s2s_eventalign(int device, void* stream, const int16_t* m, const int64_t* m_offs, const int16_t* l, const int64_t* l_offs,
+                   const int32_t* ev_start, const int32_t* ev_len, const int64_t* ev_offs, int32_t P, int32_t width, int32_t skip_penalty,
+                   int32_t trim_penalty, int32_t unknown_cost, int64_t* cost, uint8_t* scratch, const int64_t* scratch_offs,
+                   int32_t* first_event, int32_t* end_event, int32_t* ev_kmer, int32_t* k_start, int32_t* k_len, int32_t* k_events);
+int s2s_event_means_host(const int64_t* S, const int32_t* ev_len, const int64_t* ev_offs, const int32_t* n_events, int32_t R,
+                         int64_t capacity, int64_t* m_offs, int16_t* means, int32_t threads);
+int s2s_eventalign_host(const int16_t* m, const int64_t* m_offs, const int16_t* l, const int64_t* l_offs, const int32_t* ev_start,
+                        const int32_t* ev_len, const int64_t* ev_offs, int32_t P, int32_t width, int32_t skip_penalty,
+                        int32_t trim_penalty, int32_t unknown_cost, int64_t* cost, int32_t* first_event, int32_t* end_event,
+                        int32_t* ev_kmer, int32_t* k_start, int32_t* k_len, int32_t* k_events, int32_t threads);
+
 /* ---- host-side helper (no GPU work, no handle): replays the DRAWS of the reference's read sampler (utils.py:415-479
  * `sampling`, with the read-length law of utils.py:325-331 `draw_expon_dis`) without building a read, so that a rank of a sharded
  * run finds the generator state of its first read in microseconds per thousand reads instead of replaying them in the

@@ -719,5 +719,82 @@ def segment(signals, out, window_short, window_long, threshold_short, threshold_
                    f"mean samples per event {per}")
 
 
+@main.command()
+@click.argument("seqs", type=click.Path(dir_okay=False, exists=True))
+@click.argument("signals", type=click.Path(dir_okay=False))
+@click.option("--kmer-model", "model", required=True, type=click.Path(dir_okay=False, exists=True),
+              help="Pore model: the file `predict --kmer-model` writes, or a nanopolish-style table with the columns kmer and level_mean.")
+@click.option("-o", "--out", required=True, type=click.Path(dir_okay=False), help="Output event table (.events.tsv).")
+@click.option("--samples", "with_samples", is_flag=True, help="Add the `samples` column: every row's samples in pA.")
+@click.option("--band-width", default=128, type=int, show_default=True,
+              help="Cells of the adaptive band, a multiple of 64 in 64..1024.  A choice, not a measurement.")
+@click.option("--skip-penalty", default=128, type=int, show_default=True,
+              help="Cost of a k-mer that gets no event, in 1/64 MAD.  The default, two MADs, is a choice, not a measurement.")
+@click.option("--trim-penalty", default=64, type=int, show_default=True,
+              help="Cost of an event trimmed at either end, in 1/64 MAD.  The default, one MAD, is a choice, not a measurement.")
+@click.option("--unknown-cost", default=64, type=int, show_default=True,
+              help="Cost per event on a k-mer the model has no level for (or with a letter outside ACGT), in 1/64 MAD.  The default, "
+                   "one MAD, is a choice, not a measurement.")
+@click.option("--rna", is_flag=True, help="The stored signal is reversed (RNA profiles): read the levels back to front; position stays in "
+                                          "read coordinates and start_idx falls as it rises, as in predict --events.")
+@click.option("--window-short", default=3, type=int, show_default=True, help="Window of the short event detector in samples (1..32).")
+@click.option("--window-long", default=6, type=int, show_default=True, help="Window of the long event detector in samples (short..32).")
+@click.option("--threshold-short", default=1.4, type=float, show_default=True, help="Threshold t of the short detector (see segment).")
+@click.option("--threshold-long", default=9.0, type=float, show_default=True, help="Threshold t of the long detector (see segment).")
+@click.option("--cpu", is_flag=True, help="Compute on host threads instead of the GPU (the same bytes).")
+@click.option("--json", "as_json", is_flag=True, help="Print the summary as one JSON object.")
+@click.option("--summary", "summary_out", default=None, type=click.Path(dir_okay=False), help="Also write one row per read here (.tsv).")
+@click.option("--max-samples", default=1 << 27, type=int, show_default=True, help="Samples per batch.")
+@click.option("--trace-memory", default=8 << 30, type=int, show_default=True,
+              help="Bytes of decision scratch per batch, counted by the most events a record can have; a read that may need more on its "
+                   "own is refused by its id.")
+def eventalign(seqs, signals, model, out, with_samples, band_width, skip_penalty, trim_penalty, unknown_cost, rna, window_short,
+               window_long, threshold_short, threshold_long, cpu, as_json, summary_out, max_samples, trace_memory):
+    """Align the detected events of every UNTRIMMED record of a .blow5 / .slow5 file to the levels a pore model expects for the k-mers
+    of its sequence (SEQS: FASTA or FASTQ, record names = read ids) and write the event table predict --events writes, one row per
+    k-mer that got events.  Events come from the detector of `segment`; their means are median / MAD normalised over the whole record;
+    the alignment runs in an adaptive band with free ends, so adapter, stall and trailing samples are trimmed.  Exact integers;
+    unvalidated against f5c / nanopolish / uncalled4.  Junk beyond half of a record's events defeats the normalisation."""
+    _signal_files("eventalign", signals)
+    if max_samples < 1:
+        raise click.BadParameter("must be >= 1", param_hint="--max-samples")
+    if trace_memory < 1:
+        raise click.BadParameter("must be >= 1", param_hint="--trace-memory")
+    import json
+    if not cpu:
+        import torch  # noqa: F401  (before the library: see engine.py)
+    from . import eventalign as EA, segment as SEG
+    if not 64 <= band_width <= EA.MAX_WIDTH or band_width % 64:
+        raise click.BadParameter(f"must be a multiple of 64 in 64..{EA.MAX_WIDTH}", param_hint="--band-width")
+    if not 0 <= skip_penalty <= EA.MAX_SKIP_PENALTY:
+        raise click.BadParameter(f"must be 0..{EA.MAX_SKIP_PENALTY}", param_hint="--skip-penalty")
+    if not 0 <= trim_penalty <= EA.MAX_TRIM_PENALTY:
+        raise click.BadParameter(f"must be 0..{EA.MAX_TRIM_PENALTY}", param_hint="--trim-penalty")
+    if not 0 <= unknown_cost <= EA.MAX_UNKNOWN_COST:
+        raise click.BadParameter(f"must be 0..{EA.MAX_UNKNOWN_COST}", param_hint="--unknown-cost")
+    if not 1 <= window_short <= SEG.MAX_WINDOW:
+        raise click.BadParameter(f"must be 1..{SEG.MAX_WINDOW}", param_hint="--window-short")
+    if not window_short <= window_long <= SEG.MAX_WINDOW:
+        raise click.BadParameter(f"must be --window-short..{SEG.MAX_WINDOW}", param_hint="--window-long")
+    for hint, t in (("--threshold-short", threshold_short), ("--threshold-long", threshold_long)):
+        try:
+            SEG.threshold_int(t)
+        except ValueError as e:
+            raise click.BadParameter(str(e), param_hint=hint)
+    s = EA.eventalign_files(seqs, signals, model, out, band_width=band_width, skip_penalty=skip_penalty, trim_penalty=trim_penalty,
+                            unknown_cost=unknown_cost, rna=rna, window_short=window_short, window_long=window_long,
+                            threshold_short=threshold_short, threshold_long=threshold_long, with_samples=with_samples, cpu=cpu,
+                            summary_out=summary_out, max_samples=max_samples, trace_memory=trace_memory)
+    if as_json:
+        click.echo(json.dumps(s))
+    else:
+        per = "nan" if s["mean_cost_per_event"] is None else f"{s['mean_cost_per_event']:.4f}"
+        click.echo(f"{s['events']} rows of {s['solved']} reads -> {out}  [k {s['k']}, band width {band_width}, skip penalty {skip_penalty}, "
+                   f"trim penalty {trim_penalty}, unknown cost {unknown_cost}; of {s['records']} records {s['unreached']} unreached, "
+                   f"{s['refused']} refused, {s['no_sequence']} without a sequence, {s['no_known_level']} without a known level; "
+                   f"{s['aligned_events']} aligned events, {s['skipped_kmers']} skipped k-mers; {s['trimmed_head_samples']} / "
+                   f"{s['trimmed_tail_samples']} samples trimmed at head / tail]  mean cost per aligned event {per} MAD")
+
+
 if __name__ == "__main__":
     main()

@@ -19,6 +19,7 @@
 #include "s2s_sdtw.h"
 #include "s2s_resquiggle.h"
 #include "s2s_segment.h"
+#include "s2s_eventalign.h"
 
 #include <cctype>
 #include <cstdio>
@@ -2735,6 +2736,54 @@ int s2s_segment(int device, void* stream_, const int16_t* samples, const int64_t
     hipLaunchKernelGGL(s2s_segment_compact_kernel, dim3((unsigned)tiles), dim3(S2S_SEG_THREADS), 0, stream,
                        reinterpret_cast<const long long*>(offs), R, (long long)total, (long long)tiles, words, wrank, trank,
                        reinterpret_cast<const long long*>(ev_offs), ev_start, ev_len, n_events);
+    HIP_TRY(nullptr, hipGetLastError());
+    return S2S_OK;
+}
+
+// ---- eventalign (s2s_eventalign.h); s2s_eventalign_scratch_bytes is in s2s_host.cpp
+int s2s_event_means(int device, void* stream_, const int64_t* S, const int32_t* ev_len, const int64_t* ev_offs, const int32_t* n_events,
+                    int32_t R, int64_t capacity, int64_t* m_offs, int16_t* means) {
+    if (R < 0 || capacity < 0 || !ev_offs || !m_offs || (R > 0 && (!n_events || (capacity > 0 && (!S || !ev_len || !means)))))
+        return fail(nullptr, S2S_ERR_ARG, "s2s_event_means: bad argument");
+    DeviceGuard guard(device);
+    if (!guard.ok) return fail(nullptr, S2S_ERR_HIP, "hipSetDevice failed");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    hipLaunchKernelGGL(s2s_event_means_scan_kernel, dim3(1), dim3(1024), 0, stream, n_events, reinterpret_cast<const long long*>(ev_offs), R,
+                       reinterpret_cast<long long*>(m_offs));
+    HIP_TRY(nullptr, hipGetLastError());
+    if (R == 0 || capacity == 0) return S2S_OK;
+    hipLaunchKernelGGL(s2s_event_means_fill_kernel, dim3(R, S2S_EVA_MEAN_SLICES), dim3(256), 0, stream, reinterpret_cast<const long long*>(S),
+                       ev_len, reinterpret_cast<const long long*>(ev_offs), n_events, (long long)capacity,
+                       reinterpret_cast<const long long*>(m_offs), means);
+    HIP_TRY(nullptr, hipGetLastError());
+    return S2S_OK;
+}
+
+int s2s_eventalign(int device, void* stream_, const int16_t* m, const int64_t* m_offs, const int16_t* l, const int64_t* l_offs,
+                   const int32_t* ev_start, const int32_t* ev_len, const int64_t* ev_offs, int32_t P, int32_t width, int32_t skip_penalty,
+                   int32_t trim_penalty, int32_t unknown_cost, int64_t* cost, uint8_t* scratch, const int64_t* scratch_offs,
+                   int32_t* first_event, int32_t* end_event, int32_t* ev_kmer, int32_t* k_start, int32_t* k_len, int32_t* k_events) {
+    if (P < 0 || !s2s_eva_params_ok(width, skip_penalty, trim_penalty, unknown_cost) || !m_offs || !l_offs || !ev_offs || !scratch_offs ||
+        (P > 0 && (!m || !l || !ev_start || !ev_len || !cost || !scratch || !first_event || !end_event || !ev_kmer || !k_start || !k_len ||
+                   !k_events)) ||
+        (reinterpret_cast<uintptr_t>(scratch) & 15u))
+        return fail(nullptr, S2S_ERR_ARG, "s2s_eventalign: bad argument (width a multiple of 64 in 64..S2S_EVA_MAX_WIDTH, skip_penalty and "
+                                          "trim_penalty 0..2^20, unknown_cost 0..65535, scratch 16-byte aligned)");
+    if (P == 0) return S2S_OK;
+    DeviceGuard guard(device);
+    if (!guard.ok) return fail(nullptr, S2S_ERR_HIP, "hipSetDevice failed");
+    static_assert(S2S_EVA_LDS_BYTES(S2S_EVA_MAX_WIDTH) == 29744 && S2S_EVA_LDS_BYTES(128) == 4656,
+                  "include/s2s_hip.h states the LDS bytes of s2s_eventalign");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    hipLaunchKernelGGL(s2s_eventalign_kernel, dim3(P), dim3(width), S2S_EVA_LDS_BYTES(width), stream, m,
+                       reinterpret_cast<const long long*>(m_offs), l, reinterpret_cast<const long long*>(l_offs), width, skip_penalty,
+                       trim_penalty, unknown_cost, reinterpret_cast<long long*>(cost), scratch,
+                       reinterpret_cast<const long long*>(scratch_offs), end_event);
+    HIP_TRY(nullptr, hipGetLastError());
+    hipLaunchKernelGGL(s2s_eventalign_trace_kernel, dim3(P), dim3(64), 0, stream, reinterpret_cast<const long long*>(m_offs),
+                       reinterpret_cast<const long long*>(l_offs), ev_start, ev_len, reinterpret_cast<const long long*>(ev_offs), width,
+                       reinterpret_cast<const long long*>(cost), scratch, reinterpret_cast<const long long*>(scratch_offs), first_event,
+                       end_event, ev_kmer, k_start, k_len, k_events);
     HIP_TRY(nullptr, hipGetLastError());
     return S2S_OK;
 }

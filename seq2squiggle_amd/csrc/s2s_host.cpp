@@ -2019,3 +2019,148 @@ extern "C" int64_t s2s_segment_format(const int32_t* ev_start, const int32_t* ev
     }
     return pos;
 }
+
+// ================================================================================ eventalign: event means against k-mer levels on the host
+// The definitions of include/s2s_hip.h (next to s2s_event_means and s2s_eventalign) band by band: three rolling bands of W cells, 2
+// bits per cell and lk per band, then the walk back.  What the kernels of s2s_eventalign.h must equal bit for bit.
+#include "s2s_eventalign.h"
+
+namespace {
+
+struct EvaOut {
+    int32_t* first;
+    int32_t* end;
+    int32_t* kmer;
+    int32_t* k_start;
+    int32_t* k_len;
+    int32_t* k_events;
+};
+
+int64_t eva_one(const int16_t* m, int64_t E, const int16_t* l, int64_t K, const int32_t* st, const int32_t* ln, int64_t W, int64_t skip,
+                int64_t trim, int64_t unknown, const EvaOut& out) {
+    auto clear = [&]() {
+        for (int64_t e = 0; e < E; ++e) out.kmer[e] = -1;
+        for (int64_t j = 0; j < K; ++j) { out.k_start[j] = -1; out.k_len[j] = 0; out.k_events[j] = 0; }
+        *out.first = *out.end = 0;
+    };
+    clear();
+    if (E <= 0 || K <= 0) return S2S_DTW_COST_EMPTY;
+    const int64_t bands = E + K - 1;
+    std::vector<int64_t> rows(3 * (size_t)W, S2S_DTW_UNREACHED);
+    std::vector<uint8_t> dec((size_t)bands * (size_t)(W / 4), 0);
+    std::vector<int32_t> lks((size_t)bands);
+    int64_t* cur = rows.data();
+    int64_t* p1 = cur + W;                          // band b - 1
+    int64_t* p2 = p1 + W;                           // band b - 2
+    auto at = [&](const int64_t* band, int64_t o) { return o >= 0 && o < W ? band[o] : S2S_DTW_UNREACHED; };
+    int64_t lk = -(W / 2), r1 = 0, best = S2S_DTW_UNREACHED, best_e = 0;
+    for (int64_t b = 0; b < bands; ++b) {
+        int64_t r = 0;
+        if (b > 0) {
+            const int64_t ll = p1[0], ur = p1[W - 1];
+            r = (ll >= S2S_DTW_UNREACHED && ur >= S2S_DTW_UNREACHED) ? (b & 1) : (ll > ur ? 1 : 0);
+        }
+        lk += r;
+        lks[(size_t)b] = (int32_t)lk;
+        uint8_t* drow = dec.data() + (size_t)b * (size_t)(W / 4);
+        for (int64_t o = 0; o < W; ++o) {
+            const int64_t j = lk + o, e = b - j;
+            int64_t v = S2S_DTW_UNREACHED;
+            unsigned code = S2S_EVA_START;
+            if (j >= 0 && j < K && e >= 0 && e < E) {
+                const int64_t c = l[j] == S2S_RSQ_UNKNOWN ? unknown : std::abs((int64_t)m[e] - (int64_t)l[j]);
+                const int64_t pd = at(p2, o + r + r1 - 1), ps = at(p1, o + r), pk = at(p1, o + r - 1);
+                if (j >= 1 && pd < v) { v = pd + c; code = S2S_EVA_DIAG; }
+                if (ps < S2S_DTW_UNREACHED && ps + c < v) { v = ps + c; code = S2S_EVA_STAY; }
+                if (j >= 1 && pk < S2S_DTW_UNREACHED && pk + skip < v) { v = pk + skip; code = S2S_EVA_SKIP; }
+                if (j == 0 && e * trim + c < v) { v = e * trim + c; code = S2S_EVA_START; }
+                if (v >= S2S_DTW_UNREACHED) code = S2S_EVA_START;
+                if (j == K - 1 && v < S2S_DTW_UNREACHED) {
+                    const int64_t f = v + (E - 1 - e) * trim;
+                    if (f < best || (f == best && e < best_e)) { best = f; best_e = e; }
+                }
+            }
+            cur[o] = v;
+            drow[o >> 2] |= (uint8_t)(code << (2 * (o & 3)));
+        }
+        r1 = r;
+        int64_t* t = p2;
+        p2 = p1; p1 = cur; cur = t;
+    }
+    if (best >= S2S_DTW_UNREACHED) return S2S_RSQ_UNREACHED;
+    int64_t e = best_e, j = K - 1, run = 0, hi = 0;
+    bool arrived = false;
+    for (int64_t step = 0; step < E + K; ++step) {
+        const int64_t b = e + j, o = j - lks[(size_t)b];
+        if (o < 0 || o >= W) break;
+        const unsigned code = (dec[(size_t)b * (size_t)(W / 4) + (size_t)(o >> 2)] >> (2 * (o & 3))) & 3u;
+        if (code == S2S_EVA_SKIP) {
+            if (run != 0 || j == 0) break;
+            --j;
+            continue;
+        }
+        out.kmer[e] = (int32_t)j;
+        if (run == 0) hi = e;
+        ++run;
+        if (code == S2S_EVA_STAY) {
+            if (e == 0) break;
+            --e;
+            continue;
+        }
+        out.k_start[j] = st[e];
+        out.k_len[j] = st[hi] + ln[hi] - st[e];
+        out.k_events[j] = (int32_t)run;
+        run = 0;
+        if (code == S2S_EVA_START) { arrived = j == 0; break; }
+        if (e == 0 || j == 0) break;
+        --e;
+        --j;
+    }
+    if (!arrived) { clear(); return best; }          // (never: a reached cell has a path)
+    *out.first = (int32_t)e;
+    *out.end = (int32_t)(best_e + 1);
+    return best;
+}
+
+}  // namespace
+
+extern "C" int64_t s2s_eventalign_scratch_bytes(int64_t E, int64_t K, int32_t width) {
+    if (width < 64 || width > S2S_EVA_MAX_WIDTH || width % 64 != 0) return S2S_ERR_ARG;
+    return s2s_eva_bytes(E, K, width);
+}
+
+extern "C" int s2s_event_means_host(const int64_t* S, const int32_t* ev_len, const int64_t* ev_offs, const int32_t* n_events, int32_t R,
+                                    int64_t capacity, int64_t* m_offs, int16_t* means, int32_t threads) {
+    if (R < 0 || capacity < 0 || threads < 1 || !ev_offs || !m_offs || (R > 0 && (!n_events || (capacity > 0 && (!S || !ev_len || !means)))))
+        return S2S_ERR_ARG;
+    if (R > 0 && ev_offs[0] < 0) return S2S_ERR_ARG;
+    for (int32_t r = 0; r < R; ++r)
+        if (ev_offs[r + 1] < ev_offs[r]) return S2S_ERR_ARG;
+    m_offs[0] = 0;
+    for (int32_t r = 0; r < R; ++r) m_offs[r + 1] = m_offs[r] + s2s_eva_count(n_events[r], ev_offs[r], ev_offs[r + 1]);
+    if (m_offs[R] > capacity) return S2S_ERR_ARG;
+    dtw_for_each(R, threads, [&](int32_t r) {
+        const int64_t eo = ev_offs[r], cnt = m_offs[r + 1] - m_offs[r];
+        for (int64_t e = 0; e < cnt; ++e) means[m_offs[r] + e] = s2s_eva_mean(S[eo + e], ev_len[eo + e]);
+    });
+    return S2S_OK;
+}
+
+extern "C" int s2s_eventalign_host(const int16_t* m, const int64_t* m_offs, const int16_t* l, const int64_t* l_offs,
+                                   const int32_t* ev_start, const int32_t* ev_len, const int64_t* ev_offs, int32_t P, int32_t width,
+                                   int32_t skip_penalty, int32_t trim_penalty, int32_t unknown_cost, int64_t* cost, int32_t* first_event,
+                                   int32_t* end_event, int32_t* ev_kmer, int32_t* k_start, int32_t* k_len, int32_t* k_events,
+                                   int32_t threads) {
+    if (P < 0 || threads < 1 || !s2s_eva_params_ok(width, skip_penalty, trim_penalty, unknown_cost) || !m_offs || !l_offs || !ev_offs ||
+        (P > 0 && (!m || !l || !ev_start || !ev_len || !cost || !first_event || !end_event || !ev_kmer || !k_start || !k_len || !k_events)) ||
+        !dtw_offsets_ok(m_offs, P) || !dtw_offsets_ok(l_offs, P) || (P > 0 && (m_offs[0] < 0 || l_offs[0] < 0)))
+        return S2S_ERR_ARG;
+    for (int32_t p = 0; p < P; ++p)
+        if (ev_offs[p] < 0 || ev_offs[p + 1] - ev_offs[p] < m_offs[p + 1] - m_offs[p]) return S2S_ERR_ARG;
+    dtw_for_each(P, threads, [&](int32_t p) {
+        const EvaOut out{first_event + p, end_event + p, ev_kmer + m_offs[p], k_start + l_offs[p], k_len + l_offs[p], k_events + l_offs[p]};
+        cost[p] = eva_one(m + m_offs[p], m_offs[p + 1] - m_offs[p], l + l_offs[p], l_offs[p + 1] - l_offs[p], ev_start + ev_offs[p],
+                          ev_len + ev_offs[p], width, skip_penalty, trim_penalty, unknown_cost, out);
+    });
+    return S2S_OK;
+}

@@ -922,6 +922,80 @@ int s2s_eventalign_host(const int16_t* m, const int64_t* m_offs, const int16_t* 
                         int32_t trim_penalty, int32_t unknown_cost, int64_t* cost, int32_t* first_event, int32_t* end_event,
                         int32_t* ev_kmer, int32_t* k_start, int32_t* k_len, int32_t* k_events, int32_t threads);
 
+/* ---- `preprocess`: the training chunks of the reference's `preprocess` (preprocess.py: process_df -> get_chunks -> pad_lengths ->
+ * typical_indices, per read: its partition_by route) cut from alignments that lie in memory as the entries above leave them, with
+ * their conventions (no handle, `device` and `stream`, stream-ordered, device pointers, int64 offs, S2S_OK / S2S_ERR_ARG /
+ * S2S_ERR_HIP).  Geometry: k = seq_kmer, te = max_dna_len, ts = max_signal_len.
+ *
+ * Read p owns the slots [l_offs[p], l_offs[p+1]) of ev_start / ev_len / S / Q / stdv (the layout of s2s_resquiggle and
+ * s2s_event_sums) and of kmers (uint8 [slots][k]: the k letters of every slot), and the record [s_offs[p], s_offs[p+1]) of the pool.
+ * A ROW is a slot with ev_len >= 1 whose interval [ev_start, ev_start + ev_len) lies inside the record (ev_start >= 0, and 0 <=
+ * s_offs[p] <= s_offs[p+1] <= total) and whose k letters are not all 'N'; a k-mer with some N is still a row.  Rows are taken in
+ * position order: slot order, or slot order reversed with `backwards` (how `resquiggle --rna` lays its slots).  n = the read's rows.
+ *   n = 0: the read gives nothing.  Otherwise te - (n mod te) PAD rows follow (1 .. te of them; n a multiple of te gives a whole
+ *   chunk of pads, as in the reference): k letters '_', length 1, one sample 0.0, deviation 0.  The read gives floor(n / te) + 1
+ *   chunks of te consecutive rows.
+ * Per chunk:
+ *   chunks          fp16 [te][k][5], one-hot over _ACGT ('_' is column 0); any other letter, N included, is an all-zero row;
+ *   chunks_lengths  int64 [te], the rows' lengths;
+ *   targets_length  int64, their sum (the true sum: the reference's int16 wraps);
+ *   targets         fp32 [ts], the rows' samples back to back in pA, zero behind;
+ *   stdevs          fp32 [te].
+ * A chunk is KEPT iff targets_length <= ts (it is always >= te > 0).  Kept chunks come out dense, in read order, then chunk order.
+ * With `reverse` (RNA) each row's samples are read back to front; the rows stay in position order.
+ * Two sample sources:
+ *   S2S_CHUNK_RAW  pool = the stored int16 x, cal[3 p .. 3 p + 3) = the record's (digitisation, offset, range) as doubles:
+ *                    pA = (float)(((double)x + offset) * range / digitisation)
+ *                  and with n the row's length and S, Q the sums s2s_event_sums left in the slot, for n <= 1,024 (n Q < 2^51 fits int64)
+ *                    deviation = (float)(sqrt((double)max(n Q - S^2, 0)) / n * range / digitisation)
+ *                  (a longer row drops its chunk anyway: its value is 0).  No expression has the shape a b + c: device code is
+ *                  built with contraction on, and both sides must round alike.
+ *   S2S_CHUNK_PA   pool = fp32 samples in pA, stdv = an fp32 deviation per slot, as an event table gave them; S, Q, cal unused.
+ *
+ *  s2s_chunk_scratch_bytes  host function: the bytes of `scratch` for `slots` pooled slots, P reads and chunk_capacity chunks (per
+ *                 tile of S2S_SEG_TILE slots 32 flag words and 32 int32 ranks, two int64 ranks per tile, per read a rank and a chunk
+ *                 offset, per chunk of the capacity a rank, per slot an int32); S2S_ERR_ARG outside the limits.
+ *  s2s_chunk_pack `total` = the pool's samples and `slots` = the caller's l_offs[P], by value: the grids depend on them, and no
+ *                 sample >= total and no slot >= slots is ever read, whatever the offsets hold.  chunk_capacity, by value: the rows
+ *                 (chunks) the five outputs hold; the sum over the reads of floor(slots_p / te) + 1, which the host knows, always
+ *                 suffices.  Outputs, dense over the kept chunks: chunks uint16 (fp16 bits) [kept][te][k][5], chunks_lengths int64
+ *                 [kept][te], targets fp32 [kept][ts], targets_lengths int64 [kept], stdevs fp32 [kept][te]; nothing behind the kept
+ *                 prefix is written.  n_rows int32 [P]; counters int64 [3]: chunks formed, chunks kept, all-N slots that were rows
+ *                 otherwise.  Chunks beyond chunk_capacity are not formed (counters[0] still counts them; the host twin:
+ *                 S2S_ERR_ARG).  scratch: 16-byte aligned, needs no initialisation.  Eight launches (csrc/s2s_chunk.h), by ranks only:
+ *                 no atomics, nothing spins or waits between workgroups.  (1) one flag per slot that is a row, by wave ballots over
+ *                 the POOLED slots (a thread finds its read by a search in l_offs), and per tile its rows and all-N rows; (2) one
+ *                 workgroup scans the tiles' two counts (the scan of s2s_segment, twice); (3) every row writes its slot at its rank, and every read
+ *                 its row count and chunk count; (4) the scan of the chunk counts; (5) per POOLED chunk, a wave: it finds its read
+ *                 by a search in the chunk offsets, lane j loads row j, the sum of the lengths decides the keep flag; (6) the scan
+ *                 of the flags; (7) per kept chunk, a wave: the lengths' prefix over the lanes by shuffles, every output sample finds
+ *                 its row by a search in that prefix, the target row is written coalesced.  One read of 2^22 slots loads the
+ *                 device like thousands of short ones.  Static LDS: 272 B in (1), 128 B in the scans, none elsewhere.
+ *                 Limits: k 1 .. 10, te 1 .. 64, ts 1 .. 1,024, P <= 2^22, P <= chunk_capacity < 2^31, slots < 2^31, total <= 2^40;
+ *                 anything outside is S2S_ERR_ARG and nothing is launched.  P = 0 writes the counters (0) and nothing else.
+ *  s2s_chunk_pack_host   the same on host pointers, in plain C++ (`preprocess --cpu`; the definition the kernels must equal bit
+ *                 for bit, floats included): reads, then chunks dealt out over `threads` >= 1 host threads; no scratch argument.
+ *                 S2S_ERR_ARG as above, and for what the device can only skip: offsets that decrease or are negative, l_offs[P] !=
+ *                 slots, s_offs[P] > total, a read of more than 2^22 slots, a calibration that is not finite or has digitisation 0,
+ *                 more chunks than chunk_capacity. */
+#define S2S_CHUNK_RAW 0
+#define S2S_CHUNK_PA 1
+#define S2S_CHUNK_MAX_K 10
+#define S2S_CHUNK_MAX_TE 64
+#define S2S_CHUNK_MAX_TS 1024
+#define S2S_CHUNK_MAX_SLOTS (((int64_t)1 << 31) - 1)
+int64_t s2s_chunk_scratch_bytes(int64_t slots, int32_t P, int64_t chunk_capacity);
+int s2s_chunk_pack(int device, void* stream, const void* pool, const int64_t* s_offs, int64_t total, int32_t source, const int64_t* l_offs,
+                   int64_t slots, const int32_t* ev_start, const int32_t* ev_len, const int64_t* S, const int64_t* Q, const double* cal,
+                   const float* stdv, const uint8_t* kmers, int32_t P, int32_t k, int32_t te, int32_t ts, int32_t reverse,
+                   int32_t backwards, int64_t chunk_capacity, uint8_t* scratch, uint16_t* chunks, int64_t* chunks_lengths, float* targets,
+                   int64_t* targets_lengths, float* stdevs, int32_t* n_rows, int64_t* counters);
+int s2s_chunk_pack_host(const void* pool, const int64_t* s_offs, int64_t total, int32_t source, const int64_t* l_offs, int64_t slots,
+                        const int32_t* ev_start, const int32_t* ev_len, const int64_t* S, const int64_t* Q, const double* cal,
+                        const float* stdv, const uint8_t* kmers, int32_t P, int32_t k, int32_t te, int32_t ts, int32_t reverse,
+                        int32_t backwards, int64_t chunk_capacity, uint16_t* chunks, int64_t* chunks_lengths, float* targets,
+                        int64_t* targets_lengths, float* stdevs, int32_t* n_rows, int64_t* counters, int32_t threads);
+
 /* ---- host-side helper (no GPU work, no handle): replays the DRAWS of the reference's read sampler (utils.py:415-479
  * `sampling`, with the read-length law of utils.py:325-331 `draw_expon_dis`) without building a read, so that a rank of a sharded
  * run finds the generator state of its first read in microseconds per thousand reads instead of replaying them in the

@@ -641,8 +641,16 @@ def compare(a, b, out, band, normalise, by_order, max_samples, cpu, as_json, pat
 @click.option("--max-samples", default=1 << 27, type=int, show_default=True, help="Samples per batch.")
 @click.option("--trace-memory", default=8 << 30, type=int, show_default=True,
               help="Bytes of decision scratch per batch; a read that needs more on its own is refused by its id.")
+@click.option("--chunks", "chunks_out", default=None, type=click.Path(file_okay=False),
+              help="Also write the training chunks of the solved reads under this directory (what `preprocess` makes of the table, "
+                   "cut on the device from the alignment itself; no text in between).")
+@click.option("-y", "--config", default=None, type=click.Path(dir_okay=False, exists=True),
+              help="With --chunks: YAML configuration file with seq_kmer, max_dna_len and max_signal_len.")
+@click.option("--seq-kmer", default=None, type=int, help="k of the chunks' k-mers (default: seq_kmer of the config).")
+@click.option("--max-dna-len", default=None, type=int, help="k-mers per chunk, 1..64 (default: max_dna_len of the config).")
+@click.option("--max-signal-len", default=None, type=int, help="Samples per chunk, 1..1024 (default: max_signal_len of the config).")
 def resquiggle(seqs, signals, model, out, with_samples, band, skip_penalty, unknown_cost, rna, intervals, cpu, as_json, summary_out,
-               max_samples, trace_memory):
+               max_samples, trace_memory, chunks_out, config, seq_kmer, max_dna_len, max_signal_len):
     """Align every record of a .blow5 / .slow5 file to the levels a pore model expects for the k-mers of its sequence (SEQS: FASTA or
     FASTQ, record names = read ids) and write the event table predict --events writes: read_name, position, model_kmer, start_idx,
     end_idx, event_level_mean, event_stdv.  Both ends are pinned: the first sample belongs to the first k-mer, the last to the last.
@@ -662,9 +670,10 @@ def resquiggle(seqs, signals, model, out, with_samples, band, skip_penalty, unkn
         raise click.BadParameter(f"must be 0..{R.MAX_SKIP_PENALTY}", param_hint="--skip-penalty")
     if not 0 <= unknown_cost <= R.MAX_UNKNOWN_COST:
         raise click.BadParameter(f"must be 0..{R.MAX_UNKNOWN_COST}", param_hint="--unknown-cost")
+    chunks = None if chunks_out is None else (chunks_out,) + _chunk_geometry(config, seq_kmer, max_dna_len, max_signal_len)
     s = R.resquiggle_files(seqs, signals, model, out, band=band, skip_penalty=skip_penalty, unknown_cost=unknown_cost, rna=rna,
                            intervals=intervals, with_samples=with_samples, cpu=cpu, summary_out=summary_out, max_samples=max_samples,
-                           trace_memory=trace_memory)
+                           trace_memory=trace_memory, chunks=chunks)
     if as_json:
         click.echo(json.dumps(s))
     else:
@@ -748,8 +757,17 @@ def segment(signals, out, window_short, window_long, threshold_short, threshold_
 @click.option("--trace-memory", default=8 << 30, type=int, show_default=True,
               help="Bytes of decision scratch per batch, counted by the most events a record can have; a read that may need more on its "
                    "own is refused by its id.")
+@click.option("--chunks", "chunks_out", default=None, type=click.Path(file_okay=False),
+              help="Also write the training chunks of the solved reads under this directory (what `preprocess` makes of the table, "
+                   "cut on the device from the alignment itself; no text in between).")
+@click.option("-y", "--config", default=None, type=click.Path(dir_okay=False, exists=True),
+              help="With --chunks: YAML configuration file with seq_kmer, max_dna_len and max_signal_len.")
+@click.option("--seq-kmer", default=None, type=int, help="k of the chunks' k-mers (default: seq_kmer of the config).")
+@click.option("--max-dna-len", default=None, type=int, help="k-mers per chunk, 1..64 (default: max_dna_len of the config).")
+@click.option("--max-signal-len", default=None, type=int, help="Samples per chunk, 1..1024 (default: max_signal_len of the config).")
 def eventalign(seqs, signals, model, out, with_samples, band_width, skip_penalty, trim_penalty, unknown_cost, rna, window_short,
-               window_long, threshold_short, threshold_long, cpu, as_json, summary_out, max_samples, trace_memory):
+               window_long, threshold_short, threshold_long, cpu, as_json, summary_out, max_samples, trace_memory, chunks_out, config,
+               seq_kmer, max_dna_len, max_signal_len):
     """Align the detected events of every UNTRIMMED record of a .blow5 / .slow5 file to the levels a pore model expects for the k-mers
     of its sequence (SEQS: FASTA or FASTQ, record names = read ids) and write the event table predict --events writes, one row per
     k-mer that got events.  Events come from the detector of `segment`; their means are median / MAD normalised over the whole record;
@@ -781,10 +799,11 @@ def eventalign(seqs, signals, model, out, with_samples, band_width, skip_penalty
             SEG.threshold_int(t)
         except ValueError as e:
             raise click.BadParameter(str(e), param_hint=hint)
+    chunks = None if chunks_out is None else (chunks_out,) + _chunk_geometry(config, seq_kmer, max_dna_len, max_signal_len)
     s = EA.eventalign_files(seqs, signals, model, out, band_width=band_width, skip_penalty=skip_penalty, trim_penalty=trim_penalty,
                             unknown_cost=unknown_cost, rna=rna, window_short=window_short, window_long=window_long,
                             threshold_short=threshold_short, threshold_long=threshold_long, with_samples=with_samples, cpu=cpu,
-                            summary_out=summary_out, max_samples=max_samples, trace_memory=trace_memory)
+                            summary_out=summary_out, max_samples=max_samples, trace_memory=trace_memory, chunks=chunks)
     if as_json:
         click.echo(json.dumps(s))
     else:
@@ -794,6 +813,61 @@ def eventalign(seqs, signals, model, out, with_samples, band_width, skip_penalty
                    f"{s['refused']} refused, {s['no_sequence']} without a sequence, {s['no_known_level']} without a known level; "
                    f"{s['aligned_events']} aligned events, {s['skipped_kmers']} skipped k-mers; {s['trimmed_head_samples']} / "
                    f"{s['trimmed_tail_samples']} samples trimmed at head / tail]  mean cost per aligned event {per} MAD")
+
+
+def _chunk_geometry(config, seq_kmer, max_dna_len, max_signal_len):
+    """(k, te, ts) of the training chunks: the three keys of the config (the packaged config.yaml by default), each overridden by
+    its option; a value outside the limits of s2s_chunk_pack is a BadParameter that names the option."""
+    from . import preprocess as PP
+    cfg = set_config(config)
+    given = (("--seq-kmer", "seq_kmer", seq_kmer, PP.MAX_K), ("--max-dna-len", "max_dna_len", max_dna_len, PP.MAX_TE),
+             ("--max-signal-len", "max_signal_len", max_signal_len, PP.MAX_TS))
+    out = []
+    for hint, key, value, most in given:
+        value = int(cfg[key]) if value is None else int(value)
+        if not 1 <= value <= most:
+            raise click.BadParameter(f"must be 1..{most}", param_hint=hint)
+        out.append(value)
+    return tuple(out)
+
+
+@main.command()
+@click.argument("events", type=click.Path(dir_okay=False, exists=True))
+@click.argument("outdir", type=click.Path(file_okay=False))
+@click.option("-y", "--config", default=None, type=click.Path(dir_okay=False, exists=True),
+              help="YAML configuration file with seq_kmer, max_dna_len and max_signal_len (default: the packaged config.yaml).")
+@click.option("--seq-kmer", default=None, type=int, help="k of the chunks' k-mers (default: seq_kmer of the config).")
+@click.option("--max-dna-len", default=None, type=int, help="k-mers per chunk, 1..64 (default: max_dna_len of the config).")
+@click.option("--max-signal-len", default=None, type=int, help="Samples per chunk, 1..1024 (default: max_signal_len of the config).")
+@click.option("--rna", is_flag=True, help="The stored signal is reversed (RNA profiles): read every row's samples back to front.")
+@click.option("--chunks-per-file", default=100_000, type=int, show_default=True, help="Chunks per numbered file set.  A choice.")
+@click.option("--max-chunks", default=None, type=int, help="Stop after this many kept chunks.")
+@click.option("--max-samples", default=1 << 27, type=int, show_default=True, help="Samples per batch.")
+@click.option("--cpu", is_flag=True, help="Compute on host threads instead of the GPU (the same bytes).")
+@click.option("--json", "as_json", is_flag=True, help="Print the summary as one JSON object.")
+def preprocess(events, outdir, config, seq_kmer, max_dna_len, max_signal_len, rna, chunks_per_file, max_chunks, max_samples, cpu, as_json):
+    """Cut an event table with a `samples` column (predict --events --events-samples, resquiggle --samples, eventalign --samples) into
+    the training chunks the reference's preprocess writes -- chunks-NNNN.npy, chunks_lengths-, targets-, targets_lengths-, stdevs-
+    under OUTDIR, the directory `evaluate` reads.  Per read, in the table's order; no random permutation."""
+    if max_samples < 1:
+        raise click.BadParameter("must be >= 1", param_hint="--max-samples")
+    if chunks_per_file < 1:
+        raise click.BadParameter("must be >= 1", param_hint="--chunks-per-file")
+    if max_chunks is not None and max_chunks < 0:
+        raise click.BadParameter("must be >= 0", param_hint="--max-chunks")
+    import json
+    if not cpu:
+        import torch  # noqa: F401  (before the library: see engine.py)
+    from . import preprocess as PP
+    k, te, ts = _chunk_geometry(config, seq_kmer, max_dna_len, max_signal_len)
+    s = PP.preprocess_table(events, outdir, k, te, ts, rna=rna, chunks_per_file=chunks_per_file, max_chunks=max_chunks,
+                            max_samples=max_samples, cpu=cpu)
+    if as_json:
+        click.echo(json.dumps(s))
+    else:
+        click.echo(f"{s['chunks_written']} chunks in {s['files']} file set(s) -> {outdir}  [k {k}, {te} k-mers, {ts} samples; "
+                   f"{s['reads']} reads, {s['rows']} rows, {s['all_n_rows']} all-N rows dropped, {s['pad_rows']} pad rows; "
+                   f"{s['chunks_formed']} chunks formed, {s['chunks_kept']} kept, {s['chunks_too_long']} dropped as too long]")
 
 
 if __name__ == "__main__":

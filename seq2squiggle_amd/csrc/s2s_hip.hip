@@ -20,6 +20,7 @@
 #include "s2s_resquiggle.h"
 #include "s2s_segment.h"
 #include "s2s_eventalign.h"
+#include "s2s_chunk.h"
 
 #include <cctype>
 #include <cstdio>
@@ -2784,6 +2785,70 @@ int s2s_eventalign(int device, void* stream_, const int16_t* m, const int64_t* m
                        reinterpret_cast<const long long*>(l_offs), ev_start, ev_len, reinterpret_cast<const long long*>(ev_offs), width,
                        reinterpret_cast<const long long*>(cost), scratch, reinterpret_cast<const long long*>(scratch_offs), first_event,
                        end_event, ev_kmer, k_start, k_len, k_events);
+    HIP_TRY(nullptr, hipGetLastError());
+    return S2S_OK;
+}
+
+// ---- preprocess (s2s_chunk.h); s2s_chunk_scratch_bytes is in s2s_host.cpp
+int s2s_chunk_pack(int device, void* stream_, const void* pool, const int64_t* s_offs, int64_t total, int32_t source, const int64_t* l_offs,
+                   int64_t slots, const int32_t* ev_start, const int32_t* ev_len, const int64_t* S, const int64_t* Q, const double* cal,
+                   const float* stdv, const uint8_t* kmers, int32_t P, int32_t k, int32_t te, int32_t ts, int32_t reverse,
+                   int32_t backwards, int64_t chunk_capacity, uint8_t* scratch, uint16_t* chunks, int64_t* chunks_lengths, float* targets,
+                   int64_t* targets_lengths, float* stdevs, int32_t* n_rows, int64_t* counters) {
+    const bool work = P > 0 && slots > 0;
+    if (!s2s_chk_params_ok(source, k, te, ts) || !s2s_chk_counts_ok(P, total, slots, chunk_capacity) || chunk_capacity < P || !s_offs ||
+        !l_offs || !counters || (P > 0 && !n_rows) ||
+        (work && (!ev_start || !ev_len || !kmers || !scratch || !chunks || !chunks_lengths || !targets || !targets_lengths || !stdevs ||
+                  (total > 0 && !pool) || (source == S2S_CHUNK_RAW ? (!S || !Q || !cal) : !stdv))) ||
+        (reinterpret_cast<uintptr_t>(scratch) & 15u))
+        return fail(nullptr, S2S_ERR_ARG, "s2s_chunk_pack: bad argument (source 0 / 1, k 1..10, te 1..64, ts 1..1024, P <= 2^22, P <= "
+                                          "chunk_capacity < 2^31, slots < 2^31, total <= 2^40, scratch 16-byte aligned)");
+    DeviceGuard guard(device);
+    if (!guard.ok) return fail(nullptr, S2S_ERR_HIP, "hipSetDevice failed");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    HIP_TRY(nullptr, hipMemsetAsync(counters, 0, 3 * sizeof(int64_t), stream));
+    if (P > 0) HIP_TRY(nullptr, hipMemsetAsync(n_rows, 0, (size_t)P * sizeof(int32_t), stream));
+    if (!work) return S2S_OK;
+    static_assert(S2S_CHK_LDS_BYTES == 272, "include/s2s_hip.h states the LDS bytes of s2s_chunk_pack");
+    const S2SChkScratch at = s2s_chk_layout(slots, P, chunk_capacity);
+    const int64_t tiles = s2s_chk_tiles(slots);
+    unsigned long long* words = reinterpret_cast<unsigned long long*>(scratch + at.words);
+    long long* trank = reinterpret_cast<long long*>(scratch + at.trank);
+    long long* nrank = reinterpret_cast<long long*>(scratch + at.nrank);
+    long long* r_offs = reinterpret_cast<long long*>(scratch + at.r_offs);
+    long long* c_offs = reinterpret_cast<long long*>(scratch + at.c_offs);
+    long long* krank = reinterpret_cast<long long*>(scratch + at.krank);
+    int* wrank = reinterpret_cast<int*>(scratch + at.wrank);
+    int* rows = reinterpret_cast<int*>(scratch + at.rows);
+    S2SChkIn in;
+    in.pool = pool;
+    in.s_offs = reinterpret_cast<const long long*>(s_offs);
+    in.l_offs = reinterpret_cast<const long long*>(l_offs);
+    in.ev_start = ev_start; in.ev_len = ev_len;
+    in.S = reinterpret_cast<const long long*>(S); in.Q = reinterpret_cast<const long long*>(Q);
+    in.cal = source == S2S_CHUNK_RAW ? cal : nullptr;
+    in.stdv = stdv; in.kmers = kmers;
+    in.total = total; in.slots = slots; in.capacity = chunk_capacity;
+    in.P = P; in.source = source; in.k = k; in.te = te; in.ts = ts; in.reverse = reverse ? 1 : 0; in.backwards = backwards ? 1 : 0;
+    const unsigned waves = (unsigned)((chunk_capacity + S2S_CHK_WAVES - 1) / S2S_CHK_WAVES);
+    hipLaunchKernelGGL(s2s_chunk_flags_kernel, dim3((unsigned)tiles), dim3(S2S_CHK_THREADS), 0, stream, in, words, wrank, trank, nrank);
+    HIP_TRY(nullptr, hipGetLastError());
+    hipLaunchKernelGGL(s2s_segment_scan_kernel, dim3(1), dim3(1024), 0, stream, trank, (long long)tiles);
+    HIP_TRY(nullptr, hipGetLastError());
+    hipLaunchKernelGGL(s2s_segment_scan_kernel, dim3(1), dim3(1024), 0, stream, nrank, (long long)tiles);
+    HIP_TRY(nullptr, hipGetLastError());
+    hipLaunchKernelGGL(s2s_chunk_compact_kernel, dim3((unsigned)tiles), dim3(S2S_CHK_THREADS), 0, stream, in, words, wrank, trank, rows,
+                       r_offs, c_offs, n_rows);
+    HIP_TRY(nullptr, hipGetLastError());
+    hipLaunchKernelGGL(s2s_segment_scan_kernel, dim3(1), dim3(1024), 0, stream, c_offs, (long long)P);
+    HIP_TRY(nullptr, hipGetLastError());
+    hipLaunchKernelGGL(s2s_chunk_lengths_kernel, dim3(waves), dim3(S2S_CHK_THREADS), 0, stream, in, rows, r_offs, c_offs, n_rows, krank);
+    HIP_TRY(nullptr, hipGetLastError());
+    hipLaunchKernelGGL(s2s_segment_scan_kernel, dim3(1), dim3(1024), 0, stream, krank, (long long)chunk_capacity);
+    HIP_TRY(nullptr, hipGetLastError());
+    hipLaunchKernelGGL(s2s_chunk_write_kernel, dim3(waves), dim3(S2S_CHK_THREADS), 0, stream, in, rows, r_offs, c_offs, n_rows, krank, nrank,
+                       (long long)tiles, chunks, reinterpret_cast<long long*>(chunks_lengths), targets,
+                       reinterpret_cast<long long*>(targets_lengths), stdevs, reinterpret_cast<long long*>(counters));
     HIP_TRY(nullptr, hipGetLastError());
     return S2S_OK;
 }

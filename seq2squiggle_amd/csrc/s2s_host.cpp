@@ -2164,3 +2164,115 @@ extern "C" int s2s_eventalign_host(const int16_t* m, const int64_t* m_offs, cons
     });
     return S2S_OK;
 }
+
+// ================================================================================ preprocess: training chunks on the host
+// The definition of include/s2s_hip.h (next to s2s_chunk_pack) read by read: the rows in position order, the pads, the chunks, the
+// keep rule.  What the kernels of s2s_chunk.h must equal bit for bit, floats included.
+#include "s2s_chunk.h"
+
+extern "C" int64_t s2s_chunk_scratch_bytes(int64_t slots, int32_t P, int64_t chunk_capacity) {
+    if (!s2s_chk_counts_ok(P, 0, slots, chunk_capacity)) return S2S_ERR_ARG;
+    return s2s_chk_layout(slots, P, chunk_capacity).bytes;
+}
+
+extern "C" int s2s_chunk_pack_host(const void* pool, const int64_t* s_offs, int64_t total, int32_t source, const int64_t* l_offs,
+                                   int64_t slots, const int32_t* ev_start, const int32_t* ev_len, const int64_t* S, const int64_t* Q,
+                                   const double* cal, const float* stdv, const uint8_t* kmers, int32_t P, int32_t k, int32_t te, int32_t ts,
+                                   int32_t reverse, int32_t backwards, int64_t chunk_capacity, uint16_t* chunks, int64_t* chunks_lengths,
+                                   float* targets, int64_t* targets_lengths, float* stdevs, int32_t* n_rows, int64_t* counters,
+                                   int32_t threads) {
+    const bool work = P > 0 && slots > 0;
+    const bool raw = source == S2S_CHUNK_RAW;
+    if (threads < 1 || !s2s_chk_params_ok(source, k, te, ts) || !s2s_chk_counts_ok(P, total, slots, chunk_capacity) || chunk_capacity < P ||
+        !s_offs || !l_offs || !counters || (P > 0 && !n_rows) ||
+        (work && (!ev_start || !ev_len || !kmers || !chunks || !chunks_lengths || !targets || !targets_lengths || !stdevs ||
+                  (total > 0 && !pool) || (raw ? (!S || !Q || !cal) : !stdv))))
+        return S2S_ERR_ARG;
+    if (P > 0 && (s_offs[0] < 0 || l_offs[0] < 0 || s_offs[P] > total || l_offs[P] != slots)) return S2S_ERR_ARG;
+    for (int32_t p = 0; p < P; ++p) {
+        if (s_offs[p + 1] < s_offs[p] || l_offs[p + 1] < l_offs[p] || l_offs[p + 1] - l_offs[p] > S2S_DTW_MAX_SAMPLES) return S2S_ERR_ARG;
+        if (work && raw && !(std::isfinite(cal[3 * p]) && std::isfinite(cal[3 * p + 1]) && std::isfinite(cal[3 * p + 2]) && cal[3 * p] != 0.0))
+            return S2S_ERR_ARG;
+    }
+    counters[0] = counters[1] = counters[2] = 0;
+    for (int32_t p = 0; p < P; ++p) n_rows[p] = 0;
+    if (!work) return S2S_OK;
+
+    // the reads' rows, in position order
+    std::vector<std::vector<int64_t>> rows((size_t)P);
+    std::vector<int64_t> all_n((size_t)P, 0);
+    dtw_for_each(P, threads, [&](int32_t p) {
+        auto& mine = rows[(size_t)p];
+        for (int64_t g = l_offs[p]; g < l_offs[p + 1]; ++g) {
+            const int row = s2s_chunk_row(ev_start[g], ev_len[g], s_offs[p], s_offs[p + 1], total, kmers + g * k, k);
+            if (row == 1) mine.push_back(g);
+            all_n[(size_t)p] += row == 2;
+        }
+        if (backwards) std::reverse(mine.begin(), mine.end());
+        n_rows[p] = (int32_t)mine.size();
+    });
+    std::vector<int64_t> c_offs((size_t)P + 1, 0);
+    for (int32_t p = 0; p < P; ++p) {
+        const int64_t n = (int64_t)rows[(size_t)p].size();
+        c_offs[(size_t)p + 1] = c_offs[(size_t)p] + (n > 0 ? n / te + 1 : 0);
+        counters[2] += all_n[(size_t)p];
+    }
+    const int64_t formed = c_offs[(size_t)P];
+    counters[0] = formed;
+    if (formed > chunk_capacity) return S2S_ERR_ARG;
+    std::vector<int32_t> read_of((size_t)formed);
+    for (int32_t p = 0; p < P; ++p)
+        for (int64_t c = c_offs[(size_t)p]; c < c_offs[(size_t)p + 1]; ++c) read_of[(size_t)c] = p;
+
+    // row j of chunk c: its slot, or -1 for a pad; its length
+    auto row_of = [&](int64_t c, int32_t j, int64_t& len) {
+        const int32_t p = read_of[(size_t)c];
+        const auto& mine = rows[(size_t)p];
+        const int64_t i = (c - c_offs[(size_t)p]) * te + j;
+        if (i >= (int64_t)mine.size()) { len = 1; return (int64_t)-1; }
+        len = ev_len[mine[(size_t)i]];
+        return mine[(size_t)i];
+    };
+    std::vector<int64_t> dest((size_t)formed + 1, 0);                       // the kept chunks before chunk c
+    dtw_for_each((int32_t)formed, threads, [&](int32_t c) {
+        int64_t tl = 0, len;
+        for (int32_t j = 0; j < te; ++j) { row_of(c, j, len); tl += len; }
+        dest[(size_t)c + 1] = tl <= ts;
+    });
+    for (int64_t c = 0; c < formed; ++c) dest[(size_t)c + 1] += dest[(size_t)c];
+    counters[1] = dest[(size_t)formed];
+    dtw_for_each((int32_t)formed, threads, [&](int32_t c) {
+        if (dest[(size_t)c + 1] == dest[(size_t)c]) return;
+        const int64_t at = dest[(size_t)c];
+        const int32_t p = read_of[(size_t)c];
+        uint16_t* hot = chunks + at * te * k * 5;
+        float* tg = targets + at * ts;
+        std::fill(hot, hot + (int64_t)te * k * 5, (uint16_t)0);
+        std::fill(tg, tg + ts, 0.0f);
+        int64_t t = 0;
+        for (int32_t j = 0; j < te; ++j) {
+            int64_t len;
+            const int64_t g = row_of(c, j, len);
+            chunks_lengths[at * te + j] = len;
+            float dev = 0.0f;
+            for (int32_t q = 0; q < k; ++q) {
+                const int32_t col = g < 0 ? 0 : s2s_chunk_column(kmers[g * k + q]);
+                if (col >= 0) hot[(j * k + q) * 5 + col] = S2S_CHK_ONE;
+            }
+            if (g < 0) {
+                t += 1;                                                      // (the pad's sample 0.0 is there)
+            } else {
+                const int64_t first = s_offs[p] + ev_start[g];
+                for (int64_t o = 0; o < len; ++o) {
+                    const int64_t idx = first + (reverse ? len - 1 - o : o);
+                    tg[t++] = raw ? s2s_chunk_pa(static_cast<const int16_t*>(pool)[idx], cal[3 * p], cal[3 * p + 1], cal[3 * p + 2])
+                                  : static_cast<const float*>(pool)[idx];
+                }
+                dev = raw ? s2s_chunk_stdv(len, S[g], Q[g], cal[3 * p], cal[3 * p + 2]) : stdv[g];
+            }
+            stdevs[at * te + j] = dev;
+        }
+        targets_lengths[at] = t;
+    });
+    return S2S_OK;
+}

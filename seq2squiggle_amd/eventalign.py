@@ -88,11 +88,13 @@ def _levels(lev_list, known_list, cpu: bool, device: int, threads, norm: bool, l
 
 
 def _run_batch(sig_list, lev_list, known_list, W: int, skip_penalty: int, trim_penalty: int, unknown_cost: int, seg, cpu: bool,
-               device: int = 0, threads: int = None):
+               device: int = 0, threads: int = None, chunks=None):
     """One batch of reads, the whole chain.  sig_list: the stored int16 samples; lev_list: int16 levels per k-mer (any value where
     known_list is False); seg: (w_short, w_long, T_short, T_long).  -> dict(cost int64 [P], first / end / n_events int32 [P], per read
     ev_start / ev_len / kmer (its events) and k_start / k_len / k_events / S / Q (its k-mers; S, Q over the raw samples), med / mad
-    int32 [P] of the event means, lmed / lmad int32 [P] of the known levels)."""
+    int32 [P] of the event means, lmed / lmad int32 [P] of the known levels).  chunks: (preprocess.Chunker, the records' calibrations,
+    the cleaned sequences) -- the training chunks are packed from the device buffers behind the last sums; without it nothing else is
+    uploaded or launched."""
     from ._lib import lib
     P = len(sig_list)
     w_s = seg[0]
@@ -100,7 +102,8 @@ def _run_batch(sig_list, lev_list, known_list, W: int, skip_penalty: int, trim_p
 
     def tables(offs):
         cap = capacity(np.diff(offs), w_s)
-        return slots(cap), device_only(lambda: slots([scratch_bytes(c, k, W) for c, k in zip(cap, K)]))
+        extra = chunks[0].tables(chunks[1], chunks[2]) if chunks is not None else []
+        return [slots(cap), device_only(lambda: slots([scratch_bytes(c, k, W) for c, k in zip(cap, K)]))] + extra
     B = Batch(sig_list, tables, cpu, device, threads)
     ev_offs = B.tables[0]
     ET, KT = int(ev_offs[-1]), int(sum(K))
@@ -125,6 +128,8 @@ def _run_batch(sig_list, lev_list, known_list, W: int, skip_penalty: int, trim_p
            skip_penalty, trim_penalty, unknown_cost, res.ptr("cost"), B.scratch(lambda: B.tables[1][-1]), B.table(1), res.ptr("first"),
            res.ptr("end"), res.ptr("kmer"), res.ptr("k_start"), res.ptr("k_len"), res.ptr("k_events"))
     B.call("event_sums", B.samples, B.offs(), res.ptr("k_start"), res.ptr("k_len"), l_offs, P, res.ptr("S"), res.ptr("Q"))
+    if chunks is not None:
+        chunks[0].pack(B, P, l_offs, K, res.ptr("k_start"), res.ptr("k_len"), res.ptr("S"), res.ptr("Q"), B.table(2), B.table(3))
     r = res.fetch()
     lo, mo, ne = BL.tables[0], r["m_offs"], r["n_events"]
     per_k = lambda a: [a[lo[p]:lo[p + 1]] for p in range(P)]                         # noqa: E731
@@ -179,7 +184,7 @@ def eventalign_files(seqs, signals, model, out, band_width: int = DEFAULT_BAND_W
                      window_short: int = DEFAULT_WINDOW_SHORT, window_long: int = DEFAULT_WINDOW_LONG,
                      threshold_short: float = DEFAULT_THRESHOLD_SHORT, threshold_long: float = DEFAULT_THRESHOLD_LONG,
                      with_samples: bool = False, cpu: bool = False, device: int = 0, summary_out=None,
-                     max_samples: int = DEFAULT_MAX_SAMPLES, trace_memory: int = DEFAULT_TRACE_MEMORY) -> dict:
+                     max_samples: int = DEFAULT_MAX_SAMPLES, trace_memory: int = DEFAULT_TRACE_MEMORY, chunks=None) -> dict:
     """Write OUT (EVENT_COLUMNS, plus `samples` with with_samples; records in the order of SIGNALS, one row per unskipped k-mer, by
     position) and return the counters: reads solved, unreached (no path inside the band), refused (more than 2^22 samples or k-mers,
     or a walk back that may need more than trace_memory on its own -- by read id, before the batch computes), without a sequence,
@@ -187,7 +192,8 @@ def eventalign_files(seqs, signals, model, out, band_width: int = DEFAULT_BAND_W
     tail, and the mean cost per aligned event in MADs.  A batch holds reads until their samples pass max_samples or the bound of
     their decision scratch (that of s2s_segment_capacity events) passes trace_memory (at least one read).  rna: the stored signal is
     reversed, so the levels are read back to front; `position` stays in read coordinates.  summary_out: one row per read
-    (SUMMARY_COLUMNS)."""
+    (SUMMARY_COLUMNS).  chunks: (OUTDIR, seq_kmer, max_dna_len, max_signal_len) -- also write the training chunks of the solved reads
+    there (preprocess.Chunker), from the device buffers; their counters come back under "chunks"."""
     W, skip_penalty, trim_penalty, unknown_cost = _check_params(band_width, skip_penalty, trim_penalty, unknown_cost)
     seg = _check_segment(window_short, window_long, threshold_int(threshold_short), threshold_int(threshold_long))
     if int(max_samples) < 1 or int(trace_memory) < 1:
@@ -195,6 +201,12 @@ def eventalign_files(seqs, signals, model, out, band_width: int = DEFAULT_BAND_W
     if not cpu:
         import torch  # noqa: F401  (before the library: see engine.py)
     k, levels = read_model(str(model))
+    chunker = None
+    if chunks is not None:
+        from .preprocess import Chunker
+        if int(chunks[1]) != k:
+            raise click.ClickException(f"--seq-kmer {int(chunks[1])} is not the model's k = {k}")
+        chunker = Chunker(chunks[0], k, chunks[2], chunks[3], rna)
     table, has = level_ints(levels)
     sequences = read_sequences(str(seqs))
     cnt = dict(records=0, solved=0, unreached=0, refused=0, no_sequence=0, no_known_level=0, events=0, aligned_events=0, skipped_kmers=0,
@@ -216,7 +228,8 @@ def eventalign_files(seqs, signals, model, out, band_width: int = DEFAULT_BAND_W
         def flush(batch):
             t0 = time.perf_counter()
             r = _run_batch([b[2] for b in batch], [b[3] for b in batch], [b[4] for b in batch], W, skip_penalty, trim_penalty,
-                           unknown_cost, seg, cpu, device)
+                           unknown_cost, seg, cpu, device,
+                           chunks=None if chunker is None else (chunker, [b[5] for b in batch], [b[1] for b in batch]))
             t1 = time.perf_counter()
             for p, (rid, clean, sig, _, _, cal, no, _) in enumerate(batch):
                 c, ke, E = int(r["cost"][p]), r["k_events"][p], max(int(r["n_events"][p]), 0)
@@ -282,6 +295,8 @@ def eventalign_files(seqs, signals, model, out, band_width: int = DEFAULT_BAND_W
              solve_seconds=tot["solve_s"], format_seconds=tot["format_s"])
     if summary_out is not None:
         s["summary_out"] = str(summary_out)
+    if chunker is not None:
+        s["chunks"] = chunker.close("eventalign")
     logger.info("eventalign: %d record(s): %d solved, %d unreached, %d refused, %d without a sequence, %d without a known level; %d "
                 "event row(s) of %d aligned event(s), %d skipped k-mer(s); %d / %d sample(s) trimmed at head / tail; mean cost per "
                 "aligned event %s MAD", cnt["records"], cnt["solved"], cnt["unreached"], cnt["refused"], cnt["no_sequence"],

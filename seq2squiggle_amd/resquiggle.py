@@ -147,11 +147,13 @@ def scratch_bytes(n: int, K: int, band: int) -> int:
 
 
 def _run_batch(sig_list, lev_list, known_list, band: int, skip_penalty: int, unknown_cost: int, norm: bool, cpu: bool, device: int = 0,
-               threads: int = None, sums: bool = True):
+               threads: int = None, sums: bool = True, chunks=None):
     """One batch of reads.  sig_list: the stored int16 samples; lev_list: int16 levels per k-mer (any value where known_list is False).
     norm: samples are normalised by their own median / MAD and the levels by the median / MAD of the read's KNOWN levels, both by
     s2s_signal_median_mad / s2s_signal_normalise at scale 64 (else both enter as they are); k-mers without a level get S2S_RSQ_UNKNOWN.
-    -> dict(cost int64 [P], start / len int32 per read, S / Q int64 per read (raw samples), med / mad int32 [2 P]: samples, then levels)."""
+    -> dict(cost int64 [P], start / len int32 per read, S / Q int64 per read (raw samples), med / mad int32 [2 P]: samples, then levels).
+    chunks: (preprocess.Chunker, the records' calibrations, the cleaned sequences) -- the training chunks are packed from the device
+    buffers behind the sums; without it nothing else is uploaded or launched."""
     P = len(sig_list)
     known_recs = [np.asarray(l, np.int16)[np.asarray(kn, bool)] for l, kn in zip(lev_list, known_list)]
     full_recs = [np.where(np.asarray(kn, bool), np.asarray(l, np.int16), np.int16(0)).astype(np.int16) for l, kn in zip(lev_list, known_list)]
@@ -161,9 +163,10 @@ def _run_batch(sig_list, lev_list, known_list, band: int, skip_penalty: int, unk
         """The pool is 3 P records: samples, known levels, all levels -> l_offs int64 [P + 1]: the reads' slots of k-mers (the offsets
         of the third part from its start); s_offs int64 [P + 1]: their slots of decision scratch (device only)."""
         lens = np.diff(offs)
-        return (offs[2 * P:] - offs[2 * P]).astype(np.int64), slots([scratch_bytes(lens[p], lens[2 * P + p], band) for p in range(P)])
+        extra = chunks[0].tables(chunks[1], chunks[2]) if chunks is not None else []
+        return [(offs[2 * P:] - offs[2 * P]).astype(np.int64), slots([scratch_bytes(lens[p], lens[2 * P + p], band) for p in range(P)])] + extra
     B = Batch(list(sig_list) + known_recs + full_recs, tables, cpu, device, threads)
-    l_offs, s_offs = B.tables
+    l_offs, s_offs = B.tables[:2]
     KT, l0 = int(l_offs[-1]), int(B.host_offs[2 * P])
     res = B.alloc(cost=(np.int64, P), S=(np.int64, KT), Q=(np.int64, KT), start=(np.int32, KT), len=(np.int32, KT),
                   med=(np.int32, 2 * P), mad=(np.int32, 2 * P))
@@ -173,6 +176,8 @@ def _run_batch(sig_list, lev_list, known_list, band: int, skip_penalty: int, unk
            B.scratch(s_offs[-1]), device_only(B.table(1)), res.ptr("start"), res.ptr("len"))
     if sums:
         B.call("event_sums", B.samples, B.offs(), res.ptr("start"), res.ptr("len"), B.table(0), P, res.ptr("S"), res.ptr("Q"))
+    if chunks is not None:
+        chunks[0].pack(B, P, B.table(0), np.diff(l_offs), res.ptr("start"), res.ptr("len"), res.ptr("S"), res.ptr("Q"), B.table(2), B.table(3))
     r = res.fetch()
     cut = lambda a: [a[l_offs[p]:l_offs[p + 1]] for p in range(P)]      # noqa: E731
     return dict(cost=r["cost"], start=cut(r["start"]), len=cut(r["len"]), S=cut(r["S"]), Q=cut(r["Q"]), med=r["med"], mad=r["mad"])
@@ -252,7 +257,7 @@ def format_rows(rid: str, clean: str, k: int, start, length, S, Q, signal: np.nd
 def resquiggle_files(seqs, signals, model, out, band: int = DEFAULT_BAND, skip_penalty: int = DEFAULT_SKIP_PENALTY,
                      unknown_cost: int = DEFAULT_UNKNOWN_COST, rna: bool = False, intervals=None, with_samples: bool = False,
                      cpu: bool = False, device: int = 0, summary_out=None, max_samples: int = DEFAULT_MAX_SAMPLES,
-                     trace_memory: int = DEFAULT_TRACE_MEMORY) -> dict:
+                     trace_memory: int = DEFAULT_TRACE_MEMORY, chunks=None) -> dict:
     """Write OUT (EVENT_COLUMNS, plus `samples` with with_samples; records in the order of SIGNALS, rows by position) and return the
     counters: reads solved, unreached (no path: more than two k-mers per sample, or the band too narrow), refused (more than 2^22
     samples or k-mers, or a walk back that needs more than trace_memory on its own -- by read id, before the batch computes),
@@ -261,13 +266,20 @@ def resquiggle_files(seqs, signals, model, out, band: int = DEFAULT_BAND, skip_p
     samples pass max_samples or their decision scratch passes trace_memory (at least one read).  rna: the stored signal is reversed,
     so the levels are read back to front; `position` stays in read coordinates and start_idx falls as it rises.  intervals: restrict
     every record that has a row to [b_start, b_end) (read_intervals); rows come out in the record's own coordinates.
-    summary_out: one row per read (SUMMARY_COLUMNS)."""
+    summary_out: one row per read (SUMMARY_COLUMNS).  chunks: (OUTDIR, seq_kmer, max_dna_len, max_signal_len) -- also write the
+    training chunks of the solved reads there (preprocess.Chunker), from the device buffers; their counters come back under "chunks"."""
     band, skip_penalty, unknown_cost = _check_params(band, skip_penalty, unknown_cost)
     if int(max_samples) < 1 or int(trace_memory) < 1:
         raise ValueError("max_samples and trace_memory must be >= 1")
     if not cpu:
         import torch  # noqa: F401  (before the library: see engine.py)
     k, levels = read_model(str(model))
+    chunker = None
+    if chunks is not None:
+        from .preprocess import Chunker
+        if int(chunks[1]) != k:
+            raise click.ClickException(f"--seq-kmer {int(chunks[1])} is not the model's k = {k}")
+        chunker = Chunker(chunks[0], k, chunks[2], chunks[3], rna)
     table, has = level_ints(levels)
     sequences = read_sequences(str(seqs))
     iv = read_intervals(str(intervals)) if intervals is not None else None
@@ -288,7 +300,7 @@ def resquiggle_files(seqs, signals, model, out, band: int = DEFAULT_BAND, skip_p
         def flush(batch):
             t0 = time.perf_counter()
             r = _run_batch([b[2] for b in batch], [b[3] for b in batch], [b[4] for b in batch], band, skip_penalty, unknown_cost, True,
-                           cpu, device)
+                           cpu, device, chunks=None if chunker is None else (chunker, [b[5] for b in batch], [b[1] for b in batch]))
             t1 = time.perf_counter()
             P = len(batch)
             for p, (rid, clean, sig, _, _, cal, b0, b1, no, _) in enumerate(batch):
@@ -352,6 +364,8 @@ def resquiggle_files(seqs, signals, model, out, band: int = DEFAULT_BAND, skip_p
              solve_seconds=tot["solve_s"], format_seconds=tot["format_s"])
     if summary_out is not None:
         s["summary_out"] = str(summary_out)
+    if chunker is not None:
+        s["chunks"] = chunker.close("resquiggle")
     logger.info("resquiggle: %d record(s): %d solved, %d unreached, %d refused, %d without a sequence, %d without a known level; %d "
                 "event(s), %d skipped k-mer(s); mean cost per sample %s MAD", cnt["records"], cnt["solved"], cnt["unreached"],
                 cnt["refused"], cnt["no_sequence"], cnt["no_known_level"], cnt["events"], cnt["skipped_kmers"],

@@ -79,17 +79,18 @@ class device_only:
 
 class Fields:
     """One result buffer of named, typed fields (`Batch.alloc`), zeroed.  Every field starts at a multiple of 8 bytes; a field of
-    no items still owns one, so that its pointer is a valid one.  `buf`: the buffer, numpy or torch uint8."""
+    no items still owns one, so that its pointer is a valid one.  `buf`: the buffer, numpy or torch uint8.  zero=False: the buffer
+    is left uninitialised (outputs of which only a prefix is ever read: `prefix`)."""
 
-    def __init__(self, batch: "Batch", fields: dict):
+    def __init__(self, batch: "Batch", fields: dict, zero: bool = True):
         self.fields = {name: (np.dtype(dt), int(count)) for name, (dt, count) in fields.items()}
         starts, nbytes = _layout([dt.itemsize * max(count, 1) for dt, count in self.fields.values()])
         self._at = dict(zip(self.fields, starts))
         if batch.cpu:
-            self.buf = np.zeros(nbytes, np.uint8)
+            self.buf = (np.zeros if zero else np.empty)(nbytes, np.uint8)
             self._base = self.buf.ctypes.data
         else:
-            self.buf = batch.torch.zeros(nbytes, dtype=batch.torch.uint8, device=batch.where)
+            self.buf = (batch.torch.zeros if zero else batch.torch.empty)(nbytes, dtype=batch.torch.uint8, device=batch.where)
             self._base = self.buf.data_ptr()
 
     def ptr(self, name: str) -> int:
@@ -99,6 +100,12 @@ class Fields:
         """-> {name: numpy array}: views of the host buffer, or of the ONE device-to-host copy of the whole buffer."""
         raw = self.buf if isinstance(self.buf, np.ndarray) else self.buf.cpu().numpy()
         return {name: raw[self._at[name]:self._at[name] + dt.itemsize * count].view(dt) for name, (dt, count) in self.fields.items()}
+
+    def prefix(self, name: str, count: int) -> np.ndarray:
+        """The first `count` items of one field on the host: a copy down of these bytes alone."""
+        dt, have = self.fields[name]
+        part = self.buf[self._at[name]:self._at[name] + dt.itemsize * min(int(count), have)]
+        return (part.copy() if isinstance(part, np.ndarray) else part.cpu().numpy()).view(dt)
 
 
 class Batch:
@@ -145,6 +152,10 @@ class Batch:
     def alloc(self, **fields) -> Fields:
         """field=(dtype, count), ... -> one zeroed result buffer on the batch's side."""
         return Fields(self, fields)
+
+    def alloc_raw(self, **fields) -> Fields:
+        """`alloc` without the zeroing."""
+        return Fields(self, fields, zero=False)
 
     def scratch(self, nbytes) -> device_only:
         """Uninitialised device scratch of nbytes (at least 16; a number, or a function that returns it); nothing on the host, whose

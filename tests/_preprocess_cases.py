@@ -1,0 +1,119 @@
+"""Inputs of s2s_chunk_pack for the tests of `preprocess`: reads with given row lengths, both sample sources, and the edge cases
+the issue lists.  A case is a dict of host arrays; `ref` runs the numpy restatement on it, `run` the package (host twin or device)."""
+import numpy as np
+
+import _preprocess_ref as R
+
+GEOMETRIES = ((1, 1, 1), (5, 37, 6), (16, 250, 9), (64, 1024, 10))      # (te, ts, k)
+CAL = (8192.0, -243.0, 1437.976)
+KEYS = ("chunks", "chunks_lengths", "targets", "targets_lengths", "stdevs", "n_rows", "counters")
+
+
+def sums(case):
+    """S, Q of every slot as s2s_event_sums leaves them (0, 0 for a skipped slot or an interval outside the record)."""
+    S, Q = np.zeros(len(case["ev_start"]), np.int64), np.zeros(len(case["ev_start"]), np.int64)
+    for p, rec in enumerate(case["records"]):
+        for g in range(case["l_offs"][p], case["l_offs"][p + 1]):
+            st, ln = int(case["ev_start"][g]), int(case["ev_len"][g])
+            if st >= 0 and ln > 0 and st + ln <= len(rec):
+                x = rec[st:st + ln].astype(np.int64)
+                S[g], Q[g] = x.sum(), (x * x).sum()
+    case["S"], case["Q"] = S, Q
+    return case
+
+
+def make(rng, k, lens_per_read, letters=b"ACGT", gaps=True, tail=3):
+    """Reads whose slots have the given lengths (0: a skipped slot), laid left to right in their records with random gaps."""
+    records, start, length, kmers = [], [], [], []
+    for lens in lens_per_read:
+        lens = np.asarray(lens, np.int64)
+        gap = rng.integers(0, 3, len(lens)) if gaps else np.zeros(len(lens), np.int64)
+        st = np.cumsum(lens + gap) - lens
+        st[lens == 0] = -1
+        records.append(rng.integers(-3000, 3000, int((lens + gap).sum()) + tail).astype(np.int16))
+        start.append(st)
+        length.append(lens)
+        kmers.append(rng.choice(np.frombuffer(letters, np.uint8), (len(lens), k)))
+    case = dict(records=records, l_offs=np.concatenate([[0], np.cumsum([len(x) for x in length])]).astype(np.int64),
+                s_offs=np.concatenate([[0], np.cumsum([len(r) for r in records])]).astype(np.int64),
+                ev_start=np.concatenate(start + [np.zeros(0, np.int64)]).astype(np.int32),
+                ev_len=np.concatenate(length + [np.zeros(0, np.int64)]).astype(np.int32),
+                kmers=np.concatenate(kmers + [np.zeros((0, k), np.uint8)]).astype(np.uint8), k=k,
+                cal=np.tile(CAL, (len(records), 1)).reshape(-1))
+    case["flat"] = np.concatenate(records + [np.zeros(0, np.int16)])
+    case["pool"] = (case["flat"].astype(np.float64) / 7.0).astype(np.float32)
+    case["stdv"] = rng.random(len(case["ev_start"])).astype(np.float32)
+    return sums(case)
+
+
+def row_lengths(rng, n, te, ts):
+    """n row lengths around ts / te: some chunks pass ts, some do not."""
+    return rng.integers(1, max(2, 2 * ts // te + 1), n)
+
+
+def ref(case, source, te, ts, reverse=False, backwards=False):
+    if source == R.RAW:
+        return R.pack(case["flat"], case["s_offs"], R.RAW, case["l_offs"], case["ev_start"], case["ev_len"], case["S"], case["Q"],
+                      case["cal"], None, case["kmers"], case["k"], te, ts, reverse, backwards)
+    return R.pack(case["pool"], case["s_offs"], R.PA, case["l_offs"], case["ev_start"], case["ev_len"], None, None, None, case["stdv"],
+                  case["kmers"], case["k"], te, ts, reverse, backwards)
+
+
+def run(case, source, te, ts, reverse=False, backwards=False, cpu=True, **kw):
+    from seq2squiggle_amd import preprocess as PP
+    if source == R.RAW:
+        out = PP.pack(case["l_offs"], case["ev_start"], case["ev_len"], case["kmers"], case["k"], te, ts, records=case["records"],
+                      S=case["S"], Q=case["Q"], cal=case["cal"], reverse=reverse, backwards=backwards, cpu=cpu, **kw)
+    else:
+        out = PP.pack(case["l_offs"], case["ev_start"], case["ev_len"], case["kmers"], case["k"], te, ts, pool=case["pool"],
+                      s_offs=case["s_offs"], stdv=case["stdv"], reverse=reverse, backwards=backwards, cpu=cpu, **kw)
+    out["chunks"] = out["chunks"].view(np.uint16)
+    return out
+
+
+def same(a, b, what=""):
+    for key in KEYS:
+        x, y = a[key], b[key]
+        assert x.dtype == y.dtype and x.shape == y.shape, (what, key, x.dtype, y.dtype, x.shape, y.shape)
+        if x.tobytes() != y.tobytes():
+            bad = np.flatnonzero(x.reshape(-1).view(np.uint8 if x.dtype.kind == "f" else x.dtype) !=
+                                 y.reshape(-1).view(np.uint8 if y.dtype.kind == "f" else y.dtype))
+            raise AssertionError((what, key, "first difference at", int(bad[0]), "of", x.size))
+
+
+def standard(te, ts, k, seed=0):
+    """The six row counts of the issue in one batch, N letters among the k-mers (none all N: every slot is a row)."""
+    rng = np.random.default_rng([seed, te, ts, k])
+    case = make(rng, k, [row_lengths(rng, n, te, ts) for n in (0, 1, te - 1, te, te + 1, 3 * te)], letters=b"ACGTN")
+    case["kmers"][(case["kmers"] == ord("N")).all(axis=1), 0] = ord("A")
+    return case
+
+
+def edges(te, ts, k, seed=1):
+    """-> {name: case}: the specific cases of the issue at one geometry."""
+    rng = np.random.default_rng([seed, te, ts, k])
+    out = {}
+    even = np.full(te, ts // te)
+    even[:ts - even.sum()] += 1                     # te lengths that sum to ts (ts >= te at every geometry in use)
+    over = even.copy()
+    over[-1] += 1
+    out["exactly_ts_and_one_more"] = make(rng, k, [even, over, even])
+    out["row_longer_than_ts"] = make(rng, k, [[1, ts + 1, 1], [1] * te])
+    out["row_longer_than_int16"] = make(rng, k, [[1, 40000, 1], [1] * (te + 1), [33000] * min(te, 4)])
+    out["skipped_slots"] = make(rng, k, [[1, 0, 2, 0, 0, 1] * te, [0] * 5, [0, 1]])
+    c = make(rng, k, [[2, 1, 2, 1, 1], [1] * (2 * te)], tail=0, gaps=False)
+    c["ev_start"][1] = -1                           # before the record
+    c["ev_start"][4] += 1                           # its last sample would lie behind the record's end
+    c["ev_start"][5 + te] = 1 << 30
+    out["interval_outside"] = sums(c)
+    c = make(rng, k, [[1] * (te + 2), [2] * 3])
+    c["kmers"][0] = ord("N")                        # all N: dropped
+    c["kmers"][2] = ord("N")
+    c["kmers"][2, 0] = ord("A")                     # k - 1 N: kept (at k = 1 no N is left)
+    c["kmers"][3, k - 1] = ord("N")                 # one N: kept, that letter's one-hot row all zero (at k = 1 it is all N: dropped)
+    c["kmers"][te + 3] = ord("N")
+    out["n_letters"] = c
+    # (at te = 1 a read with rows always keeps its chunk of pads: there only a batch without rows keeps nothing)
+    out["keeps_nothing"] = make(rng, k, [[ts + 1] * 3, [ts] * (te + 1)] if te > 3 else [[0, 0, 0]])
+    out["no_rows"] = make(rng, k, [[0, 0], []])
+    return out

@@ -1,0 +1,76 @@
+"""s2s_chunk_pack on the device against its host twin, bit for bit (floats included): the cases of tests/test_preprocess_cpu.py, and
+the sizes at which the kernels of csrc/s2s_chunk.h take another trip -- more reads than one block of the scan, more chunks than 64
+trips of it, one read far longer than all others (the pooled split), a full wave of rows, and a chunk whose first row alone passes
+ts.  All tiny: each takes well under a second of device time."""
+import numpy as np
+import pytest
+
+import _preprocess_cases as C
+import _preprocess_ref as R
+
+pytestmark = pytest.mark.gpu
+
+
+def both(case, source, te, ts, **kw):
+    host = C.run(case, source, te, ts, cpu=True, **kw)
+    dev = C.run(case, source, te, ts, cpu=False, **kw)
+    C.same(host, dev, (source, te, ts, kw))
+    return host
+
+
+@pytest.mark.parametrize("te,ts,k", C.GEOMETRIES)
+def test_device_equals_host_on_the_standard_batch(te, ts, k):
+    case = C.standard(te, ts, k)
+    for source in (R.RAW, R.PA):
+        for reverse in (False, True):
+            for backwards in (False, True):
+                both(case, source, te, ts, reverse=reverse, backwards=backwards)
+
+
+@pytest.mark.parametrize("te,ts,k", C.GEOMETRIES)
+def test_device_equals_host_on_the_edge_cases(te, ts, k):
+    for name, case in C.edges(te, ts, k).items():
+        for source in (R.RAW, R.PA):
+            r = both(case, source, te, ts, reverse=(source == R.PA))
+            if name in ("keeps_nothing", "no_rows"):
+                assert r["counters"][1] == 0 and r["targets"].shape == (0, ts)
+
+
+def test_more_reads_than_one_scan_block():
+    rng = np.random.default_rng(3)
+    case = C.make(rng, 6, [rng.integers(1, 9, rng.integers(1, 4)) for _ in range(3000)], letters=b"ACGTN")
+    r = both(case, R.RAW, 5, 37)
+    assert r["counters"][0] == 3000 and 0 < r["counters"][1] <= 3000
+    both(case, R.PA, 5, 37, backwards=True)
+
+
+def test_more_chunks_than_64_trips_of_the_scan():
+    rng = np.random.default_rng(4)
+    case = C.make(rng, 1, [rng.integers(1, 3, 7000) for _ in range(10)], gaps=False)
+    r = both(case, R.RAW, 1, 1)
+    assert r["counters"][0] == 70010 and 10 < r["counters"][1] < 70010           # rows of 2 samples are dropped, the pad chunks kept
+
+
+def test_one_long_read_beside_short_ones():
+    rng = np.random.default_rng(5)
+    lens = [rng.integers(1, 30, rng.integers(1, 40)) for _ in range(50)]
+    lens.insert(17, rng.integers(8, 24, 200000))
+    case = C.make(rng, 9, lens, letters=b"ACGTN", gaps=False)
+    r = both(case, R.RAW, 16, 250)
+    assert r["n_rows"][17] > 190000 and r["counters"][1] > 1000
+    both(case, R.PA, 16, 250, reverse=True, backwards=True)
+
+
+def test_a_full_wave_of_rows():
+    rng = np.random.default_rng(6)
+    case = C.make(rng, 10, [[16] * 64, [16] * 128, [16] * 63 + [17]])
+    r = both(case, R.RAW, 64, 1024, reverse=True)
+    # every read ends with a chunk of 64 pads; the read with a row of 17 samples keeps that chunk alone
+    assert list(r["targets_lengths"]) == [1024, 64, 1024, 1024, 64, 64]
+
+
+def test_first_row_alone_exceeds_ts():
+    rng = np.random.default_rng(7)
+    case = C.make(rng, 9, [[251] + [1] * 15 + [3] * 16, [5000] + [1] * 40])
+    r = both(case, R.RAW, 16, 250)
+    assert r["counters"][0] == 6 and r["counters"][1] == 4

@@ -1,5 +1,7 @@
 """Inputs of s2s_chunk_pack for the tests of `preprocess`: reads with given row lengths, both sample sources, and the edge cases
 the issue lists.  A case is a dict of host arrays; `ref` runs the numpy restatement on it, `run` the package (host twin or device)."""
+import os
+
 import numpy as np
 
 import _preprocess_ref as R
@@ -51,12 +53,12 @@ def row_lengths(rng, n, te, ts):
     return rng.integers(1, max(2, 2 * ts // te + 1), n)
 
 
-def ref(case, source, te, ts, reverse=False, backwards=False):
+def ref(case, source, te, ts, reverse=False, backwards=False, capacity=None):
     if source == R.RAW:
         return R.pack(case["flat"], case["s_offs"], R.RAW, case["l_offs"], case["ev_start"], case["ev_len"], case["S"], case["Q"],
-                      case["cal"], None, case["kmers"], case["k"], te, ts, reverse, backwards)
+                      case["cal"], None, case["kmers"], case["k"], te, ts, reverse, backwards, capacity)
     return R.pack(case["pool"], case["s_offs"], R.PA, case["l_offs"], case["ev_start"], case["ev_len"], None, None, None, case["stdv"],
-                  case["kmers"], case["k"], te, ts, reverse, backwards)
+                  case["kmers"], case["k"], te, ts, reverse, backwards, capacity)
 
 
 def run(case, source, te, ts, reverse=False, backwards=False, cpu=True, **kw):
@@ -79,6 +81,94 @@ def same(a, b, what=""):
             bad = np.flatnonzero(x.reshape(-1).view(np.uint8 if x.dtype.kind == "f" else x.dtype) !=
                                  y.reshape(-1).view(np.uint8 if y.dtype.kind == "f" else y.dtype))
             raise AssertionError((what, key, "first difference at", int(bad[0]), "of", x.size))
+
+
+# ------------------------------------------------------------------ the goldens of the reference's own chunk cutting
+def golden(te, ts, k):
+    """tests/golden/preprocess_<te>x<ts>x<k>.npz (tools/make_goldens.py preprocess): the reference's own functions on a table."""
+    with np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", f"preprocess_{te}x{ts}x{k}.npz")) as z:
+        return {key: z[key] for key in z.files}
+
+
+def golden_case(g, only=None, as_listed=False):
+    """The table of a golden as the arrays of the pa source: the reads in order of first appearance (only: that read alone), the
+    rows of a read by position (as_listed: in the order of the table's lines), a row's interval where its samples lie in the pool,
+    every text parsed as a double and rounded to fp32.  A parser of its own: nothing of the package reads the table here."""
+    k = int(g["geometry"][2])
+    reads = {}
+    for line in g["table"].tobytes().decode("ascii").split("\n")[1:]:
+        if line:
+            v = line.split("\t")
+            assert int(v[4]) - int(v[3]) == len(v[7].split(",")) and len(v[2]) == k
+            reads.setdefault(v[0], []).append((int(v[1]), v[2], np.float32(float(v[6])), [np.float32(float(x)) for x in v[7].split(",")]))
+    assert list(reads) == [str(n) for n in g["names"]]
+    kmers, lens, stdv, pool, counts = [], [], [], [], []
+    for name, rows in reads.items():
+        if only is not None and name != only:
+            continue
+        assert len({r[0] for r in rows}) == len(rows)                        # positions are unique: no tie for any sort to break
+        rows = rows if as_listed else sorted(rows, key=lambda r: r[0])
+        counts.append(len(rows))
+        for _, kmer, dev, x in rows:
+            kmers.append(kmer)
+            lens.append(len(x))
+            stdv.append(dev)
+            pool.extend(x)
+    lens = np.array(lens, np.int64)
+    l_offs = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    return dict(k=k, l_offs=l_offs, s_offs=np.concatenate([[0], np.cumsum(lens)])[l_offs].astype(np.int64),
+                ev_start=np.concatenate([np.cumsum(r) - r for r in np.split(lens, l_offs[1:-1])]).astype(np.int32), ev_len=lens.astype(np.int32),
+                kmers=np.frombuffer("".join(kmers).encode("ascii"), np.uint8).reshape(-1, k).copy(), pool=np.array(pool, np.float32),
+                stdv=np.array(stdv, np.float32))
+
+
+def golden_rows_of(g, name):
+    """The rows of the reference's filtered arrays that come from read `name`: its chunks among the unfiltered ones, then the filter."""
+    i = [str(n) for n in g["names"]].index(name)
+    first = int(g["chunks_per_read"][:i].sum())
+    return np.flatnonzero((g["kept"] >= first) & (g["kept"] < first + int(g["chunks_per_read"][i])))
+
+
+def same_as_golden(g, rna, got, rows=None, what=""):
+    """got (the arrays of C.run, or the files of the command) against the reference's arrays, after the documented mechanical mappings
+    and nothing else: chunks bit for bit as fp16; the two lengths as integers (the reference: int64 and int16); targets bit for bit;
+    stdevs = the reference's float64 [N, 1, 1, te] squeezed and cast to float32."""
+    te, ts, k = (int(v) for v in g["geometry"])
+    want = {kind: g[("rna_" if rna else "dna_") + kind] for kind in ("chunks", "chunks_lengths", "targets", "targets_lengths", "stdevs")}
+    if rows is not None:
+        want = {kind: v[rows] for kind, v in want.items()}
+    N = len(want["targets_lengths"])
+    assert want["chunks"].dtype == np.float16 and want["chunks"].shape == (N, te, k, 5) and want["targets"].dtype == np.float32
+    chunks = np.asarray(got["chunks"])
+    assert chunks.dtype in (np.float16, np.uint16) and chunks.shape == (N, te, k, 5), (what, chunks.dtype, chunks.shape)
+    assert chunks.view(np.uint16).tobytes() == want["chunks"].view(np.uint16).tobytes(), (what, "chunks")
+    for kind in ("chunks_lengths", "targets_lengths"):
+        assert got[kind].dtype.kind == "i" and want[kind].dtype.kind == "i" and got[kind].shape == want[kind].shape, (what, kind)
+        assert np.array_equal(got[kind].astype(np.int64), want[kind].astype(np.int64)), (what, kind)
+    assert got["targets"].dtype == np.float32 and got["targets"].shape == (N, ts) == want["targets"].shape, (what, "targets")
+    assert got["targets"].tobytes() == want["targets"].tobytes(), (what, "targets")
+    dev = want["stdevs"].reshape(N, te).astype(np.float32)
+    assert got["stdevs"].dtype == np.float32 and got["stdevs"].shape == (N, te) and got["stdevs"].tobytes() == dev.tobytes(), (what, "stdevs")
+    return N
+
+
+def command(g, outdir, rna, cpu):
+    """`preprocess TABLE OUTDIR` on the golden's table text -> (the arrays of the files written, the JSON summary)."""
+    import json
+
+    from click.testing import CliRunner
+
+    from seq2squiggle_amd import cli, evaluate
+    te, ts, k = (int(v) for v in g["geometry"])
+    os.makedirs(outdir, exist_ok=True)
+    path = os.path.join(str(outdir), "events.tsv")
+    with open(path, "wb") as f:
+        f.write(g["table"].tobytes())
+    args = ["preprocess", path, os.path.join(str(outdir), "out"), "--seq-kmer", k, "--max-dna-len", te, "--max-signal-len", ts, "--json"]
+    r = CliRunner().invoke(cli.main, [str(a) for a in args + (["--rna"] if rna else []) + (["--cpu"] if cpu else [])], catch_exceptions=False)
+    assert r.exit_code == 0, r.output
+    files = evaluate.discover(os.path.join(str(outdir), "out"))
+    return ({kind: np.concatenate([np.load(f[kind]) for f in files]) for kind in evaluate.KINDS}, json.loads(r.output.strip().splitlines()[-1]))
 
 
 def standard(te, ts, k, seed=0):

@@ -36,9 +36,14 @@ def pa_raw(x, cal):
     return ((x.astype(np.float64) + offset) * rng / digitisation).astype(np.float32)
 
 
-def pack(pool, s_offs, source, l_offs, ev_start, ev_len, S, Q, cal, stdv, kmers, k, te, ts, reverse=False, backwards=False):
+def pack(pool, s_offs, source, l_offs, ev_start, ev_len, S, Q, cal, stdv, kmers, k, te, ts, reverse=False, backwards=False, capacity=None):
     """-> dict(chunks uint16 [N, te, k, 5] (fp16 bits), chunks_lengths int64 [N, te], targets float32 [N, ts], targets_lengths int64
-    [N], stdevs float32 [N, te], n_rows int32 [P], counters int64 [3]: formed, kept, all-N rows)."""
+    [N], stdevs float32 [N, te], n_rows int32 [P], counters int64 [3]: formed, kept, all-N rows).
+    capacity (the header's rule for the device entry): "chunks beyond chunk_capacity are not formed (counters[0] still counts them)" --
+    of the chunks in read order, then chunk order, only the first `capacity` exist; the kept ones among them come out and are what
+    counters[1] counts; n_rows and counters[0] are those of the whole batch.
+    Offsets (the header's definition of a row): a read has rows only if 0 <= l_offs[p] <= l_offs[p+1] <= slots and 0 <= s_offs[p] <=
+    s_offs[p+1] <= total, with slots = len(ev_len) and total = len(pool)."""
     P = len(l_offs) - 1
     kmers = np.asarray(kmers, np.uint8).reshape(-1, k)
     out = {"chunks": [], "chunks_lengths": [], "targets": [], "targets_lengths": [], "stdevs": []}
@@ -46,6 +51,8 @@ def pack(pool, s_offs, source, l_offs, ev_start, ev_len, S, Q, cal, stdv, kmers,
     for p in range(P):
         lo, hi, s0 = int(l_offs[p]), int(l_offs[p + 1]), int(s_offs[p])
         n_samples = int(s_offs[p + 1]) - s0
+        if not (0 <= lo <= hi <= len(ev_len) and 0 <= s0 <= s0 + n_samples <= len(pool)):
+            continue
         rows, all_n = rows_of_read(ev_start[lo:hi], ev_len[lo:hi], n_samples, kmers[lo:hi], backwards)
         all_n_total += all_n
         n = n_rows[p] = len(rows)
@@ -70,7 +77,7 @@ def pack(pool, s_offs, source, l_offs, ev_start, ev_len, S, Q, cal, stdv, kmers,
         for a in range(0, len(letters), te):
             formed += 1
             tl = sum(lengths[a:a + te])
-            if tl > ts:
+            if tl > ts or (capacity is not None and formed > capacity):
                 continue
             hot = np.zeros((te, k, 5), np.uint16)
             for r, word in enumerate(letters[a:a + te]):

@@ -74,3 +74,24 @@ def test_first_row_alone_exceeds_ts():
     case = C.make(rng, 9, [[251] + [1] * 15 + [3] * 16, [5000] + [1] * 40])
     r = both(case, R.RAW, 16, 250)
     assert r["counters"][0] == 6 and r["counters"][1] == 4
+
+
+# ------------------------------------------------------------------ the reference's own chunk cutting (tests/golden/preprocess_*.npz)
+@pytest.mark.parametrize("te,ts,k", C.GEOMETRIES)
+def test_device_equals_the_reference_goldens(te, ts, k, tmp_path):
+    """The `preprocess` command on the golden's table text and `pack` on its arrays, on the device, against what the reference's own
+    functions gave (tests/test_preprocess_golden_cpu.py holds the host to the same files): every byte, after the documented mappings.
+    The read listed with falling positions goes in alone, its slots in the table's order, with backwards=True."""
+    g = C.golden(te, ts, k)
+    case = C.golden_case(g)
+    falling = str(g["falling_read"])
+    listed, rows = C.golden_case(g, only=falling, as_listed=True), C.golden_rows_of(g, falling)
+    for rna in (False, True):
+        got, s = C.command(g, tmp_path / ("rna" if rna else "dna"), rna, cpu=False)
+        assert C.same_as_golden(g, rna, got, what=("command", rna)) == len(g["kept"]) > 0
+        assert (s["chunks_formed"], s["chunks_kept"], s["all_n_rows"]) == (len(g["t_lengths"]), len(g["kept"]), 3)
+        got = C.run(case, R.PA, te, ts, reverse=rna, cpu=False)
+        C.same_as_golden(g, rna, got, what=("pack", rna))
+        assert got["counters"].tolist() == [len(g["t_lengths"]), len(g["kept"]), 3]
+        got = C.run(listed, R.PA, te, ts, reverse=rna, backwards=True, cpu=False)
+        assert C.same_as_golden(g, rna, got, rows=rows, what=("pack backwards", rna)) == len(rows) >= 2

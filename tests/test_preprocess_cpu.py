@@ -178,7 +178,7 @@ def test_command_equals_the_restatement_whatever_the_batching(table):
     want = restated(reads, 4, 5, 37)
     got = whole(d / "all")
     assert got["chunks"].dtype == np.float16 and got["chunks"].shape == (len(want["targets"]), 5, 4, 5)
-    assert got["stdevs"].dtype == np.float32 and got["stdevs"].shape == (len(want["targets"]), 5)       # [N, te], not the reference's [N, 1, te]
+    assert got["stdevs"].dtype == np.float32 and got["stdevs"].shape == (len(want["targets"]), 5)       # [N, te], not the reference's [N, 1, 1, te]
     assert got["targets_lengths"].dtype == np.int64 and got["chunks_lengths"].dtype == np.int64
     for kind in evaluate.KINDS:
         assert got[kind].view(want[kind].dtype).tobytes() == want[kind].tobytes(), kind

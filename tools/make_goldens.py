@@ -9,7 +9,7 @@ modules / predict_step / export / BLOW5Writer.save with *injected* random
 variates.  Outputs (data only -- inputs and expected outputs) go to
 tests/golden/.  Nothing of the reference's source text is written.
 
-    python tools/make_goldens.py [pod5 | mixed16 | wide]
+    python tools/make_goldens.py [pod5 | mixed16 | wide | preprocess]
 """
 import os
 import sys
@@ -588,8 +588,155 @@ def wide_goldens():
               "bytes", os.path.getsize(os.path.join(OUT, f"wide_{tag}.npz")))
 
 
+# ----------------------------------------------------------------------------- preprocess
+TABLE_HEAD = "read_name\tposition\tmodel_kmer\tstart_idx\tend_idx\tevent_level_mean\tevent_stdv\tsamples"
+
+
+def save_npz(path, arrays):
+    """np.savez_compressed with every member dated 1980-01-01: the same arrays give the same bytes."""
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for name, a in arrays.items():
+            info = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            with z.open(info, "w", force_zip64=True) as f:
+                np.lib.format.write_array(f, np.asanyarray(a), allow_pickle=False)
+
+
+def preprocess_table(te, ts, k):
+    """-> (the table's text, the name of the read laid with falling positions, the largest sample total of a chunk): the reads of one
+    golden.  Why every choice is what it is:
+      * one frame per read (partition_by=True): the reference's route that cuts chunks inside a read, the one our entry follows;
+      * positions are unique inside a read and have gaps: the reference's sort by position has no ties to break (the stand-in's
+        tie order cannot show), and a position is never usable as an index;
+      * sample texts are multiples of 0.125 printed %.3f, event_stdv a multiple of 0.0625 printed %.4f: exact in fp32, so polars'
+        cast, the stand-in's and the package's double-then-fp32 parse give the same bits;
+      * end_idx - start_idx is the row's sample count and >= 1 (a row without samples is undefined in the reference: its samples
+        text is empty while its length is not counted; it is left out); start_idx has gaps, which nothing may read;
+      * a chunk holds fewer than 32,768 samples: pad_lengths' int16 lengths neither wrap nor (numpy 2) raise;
+      * no read has only all-N rows: the reference would run process_df on an empty frame, where the stand-in, not polars, would
+        decide what an empty column is.
+    The reads: 1, te - 1, te, te + 1 and 3 te rows; a chunk of exactly ts samples and one of ts + 1; a row alone longer than ts;
+    k-mers with some N, all-N rows at both ends and in the middle of a read; one read listed with position falling while start_idx
+    rises (the reverse strand of `predict --events`); one read listed in shuffled order; the reads' lines interleaved, first
+    appearances not in name order.  Chunks are made to pass or miss ts in turn, so that both kinds are many."""
+    rng = np.random.default_rng([31, te, ts, k])
+    b = max(1, ts // te)
+
+    def group(m, keep=True, total=None):
+        """The lengths of m rows that share a chunk with te - m pads: at most ts samples in all, more than ts, or exactly `total`."""
+        if total is None and keep:
+            return rng.integers(1, b + 1, m)
+        total = ts + int(rng.integers(1, 4)) if total is None else total
+        ln = np.ones(m, np.int64)
+        np.add.at(ln, rng.integers(0, m, total - (te - m) - m), 1)
+        return ln
+
+    def kmers(n, some_n=()):
+        out = rng.choice(list("ACGT"), (n, k))
+        for j in some_n:
+            out[j, rng.integers(0, k, max(1, k // 3))] = "N"
+        return ["".join(r) for r in out]
+
+    reads = {"solo": group(1), "full": group(te, total=ts), "full_and_one": np.concatenate([group(te, total=ts + 1), group(1)]),
+             "three": np.concatenate([group(te, False), group(te), group(te, False)]),
+             "long_row": np.array([1, ts + 1 + int(rng.integers(0, 3)), 1]),
+             "falling": np.concatenate([group(te), group(te, False), group(1)])}
+    if te > 1:
+        reads["short"] = group(te - 1, False)
+    rows = {name: list(zip(kmers(len(ln)), ln.tolist())) for name, ln in reads.items()}
+    ln = group(te, False)                            # te rows between and around three all-N rows; some N in two of the rows
+    real = list(zip(kmers(te, some_n=sorted({0, te - 1}) if k > 1 else ()), ln.tolist()))
+    mid = (te + 1) // 2
+    n_row = lambda: ("N" * k, int(rng.integers(1, b + 2)))      # noqa: E731
+    rows["with_n"] = [n_row()] + real[:mid] + [n_row()] + real[mid:] + [n_row()]
+    biggest = 0
+    lines = {}
+    for name, rs in rows.items():
+        pos = int(rng.integers(0, 1000)) + np.cumsum(rng.integers(1, 4, len(rs)))
+        order = list(range(len(rs)))
+        if name == "falling":
+            order = order[::-1]
+        if name == "three":
+            order = [int(i) for i in rng.permutation(len(rs))]
+        at, mine = int(rng.integers(0, 50)), []
+        for i in order:
+            kmer, n = rs[i]
+            x = rng.integers(320, 1200, n) / 8.0
+            at += int(rng.integers(0, 3))
+            mine.append(f"{name}\t{pos[i]}\t{kmer}\t{at}\t{at + n}\t{x.mean():.4f}\t{rng.integers(1, 200) / 16.0:.4f}\t" +
+                        ",".join("%.3f" % v for v in x))
+            at += n
+        lines[name] = mine
+        real_ln = [n for kmer, n in rs if kmer != "N" * k]
+        biggest = max([biggest] + [sum(real_ln[a:a + te]) + te for a in range(0, len(real_ln), te)])
+    names = sorted(lines, key=lambda s: rng.random())
+    left = {name: list(lines[name]) for name in names}
+    table = [TABLE_HEAD]
+    while left:
+        name = names[int(rng.integers(0, len(names)))]
+        if name in left:
+            table.append(left[name].pop(0))
+            if not left[name]:
+                del left[name]
+    return "\n".join(table) + "\n", "falling", biggest
+
+
+def preprocess_goldens():
+    """The reference's own chunk cutting -> tests/golden/preprocess_<te>x<ts>x<k>.npz.  polars is not in the image: the reference's
+    preprocess.py is imported over tools/polars_standin.py, and its split_eventtable_in_chunks(partition_by=True) (process_df,
+    get_dna2signal_idxs, get_chunks, regular_break_points, one_hot_encode, pad_lengths, ChunkDataSet) -> typical_indices -> filter_chunks
+    -> save_chunks run unmodified.  process_events is not used (it passes `parition_by=`, a TypeError), and typical_indices' result goes
+    to filter_chunks as it is, where process_events would permute it at random.  Per file: the table's bytes, the reads in order of
+    first appearance with the chunks the reference cuts from each alone, the unfiltered t_lengths, the kept indices, and for rna in
+    (False, True) the five arrays as save_chunks writes them, dtypes and shapes untouched."""
+    import tempfile
+    here = os.path.dirname(os.path.abspath(__file__))
+    sys.path.insert(0, here)
+    sys.path.insert(0, os.path.join(os.path.dirname(here), "tests"))
+    import polars_standin as PS
+    sys.modules["polars"] = PS
+    import seq2squiggle.preprocess as RP
+    from _preprocess_cases import GEOMETRIES
+    for te, ts, k in GEOMETRIES:
+        text, falling, biggest = preprocess_table(te, ts, k)
+        assert biggest < 32768, biggest
+        cfg = dict(max_dna_len=te, max_signal_len=ts, seq_kmer=k)
+        body = text.split("\n")[1:-1]
+        names = list(dict.fromkeys(line.split("\t")[0] for line in body))
+        assert names != sorted(names) and any(a.split("\t")[0] != b.split("\t")[0] for a, b in zip(body, body[1:]))
+        per_read = [len(RP.split_eventtable_in_chunks(PS.from_table_text("\n".join([TABLE_HEAD] + [x for x in body if x.split("\t")[0] == n]) + "\n"),
+                                                      cfg, None, partition_by=True, rna=False)) for n in names]
+        out = {"table": np.frombuffer(text.encode("ascii"), np.uint8), "geometry": np.array([te, ts, k], np.int64), "names": np.array(names),
+               "falling_read": np.array(falling), "chunks_per_read": np.array(per_read, np.int64)}
+        for rna in (False, True):
+            ds = RP.split_eventtable_in_chunks(PS.from_table_text(text), cfg, None, partition_by=True, rna=rna)
+            t_all = np.array(ds.t_lengths)
+            idx = RP.typical_indices(ds.t_lengths, ts)
+            kept = RP.filter_chunks(ds, idx, ts)
+            with tempfile.TemporaryDirectory() as d:
+                RP.save_chunks(kept, d)
+                for kind in ("chunks", "chunks_lengths", "targets", "targets_lengths", "stdevs"):
+                    out[("rna_" if rna else "dna_") + kind] = np.load(os.path.join(d, kind + ".npy"))
+            if rna:
+                assert np.array_equal(out["t_lengths"], t_all) and np.array_equal(out["kept"], idx)
+            out["t_lengths"], out["kept"] = t_all, np.asarray(idx)
+        N, n_kept = len(out["t_lengths"]), len(out["kept"])
+        assert N == sum(per_read) and 4 * n_kept >= N and 4 * (N - n_kept) >= N, (N, n_kept)      # both kinds: a quarter at least
+        assert ts in out["t_lengths"] and ts + 1 in out["t_lengths"]
+        assert ts == 1 or not np.array_equal(out["dna_targets"], out["rna_targets"])     # (at ts = 1 a kept row has one sample to reverse)
+        path = os.path.join(OUT, f"preprocess_{te}x{ts}x{k}.npz")
+        save_npz(path, out)
+        print(f"preprocess {te}/{ts}/{k}: {len(body)} rows of {len(names)} reads, {N} chunks, {n_kept} kept; stdevs",
+              out["dna_stdevs"].shape, out["dna_stdevs"].dtype, "targets_lengths", out["dna_targets_lengths"].dtype, "chunks_lengths",
+              out["dna_chunks_lengths"].dtype, "bytes", os.path.getsize(path))
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
+    if sys.argv[1:] == ["preprocess"]:    # only the chunk-cutting goldens (the reference's preprocess.py over tools/polars_standin.py)
+        preprocess_goldens()
+        return
     if sys.argv[1:] == ["wide"]:          # only the wide goldens (they read the committed checkpoints)
         wide_goldens()
         return

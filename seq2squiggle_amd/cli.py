@@ -616,83 +616,128 @@ def compare(a, b, out, band, normalise, by_order, max_samples, cpu, as_json, pat
                    f"{a}, {s['unpaired_b']} of {s['records_b']} in {b}]  dtw_per_sample mean {fmt(s['mean_dtw_per_sample'])}  "
                    f"median {fmt(s['median_dtw_per_sample'])}")
 
+
+def _options(*decorators):
+    """Several click decorators as one; --help lists their options in the order given."""
+    def stack(f):
+        for d in reversed(decorators):
+            f = d(f)
+        return f
+    return stack
+
+
+def _in_range(value, lo, hi, hint, lo_name=None) -> None:
+    """A BadParameter that names the option `hint` unless lo <= value <= hi (hi None: no upper end)."""
+    if value < lo or (hi is not None and value > hi):
+        raise click.BadParameter(f"must be >= {lo}" if hi is None else f"must be {lo_name or lo}..{hi}", param_hint=hint)
+
+
+def _echo_summary(s: dict, as_json: bool, text: str) -> None:
+    """The end of a signal command: the summary as one JSON object with --json, else the text line."""
+    import json
+    click.echo(json.dumps(s) if as_json else text)
+
+
+def _detector_options(detector: str, short_tail: str, long_tail: str):
+    """The four options of segment's event detector, for `segment` and `eventalign`."""
+    return _options(
+        click.option("--window-short", default=3, type=int, show_default=True, help=f"Window of the short {detector} in samples (1..32)."),
+        click.option("--window-long", default=6, type=int, show_default=True, help=f"Window of the long {detector} in samples (short..32)."),
+        click.option("--threshold-short", default=1.4, type=float, show_default=True, help=f"Threshold t of the short detector{short_tail}"),
+        click.option("--threshold-long", default=9.0, type=float, show_default=True, help=f"Threshold t of the long detector{long_tail}"))
+
+
+def _check_detector(window_short, window_long, threshold_short, threshold_long) -> None:
+    from . import segment as SEG
+    _in_range(window_short, 1, SEG.MAX_WINDOW, "--window-short")
+    _in_range(window_long, window_short, SEG.MAX_WINDOW, "--window-long", "--window-short")
+    for hint, t in (("--threshold-short", threshold_short), ("--threshold-long", threshold_long)):
+        try:
+            SEG.threshold_int(t)
+        except ValueError as e:
+            raise click.BadParameter(str(e), param_hint=hint)
+
+
+def _aligner_options(rows: str, unit: str, trace_memory: str, band, after_skip=(), after_rna=()):
+    """The options of the commands that align reads to a pore model (pore_align.align_files), in --help's order.  rows / unit / trace_memory:
+    the command's own words in the help of --samples, of --skip-penalty and --unknown-cost, and of --trace-memory; band, after_skip,
+    after_rna: its own options."""
+    return _options(
+        click.argument("seqs", type=click.Path(dir_okay=False, exists=True)),
+        click.argument("signals", type=click.Path(dir_okay=False)),
+        click.option("--kmer-model", "model", required=True, type=click.Path(dir_okay=False, exists=True),
+                     help="Pore model: the file `predict --kmer-model` writes, or a nanopolish-style table with the columns kmer and level_mean."),
+        click.option("-o", "--out", required=True, type=click.Path(dir_okay=False), help="Output event table (.events.tsv)."),
+        click.option("--samples", "with_samples", is_flag=True, help=f"Add the `samples` column: every {rows} samples in pA."),
+        band,
+        click.option("--skip-penalty", default=128, type=int, show_default=True,
+                     help=f"Cost of a k-mer that gets no {unit}, in 1/64 MAD.  The default, two MADs, is a choice, not a measurement."),
+        *after_skip,
+        click.option("--unknown-cost", default=64, type=int, show_default=True,
+                     help=f"Cost per {unit} on a k-mer the model has no level for (or with a letter outside ACGT), in 1/64 MAD.  The "
+                          "default, one MAD, is a choice, not a measurement."),
+        click.option("--rna", is_flag=True, help="The stored signal is reversed (RNA profiles): read the levels back to front; position stays in "
+                                                 "read coordinates and start_idx falls as it rises, as in predict --events."),
+        *after_rna,
+        click.option("--cpu", is_flag=True, help="Compute on host threads instead of the GPU (the same bytes)."),
+        click.option("--json", "as_json", is_flag=True, help="Print the summary as one JSON object."),
+        click.option("--summary", "summary_out", default=None, type=click.Path(dir_okay=False), help="Also write one row per read here (.tsv)."),
+        click.option("--max-samples", default=1 << 27, type=int, show_default=True, help="Samples per batch."),
+        click.option("--trace-memory", default=8 << 30, type=int, show_default=True, help=trace_memory),
+        click.option("--chunks", "chunks_out", default=None, type=click.Path(file_okay=False),
+                     help="Also write the training chunks of the solved reads under this directory (what `preprocess` makes of the table, "
+                          "cut on the device from the alignment itself; no text in between)."),
+        click.option("-y", "--config", default=None, type=click.Path(dir_okay=False, exists=True),
+                     help="With --chunks: YAML configuration file with seq_kmer, max_dna_len and max_signal_len."),
+        click.option("--seq-kmer", default=None, type=int, help="k of the chunks' k-mers (default: seq_kmer of the config)."),
+        click.option("--max-dna-len", default=None, type=int, help="k-mers per chunk, 1..64 (default: max_dna_len of the config)."),
+        click.option("--max-signal-len", default=None, type=int, help="Samples per chunk, 1..1024 (default: max_signal_len of the config)."))
+
+
+def _aligner_start(command: str, signals, max_samples, trace_memory, cpu) -> None:
+    """The checks both aligners begin with, and torch before the library."""
+    _signal_files(command, signals)
+    _in_range(max_samples, 1, None, "--max-samples")
+    _in_range(trace_memory, 1, None, "--trace-memory")
+    if not cpu:
+        import torch  # noqa: F401  (before the library: see engine.py)
+
+
 @main.command()
-@click.argument("seqs", type=click.Path(dir_okay=False, exists=True))
-@click.argument("signals", type=click.Path(dir_okay=False))
-@click.option("--kmer-model", "model", required=True, type=click.Path(dir_okay=False, exists=True),
-              help="Pore model: the file `predict --kmer-model` writes, or a nanopolish-style table with the columns kmer and level_mean.")
-@click.option("-o", "--out", required=True, type=click.Path(dir_okay=False), help="Output event table (.events.tsv).")
-@click.option("--samples", "with_samples", is_flag=True, help="Add the `samples` column: every event's samples in pA.")
-@click.option("--band", default=512, type=int, show_default=True,
-              help="Half width of the band in k-mers around the diagonal.  A choice, not a measurement.")
-@click.option("--skip-penalty", default=128, type=int, show_default=True,
-              help="Cost of a k-mer that gets no sample, in 1/64 MAD.  The default, two MADs, is a choice, not a measurement.")
-@click.option("--unknown-cost", default=64, type=int, show_default=True,
-              help="Cost per sample on a k-mer the model has no level for (or with a letter outside ACGT), in 1/64 MAD.  The default, "
-                   "one MAD, is a choice, not a measurement.")
-@click.option("--rna", is_flag=True, help="The stored signal is reversed (RNA profiles): read the levels back to front; position stays in "
-                                          "read coordinates and start_idx falls as it rises, as in predict --events.")
-@click.option("--intervals", default=None, type=click.Path(dir_okay=False, exists=True),
-              help="A table of compare --open-ends: restrict every record to its [b_start, b_end) (an untrimmed real read); rows come out "
-                   "in the record's own coordinates.")
-@click.option("--cpu", is_flag=True, help="Compute on host threads instead of the GPU (the same bytes).")
-@click.option("--json", "as_json", is_flag=True, help="Print the summary as one JSON object.")
-@click.option("--summary", "summary_out", default=None, type=click.Path(dir_okay=False), help="Also write one row per read here (.tsv).")
-@click.option("--max-samples", default=1 << 27, type=int, show_default=True, help="Samples per batch.")
-@click.option("--trace-memory", default=8 << 30, type=int, show_default=True,
-              help="Bytes of decision scratch per batch; a read that needs more on its own is refused by its id.")
-@click.option("--chunks", "chunks_out", default=None, type=click.Path(file_okay=False),
-              help="Also write the training chunks of the solved reads under this directory (what `preprocess` makes of the table, "
-                   "cut on the device from the alignment itself; no text in between).")
-@click.option("-y", "--config", default=None, type=click.Path(dir_okay=False, exists=True),
-              help="With --chunks: YAML configuration file with seq_kmer, max_dna_len and max_signal_len.")
-@click.option("--seq-kmer", default=None, type=int, help="k of the chunks' k-mers (default: seq_kmer of the config).")
-@click.option("--max-dna-len", default=None, type=int, help="k-mers per chunk, 1..64 (default: max_dna_len of the config).")
-@click.option("--max-signal-len", default=None, type=int, help="Samples per chunk, 1..1024 (default: max_signal_len of the config).")
+@_aligner_options(
+    "event's", "sample", "Bytes of decision scratch per batch; a read that needs more on its own is refused by its id.",
+    click.option("--band", default=512, type=int, show_default=True,
+                 help="Half width of the band in k-mers around the diagonal.  A choice, not a measurement."),
+    after_rna=[click.option("--intervals", default=None, type=click.Path(dir_okay=False, exists=True),
+                            help="A table of compare --open-ends: restrict every record to its [b_start, b_end) (an untrimmed real read); "
+                                 "rows come out in the record's own coordinates.")])
 def resquiggle(seqs, signals, model, out, with_samples, band, skip_penalty, unknown_cost, rna, intervals, cpu, as_json, summary_out,
                max_samples, trace_memory, chunks_out, config, seq_kmer, max_dna_len, max_signal_len):
     """Align every record of a .blow5 / .slow5 file to the levels a pore model expects for the k-mers of its sequence (SEQS: FASTA or
     FASTQ, record names = read ids) and write the event table predict --events writes: read_name, position, model_kmer, start_idx,
     end_idx, event_level_mean, event_stdv.  Both ends are pinned: the first sample belongs to the first k-mer, the last to the last.
     Exact integers on median / MAD normalised samples and levels; unvalidated against f5c / uncalled4."""
-    _signal_files("resquiggle", signals)
-    if max_samples < 1:
-        raise click.BadParameter("must be >= 1", param_hint="--max-samples")
-    if trace_memory < 1:
-        raise click.BadParameter("must be >= 1", param_hint="--trace-memory")
-    import json
-    if not cpu:
-        import torch  # noqa: F401  (before the library: see engine.py)
+    _aligner_start("resquiggle", signals, max_samples, trace_memory, cpu)
     from . import resquiggle as R, signal_batch as SB
-    if not 1 <= band <= SB.max_band():
-        raise click.BadParameter(f"must be 1..{SB.max_band()}", param_hint="--band")
-    if not 0 <= skip_penalty <= R.MAX_SKIP_PENALTY:
-        raise click.BadParameter(f"must be 0..{R.MAX_SKIP_PENALTY}", param_hint="--skip-penalty")
-    if not 0 <= unknown_cost <= R.MAX_UNKNOWN_COST:
-        raise click.BadParameter(f"must be 0..{R.MAX_UNKNOWN_COST}", param_hint="--unknown-cost")
+    _in_range(band, 1, SB.max_band(), "--band")
+    _in_range(skip_penalty, 0, R.MAX_SKIP_PENALTY, "--skip-penalty")
+    _in_range(unknown_cost, 0, R.MAX_UNKNOWN_COST, "--unknown-cost")
     chunks = None if chunks_out is None else (chunks_out,) + _chunk_geometry(config, seq_kmer, max_dna_len, max_signal_len)
     s = R.resquiggle_files(seqs, signals, model, out, band=band, skip_penalty=skip_penalty, unknown_cost=unknown_cost, rna=rna,
                            intervals=intervals, with_samples=with_samples, cpu=cpu, summary_out=summary_out, max_samples=max_samples,
                            trace_memory=trace_memory, chunks=chunks)
-    if as_json:
-        click.echo(json.dumps(s))
-    else:
-        per = "nan" if s["mean_cost_per_sample"] is None else f"{s['mean_cost_per_sample']:.4f}"
-        click.echo(f"{s['events']} events of {s['solved']} reads -> {out}  [k {s['k']}, band {band}, skip penalty {skip_penalty}, unknown "
-                   f"cost {unknown_cost}; of {s['records']} records {s['unreached']} unreached, {s['refused']} refused, "
-                   f"{s['no_sequence']} without a sequence, {s['no_known_level']} without a known level; {s['skipped_kmers']} skipped "
-                   f"k-mers]  mean cost per sample {per} MAD")
+    per = "nan" if s["mean_cost_per_sample"] is None else f"{s['mean_cost_per_sample']:.4f}"
+    _echo_summary(s, as_json,
+                  f"{s['events']} events of {s['solved']} reads -> {out}  [k {s['k']}, band {band}, skip penalty {skip_penalty}, unknown "
+                  f"cost {unknown_cost}; of {s['records']} records {s['unreached']} unreached, {s['refused']} refused, "
+                  f"{s['no_sequence']} without a sequence, {s['no_known_level']} without a known level; {s['skipped_kmers']} skipped "
+                  f"k-mers]  mean cost per sample {per} MAD")
 
 
 @main.command()
 @click.argument("signals", type=click.Path(dir_okay=False))
 @click.option("-o", "--out", required=True, type=click.Path(dir_okay=False), help="Output event table (.events.tsv).")
-@click.option("--window-short", default=3, type=int, show_default=True, help="Window of the short detector in samples (1..32).")
-@click.option("--window-long", default=6, type=int, show_default=True, help="Window of the long detector in samples (short..32).")
-@click.option("--threshold-short", default=1.4, type=float, show_default=True,
-              help="Threshold t of the short detector on Welch's t between the two windows.  A choice, not a measurement.")
-@click.option("--threshold-long", default=9.0, type=float, show_default=True,
-              help="Threshold t of the long detector.  A choice, not a measurement.")
+@_detector_options("detector", " on Welch's t between the two windows.  A choice, not a measurement.", ".  A choice, not a measurement.")
 @click.option("--cpu", is_flag=True, help="Compute on host threads instead of the GPU (the same bytes).")
 @click.option("--json", "as_json", is_flag=True, help="Print the summary as one JSON object.")
 @click.option("--summary", "summary_out", default=None, type=click.Path(dir_okay=False), help="Also write one row per read here (.tsv).")
@@ -702,69 +747,29 @@ def segment(signals, out, window_short, window_long, threshold_short, threshold_
     event: read_name, event_index, start_idx, end_idx, event_level_mean, event_stdv.  A boundary is a peak of a windowed t-statistic,
     short window or long; exact integers.  Not scrappie's detector; unvalidated against scrappie / f5c / uncalled4."""
     _signal_files("segment", signals)
-    if max_samples < 1:
-        raise click.BadParameter("must be >= 1", param_hint="--max-samples")
-    import json
+    _in_range(max_samples, 1, None, "--max-samples")
     if not cpu:
         import torch  # noqa: F401  (before the library: see engine.py)
     from . import segment as SEG
-    if not 1 <= window_short <= SEG.MAX_WINDOW:
-        raise click.BadParameter(f"must be 1..{SEG.MAX_WINDOW}", param_hint="--window-short")
-    if not window_short <= window_long <= SEG.MAX_WINDOW:
-        raise click.BadParameter(f"must be --window-short..{SEG.MAX_WINDOW}", param_hint="--window-long")
-    for hint, t in (("--threshold-short", threshold_short), ("--threshold-long", threshold_long)):
-        try:
-            SEG.threshold_int(t)
-        except ValueError as e:
-            raise click.BadParameter(str(e), param_hint=hint)
+    _check_detector(window_short, window_long, threshold_short, threshold_long)
     s = SEG.segment_files(signals, out, window_short=window_short, window_long=window_long, threshold_short=threshold_short,
                           threshold_long=threshold_long, cpu=cpu, summary_out=summary_out, max_samples=max_samples)
-    if as_json:
-        click.echo(json.dumps(s))
-    else:
-        per = "nan" if s["mean_samples_per_event"] is None else f"{s['mean_samples_per_event']:.3f}"
-        click.echo(f"{s['events']} events of {s['records'] - s['refused']} records -> {out}  [windows {window_short} / {window_long}, "
-                   f"thresholds {threshold_short} / {threshold_long}; {s['samples']} samples, {s['refused']} record(s) refused: too long]  "
-                   f"mean samples per event {per}")
+    per = "nan" if s["mean_samples_per_event"] is None else f"{s['mean_samples_per_event']:.3f}"
+    _echo_summary(s, as_json,
+                  f"{s['events']} events of {s['records'] - s['refused']} records -> {out}  [windows {window_short} / {window_long}, "
+                  f"thresholds {threshold_short} / {threshold_long}; {s['samples']} samples, {s['refused']} record(s) refused: too long]  "
+                  f"mean samples per event {per}")
 
 
 @main.command()
-@click.argument("seqs", type=click.Path(dir_okay=False, exists=True))
-@click.argument("signals", type=click.Path(dir_okay=False))
-@click.option("--kmer-model", "model", required=True, type=click.Path(dir_okay=False, exists=True),
-              help="Pore model: the file `predict --kmer-model` writes, or a nanopolish-style table with the columns kmer and level_mean.")
-@click.option("-o", "--out", required=True, type=click.Path(dir_okay=False), help="Output event table (.events.tsv).")
-@click.option("--samples", "with_samples", is_flag=True, help="Add the `samples` column: every row's samples in pA.")
-@click.option("--band-width", default=128, type=int, show_default=True,
-              help="Cells of the adaptive band, a multiple of 64 in 64..1024.  A choice, not a measurement.")
-@click.option("--skip-penalty", default=128, type=int, show_default=True,
-              help="Cost of a k-mer that gets no event, in 1/64 MAD.  The default, two MADs, is a choice, not a measurement.")
-@click.option("--trim-penalty", default=64, type=int, show_default=True,
-              help="Cost of an event trimmed at either end, in 1/64 MAD.  The default, one MAD, is a choice, not a measurement.")
-@click.option("--unknown-cost", default=64, type=int, show_default=True,
-              help="Cost per event on a k-mer the model has no level for (or with a letter outside ACGT), in 1/64 MAD.  The default, "
-                   "one MAD, is a choice, not a measurement.")
-@click.option("--rna", is_flag=True, help="The stored signal is reversed (RNA profiles): read the levels back to front; position stays in "
-                                          "read coordinates and start_idx falls as it rises, as in predict --events.")
-@click.option("--window-short", default=3, type=int, show_default=True, help="Window of the short event detector in samples (1..32).")
-@click.option("--window-long", default=6, type=int, show_default=True, help="Window of the long event detector in samples (short..32).")
-@click.option("--threshold-short", default=1.4, type=float, show_default=True, help="Threshold t of the short detector (see segment).")
-@click.option("--threshold-long", default=9.0, type=float, show_default=True, help="Threshold t of the long detector (see segment).")
-@click.option("--cpu", is_flag=True, help="Compute on host threads instead of the GPU (the same bytes).")
-@click.option("--json", "as_json", is_flag=True, help="Print the summary as one JSON object.")
-@click.option("--summary", "summary_out", default=None, type=click.Path(dir_okay=False), help="Also write one row per read here (.tsv).")
-@click.option("--max-samples", default=1 << 27, type=int, show_default=True, help="Samples per batch.")
-@click.option("--trace-memory", default=8 << 30, type=int, show_default=True,
-              help="Bytes of decision scratch per batch, counted by the most events a record can have; a read that may need more on its "
-                   "own is refused by its id.")
-@click.option("--chunks", "chunks_out", default=None, type=click.Path(file_okay=False),
-              help="Also write the training chunks of the solved reads under this directory (what `preprocess` makes of the table, "
-                   "cut on the device from the alignment itself; no text in between).")
-@click.option("-y", "--config", default=None, type=click.Path(dir_okay=False, exists=True),
-              help="With --chunks: YAML configuration file with seq_kmer, max_dna_len and max_signal_len.")
-@click.option("--seq-kmer", default=None, type=int, help="k of the chunks' k-mers (default: seq_kmer of the config).")
-@click.option("--max-dna-len", default=None, type=int, help="k-mers per chunk, 1..64 (default: max_dna_len of the config).")
-@click.option("--max-signal-len", default=None, type=int, help="Samples per chunk, 1..1024 (default: max_signal_len of the config).")
+@_aligner_options(
+    "row's", "event", "Bytes of decision scratch per batch, counted by the most events a record can have; a read that may need more on "
+                      "its own is refused by its id.",
+    click.option("--band-width", default=128, type=int, show_default=True,
+                 help="Cells of the adaptive band, a multiple of 64 in 64..1024.  A choice, not a measurement."),
+    after_skip=[click.option("--trim-penalty", default=64, type=int, show_default=True,
+                             help="Cost of an event trimmed at either end, in 1/64 MAD.  The default, one MAD, is a choice, not a measurement.")],
+    after_rna=[_detector_options("event detector", " (see segment).", " (see segment).")])
 def eventalign(seqs, signals, model, out, with_samples, band_width, skip_penalty, trim_penalty, unknown_cost, rna, window_short,
                window_long, threshold_short, threshold_long, cpu, as_json, summary_out, max_samples, trace_memory, chunks_out, config,
                seq_kmer, max_dna_len, max_signal_len):
@@ -773,46 +778,26 @@ def eventalign(seqs, signals, model, out, with_samples, band_width, skip_penalty
     k-mer that got events.  Events come from the detector of `segment`; their means are median / MAD normalised over the whole record;
     the alignment runs in an adaptive band with free ends, so adapter, stall and trailing samples are trimmed.  Exact integers;
     unvalidated against f5c / nanopolish / uncalled4.  Junk beyond half of a record's events defeats the normalisation."""
-    _signal_files("eventalign", signals)
-    if max_samples < 1:
-        raise click.BadParameter("must be >= 1", param_hint="--max-samples")
-    if trace_memory < 1:
-        raise click.BadParameter("must be >= 1", param_hint="--trace-memory")
-    import json
-    if not cpu:
-        import torch  # noqa: F401  (before the library: see engine.py)
-    from . import eventalign as EA, segment as SEG
+    _aligner_start("eventalign", signals, max_samples, trace_memory, cpu)
+    from . import eventalign as EA
     if not 64 <= band_width <= EA.MAX_WIDTH or band_width % 64:
         raise click.BadParameter(f"must be a multiple of 64 in 64..{EA.MAX_WIDTH}", param_hint="--band-width")
-    if not 0 <= skip_penalty <= EA.MAX_SKIP_PENALTY:
-        raise click.BadParameter(f"must be 0..{EA.MAX_SKIP_PENALTY}", param_hint="--skip-penalty")
-    if not 0 <= trim_penalty <= EA.MAX_TRIM_PENALTY:
-        raise click.BadParameter(f"must be 0..{EA.MAX_TRIM_PENALTY}", param_hint="--trim-penalty")
-    if not 0 <= unknown_cost <= EA.MAX_UNKNOWN_COST:
-        raise click.BadParameter(f"must be 0..{EA.MAX_UNKNOWN_COST}", param_hint="--unknown-cost")
-    if not 1 <= window_short <= SEG.MAX_WINDOW:
-        raise click.BadParameter(f"must be 1..{SEG.MAX_WINDOW}", param_hint="--window-short")
-    if not window_short <= window_long <= SEG.MAX_WINDOW:
-        raise click.BadParameter(f"must be --window-short..{SEG.MAX_WINDOW}", param_hint="--window-long")
-    for hint, t in (("--threshold-short", threshold_short), ("--threshold-long", threshold_long)):
-        try:
-            SEG.threshold_int(t)
-        except ValueError as e:
-            raise click.BadParameter(str(e), param_hint=hint)
+    _in_range(skip_penalty, 0, EA.MAX_SKIP_PENALTY, "--skip-penalty")
+    _in_range(trim_penalty, 0, EA.MAX_TRIM_PENALTY, "--trim-penalty")
+    _in_range(unknown_cost, 0, EA.MAX_UNKNOWN_COST, "--unknown-cost")
+    _check_detector(window_short, window_long, threshold_short, threshold_long)
     chunks = None if chunks_out is None else (chunks_out,) + _chunk_geometry(config, seq_kmer, max_dna_len, max_signal_len)
     s = EA.eventalign_files(seqs, signals, model, out, band_width=band_width, skip_penalty=skip_penalty, trim_penalty=trim_penalty,
                             unknown_cost=unknown_cost, rna=rna, window_short=window_short, window_long=window_long,
                             threshold_short=threshold_short, threshold_long=threshold_long, with_samples=with_samples, cpu=cpu,
                             summary_out=summary_out, max_samples=max_samples, trace_memory=trace_memory, chunks=chunks)
-    if as_json:
-        click.echo(json.dumps(s))
-    else:
-        per = "nan" if s["mean_cost_per_event"] is None else f"{s['mean_cost_per_event']:.4f}"
-        click.echo(f"{s['events']} rows of {s['solved']} reads -> {out}  [k {s['k']}, band width {band_width}, skip penalty {skip_penalty}, "
-                   f"trim penalty {trim_penalty}, unknown cost {unknown_cost}; of {s['records']} records {s['unreached']} unreached, "
-                   f"{s['refused']} refused, {s['no_sequence']} without a sequence, {s['no_known_level']} without a known level; "
-                   f"{s['aligned_events']} aligned events, {s['skipped_kmers']} skipped k-mers; {s['trimmed_head_samples']} / "
-                   f"{s['trimmed_tail_samples']} samples trimmed at head / tail]  mean cost per aligned event {per} MAD")
+    per = "nan" if s["mean_cost_per_event"] is None else f"{s['mean_cost_per_event']:.4f}"
+    _echo_summary(s, as_json,
+                  f"{s['events']} rows of {s['solved']} reads -> {out}  [k {s['k']}, band width {band_width}, skip penalty {skip_penalty}, "
+                  f"trim penalty {trim_penalty}, unknown cost {unknown_cost}; of {s['records']} records {s['unreached']} unreached, "
+                  f"{s['refused']} refused, {s['no_sequence']} without a sequence, {s['no_known_level']} without a known level; "
+                  f"{s['aligned_events']} aligned events, {s['skipped_kmers']} skipped k-mers; {s['trimmed_head_samples']} / "
+                  f"{s['trimmed_tail_samples']} samples trimmed at head / tail]  mean cost per aligned event {per} MAD")
 
 
 def _chunk_geometry(config, seq_kmer, max_dna_len, max_signal_len):
@@ -825,8 +810,7 @@ def _chunk_geometry(config, seq_kmer, max_dna_len, max_signal_len):
     out = []
     for hint, key, value, most in given:
         value = int(cfg[key]) if value is None else int(value)
-        if not 1 <= value <= most:
-            raise click.BadParameter(f"must be 1..{most}", param_hint=hint)
+        _in_range(value, 1, most, hint)
         out.append(value)
     return tuple(out)
 

@@ -7,27 +7,23 @@ that decides an output byte is an integer function stated in include/s2s_hip.h n
 batching.  Per batch of reads: the samples with their slot tables go up in one copy and the levels in a second (signal_batch.Batch,
 one each), then s2s_segment, s2s_event_sums, s2s_event_means, s2s_signal_median_mad and s2s_signal_normalise on the pool of means
 and on the levels, s2s_eventalign, s2s_event_sums on the k-mer intervals -- every slot sized by s2s_segment_capacity, so nothing
-returns to the host in between -- and one copy down; the rows are formatted on the host in Python.  The defaults 128 / 128 / 64 / 64
-are choices, not measurements.  The event means are normalised over the WHOLE record: junk at the ends of up to about a quarter of
+returns to the host in between -- and one copy down.  The model, the sequences, the files and the rows are pore_align's
+(align_files); this module holds the solver of a batch and what it counts per read.  The defaults 128 / 128 / 64 / 64 are choices,
+not measurements.  The event means are normalised over the WHOLE record: junk at the ends of up to about a quarter of
 the events still aligns, but when junk is more than half the events the junk is the median and the alignment is meaningless.  The
 reference has no such command, and no f5c / nanopolish / uncalled4 was at hand: the output is unvalidated against them -- DESIGN.md
 section 6."""
-import logging
-import os
-import time
 from typing import Sequence
 
 import numpy as np
 
-from .compare import EVENT_COLUMNS
-from .resquiggle import (MAX_SKIP_PENALTY, MAX_UNKNOWN_COST, UNKNOWN, UNREACHED, format_rows, kmer_codes, level_ints, read_model,
-                         read_sequences)
+from .compare import EVENT_COLUMNS  # noqa: F401  (the columns of OUT, under this module's name too)
+from .pore_align import (DEFAULT_MAX_SAMPLES, DEFAULT_TRACE_MEMORY, MAX_SKIP_PENALTY, MAX_UNKNOWN_COST, UNKNOWN, Aligner, align_files,
+                         split_levels)
 from .segment import (DEFAULT_THRESHOLD_LONG, DEFAULT_THRESHOLD_SHORT, DEFAULT_WINDOW_LONG, DEFAULT_WINDOW_SHORT, capacity,
                       threshold_int)
 from .segment import _check_params as _check_segment
-from .signal_batch import MAX_SAMPLES, SCALE, Batch, batches, calibration, device_only, open_records, slots
-
-logger = logging.getLogger("seq2squiggle")
+from .signal_batch import MAX_SAMPLES, SCALE, Batch, device_only, slots
 
 MAX_WIDTH = 1024                 # S2S_EVA_MAX_WIDTH
 MAX_TRIM_PENALTY = 1 << 20       # S2S_EVA_MAX_TRIM_PENALTY
@@ -35,8 +31,6 @@ DEFAULT_BAND_WIDTH = 128         # cells of a band                              
 DEFAULT_SKIP_PENALTY = 128       # two MADs (64 units each) for a k-mer without an event    } choices, not measurements
 DEFAULT_TRIM_PENALTY = 64        # one MAD per trimmed event                                }
 DEFAULT_UNKNOWN_COST = 64        # one MAD per event on a k-mer without a level             }
-DEFAULT_MAX_SAMPLES = 1 << 27    # samples per batch
-DEFAULT_TRACE_MEMORY = 8 << 30   # bytes of decision scratch per batch
 SUMMARY_COLUMNS = ("read_id", "n_samples", "n_kmers", "status", "cost", "cost_per_event", "events", "aligned_events", "skipped",
                    "trim_head", "trim_tail", "med", "mad", "level_med", "level_mad")
 
@@ -73,11 +67,7 @@ def _levels(lev_list, known_list, cpu: bool, device: int, threads, norm: bool, l
     levels the solver takes, pointer of l_offs).  norm: median / MAD of the known levels into lmed / lmad (int32 pointers, P values
     each, behind P unused ones), all levels normalised by them; k-mers without a level get S2S_RSQ_UNKNOWN either way."""
     P = len(lev_list)
-    kn = [np.asarray(k, bool).reshape(-1) for k in known_list]
-    lev = [np.asarray(l, np.int16).reshape(-1) for l in lev_list]
-    known_recs = [l[k] for l, k in zip(lev, kn)]
-    full_recs = [np.where(k, l, np.int16(0)).astype(np.int16) for l, k in zip(lev, kn)]
-    unknown = ~np.concatenate(kn + [np.zeros(0, bool)])
+    known_recs, full_recs, unknown = split_levels(lev_list, known_list)
     BL = Batch(known_recs + full_recs, lambda offs: ((offs[P:] - offs[P]).astype(np.int64),), cpu, device, threads)
     l0 = int(BL.host_offs[P])
     if norm:
@@ -179,127 +169,43 @@ def eventalign(means: Sequence[np.ndarray], levels: Sequence[np.ndarray], band_w
                 **{k: [r[k][lo[p]:lo[p + 1]] for p in range(P)] for k in ("k_start", "k_len", "k_events")})
 
 
+def _account(r, p: int, n: int):
+    """pore_align.Aligner.account: the read p of a _run_batch result, n samples long."""
+    c, ke, E = int(r["cost"][p]), r["k_events"][p], max(int(r["n_events"][p]), 0)
+    mm = (int(r["med"][p]), int(r["mad"][p]), int(r["lmed"][p]), int(r["lmad"][p]))
+    if c < 0:
+        return c, len(ke), mm, (E, 0, 0, 0, 0)
+    first, end = int(r["first"][p]), int(r["end"][p])
+    rows, aligned = int((ke > 0).sum()), end - first
+    head = int(r["ev_start"][p][first])
+    tail = n - int(r["ev_start"][p][end - 1] + r["ev_len"][p][end - 1])
+    moves = dict(events=rows, aligned_events=aligned, skipped_kmers=len(ke) - rows, trimmed_head_samples=head, trimmed_tail_samples=tail)
+    return (c, len(ke), mm, (E, aligned, len(ke) - rows, head, tail), aligned, moves,
+            (r["k_start"][p], r["k_len"][p], r["S"][p], r["Q"][p]))
+
+
 def eventalign_files(seqs, signals, model, out, band_width: int = DEFAULT_BAND_WIDTH, skip_penalty: int = DEFAULT_SKIP_PENALTY,
                      trim_penalty: int = DEFAULT_TRIM_PENALTY, unknown_cost: int = DEFAULT_UNKNOWN_COST, rna: bool = False,
                      window_short: int = DEFAULT_WINDOW_SHORT, window_long: int = DEFAULT_WINDOW_LONG,
                      threshold_short: float = DEFAULT_THRESHOLD_SHORT, threshold_long: float = DEFAULT_THRESHOLD_LONG,
                      with_samples: bool = False, cpu: bool = False, device: int = 0, summary_out=None,
                      max_samples: int = DEFAULT_MAX_SAMPLES, trace_memory: int = DEFAULT_TRACE_MEMORY, chunks=None) -> dict:
-    """Write OUT (EVENT_COLUMNS, plus `samples` with with_samples; records in the order of SIGNALS, one row per unskipped k-mer, by
-    position) and return the counters: reads solved, unreached (no path inside the band), refused (more than 2^22 samples or k-mers,
-    or a walk back that may need more than trace_memory on its own -- by read id, before the batch computes), without a sequence,
-    without a known level, events (the rows: k-mers with events), aligned events, skipped k-mers, the samples trimmed at head and
-    tail, and the mean cost per aligned event in MADs.  A batch holds reads until their samples pass max_samples or the bound of
-    their decision scratch (that of s2s_segment_capacity events) passes trace_memory (at least one read).  rna: the stored signal is
-    reversed, so the levels are read back to front; `position` stays in read coordinates.  summary_out: one row per read
-    (SUMMARY_COLUMNS).  chunks: (OUTDIR, seq_kmer, max_dna_len, max_signal_len) -- also write the training chunks of the solved reads
-    there (preprocess.Chunker), from the device buffers; their counters come back under "chunks"."""
+    """pore_align.align_files with this module's solver (one row per unskipped k-mer) -> the counters: reads solved, unreached (no
+    path inside the band), refused (or a walk back that may need more than trace_memory on its own: the bound of a read's decision
+    scratch is that of s2s_segment_capacity events), without a sequence, without a known level, events (the rows: k-mers with
+    events), aligned events, skipped k-mers, the samples trimmed at head and tail, and the mean cost per aligned event in MADs.
+    summary_out: one row per read (SUMMARY_COLUMNS)."""
     W, skip_penalty, trim_penalty, unknown_cost = _check_params(band_width, skip_penalty, trim_penalty, unknown_cost)
     seg = _check_segment(window_short, window_long, threshold_int(threshold_short), threshold_int(threshold_long))
-    if int(max_samples) < 1 or int(trace_memory) < 1:
-        raise ValueError("max_samples and trace_memory must be >= 1")
-    if not cpu:
-        import torch  # noqa: F401  (before the library: see engine.py)
-    k, levels = read_model(str(model))
-    chunker = None
-    if chunks is not None:
-        from .preprocess import Chunker
-        if int(chunks[1]) != k:
-            raise click.ClickException(f"--seq-kmer {int(chunks[1])} is not the model's k = {k}")
-        chunker = Chunker(chunks[0], k, chunks[2], chunks[3], rna)
-    table, has = level_ints(levels)
-    sequences = read_sequences(str(seqs))
-    cnt = dict(records=0, solved=0, unreached=0, refused=0, no_sequence=0, no_known_level=0, events=0, aligned_events=0, skipped_kmers=0,
-               trimmed_head_samples=0, trimmed_tail_samples=0)
-    tot = dict(cost=0, solve_s=0.0, format_s=0.0)
-    with open(out, "w") as f, open(summary_out or os.devnull, "w") as fs:
-        f.write("\t".join(EVENT_COLUMNS + (("samples",) if with_samples else ())) + "\n")
-        fs.write("\t".join(SUMMARY_COLUMNS) + "\n")
-
-        notes, written = {}, [0]                    # the summary rows come out in record order, whatever order they are known in
-
-        def note(no, rid, n, K, status, cost="nan", per="nan", events=0, aligned=0, skipped=0, head=0, tail=0, mm=("nan",) * 4):
-            notes[no] = (f"{rid}\t{n}\t{K}\t{status}\t{cost}\t{per}\t{events}\t{aligned}\t{skipped}\t{head}\t{tail}\t{mm[0]}\t{mm[1]}\t"
-                         f"{mm[2]}\t{mm[3]}\n")
-            while written[0] in notes:
-                fs.write(notes.pop(written[0]))
-                written[0] += 1
-
-        def flush(batch):
-            t0 = time.perf_counter()
-            r = _run_batch([b[2] for b in batch], [b[3] for b in batch], [b[4] for b in batch], W, skip_penalty, trim_penalty,
-                           unknown_cost, seg, cpu, device,
-                           chunks=None if chunker is None else (chunker, [b[5] for b in batch], [b[1] for b in batch]))
-            t1 = time.perf_counter()
-            for p, (rid, clean, sig, _, _, cal, no, _) in enumerate(batch):
-                c, ke, E = int(r["cost"][p]), r["k_events"][p], max(int(r["n_events"][p]), 0)
-                mm = (int(r["med"][p]), int(r["mad"][p]), int(r["lmed"][p]), int(r["lmad"][p]))
-                if c < 0:
-                    cnt["unreached"] += 1
-                    note(no, rid, len(sig), len(ke), "unreached", events=E, mm=mm)
-                    continue
-                first, end = int(r["first"][p]), int(r["end"][p])
-                rows, aligned = int((ke > 0).sum()), end - first
-                head = int(r["ev_start"][p][first])
-                tail = len(sig) - int(r["ev_start"][p][end - 1] + r["ev_len"][p][end - 1])
-                cnt["solved"] += 1
-                cnt["events"] += rows
-                cnt["aligned_events"] += aligned
-                cnt["skipped_kmers"] += len(ke) - rows
-                cnt["trimmed_head_samples"] += head
-                cnt["trimmed_tail_samples"] += tail
-                tot["cost"] += c
-                f.write(format_rows(rid, clean, k, r["k_start"][p], r["k_len"][p], r["S"][p], r["Q"][p], sig, cal, rna, 0, with_samples))
-                note(no, rid, len(sig), len(ke), "solved", c, "%.6f" % (c / aligned / SCALE), E, aligned, len(ke) - rows, head, tail, mm)
-            tot["solve_s"] += t1 - t0
-            tot["format_s"] += time.perf_counter() - t1
-
-        def reads():
-            """The records that go to the solver, as flush takes them; the others are counted and noted here."""
-            for rec in open_records(str(signals)):
-                no = cnt["records"]
-                cnt["records"] += 1
-                rid, sig = rec["read_id"], np.asarray(rec["signal"], np.int16)
-                cal = calibration(rec)
-                clean = sequences.get(rid)
-                codes = kmer_codes(clean, k) if clean is not None else np.zeros(0, np.int64)
-                if not len(codes):
-                    cnt["no_sequence"] += 1
-                    note(no, rid, len(sig), 0, "no_sequence")
-                    continue
-                known = (codes >= 0) & has[np.maximum(codes, 0)]
-                lev = table[np.maximum(codes, 0)]
-                if rna:
-                    known, lev = known[::-1], lev[::-1]
-                if not known.any():
-                    cnt["no_known_level"] += 1
-                    note(no, rid, len(sig), len(codes), "no_known_level")
-                    continue
-                long = len(sig) > MAX_SAMPLES or len(codes) > MAX_SAMPLES
-                need = 0 if long else scratch_bound(len(sig), len(codes), W, seg[0])
-                if long or need > trace_memory:
-                    cnt["refused"] += 1
-                    logger.warning("eventalign: read %s refused: %d samples against %d k-mers at band width %d (limit %d each; up to %d "
-                                   "bytes of decision scratch against --trace-memory %d)", rid, len(sig), len(codes), W, MAX_SAMPLES, need,
-                                   trace_memory)
-                    note(no, rid, len(sig), len(codes), "refused")
-                    continue
-                yield rid, clean, sig, lev, known, cal, no, need
-
-        for batch in batches(reads(), lambda b: (len(b[2]), b[7]), (max_samples, trace_memory)):
-            flush(batch)
-    s = dict(seqs=str(seqs), signals=str(signals), model=str(model), out=str(out), k=k, band_width=W, skip_penalty=skip_penalty,
-             trim_penalty=trim_penalty, unknown_cost=unknown_cost, rna=bool(rna), window_short=seg[0], window_long=seg[1],
-             threshold_short=float(threshold_short), threshold_long=float(threshold_long), **cnt,
-             mean_cost_per_event=(tot["cost"] / cnt["aligned_events"] / SCALE) if cnt["aligned_events"] else None,
-             solve_seconds=tot["solve_s"], format_seconds=tot["format_s"])
-    if summary_out is not None:
-        s["summary_out"] = str(summary_out)
-    if chunker is not None:
-        s["chunks"] = chunker.close("eventalign")
-    logger.info("eventalign: %d record(s): %d solved, %d unreached, %d refused, %d without a sequence, %d without a known level; %d "
-                "event row(s) of %d aligned event(s), %d skipped k-mer(s); %d / %d sample(s) trimmed at head / tail; mean cost per "
-                "aligned event %s MAD", cnt["records"], cnt["solved"], cnt["unreached"], cnt["refused"], cnt["no_sequence"],
-                cnt["no_known_level"], cnt["events"], cnt["aligned_events"], cnt["skipped_kmers"], cnt["trimmed_head_samples"],
-                cnt["trimmed_tail_samples"], "nan" if s["mean_cost_per_event"] is None else "%.4f" % s["mean_cost_per_event"])
-    return s
+    return align_files(Aligner(
+        name="eventalign", columns=SUMMARY_COLUMNS,
+        counters=("events", "aligned_events", "skipped_kmers", "trimmed_head_samples", "trimmed_tail_samples"),
+        params=dict(band_width=W, skip_penalty=skip_penalty, trim_penalty=trim_penalty, unknown_cost=unknown_cost, rna=bool(rna),
+                    window_short=seg[0], window_long=seg[1], threshold_short=float(threshold_short), threshold_long=float(threshold_long)),
+        need=lambda n, K: scratch_bound(n, K, W, seg[0]),
+        refusal=f"eventalign: read %s refused: %d samples against %d k-mers at band width {W} (limit %d each; up to %d bytes of decision "
+                "scratch against --trace-memory %d)",
+        solve=lambda sig, lev, known, ch: _run_batch(sig, lev, known, W, skip_penalty, trim_penalty, unknown_cost, seg, cpu, device, chunks=ch),
+        account=_account, mean_key="mean_cost_per_event",
+        log_tail="%d event row(s) of %d aligned event(s), %d skipped k-mer(s); %d / %d sample(s) trimmed at head / tail; mean cost per "
+                 "aligned event %s MAD"), seqs, signals, model, out, rna, with_samples, cpu, summary_out, max_samples, trace_memory, chunks)

@@ -295,3 +295,11 @@ def test_eventalign_chunks_open(files):  # noqa: F811
     for kind in ("chunks", "chunks_lengths", "targets_lengths"):
         assert a[kind].tobytes() == b[kind].tobytes(), kind
     assert opens(d / "ea_direct", K3, 5, 48) == len(a["targets"])
+
+
+def test_eventalign_chunks_seq_kmer_mismatch_is_a_usage_error(files):  # noqa: F811
+    d, blow5, slow5, reads, cal, adc = files
+    args = ("eventalign", d / "r.fasta", blow5, "--kmer-model", d / "m.model", "-o", d / "y.tsv", "--cpu", "--chunks", d / "y", "--seq-kmer", 4)
+    r = CliRunner().invoke(cli.main, [str(a) for a in args])             # (exceptions caught: a NameError would show as r.exception)
+    assert r.exit_code != 0 and "--seq-kmer" in r.output and "Traceback" not in r.output
+    assert isinstance(r.exception, SystemExit), repr(r.exception)

@@ -1,6 +1,6 @@
 // `preprocess`: training chunks from alignments (include/s2s_hip.h states the definition next to s2s_chunk_pack).  The rows of a read
 // are the slots that pass s2s_chunk_row; they are compacted by ranks over the POOLED slots (tiles of S2S_SEG_TILE slots, the flag
-// words, ranks and scan of s2s_segment.h), the reads' chunk counts are scanned, and from there on a wave owns one of the POOLED
+// words, ranks and scan of s2s_prims.h), the reads' chunk counts are scanned, and from there on a wave owns one of the POOLED
 // chunks: it finds its read by a search in the chunk offsets, whatever that read's length.  The row test, the sample and deviation
 // formulas and the layout of the scratch are one set of functions for the kernels, the host entry and the host twin (s2s_host.cpp);
 // the four kernels follow under S2S_DTW_KERNELS.
@@ -10,9 +10,8 @@
 
 #include "../../include/s2s_hip.h"
 #include "s2s_dtw.h"
-#include "s2s_segment.h"
+#include "s2s_prims.h"
 
-#define S2S_CHK_WORDS (S2S_SEG_TILE / 64)
 #define S2S_CHK_ONE 0x3C00                          // 1.0 in fp16
 #define S2S_CHK_STDV_MAX_LEN 1024                   // n Q < 2^10 2^10 2^30 = 2^50 and S^2 <= 2^50: both fit int64
 
@@ -36,13 +35,13 @@ S2S_DTW_HD inline S2SChkScratch s2s_chk_layout(int64_t slots, int32_t P, int64_t
     const int64_t t = s2s_chk_tiles(slots);
     S2SChkScratch s;
     s.words = 0;
-    s.trank = s.words + t * S2S_CHK_WORDS * 8;
+    s.trank = s.words + t * S2S_SEG_WORDS * 8;
     s.nrank = s.trank + (t + 1) * 8;
     s.r_offs = s.nrank + (t + 1) * 8;
     s.c_offs = s.r_offs + (int64_t)P * 8;
     s.krank = s.c_offs + ((int64_t)P + 1) * 8;
     s.wrank = s.krank + (capacity + 1) * 8;
-    s.rows = s.wrank + t * S2S_CHK_WORDS * 4;
+    s.rows = s.wrank + t * S2S_SEG_WORDS * 4;
     s.bytes = (s.rows + slots * 4 + 15) / 16 * 16;
     return s;
 }
@@ -73,8 +72,8 @@ S2S_DTW_HD inline int32_t s2s_chunk_column(uint8_t letter) {
 
 #define S2S_CHK_THREADS 256
 #define S2S_CHK_WAVES (S2S_CHK_THREADS / 64)
-#define S2S_CHK_LDS_BYTES (S2S_CHK_WORDS * 8 + S2S_CHK_WAVES * 4)          // the flag kernel: a tile's words and the waves' all-N counts
-static_assert(S2S_SEG_TILE % S2S_CHK_THREADS == 0 && S2S_CHK_WORDS <= 64 && S2S_CHUNK_MAX_TE <= 64, "a wave's ballot is a flag word; a wave holds a chunk's rows");
+#define S2S_CHK_LDS_BYTES (S2S_SEG_WORDS * 8 + S2S_CHK_WAVES * 4)          // the flag kernel: a tile's words and the waves' all-N counts
+static_assert(S2S_SEG_TILE % S2S_CHK_THREADS == 0 && S2S_SEG_WORDS <= 64 && S2S_CHUNK_MAX_TE <= 64, "a wave's ballot is a flag word; a wave holds a chunk's rows");
 
 struct S2SChkIn {
     const void* pool;                               // int16 (raw) or float (pa)
@@ -95,15 +94,15 @@ struct S2SChkIn {
 __global__ __launch_bounds__(S2S_CHK_THREADS) void s2s_chunk_flags_kernel(S2SChkIn in, unsigned long long* __restrict__ words,
                                                                           int* __restrict__ wrank, long long* __restrict__ trank,
                                                                           long long* __restrict__ nrank) {
-    __shared__ unsigned long long s_words[S2S_CHK_WORDS];
+    __shared__ unsigned long long s_words[S2S_SEG_WORDS];
     __shared__ int s_n[S2S_CHK_WAVES];
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long long g0 = (long long)blockIdx.x * S2S_SEG_TILE;
     int ra, rb;
     {
         long long lo, hi;
-        s2s_seg_find(in.l_offs, 0, in.P - 1, in.slots, g0, ra, lo, hi);
-        s2s_seg_find(in.l_offs, 0, in.P - 1, in.slots, (g0 + S2S_SEG_TILE < in.slots ? g0 + S2S_SEG_TILE : in.slots) - 1, rb, lo, hi);
+        s2s_record_find(in.l_offs, 0, in.P - 1, in.slots, g0, ra, lo, hi);
+        s2s_record_find(in.l_offs, 0, in.P - 1, in.slots, (g0 + S2S_SEG_TILE < in.slots ? g0 + S2S_SEG_TILE : in.slots) - 1, rb, lo, hi);
         if (rb < ra) rb = ra;
     }
     int all_n = 0;
@@ -112,7 +111,7 @@ __global__ __launch_bounds__(S2S_CHK_THREADS) void s2s_chunk_flags_kernel(S2SChk
         const long long g = g0 + e;
         int p, row = 0;
         long long lo, hi;
-        if (g < in.slots && s2s_seg_find(in.l_offs, ra, rb, in.slots, g, p, lo, hi))
+        if (g < in.slots && s2s_record_find(in.l_offs, ra, rb, in.slots, g, p, lo, hi))
             row = s2s_chunk_row(in.ev_start[g], in.ev_len[g], in.s_offs[p], in.s_offs[p + 1], in.total, in.kmers + g * in.k, in.k);
         const unsigned long long word = __ballot(row == 1);
         all_n += __popcll(__ballot(row == 2));
@@ -120,18 +119,11 @@ __global__ __launch_bounds__(S2S_CHK_THREADS) void s2s_chunk_flags_kernel(S2SChk
     }
     if (lane == 0) s_n[wave] = all_n;
     __syncthreads();
-    if (tid < S2S_CHK_WORDS) {
-        int before = 0;
-        for (int q = 0; q < tid; ++q) before += __popcll(s_words[q]);
-        const long long at = (long long)blockIdx.x * S2S_CHK_WORDS + tid;
-        words[at] = s_words[tid];
-        wrank[at] = before;
-        if (tid == S2S_CHK_WORDS - 1) {
-            trank[blockIdx.x + 1] = before + __popcll(s_words[tid]);         // the two counts of the tile; launch 2 scans them
-            int n = 0;
-            for (int q = 0; q < S2S_CHK_WAVES; ++q) n += s_n[q];
-            nrank[blockIdx.x + 1] = n;
-        }
+    s2s_bitmap_publish(s_words, tid, blockIdx.x, words, wrank, trank);
+    if (tid == 0) {                                 // the tile's other count; launch 2 scans the two
+        int n = 0;
+        for (int q = 0; q < S2S_CHK_WAVES; ++q) n += s_n[q];
+        nrank[blockIdx.x + 1] = n;
     }
 }
 
@@ -146,8 +138,8 @@ __global__ __launch_bounds__(S2S_CHK_THREADS) void s2s_chunk_compact_kernel(S2SC
         const long long lo = in.l_offs[p], hi = in.l_offs[p + 1];
         long long at = 0, n = 0;
         if (lo >= 0 && hi >= lo && hi <= in.slots) {
-            at = s2s_seg_rank(words, wrank, trank, lo);
-            n = s2s_seg_rank(words, wrank, trank, hi) - at;
+            at = s2s_bitmap_rank(words, wrank, trank, lo);
+            n = s2s_bitmap_rank(words, wrank, trank, hi) - at;
         }
         r_offs[p] = at;
         n_rows[p] = (int)n;
@@ -158,7 +150,7 @@ __global__ __launch_bounds__(S2S_CHK_THREADS) void s2s_chunk_compact_kernel(S2SC
         const long long g = g0 + tid + S2S_CHK_THREADS * j;
         const int bit = (int)(g & 63);
         const unsigned long long word = words[g >> 6];
-        if ((word >> bit) & 1ull) rows[trank[t] + wrank[g >> 6] + __popcll(word & ((1ull << bit) - 1ull))] = (int)g;
+        if ((word >> bit) & 1ull) rows[s2s_bitmap_rank_in(trank[t], wrank, g, word)] = (int)g;
     }
 }
 
@@ -175,11 +167,7 @@ struct S2SChkRow {
 // with the read behind them).
 __device__ inline S2SChkRow s2s_chunk_load(const S2SChkIn& in, const int* __restrict__ rows, const long long* __restrict__ r_offs,
                                            const long long* __restrict__ c_offs, const int* __restrict__ n_rows, long long c, int lane) {
-    int a = 0, b = in.P - 1;
-    while (a < b) {
-        const int m = a + (b - a + 1) / 2;
-        if (c_offs[m] <= c) a = m; else b = m - 1;
-    }
+    const int a = s2s_last_le(0, in.P - 1, c, [&](int m) { return c_offs[m]; });
     S2SChkRow r;
     r.p = a;
     r.lo = in.s_offs[a];
@@ -197,11 +185,6 @@ __device__ inline S2SChkRow s2s_chunk_load(const S2SChkIn& in, const int* __rest
     return r;
 }
 
-__device__ inline long long s2s_chunk_wave_sum(long long v) {
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
 // Launch 5: krank[c + 1] = 1 for a chunk that is kept, else 0 -- over the whole capacity, which launch 6 scans.
 __global__ __launch_bounds__(S2S_CHK_THREADS) void s2s_chunk_lengths_kernel(S2SChkIn in, const int* __restrict__ rows,
                                                                             const long long* __restrict__ r_offs,
@@ -214,7 +197,7 @@ __global__ __launch_bounds__(S2S_CHK_THREADS) void s2s_chunk_lengths_kernel(S2SC
     long long keep = 0;
     if (c < formed) {
         const S2SChkRow r = s2s_chunk_load(in, rows, r_offs, c_offs, n_rows, c, lane);
-        const long long tl = s2s_chunk_wave_sum(r.len), bad = s2s_chunk_wave_sum(r.ok ? 0 : 1);
+        const long long tl = s2s_wave_sum<long long>(r.len), bad = s2s_wave_sum<long long>(r.ok ? 0 : 1);
         keep = tl <= in.ts && bad == 0 ? 1 : 0;
     }
     if (lane == 0) krank[c + 1] = keep;
@@ -243,11 +226,7 @@ __global__ __launch_bounds__(S2S_CHK_THREADS) void s2s_chunk_write_kernel(S2SChk
     const long long at = krank[c];
     const int te = in.te, k = in.k, ts = in.ts;
     const S2SChkRow r = s2s_chunk_load(in, rows, r_offs, c_offs, n_rows, c, lane);
-    int incl = r.len;                               // the rows' lengths: inclusive prefix over the lanes, <= ts here
-    for (int d = 1; d < 64; d <<= 1) {
-        const int u = __shfl_up(incl, d);
-        if (lane >= d) incl += u;
-    }
+    const int incl = s2s_wave_prefix(r.len, lane);  // the rows' lengths: inclusive prefix over the lanes, <= ts here
     const int excl = incl - r.len, tl = __shfl(incl, 63);
     const double dig = in.cal ? in.cal[3 * r.p] : 1.0, off = in.cal ? in.cal[3 * r.p + 1] : 0.0, rng = in.cal ? in.cal[3 * r.p + 2] : 1.0;
     if (lane < te) {

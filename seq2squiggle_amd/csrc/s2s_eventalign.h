@@ -45,35 +45,13 @@ S2S_DTW_HD inline int64_t s2s_eva_count(int64_t n_events, int64_t eo, int64_t eo
 #define S2S_EVA_REFILL 256                          // bands per refill of the two staged windows (a power of two)
 #define S2S_EVA_LDS_BYTES(W) (3 * ((size_t)(W) + 2) * 8 + 2 * ((size_t)(W) + S2S_EVA_REFILL) * 2)
 
-// Launch 1 of s2s_event_means: m_offs[r] = the means of the records before r, m_offs[R] = all.  One workgroup, 1,024 records per step
-// and a carry (the scan of s2s_segment_scan_kernel).
-__global__ __launch_bounds__(1024) void s2s_event_means_scan_kernel(const int* __restrict__ n_events, const long long* __restrict__ ev_offs,
-                                                                     int R, long long* __restrict__ m_offs) {
-    __shared__ long long wsum[16];
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    long long carry = 0;
-    for (int base = 0; base < R; base += 1024) {    // (uniform)
-        const int at = base + tid;
-        const long long own = at < R ? s2s_eva_count(n_events[at], ev_offs[at], ev_offs[at + 1]) : 0;
-        long long v = own;
-        for (int d = 1; d < 64; d <<= 1) {
-            const long long u = __shfl_up(v, d);
-            if (lane >= d) v += u;
-        }
-        if (lane == 63) wsum[wave] = v;
-        __syncthreads();
-        long long before = 0, all = 0;
-        for (int q = 0; q < 16; ++q) {
-            const long long u = wsum[q];
-            before += q < wave ? u : 0;
-            all += u;
-        }
-        if (at < R) m_offs[at] = carry + before + v - own;
-        carry += all;
-        __syncthreads();
-    }
-    if (tid == 0) m_offs[R] = carry;
-}
+// Launch 1 of s2s_event_means is s2s_scan_kernel<1, S2SEvaCounts> (s2s_prims.h): m_offs[r] = the means of the records before r,
+// m_offs[R] = all.
+struct S2SEvaCounts {
+    const int* n_events;
+    const long long* ev_offs;
+    __device__ long long operator()(long long r) const { return s2s_eva_count(n_events[r], ev_offs[r], ev_offs[r + 1]); }
+};
 
 // Launch 2: the means of record blockIdx.x, its events strided over the workgroups of blockIdx.y.  A record whose means would end
 // beyond `capacity` writes none.

@@ -18,6 +18,7 @@
 #include "s2s_dtw.h"
 #include "s2s_sdtw.h"
 #include "s2s_resquiggle.h"
+#include "s2s_prims.h"
 #include "s2s_segment.h"
 #include "s2s_eventalign.h"
 #include "s2s_chunk.h"
@@ -762,46 +763,7 @@ __global__ __launch_bounds__(256) void s2s_count_kernel(const float* __restrict_
     if (lane == 0) counts[b] = n;
 }
 
-// exclusive scan of counts[B] -> offs[B+1] (int64), one workgroup walking the array, 8 consecutive elements per thread and step
-// (131,072 chunk counts = 16 steps)
-__global__ __launch_bounds__(1024) void s2s_scan_kernel(const int* __restrict__ counts, int B, long long* __restrict__ offs) {
-    __shared__ long long wsum[16];
-    __shared__ long long carry_s;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    if (tid == 0) carry_s = 0;
-    __syncthreads();
-    for (int base = 0; base < B; base += 8192) {
-        const int i0 = base + 8 * tid;
-        int c[8];
-        if (i0 + 8 <= B) {                                     // (the workspace is 16-byte aligned, i0 a multiple of 8)
-            const int4 a = *reinterpret_cast<const int4*>(counts + i0), b = *reinterpret_cast<const int4*>(counts + i0 + 4);
-            c[0] = a.x; c[1] = a.y; c[2] = a.z; c[3] = a.w; c[4] = b.x; c[5] = b.y; c[6] = b.z; c[7] = b.w;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) c[k] = (i0 + k < B) ? counts[i0 + k] : 0;
-        }
-        long long v = 0;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v += c[k];
-        long long x = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const long long y = __shfl_up(x, o, 64); if (lane >= o) x += y; }
-        if (lane == 63) wsum[w] = x;
-        __syncthreads();
-        long long pre = carry_s;
-        for (int j = 0; j < w; ++j) pre += wsum[j];
-        long long run = pre + x - v;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            if (i0 + k < B) offs[i0 + k] = run;
-            run += c[k];
-        }
-        __syncthreads();
-        if (tid == 1023) carry_s = pre + x;
-        __syncthreads();
-    }
-    if (tid == 0) offs[B] = carry_s;
-}
+// the exclusive scan of counts[B] -> offs[B+1] (int64) is s2s_scan_kernel<8, S2SScanInts> (s2s_prims.h): 131,072 chunk counts = 16 steps
 
 __global__ __launch_bounds__(256) void s2s_read_offsets_kernel(const long long* __restrict__ offs, const int* __restrict__ read_first,
                                                                int R, long long* __restrict__ out_offsets) {
@@ -1382,6 +1344,18 @@ int fail(s2s_handle* h, int code, const std::string& msg) {
             return fail((h), S2S_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
+// A kernel launch and the error it left, if any.  A kernel with a comma in its template arguments goes in parentheses.
+#define S2S_LAUNCH(h, kernel, grid, block, lds, stream, ...)                    \
+    do {                                                                        \
+        hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);      \
+        HIP_TRY(h, hipGetLastError());                                          \
+    } while (0)
+
+// The ABI's int64_t is the kernels' long long.
+static_assert(sizeof(int64_t) == sizeof(long long), "int64_t arrays are passed to the kernels as long long");
+inline const long long* as_ll(const int64_t* p) { return reinterpret_cast<const long long*>(p); }
+inline long long* as_ll(int64_t* p) { return reinterpret_cast<long long*>(p); }
+
 // Scratch that has outgrown its first home inside the handle's slab is an allocation of its own.
 void free_scratch(s2s_handle* h, void* p) {
     const char* c = static_cast<const char*>(p);
@@ -1399,6 +1373,11 @@ struct DeviceGuard {
     }
     ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
+// The guard of a handle-free entry, `guard`, for the rest of the function; RETURNS S2S_ERR_HIP where the device cannot be made current.
+// Two statements: it stands as a statement of its own at function scope, never under an un-braced `if` or `else`.
+#define GUARD_OR_RETURN(h, dev) \
+    DeviceGuard guard(dev);     \
+    if (!guard.ok) return fail((h), S2S_ERR_HIP, "hipSetDevice failed")
 
 size_t layer_floats() { return 4 * (64 * 64 + 64) + 2 * 64 + (256 * 64 + 256) + (64 * 256 + 64) + 2 * 64; }
 size_t mlp_floats() { return 64 * 64 + 64 + 64 + 1; }
@@ -2365,7 +2344,8 @@ int s2s_export_reads(s2s_handle* h, void* stream_, const float* signal, int32_t 
     if (B > 0)
         hipLaunchKernelGGL(tuned_rows ? s2s_count_kernel<S2S_T_DEC> : s2s_count_kernel<0>, dim3((B + 3) / 4), dim3(256), 0, stream, signal, B,
                            h->ws_counts, ts);
-    hipLaunchKernelGGL(s2s_scan_kernel, dim3(1), dim3(1024), 0, stream, h->ws_counts, B, h->ws_offs);
+    hipLaunchKernelGGL((s2s_scan_kernel<8, S2SScanInts>), dim3(1), dim3(1024), 0, stream, S2SScanInts{h->ws_counts}, (long long)B,
+                       h->ws_offs);
     hipLaunchKernelGGL(s2s_read_offsets_kernel, dim3((R + 256) / 256), dim3(256), 0, stream, h->ws_offs, read_first, R,
                        reinterpret_cast<long long*>(out_offsets));
     if (B > 0 && (out_pa || out_dac))
@@ -2384,9 +2364,8 @@ int s2s_align_chunks(s2s_handle* h, void* stream_, const float* signal, const in
     DeviceGuard guard(h->device);
     if (!guard.ok) return fail(h, S2S_ERR_HIP, "hipSetDevice failed");
     const int te = h->cfg.max_dna_len, ts = h->cfg.max_signal_len;    // S2S_T_ENC / S2S_T_DEC except for a geometry-mode handle
-    hipLaunchKernelGGL(ts == S2S_T_DEC ? s2s_align_kernel<S2S_T_DEC> : s2s_align_kernel<0>, dim3((B + 3) / 4), dim3(256), 0,
-                       static_cast<hipStream_t>(stream_), signal, dur, B, reinterpret_cast<unsigned short*>(out_seg), te, ts);
-    HIP_TRY(h, hipGetLastError());
+    S2S_LAUNCH(h, ts == S2S_T_DEC ? s2s_align_kernel<S2S_T_DEC> : s2s_align_kernel<0>, dim3((B + 3) / 4), dim3(256), 0,
+               static_cast<hipStream_t>(stream_), signal, dur, B, reinterpret_cast<unsigned short*>(out_seg), te, ts);
     return S2S_OK;
 }
 
@@ -2400,10 +2379,9 @@ int s2s_event_stats(s2s_handle* h, void* stream_, const float* signal, const int
     DeviceGuard guard(h->device);
     if (!guard.ok) return fail(h, S2S_ERR_HIP, "hipSetDevice failed");
     const int te = h->cfg.max_dna_len, ts = h->cfg.max_signal_len;    // S2S_T_ENC / S2S_T_DEC except for a geometry-mode handle
-    hipLaunchKernelGGL(ts == S2S_T_DEC ? s2s_event_stats_kernel<S2S_T_DEC> : s2s_event_stats_kernel<0>, dim3((B + 3) / 4), dim3(256), 0,
-                       static_cast<hipStream_t>(stream_), signal, dur, B, digitisation, range, offset,
-                       reinterpret_cast<unsigned short*>(out_seg), out_sum, reinterpret_cast<long long*>(out_sumsq), te, ts);
-    HIP_TRY(h, hipGetLastError());
+    S2S_LAUNCH(h, ts == S2S_T_DEC ? s2s_event_stats_kernel<S2S_T_DEC> : s2s_event_stats_kernel<0>, dim3((B + 3) / 4), dim3(256), 0,
+               static_cast<hipStream_t>(stream_), signal, dur, B, digitisation, range, offset, reinterpret_cast<unsigned short*>(out_seg),
+               out_sum, reinterpret_cast<long long*>(out_sumsq), te, ts);
     return S2S_OK;
 }
 
@@ -2431,10 +2409,9 @@ int s2s_kmer_table_accumulate(s2s_handle* h, void* stream_, const float* signal,
     const size_t lds_bytes = lds ? (size_t)s2s_kmer_table_rows(k) * S2S_KMER_TABLE_FIELDS * sizeof(unsigned long long) : 0;
     auto kernel = lds ? (tuned_rows ? s2s_kmer_table_kernel<S2S_T_DEC, true> : s2s_kmer_table_kernel<0, true>)
                       : (tuned_rows ? s2s_kmer_table_kernel<S2S_T_DEC, false> : s2s_kmer_table_kernel<0, false>);
-    hipLaunchKernelGGL(kernel, dim3(lds && groups > 512 ? 512 : groups), dim3(256), lds_bytes, static_cast<hipStream_t>(stream_), signal,
-                       dur, read_bytes, reinterpret_cast<const long long*>(chunk_start), n_valid, B, digitisation, range, offset,
-                       reinterpret_cast<unsigned long long*>(table), te, ts, k);
-    HIP_TRY(h, hipGetLastError());
+    S2S_LAUNCH(h, kernel, dim3(lds && groups > 512 ? 512 : groups), dim3(256), lds_bytes, static_cast<hipStream_t>(stream_), signal, dur,
+               read_bytes, reinterpret_cast<const long long*>(chunk_start), n_valid, B, digitisation, range, offset,
+               reinterpret_cast<unsigned long long*>(table), te, ts, k);
     return S2S_OK;
 }
 
@@ -2455,10 +2432,9 @@ int s2s_kmer_model_accumulate(s2s_handle* h, void* stream_, const float* signal,
     const int te = h->cfg.max_dna_len, ts = h->cfg.max_signal_len;    // S2S_T_ENC / S2S_T_DEC except for a geometry-mode handle
     const int groups = (B + 3) / 4;
     auto kernel = ts == S2S_T_DEC ? s2s_kmer_model_kernel<S2S_T_DEC> : s2s_kmer_model_kernel<0>;
-    hipLaunchKernelGGL(kernel, dim3(groups > S2S_KMER_MODEL_MAX_WORKGROUPS ? S2S_KMER_MODEL_MAX_WORKGROUPS : groups), dim3(256), 0,
-                       static_cast<hipStream_t>(stream_), signal, dur, read_bytes, reinterpret_cast<const long long*>(chunk_start),
-                       n_valid, B, digitisation, range, offset, reinterpret_cast<unsigned long long*>(table), te, ts, k);
-    HIP_TRY(h, hipGetLastError());
+    S2S_LAUNCH(h, kernel, dim3(groups > S2S_KMER_MODEL_MAX_WORKGROUPS ? S2S_KMER_MODEL_MAX_WORKGROUPS : groups), dim3(256), 0,
+               static_cast<hipStream_t>(stream_), signal, dur, read_bytes, reinterpret_cast<const long long*>(chunk_start), n_valid, B,
+               digitisation, range, offset, reinterpret_cast<unsigned long long*>(table), te, ts, k);
     return S2S_OK;
 }
 
@@ -2491,7 +2467,7 @@ int s2s_svb_encode(s2s_handle* h, void* stream_, const int16_t* samples, const i
             hipLaunchKernelGGL((s2s_svb_kernel<16, false>), dim3(N), dim3(256), 0, stream, sp, ro, row_read, row_index,
                                (long long)row_samples, h->ws_svb, nullptr, nullptr, 0LL);
     }
-    hipLaunchKernelGGL(s2s_scan_kernel, dim3(1), dim3(1024), 0, stream, h->ws_svb, N, oo);
+    hipLaunchKernelGGL((s2s_scan_kernel<8, S2SScanInts>), dim3(1), dim3(1024), 0, stream, S2SScanInts{h->ws_svb}, (long long)N, oo);
     if (N > 0) {
         if (variant == 32)
             hipLaunchKernelGGL((s2s_svb_kernel<32, true>), dim3(N), dim3(256), 0, stream, sp, ro, row_read, row_index,
@@ -2500,8 +2476,7 @@ int s2s_svb_encode(s2s_handle* h, void* stream_, const int16_t* samples, const i
             hipLaunchKernelGGL((s2s_svb_kernel<16, true>), dim3(N), dim3(256), 0, stream, sp, ro, row_read, row_index,
                                (long long)row_samples, nullptr, oo, out, (long long)capacity);
     }
-    hipLaunchKernelGGL(s2s_svb_check_kernel, dim3(1), dim3(64), 0, stream, oo, N, (long long)capacity);
-    HIP_TRY(h, hipGetLastError());
+    S2S_LAUNCH(h, s2s_svb_check_kernel, dim3(1), dim3(64), 0, stream, oo, N, (long long)capacity);
     return S2S_OK;
 }
 
@@ -2512,9 +2487,8 @@ int s2s_philox_u32(s2s_handle* h, void* stream_, uint64_t seed, uint32_t c0, uin
     if (n == 0) return S2S_OK;
     DeviceGuard guard(h->device);
     if (!guard.ok) return fail(h, S2S_ERR_HIP, "hipSetDevice failed");
-    hipLaunchKernelGGL(s2s_philox_kernel, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream_),
-                       (unsigned)seed, (unsigned)(seed >> 32), c0, c1, c2, c3, n, out);
-    HIP_TRY(h, hipGetLastError());
+    S2S_LAUNCH(h, s2s_philox_kernel, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream_), (unsigned)seed,
+               (unsigned)(seed >> 32), c0, c1, c2, c3, n, out);
     return S2S_OK;
 }
 
@@ -2576,11 +2550,9 @@ int32_t s2s_dtw_max_band(void) { return S2S_DTW_MAX_BAND; }
 int s2s_signal_median_mad(int device, void* stream_, const int16_t* samples, const int64_t* offs, int32_t R, int32_t* med, int32_t* mad) {
     if (R < 0 || !offs || (R > 0 && (!samples || !med || !mad))) return fail(nullptr, S2S_ERR_ARG, "s2s_signal_median_mad: bad argument");
     if (R == 0) return S2S_OK;
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(nullptr, S2S_ERR_HIP, "hipSetDevice failed");
-    hipLaunchKernelGGL(s2s_median_mad_kernel, dim3(R), dim3(S2S_DTW_SELECT_THREADS), 0, static_cast<hipStream_t>(stream_), samples,
-                       reinterpret_cast<const long long*>(offs), med, mad);
-    HIP_TRY(nullptr, hipGetLastError());
+    GUARD_OR_RETURN(nullptr, device);
+    S2S_LAUNCH(nullptr, s2s_median_mad_kernel, dim3(R), dim3(S2S_DTW_SELECT_THREADS), 0, static_cast<hipStream_t>(stream_), samples,
+               as_ll(offs), med, mad);
     return S2S_OK;
 }
 
@@ -2589,11 +2561,9 @@ int s2s_signal_normalise(int device, void* stream_, const int16_t* samples, cons
     if (R < 0 || !offs || scale < 1 || scale > S2S_DTW_MAX_SCALE || (R > 0 && (!samples || !med || !mad || !out)))
         return fail(nullptr, S2S_ERR_ARG, "s2s_signal_normalise: bad argument (scale must be 1..8192)");
     if (R == 0) return S2S_OK;
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(nullptr, S2S_ERR_HIP, "hipSetDevice failed");
-    hipLaunchKernelGGL(s2s_normalise_kernel, dim3(R, S2S_DTW_NORM_SLICES), dim3(256), 0, static_cast<hipStream_t>(stream_), samples,
-                       reinterpret_cast<const long long*>(offs), med, mad, scale, out);
-    HIP_TRY(nullptr, hipGetLastError());
+    GUARD_OR_RETURN(nullptr, device);
+    S2S_LAUNCH(nullptr, s2s_normalise_kernel, dim3(R, S2S_DTW_NORM_SLICES), dim3(256), 0, static_cast<hipStream_t>(stream_), samples,
+               as_ll(offs), med, mad, scale, out);
     return S2S_OK;
 }
 
@@ -2602,15 +2572,12 @@ int s2s_dtw_banded(int device, void* stream_, const int16_t* a, const int64_t* a
     if (P < 0 || band < 1 || band > S2S_DTW_MAX_BAND || !a_offs || !b_offs || (P > 0 && (!a || !b || !cost)))
         return fail(nullptr, S2S_ERR_ARG, "s2s_dtw_banded: bad argument (band must be 1..S2S_DTW_MAX_BAND)");
     if (P == 0) return S2S_OK;
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(nullptr, S2S_ERR_HIP, "hipSetDevice failed");
+    GUARD_OR_RETURN(nullptr, device);
     // a diagonal holds at most 2 band + 1 cells: one wave while two strides cover it, else four
     const int threads = 2 * band + 1 <= 128 ? 64 : 256;
     const size_t lds = S2S_DTW_LDS_BYTES(band);      // 58,416 B at S2S_DTW_MAX_BAND
-    hipLaunchKernelGGL(s2s_dtw_kernel<false>, dim3(P), dim3(threads), lds, static_cast<hipStream_t>(stream_), a,
-                       reinterpret_cast<const long long*>(a_offs), b, reinterpret_cast<const long long*>(b_offs), band,
-                       reinterpret_cast<long long*>(cost), static_cast<unsigned char*>(nullptr), static_cast<const long long*>(nullptr));
-    HIP_TRY(nullptr, hipGetLastError());
+    S2S_LAUNCH(nullptr, s2s_dtw_kernel<false>, dim3(P), dim3(threads), lds, static_cast<hipStream_t>(stream_), a, as_ll(a_offs), b, as_ll(b_offs),
+               band, as_ll(cost), static_cast<unsigned char*>(nullptr), static_cast<const long long*>(nullptr));
     return S2S_OK;
 }
 
@@ -2626,19 +2593,13 @@ int s2s_dtw_path(int device, void* stream_, const int16_t* a, const int64_t* a_o
         (P > 0 && (!a || !b || !cost || !scratch || !ops || !steps)) || (reinterpret_cast<uintptr_t>(scratch) & 15u))
         return fail(nullptr, S2S_ERR_ARG, "s2s_dtw_path: bad argument (band must be 1..S2S_DTW_MAX_BAND, scratch 16-byte aligned)");
     if (P == 0) return S2S_OK;
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(nullptr, S2S_ERR_HIP, "hipSetDevice failed");
+    GUARD_OR_RETURN(nullptr, device);
     const int threads = 2 * band + 1 <= 128 ? 64 : 256;          // as s2s_dtw_banded
     const size_t lds = S2S_DTW_LDS_BYTES(band);
-    hipLaunchKernelGGL(s2s_dtw_kernel<true>, dim3(P), dim3(threads), lds, static_cast<hipStream_t>(stream_), a,
-                       reinterpret_cast<const long long*>(a_offs), b, reinterpret_cast<const long long*>(b_offs), band,
-                       reinterpret_cast<long long*>(cost), scratch, reinterpret_cast<const long long*>(scratch_offs));
-    HIP_TRY(nullptr, hipGetLastError());
-    hipLaunchKernelGGL(s2s_dtw_trace_kernel, dim3(P), dim3(64), 0, static_cast<hipStream_t>(stream_),
-                       reinterpret_cast<const long long*>(a_offs), reinterpret_cast<const long long*>(b_offs), band,
-                       reinterpret_cast<const long long*>(cost), scratch, reinterpret_cast<const long long*>(scratch_offs), ops,
-                       reinterpret_cast<const long long*>(path_offs), reinterpret_cast<long long*>(steps));
-    HIP_TRY(nullptr, hipGetLastError());
+    S2S_LAUNCH(nullptr, s2s_dtw_kernel<true>, dim3(P), dim3(threads), lds, static_cast<hipStream_t>(stream_), a, as_ll(a_offs), b, as_ll(b_offs),
+               band, as_ll(cost), scratch, as_ll(scratch_offs));
+    S2S_LAUNCH(nullptr, s2s_dtw_trace_kernel, dim3(P), dim3(64), 0, static_cast<hipStream_t>(stream_), as_ll(a_offs), as_ll(b_offs), band,
+               as_ll(cost), scratch, as_ll(scratch_offs), ops, as_ll(path_offs), as_ll(steps));
     return S2S_OK;
 }
 
@@ -2651,14 +2612,10 @@ int s2s_sdtw(int device, void* stream_, const int16_t* q, const int64_t* q_begin
     if (P < 0 || (P > 0 && (!q || !q_begin || !q_len || !t || !t_begin || !t_len || !reverse || !cost || !start || !end)))
         return fail(nullptr, S2S_ERR_ARG, "s2s_sdtw: bad argument");
     if (P == 0) return S2S_OK;
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(nullptr, S2S_ERR_HIP, "hipSetDevice failed");
+    GUARD_OR_RETURN(nullptr, device);
     static_assert(S2S_SDTW_LDS_BYTES == 57904, "include/s2s_hip.h states the LDS bytes of s2s_sdtw");
-    hipLaunchKernelGGL(s2s_sdtw_kernel, dim3(P), dim3(S2S_SDTW_THREADS), 0, static_cast<hipStream_t>(stream_), q,
-                       reinterpret_cast<const long long*>(q_begin), reinterpret_cast<const long long*>(q_len), t,
-                       reinterpret_cast<const long long*>(t_begin), reinterpret_cast<const long long*>(t_len), reverse,
-                       reinterpret_cast<long long*>(cost), reinterpret_cast<long long*>(start), reinterpret_cast<long long*>(end));
-    HIP_TRY(nullptr, hipGetLastError());
+    S2S_LAUNCH(nullptr, s2s_sdtw_kernel, dim3(P), dim3(S2S_SDTW_THREADS), 0, static_cast<hipStream_t>(stream_), q, as_ll(q_begin), as_ll(q_len),
+               t, as_ll(t_begin), as_ll(t_len), reverse, as_ll(cost), as_ll(start), as_ll(end));
     return S2S_OK;
 }
 
@@ -2677,19 +2634,14 @@ int s2s_resquiggle(int device, void* stream_, const int16_t* q, const int64_t* q
         return fail(nullptr, S2S_ERR_ARG, "s2s_resquiggle: bad argument (band must be 1..S2S_DTW_MAX_BAND, skip_penalty 0..2^20, "
                                           "unknown_cost 0..65535, scratch 16-byte aligned)");
     if (P == 0) return S2S_OK;
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(nullptr, S2S_ERR_HIP, "hipSetDevice failed");
+    GUARD_OR_RETURN(nullptr, device);
     static_assert(S2S_RSQ_LDS_BYTES(S2S_DTW_MAX_BAND) == 38272 && S2S_RSQ_LDS_BYTES(512) == 19840,
                   "include/s2s_hip.h states the LDS bytes of s2s_resquiggle");
-    hipLaunchKernelGGL(s2s_resquiggle_kernel, dim3(P), dim3(64 * s2s_rsq_waves(band)), S2S_RSQ_LDS_BYTES(band),
-                       static_cast<hipStream_t>(stream_), q, reinterpret_cast<const long long*>(q_offs), l,
-                       reinterpret_cast<const long long*>(l_offs), band, skip_penalty, unknown_cost, reinterpret_cast<long long*>(cost),
-                       scratch, reinterpret_cast<const long long*>(scratch_offs));
-    HIP_TRY(nullptr, hipGetLastError());
-    hipLaunchKernelGGL(s2s_resquiggle_trace_kernel, dim3(P), dim3(64), 0, static_cast<hipStream_t>(stream_),
-                       reinterpret_cast<const long long*>(q_offs), reinterpret_cast<const long long*>(l_offs), band,
-                       reinterpret_cast<const long long*>(cost), scratch, reinterpret_cast<const long long*>(scratch_offs), ev_start, ev_len);
-    HIP_TRY(nullptr, hipGetLastError());
+    S2S_LAUNCH(nullptr, s2s_resquiggle_kernel, dim3(P), dim3(64 * s2s_rsq_waves(band)), S2S_RSQ_LDS_BYTES(band),
+               static_cast<hipStream_t>(stream_), q, as_ll(q_offs), l, as_ll(l_offs), band, skip_penalty, unknown_cost, as_ll(cost), scratch,
+               as_ll(scratch_offs));
+    S2S_LAUNCH(nullptr, s2s_resquiggle_trace_kernel, dim3(P), dim3(64), 0, static_cast<hipStream_t>(stream_), as_ll(q_offs), as_ll(l_offs), band,
+               as_ll(cost), scratch, as_ll(scratch_offs), ev_start, ev_len);
     return S2S_OK;
 }
 
@@ -2698,12 +2650,9 @@ int s2s_event_sums(int device, void* stream_, const int16_t* samples, const int6
     if (P < 0 || !s_offs || !l_offs || (P > 0 && (!samples || !ev_start || !ev_len || !S || !Q)))
         return fail(nullptr, S2S_ERR_ARG, "s2s_event_sums: bad argument");
     if (P == 0) return S2S_OK;
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(nullptr, S2S_ERR_HIP, "hipSetDevice failed");
-    hipLaunchKernelGGL(s2s_event_sums_kernel, dim3(P, S2S_RSQ_SUM_SLICES), dim3(256), 0, static_cast<hipStream_t>(stream_), samples,
-                       reinterpret_cast<const long long*>(s_offs), ev_start, ev_len, reinterpret_cast<const long long*>(l_offs),
-                       reinterpret_cast<long long*>(S), reinterpret_cast<long long*>(Q));
-    HIP_TRY(nullptr, hipGetLastError());
+    GUARD_OR_RETURN(nullptr, device);
+    S2S_LAUNCH(nullptr, s2s_event_sums_kernel, dim3(P, S2S_RSQ_SUM_SLICES), dim3(256), 0, static_cast<hipStream_t>(stream_), samples,
+               as_ll(s_offs), ev_start, ev_len, as_ll(l_offs), as_ll(S), as_ll(Q));
     return S2S_OK;
 }
 
@@ -2721,23 +2670,17 @@ int s2s_segment(int device, void* stream_, const int16_t* samples, const int64_t
         return fail(nullptr, S2S_ERR_ARG, "s2s_segment: bad argument (windows 1 <= short <= long <= 32, thresholds 1..2^40, total 0..2^40, "
                                           "scratch 16-byte aligned)");
     if (R == 0 || total == 0) return S2S_OK;
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(nullptr, S2S_ERR_HIP, "hipSetDevice failed");
+    GUARD_OR_RETURN(nullptr, device);
     const int64_t tiles = s2s_seg_tiles(total);
     unsigned long long* words = reinterpret_cast<unsigned long long*>(scratch);
     int* wrank = reinterpret_cast<int*>(scratch + tiles * S2S_SEG_WORDS * 8);
     long long* trank = reinterpret_cast<long long*>(scratch + tiles * S2S_SEG_WORDS * 12);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    hipLaunchKernelGGL(s2s_segment_flags_kernel, dim3((unsigned)tiles), dim3(S2S_SEG_THREADS), 0, stream, samples,
-                       reinterpret_cast<const long long*>(offs), R, (long long)total, w_short, w_long, (long long)thr_short,
-                       (long long)thr_long, words, wrank, trank);
-    HIP_TRY(nullptr, hipGetLastError());
-    hipLaunchKernelGGL(s2s_segment_scan_kernel, dim3(1), dim3(1024), 0, stream, trank, (long long)tiles);
-    HIP_TRY(nullptr, hipGetLastError());
-    hipLaunchKernelGGL(s2s_segment_compact_kernel, dim3((unsigned)tiles), dim3(S2S_SEG_THREADS), 0, stream,
-                       reinterpret_cast<const long long*>(offs), R, (long long)total, (long long)tiles, words, wrank, trank,
-                       reinterpret_cast<const long long*>(ev_offs), ev_start, ev_len, n_events);
-    HIP_TRY(nullptr, hipGetLastError());
+    S2S_LAUNCH(nullptr, s2s_segment_flags_kernel, dim3((unsigned)tiles), dim3(S2S_SEG_THREADS), 0, stream, samples, as_ll(offs), R,
+               (long long)total, w_short, w_long, (long long)thr_short, (long long)thr_long, words, wrank, trank);
+    S2S_LAUNCH(nullptr, (s2s_scan_kernel<1, S2SScanNext>), dim3(1), dim3(1024), 0, stream, S2SScanNext{trank}, (long long)tiles, trank);
+    S2S_LAUNCH(nullptr, s2s_segment_compact_kernel, dim3((unsigned)tiles), dim3(S2S_SEG_THREADS), 0, stream, as_ll(offs), R, (long long)total,
+               (long long)tiles, words, wrank, trank, as_ll(ev_offs), ev_start, ev_len, n_events);
     return S2S_OK;
 }
 
@@ -2746,17 +2689,13 @@ int s2s_event_means(int device, void* stream_, const int64_t* S, const int32_t* 
                     int32_t R, int64_t capacity, int64_t* m_offs, int16_t* means) {
     if (R < 0 || capacity < 0 || !ev_offs || !m_offs || (R > 0 && (!n_events || (capacity > 0 && (!S || !ev_len || !means)))))
         return fail(nullptr, S2S_ERR_ARG, "s2s_event_means: bad argument");
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(nullptr, S2S_ERR_HIP, "hipSetDevice failed");
+    GUARD_OR_RETURN(nullptr, device);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    hipLaunchKernelGGL(s2s_event_means_scan_kernel, dim3(1), dim3(1024), 0, stream, n_events, reinterpret_cast<const long long*>(ev_offs), R,
-                       reinterpret_cast<long long*>(m_offs));
-    HIP_TRY(nullptr, hipGetLastError());
+    S2S_LAUNCH(nullptr, (s2s_scan_kernel<1, S2SEvaCounts>), dim3(1), dim3(1024), 0, stream, S2SEvaCounts{n_events, as_ll(ev_offs)},
+               (long long)R, as_ll(m_offs));
     if (R == 0 || capacity == 0) return S2S_OK;
-    hipLaunchKernelGGL(s2s_event_means_fill_kernel, dim3(R, S2S_EVA_MEAN_SLICES), dim3(256), 0, stream, reinterpret_cast<const long long*>(S),
-                       ev_len, reinterpret_cast<const long long*>(ev_offs), n_events, (long long)capacity,
-                       reinterpret_cast<const long long*>(m_offs), means);
-    HIP_TRY(nullptr, hipGetLastError());
+    S2S_LAUNCH(nullptr, s2s_event_means_fill_kernel, dim3(R, S2S_EVA_MEAN_SLICES), dim3(256), 0, stream, as_ll(S), ev_len, as_ll(ev_offs),
+               n_events, (long long)capacity, as_ll(m_offs), means);
     return S2S_OK;
 }
 
@@ -2771,21 +2710,14 @@ int s2s_eventalign(int device, void* stream_, const int16_t* m, const int64_t* m
         return fail(nullptr, S2S_ERR_ARG, "s2s_eventalign: bad argument (width a multiple of 64 in 64..S2S_EVA_MAX_WIDTH, skip_penalty and "
                                           "trim_penalty 0..2^20, unknown_cost 0..65535, scratch 16-byte aligned)");
     if (P == 0) return S2S_OK;
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(nullptr, S2S_ERR_HIP, "hipSetDevice failed");
+    GUARD_OR_RETURN(nullptr, device);
     static_assert(S2S_EVA_LDS_BYTES(S2S_EVA_MAX_WIDTH) == 29744 && S2S_EVA_LDS_BYTES(128) == 4656,
                   "include/s2s_hip.h states the LDS bytes of s2s_eventalign");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    hipLaunchKernelGGL(s2s_eventalign_kernel, dim3(P), dim3(width), S2S_EVA_LDS_BYTES(width), stream, m,
-                       reinterpret_cast<const long long*>(m_offs), l, reinterpret_cast<const long long*>(l_offs), width, skip_penalty,
-                       trim_penalty, unknown_cost, reinterpret_cast<long long*>(cost), scratch,
-                       reinterpret_cast<const long long*>(scratch_offs), end_event);
-    HIP_TRY(nullptr, hipGetLastError());
-    hipLaunchKernelGGL(s2s_eventalign_trace_kernel, dim3(P), dim3(64), 0, stream, reinterpret_cast<const long long*>(m_offs),
-                       reinterpret_cast<const long long*>(l_offs), ev_start, ev_len, reinterpret_cast<const long long*>(ev_offs), width,
-                       reinterpret_cast<const long long*>(cost), scratch, reinterpret_cast<const long long*>(scratch_offs), first_event,
-                       end_event, ev_kmer, k_start, k_len, k_events);
-    HIP_TRY(nullptr, hipGetLastError());
+    S2S_LAUNCH(nullptr, s2s_eventalign_kernel, dim3(P), dim3(width), S2S_EVA_LDS_BYTES(width), stream, m, as_ll(m_offs), l, as_ll(l_offs), width,
+               skip_penalty, trim_penalty, unknown_cost, as_ll(cost), scratch, as_ll(scratch_offs), end_event);
+    S2S_LAUNCH(nullptr, s2s_eventalign_trace_kernel, dim3(P), dim3(64), 0, stream, as_ll(m_offs), as_ll(l_offs), ev_start, ev_len, as_ll(ev_offs),
+               width, as_ll(cost), scratch, as_ll(scratch_offs), first_event, end_event, ev_kmer, k_start, k_len, k_events);
     return S2S_OK;
 }
 
@@ -2803,8 +2735,7 @@ int s2s_chunk_pack(int device, void* stream_, const void* pool, const int64_t* s
         (reinterpret_cast<uintptr_t>(scratch) & 15u))
         return fail(nullptr, S2S_ERR_ARG, "s2s_chunk_pack: bad argument (source 0 / 1, k 1..10, te 1..64, ts 1..1024, P <= 2^22, P <= "
                                           "chunk_capacity < 2^31, slots < 2^31, total <= 2^40, scratch 16-byte aligned)");
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(nullptr, S2S_ERR_HIP, "hipSetDevice failed");
+    GUARD_OR_RETURN(nullptr, device);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     HIP_TRY(nullptr, hipMemsetAsync(counters, 0, 3 * sizeof(int64_t), stream));
     if (P > 0) HIP_TRY(nullptr, hipMemsetAsync(n_rows, 0, (size_t)P * sizeof(int32_t), stream));
@@ -2822,34 +2753,25 @@ int s2s_chunk_pack(int device, void* stream_, const void* pool, const int64_t* s
     int* rows = reinterpret_cast<int*>(scratch + at.rows);
     S2SChkIn in;
     in.pool = pool;
-    in.s_offs = reinterpret_cast<const long long*>(s_offs);
-    in.l_offs = reinterpret_cast<const long long*>(l_offs);
+    in.s_offs = as_ll(s_offs); in.l_offs = as_ll(l_offs);
     in.ev_start = ev_start; in.ev_len = ev_len;
-    in.S = reinterpret_cast<const long long*>(S); in.Q = reinterpret_cast<const long long*>(Q);
+    in.S = as_ll(S); in.Q = as_ll(Q);
     in.cal = source == S2S_CHUNK_RAW ? cal : nullptr;
     in.stdv = stdv; in.kmers = kmers;
     in.total = total; in.slots = slots; in.capacity = chunk_capacity;
     in.P = P; in.source = source; in.k = k; in.te = te; in.ts = ts; in.reverse = reverse ? 1 : 0; in.backwards = backwards ? 1 : 0;
     const unsigned waves = (unsigned)((chunk_capacity + S2S_CHK_WAVES - 1) / S2S_CHK_WAVES);
-    hipLaunchKernelGGL(s2s_chunk_flags_kernel, dim3((unsigned)tiles), dim3(S2S_CHK_THREADS), 0, stream, in, words, wrank, trank, nrank);
-    HIP_TRY(nullptr, hipGetLastError());
-    hipLaunchKernelGGL(s2s_segment_scan_kernel, dim3(1), dim3(1024), 0, stream, trank, (long long)tiles);
-    HIP_TRY(nullptr, hipGetLastError());
-    hipLaunchKernelGGL(s2s_segment_scan_kernel, dim3(1), dim3(1024), 0, stream, nrank, (long long)tiles);
-    HIP_TRY(nullptr, hipGetLastError());
-    hipLaunchKernelGGL(s2s_chunk_compact_kernel, dim3((unsigned)tiles), dim3(S2S_CHK_THREADS), 0, stream, in, words, wrank, trank, rows,
-                       r_offs, c_offs, n_rows);
-    HIP_TRY(nullptr, hipGetLastError());
-    hipLaunchKernelGGL(s2s_segment_scan_kernel, dim3(1), dim3(1024), 0, stream, c_offs, (long long)P);
-    HIP_TRY(nullptr, hipGetLastError());
-    hipLaunchKernelGGL(s2s_chunk_lengths_kernel, dim3(waves), dim3(S2S_CHK_THREADS), 0, stream, in, rows, r_offs, c_offs, n_rows, krank);
-    HIP_TRY(nullptr, hipGetLastError());
-    hipLaunchKernelGGL(s2s_segment_scan_kernel, dim3(1), dim3(1024), 0, stream, krank, (long long)chunk_capacity);
-    HIP_TRY(nullptr, hipGetLastError());
-    hipLaunchKernelGGL(s2s_chunk_write_kernel, dim3(waves), dim3(S2S_CHK_THREADS), 0, stream, in, rows, r_offs, c_offs, n_rows, krank, nrank,
-                       (long long)tiles, chunks, reinterpret_cast<long long*>(chunks_lengths), targets,
-                       reinterpret_cast<long long*>(targets_lengths), stdevs, reinterpret_cast<long long*>(counters));
-    HIP_TRY(nullptr, hipGetLastError());
+    S2S_LAUNCH(nullptr, s2s_chunk_flags_kernel, dim3((unsigned)tiles), dim3(S2S_CHK_THREADS), 0, stream, in, words, wrank, trank, nrank);
+    S2S_LAUNCH(nullptr, (s2s_scan_kernel<1, S2SScanNext>), dim3(1), dim3(1024), 0, stream, S2SScanNext{trank}, (long long)tiles, trank);
+    S2S_LAUNCH(nullptr, (s2s_scan_kernel<1, S2SScanNext>), dim3(1), dim3(1024), 0, stream, S2SScanNext{nrank}, (long long)tiles, nrank);
+    S2S_LAUNCH(nullptr, s2s_chunk_compact_kernel, dim3((unsigned)tiles), dim3(S2S_CHK_THREADS), 0, stream, in, words, wrank, trank, rows,
+               r_offs, c_offs, n_rows);
+    S2S_LAUNCH(nullptr, (s2s_scan_kernel<1, S2SScanNext>), dim3(1), dim3(1024), 0, stream, S2SScanNext{c_offs}, (long long)P, c_offs);
+    S2S_LAUNCH(nullptr, s2s_chunk_lengths_kernel, dim3(waves), dim3(S2S_CHK_THREADS), 0, stream, in, rows, r_offs, c_offs, n_rows, krank);
+    S2S_LAUNCH(nullptr, (s2s_scan_kernel<1, S2SScanNext>), dim3(1), dim3(1024), 0, stream, S2SScanNext{krank}, (long long)chunk_capacity,
+               krank);
+    S2S_LAUNCH(nullptr, s2s_chunk_write_kernel, dim3(waves), dim3(S2S_CHK_THREADS), 0, stream, in, rows, r_offs, c_offs, n_rows, krank,
+               nrank, (long long)tiles, chunks, as_ll(chunks_lengths), targets, as_ll(targets_lengths), stdevs, as_ll(counters));
     return S2S_OK;
 }
 

@@ -2,16 +2,15 @@
 // only.  A position's score depends on the 2 w samples around it and on nothing else, so the work is split over the POOLED positions:
 // workgroup t owns [S2S_SEG_TILE t, S2S_SEG_TILE (t + 1)) whatever records lie there -- the inside of one long record, or thousands
 // of empty ones.  The score and the layout of the scratch are one set of functions for the kernels, the host entry and the host twin
-// (s2s_host.cpp); the three kernels follow under S2S_DTW_KERNELS.
+// (s2s_host.cpp); the two kernels follow under S2S_DTW_KERNELS, and the scan between them is s2s_prims.h's.
 #pragma once
 #include <stdint.h>
 
 #include "../../include/s2s_hip.h"
 #include "s2s_dtw.h"
+#include "s2s_prims.h"
 
-#define S2S_SEG_WORDS (S2S_SEG_TILE / 64)           // flag words of a tile
 #define S2S_SEG_MAX_HALO (3 * S2S_SEG_MAX_WINDOW)   // max(2 w_l, 3 w_s) at the largest windows
-#define S2S_SEG_MAX_TOTAL ((int64_t)1 << 40)        // pooled samples of one call: 2^29 tiles, a grid the runtime takes
 
 // max(2 w_l, 3 w_s): a long peak at p needs the long scores of [p - w_l, p + w_l], i.e. the samples [p - 2 w_l, p + 2 w_l); the merge
 // rule needs the short peaks of [p - w_s, p + w_s], those the short scores of [p - 2 w_s, p + 2 w_s], those the samples
@@ -50,31 +49,6 @@ struct S2SSegLds {
 static_assert(sizeof(S2SSegLds) == S2S_SEG_LDS_BYTES && S2S_SEG_LDS_BYTES <= 65536, "include/s2s_hip.h states the LDS bytes of s2s_segment");
 static_assert(S2S_SEG_TILE % (64 * (S2S_SEG_THREADS / 64)) == 0 && S2S_SEG_WORDS <= 64, "a wave's ballot is one whole flag word");
 
-// The record of pooled position g: the largest r in [ra, rb] with offs[r] <= g, then the check that makes any content of offs safe:
-// 0 <= offs[r] <= g < offs[r+1] <= total.  (Empty records share their offset with the record behind them: the largest r is the one
-// that holds g.)  ra, rb: 0 .. R - 1, or what the same search gave for the ends of a range that holds g.
-__device__ inline bool s2s_seg_find(const long long* __restrict__ offs, int ra, int rb, long long total, long long g, int& r, long long& lo,
-                                    long long& hi) {
-    int a = ra, b = rb;
-    while (a < b) {
-        const int m = a + (b - a + 1) / 2;
-        if (offs[m] <= g) a = m; else b = m - 1;
-    }
-    r = a;
-    lo = offs[a];
-    hi = offs[a + 1];
-    return lo >= 0 && lo <= g && g < hi && hi <= total;
-}
-
-// Flags before pooled position pos (0 <= pos <= tiles * S2S_SEG_TILE): the tile's rank, the word's rank in the tile, the bits below.
-__device__ inline long long s2s_seg_rank(const unsigned long long* __restrict__ words, const int* __restrict__ wrank,
-                                         const long long* __restrict__ trank, long long pos) {
-    const long long t = pos / S2S_SEG_TILE;
-    if ((pos & (S2S_SEG_TILE - 1)) == 0) return trank[t];        // (also pos = tiles * S2S_SEG_TILE, which has no word)
-    const long long q = pos >> 6;
-    return trank[t] + wrank[q] + __popcll(words[q] & ((1ull << (pos & 63)) - 1ull));
-}
-
 // Launch 1.  Every branch around a barrier depends on blockIdx and the arguments only.
 __global__ __launch_bounds__(S2S_SEG_THREADS) void s2s_segment_flags_kernel(
     const int16_t* __restrict__ samples, const long long* __restrict__ offs, int R, long long total, int w_s, int w_l, long long t_s,
@@ -87,15 +61,15 @@ __global__ __launch_bounds__(S2S_SEG_THREADS) void s2s_segment_flags_kernel(
     {                                               // the records of the two ends of what this tile reads (the same for every thread)
         long long lo, hi;
         const long long ga = gb < 0 ? 0 : gb, ge = (gb + ext < total ? gb + ext : total) - 1;
-        s2s_seg_find(offs, 0, R - 1, total, ga, ra, lo, hi);
-        s2s_seg_find(offs, 0, R - 1, total, ge, rb, lo, hi);
+        s2s_record_find(offs, 0, R - 1, total, ga, ra, lo, hi);
+        s2s_record_find(offs, 0, R - 1, total, ge, rb, lo, hi);
         if (rb < ra) rb = ra;                       // (offsets that decrease)
     }
     for (int e = tid; e < ext; e += S2S_SEG_THREADS) {
         const long long g = gb + e;
         int r;
         long long lo = 0, hi = 0;
-        const bool in = g >= 0 && g < total && s2s_seg_find(offs, ra, rb, total, g, r, lo, hi) && hi - lo <= S2S_DTW_MAX_SAMPLES;
+        const bool in = g >= 0 && g < total && s2s_record_find(offs, ra, rb, total, g, r, lo, hi) && hi - lo <= S2S_DTW_MAX_SAMPLES;
         const long long a = g - lo, b = hi - g;
         s.x[e] = in ? samples[g] : (int16_t)0;
         s.dl[e] = (unsigned char)(in ? (a > 255 ? 255 : a) : 0);
@@ -161,42 +135,10 @@ __global__ __launch_bounds__(S2S_SEG_THREADS) void s2s_segment_flags_kernel(
         if (lane == 0) s.words[k >> 6] = word;
     }
     __syncthreads();
-    if (tid < S2S_SEG_WORDS) {
-        int before = 0;
-        for (int q = 0; q < tid; ++q) before += __popcll(s.words[q]);
-        const long long at = (long long)blockIdx.x * S2S_SEG_WORDS + tid;
-        words[at] = s.words[tid];
-        wrank[at] = before;
-        if (tid == S2S_SEG_WORDS - 1) trank[blockIdx.x + 1] = before + __popcll(s.words[tid]);   // the tile's count; launch 2 scans it
-    }
+    s2s_bitmap_publish(s.words, tid, blockIdx.x, words, wrank, trank);       // trank[t + 1]: the tile's count; launch 2 scans it
 }
 
-// Launch 2: trank[t + 1] = the flags of the tiles 0 .. t, trank[0] = 0.  One workgroup, 1,024 tiles per step and a carry.
-__global__ __launch_bounds__(1024) void s2s_segment_scan_kernel(long long* __restrict__ trank, long long tiles) {
-    __shared__ long long wsum[16];
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    long long carry = 0;
-    for (long long base = 0; base < tiles; base += 1024) {      // (uniform)
-        const long long at = base + tid;
-        long long v = at < tiles ? trank[at + 1] : 0;
-        for (int d = 1; d < 64; d <<= 1) {
-            const long long u = __shfl_up(v, d);
-            if (lane >= d) v += u;
-        }
-        if (lane == 63) wsum[wave] = v;
-        __syncthreads();
-        long long before = 0, all = 0;
-        for (int q = 0; q < 16; ++q) {
-            const long long u = wsum[q];
-            before += q < wave ? u : 0;
-            all += u;
-        }
-        if (at < tiles) trank[at + 1] = carry + before + v;
-        carry += all;
-        __syncthreads();
-    }
-    if (tid == 0) trank[0] = 0;
-}
+// Launch 2 is s2s_scan_kernel<1, S2SScanNext> over trank: trank[t] = the flags of the tiles before t, trank[tiles] = all.
 
 // Launch 3.  The flagged positions of tile blockIdx.x write their events; the records are dealt out over all threads of the grid for
 // n_events.  The flag after a flagged position of rank k in a record whose end has rank > k + 1 is the flag of rank k + 1: in the
@@ -214,7 +156,7 @@ __global__ __launch_bounds__(S2S_SEG_THREADS) void s2s_segment_compact_kernel(
             if (hi - lo > S2S_DTW_MAX_SAMPLES) {
                 v = S2S_DTW_COST_TOO_LONG;
             } else if (hi > lo) {
-                const long long cnt = s2s_seg_rank(words, wrank, trank, hi) - s2s_seg_rank(words, wrank, trank, lo);
+                const long long cnt = s2s_bitmap_rank(words, wrank, trank, hi) - s2s_bitmap_rank(words, wrank, trank, lo);
                 const long long eo = ev_offs[r], cap = ev_offs[r + 1] - eo;
                 v = (int)(eo >= 0 && cnt <= cap ? cnt : -cnt);
             }
@@ -225,8 +167,8 @@ __global__ __launch_bounds__(S2S_SEG_THREADS) void s2s_segment_compact_kernel(
     int ra, rb;
     {
         long long lo, hi;
-        s2s_seg_find(offs, 0, R - 1, total, g0, ra, lo, hi);
-        s2s_seg_find(offs, 0, R - 1, total, (g0 + S2S_SEG_TILE < total ? g0 + S2S_SEG_TILE : total) - 1, rb, lo, hi);
+        s2s_record_find(offs, 0, R - 1, total, g0, ra, lo, hi);
+        s2s_record_find(offs, 0, R - 1, total, (g0 + S2S_SEG_TILE < total ? g0 + S2S_SEG_TILE : total) - 1, rb, lo, hi);
         if (rb < ra) rb = ra;
     }
     for (int j = 0; j < S2S_SEG_TILE / S2S_SEG_THREADS; ++j) {
@@ -236,9 +178,9 @@ __global__ __launch_bounds__(S2S_SEG_THREADS) void s2s_segment_compact_kernel(
         if (!((word >> bit) & 1ull)) continue;
         int r;
         long long lo, hi;
-        if (!s2s_seg_find(offs, ra, rb, total, g, r, lo, hi)) continue;      // (a flagged position has a record: not taken)
-        const long long rk = trank[t] + wrank[g >> 6] + __popcll(word & ((1ull << bit) - 1ull));
-        const long long r_lo = s2s_seg_rank(words, wrank, trank, lo), r_hi = s2s_seg_rank(words, wrank, trank, hi);
+        if (!s2s_record_find(offs, ra, rb, total, g, r, lo, hi)) continue;      // (a flagged position has a record: not taken)
+        const long long rk = s2s_bitmap_rank_in(trank[t], wrank, g, word);
+        const long long r_lo = s2s_bitmap_rank(words, wrank, trank, lo), r_hi = s2s_bitmap_rank(words, wrank, trank, hi);
         const long long cnt = r_hi - r_lo, idx = rk - r_lo;
         const long long eo = ev_offs[r], cap = ev_offs[r + 1] - eo;
         if (eo < 0 || cnt > cap || idx < 0 || idx >= cnt) continue;          // the slot is too small: nothing is written to it
@@ -248,17 +190,9 @@ __global__ __launch_bounds__(S2S_SEG_THREADS) void s2s_segment_compact_kernel(
             if (above) {
                 next = (g & ~63LL) + __ffsll((long long)above) - 1;
             } else {
-                long long a = t, b = tiles - 1;                   // the last tile with trank <= rk + 1
-                while (a < b) {
-                    const long long m = a + (b - a + 1) / 2;
-                    if (trank[m] <= rk + 1) a = m; else b = m - 1;
-                }
-                const int rest = (int)(rk + 1 - trank[a]);
-                int qa = 0, qb = S2S_SEG_WORDS - 1;               // the last word of it with wrank <= rest
-                while (qa < qb) {
-                    const int m = qa + (qb - qa + 1) / 2;
-                    if (wrank[a * S2S_SEG_WORDS + m] <= rest) qa = m; else qb = m - 1;
-                }
+                const long long a = s2s_last_le(t, tiles - 1, rk + 1, [&](long long m) { return trank[m]; });     // the last tile with trank <= rk + 1
+                const int rest = (int)(rk + 1 - trank[a]);          // the last word of it with wrank <= rest
+                const int qa = s2s_last_le(0, S2S_SEG_WORDS - 1, rest, [&](int m) { return wrank[a * S2S_SEG_WORDS + m]; });
                 unsigned long long w2 = words[a * S2S_SEG_WORDS + qa];
                 for (int c = rest - wrank[a * S2S_SEG_WORDS + qa]; c > 0 && w2; --c) w2 &= w2 - 1;     // (c = 0 here: the word's first flag)
                 const long long found = (a * S2S_SEG_WORDS + qa) * 64 + (w2 ? __ffsll((long long)w2) - 1 : 0);

@@ -179,6 +179,16 @@ def standard(te, ts, k, seed=0):
     return case
 
 
+MANY_READS = tuple((P, te, ts, k) for P in (1025, 2049) for te, ts, k in GEOMETRIES[:2])
+
+
+def many_reads(P, te, ts, k, seed=8):
+    """P reads of one or two rows each: more reads than one and than two steps of the scan hold, and at te = 1, where every read forms
+    two chunks or three, more than two and than four steps of chunks."""
+    rng = np.random.default_rng([seed, P, te, ts, k])
+    return make(rng, k, [row_lengths(rng, n, te, ts) for n in rng.integers(1, 3, P)])
+
+
 def edges(te, ts, k, seed=1):
     """-> {name: case}: the specific cases of the issue at one geometry."""
     rng = np.random.default_rng([seed, te, ts, k])

@@ -9,13 +9,36 @@ all of them (the module-scoped `usage`): hipcc cross-compiles for gfx950 without
   none of it static: the sweep's LDS is dynamic, 1024 c + 2 (64 c + 128) bytes for c = ceil((2 band + 1) / 64) word pairs per row,
   which the header gives for bands 512 and 1024 and the host entry pins with a static_assert.
 - The kernels of `segment` (csrc/s2s_segment.h): no scratch memory, no spilled registers, and the LDS include/s2s_hip.h states for the
-  flag pass -- static, pinned by a static_assert next to the kernel."""
+  flag pass -- static, pinned by a static_assert next to the kernel.
+- The instances of the one scan kernel (s2s_scan_kernel<ITEMS, VALUE>, csrc/s2s_prims.h): exactly the three that the entries launch,
+  each without scratch memory or spilled registers and with the 16 wave sums, 128 B, as its static LDS (scan_instances, which the
+  modules of `preprocess` and `eventalign` use too)."""
 import os
 import re
 
 import pytest
 
 from seq2squiggle_amd import _build
+
+SCAN_INSTANCES = {(8, "S2SScanInts"): "s2s_export_reads, s2s_svb_encode", (1, "S2SScanNext"): "s2s_segment, s2s_chunk_pack",
+                  (1, "S2SEvaCounts"): "s2s_event_means"}
+
+
+def scan_instances(usage):
+    """{(ITEMS, VALUE): resource usage} of every s2s_scan_kernel<ITEMS, VALUE> the library holds, after asserting that they are exactly
+    SCAN_INSTANCES -- a missing or an extra instance fails here -- and that each has no scratch, no spills and 128 B of static LDS."""
+    inst = {}
+    for name, u in usage.items():
+        if "s2s_scan_kernel" not in name:
+            continue
+        m = re.match(r"_Z15s2s_scan_kernelILi(\d+)E\d+([A-Za-z0-9]+?)EvT0_xPx$", name)      # <int ITEMS, class VALUE>(VALUE, long long, long long*)
+        assert m and (int(m.group(1)), m.group(2)) not in inst, name
+        inst[(int(m.group(1)), m.group(2))] = u
+    assert set(inst) == set(SCAN_INSTANCES), sorted(inst)
+    for k, u in inst.items():
+        assert u["ScratchSize [bytes/lane]"] == 0 and u["VGPRs Spill"] == 0 and u["SGPRs Spill"] == 0, (k, u)
+        assert u["LDS Size [bytes/block]"] == 16 * 8, (k, u)
+    return inst
 
 
 @pytest.fixture(scope="module")
@@ -78,7 +101,7 @@ def test_resquiggle_kernels_have_no_scratch_and_the_stated_lds(usage):
 
 
 def test_segment_kernels_have_no_scratch_and_the_stated_lds(usage):
-    KERNELS = ("s2s_segment_flags_kernel", "s2s_segment_scan_kernel", "s2s_segment_compact_kernel")
+    KERNELS = ("s2s_segment_flags_kernel", "s2s_segment_compact_kernel")
     TILE, MAX_WINDOW = 2048, 32
 
     def lds_bytes():
@@ -93,7 +116,8 @@ def test_segment_kernels_have_no_scratch_and_the_stated_lds(usage):
         assert u["ScratchSize [bytes/lane]"] == 0 and u["VGPRs Spill"] == 0 and u["SGPRs Spill"] == 0, (name, u)
         lds[name] = u["LDS Size [bytes/block]"]
     assert lds_bytes() == 47296 <= 65536              # what one workgroup may ask for
-    assert lds[KERNELS[0]] == lds_bytes() and lds[KERNELS[1]] == 16 * 8 and lds[KERNELS[2]] == 0, lds
+    assert lds[KERNELS[0]] == lds_bytes() and lds[KERNELS[1]] == 0, lds
+    assert (1, "S2SScanNext") in scan_instances(usage)        # launch 2: no scratch, no spills, 16 * 8 B of LDS
     header = open(os.path.join(os.path.dirname(_build.HERE), "include", "s2s_hip.h")).read()
     seg = open(os.path.join(_build.HERE, "csrc", "s2s_segment.h")).read()
     assert "S2S_SEG_LDS_BYTES\n *                 = 47,296 B" in header and "#define S2S_SEG_TILE 2048" in header

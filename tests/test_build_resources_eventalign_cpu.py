@@ -6,9 +6,9 @@ import os
 import re
 
 from seq2squiggle_amd import _build
-from test_build_resources_cpu import usage  # noqa: F401
+from test_build_resources_cpu import scan_instances, usage  # noqa: F401
 
-KERNELS = ("s2s_event_means_scan_kernel", "s2s_event_means_fill_kernel", "s2s_eventalign_kernel", "s2s_eventalign_trace_kernel")
+KERNELS = ("s2s_event_means_fill_kernel", "s2s_eventalign_kernel", "s2s_eventalign_trace_kernel")
 
 
 def lds_bytes(W):
@@ -23,9 +23,10 @@ def test_eventalign_kernels_have_no_scratch_and_the_stated_lds(usage):  # noqa: 
         (u,) = mine.values()
         assert u["ScratchSize [bytes/lane]"] == 0 and u["VGPRs Spill"] == 0 and u["SGPRs Spill"] == 0, (name, u)
         lds[name], regs[name] = u["LDS Size [bytes/block]"], u["VGPRs"]
-    assert lds == {KERNELS[0]: 16 * 8, KERNELS[1]: 0, KERNELS[2]: 0, KERNELS[3]: 0}, lds     # no static LDS in the sweep: it is asked for at launch
-    assert regs[KERNELS[2]] <= 64, regs              # 1,024 threads are four waves per SIMD, and two such workgroups fit a CU's LDS
-    assert regs[KERNELS[0]] <= 128, regs             # one workgroup of 1,024 threads
+    assert lds == {KERNELS[0]: 0, KERNELS[1]: 0, KERNELS[2]: 0}, lds     # no static LDS in the sweep: it is asked for at launch
+    assert regs[KERNELS[1]] <= 64, regs              # 1,024 threads are four waves per SIMD, and two such workgroups fit a CU's LDS
+    scan = scan_instances(usage)[(1, "S2SEvaCounts")]    # the scan of the event counts: no scratch, no spills, 16 * 8 B of LDS
+    assert scan["VGPRs"] <= 128, scan                # one workgroup of 1,024 threads
     header = open(os.path.join(os.path.dirname(_build.HERE), "include", "s2s_hip.h")).read()
     hip = open(_build.SRC).read()
     assert lds_bytes(1024) == 29744 <= 65536 and lds_bytes(128) == 4656

@@ -1,4 +1,4 @@
-"""The export kernels (s2s_count_kernel, s2s_scan_kernel, s2s_read_offsets_kernel, s2s_compact_kernel behind s2s_export_reads)
+"""The export kernels (s2s_count_kernel, s2s_scan_kernel<8, S2SScanInts>, s2s_read_offsets_kernel, s2s_compact_kernel behind s2s_export_reads)
 against the numpy restatement of their definition (tests/_export_ref.py) on crafted, not predicted, signals: every chunk geometry,
 RNA, empty reads, the scan's step and vector / tail boundaries, a workspace that grows and is reused, a capacity below the sample
 count, B == 0.  Every comparison is between integers or bit patterns (pA as uint32)."""

@@ -44,6 +44,21 @@ def test_more_reads_than_one_scan_block():
     both(case, R.PA, 5, 37, backwards=True)
 
 
+@pytest.mark.parametrize("P,te,ts,k", C.MANY_READS)
+def test_second_and_third_step_of_the_scans_over_reads_and_capacity(P, te, ts, k):
+    """s2s_chunk_pack launches the in-place instance of s2s_scan_kernel (csrc/s2s_prims.h) over the reads' chunk counts (P entries)
+    and over the chunk capacity.  The cases below already take both scans deep into later steps (3,000 reads; 70,010 chunks); what is
+    new here is the border itself: 1,025 and 2,049 reads of one or two rows leave ONE entry for the second and for the third step
+    of 1,024, and at te = 1, where every read forms at least two chunks, the capacity scan passes 2,048 and 4,096 entries.  Both sample sources; every
+    output and the three counters against the host twin, byte for byte.  The scan over the tiles takes a second step only past
+    1,024 tiles, two million slots: it is the same instance that tests/test_gpu_segment_scan.py drives past 2,048 tiles through
+    s2s_segment, so it is left out here."""
+    case = C.many_reads(P, te, ts, k)
+    for source in (R.RAW, R.PA):
+        r = both(case, source, te, ts, reverse=(source == R.PA))
+        assert len(r["n_rows"]) == P and r["counters"][0] > (2 * P if te == 1 else P) - 1 and r["counters"][1] > 0
+
+
 def test_more_chunks_than_64_trips_of_the_scan():
     rng = np.random.default_rng(4)
     case = C.make(rng, 1, [rng.integers(1, 3, 7000) for _ in range(10)], gaps=False)

@@ -303,12 +303,12 @@ def consistent(r, case, te, ts, k):
 @sources
 def test_offsets_the_device_can_only_skip(te, ts, k, source):
     """One bad offset per call; the host twin refuses each.  Why every access stays inside the stated sizes (csrc/s2s_chunk.h,
-    s2s_segment.h), whatever l_offs [P + 1] and s_offs [P + 1] hold:
-      * s2s_seg_find probes l_offs[m] for m in [ra, rb] inside [0, P - 1] and then reads l_offs[r + 1], r + 1 <= P; it says yes only
+    s2s_prims.h), whatever l_offs [P + 1] and s_offs [P + 1] hold:
+      * s2s_record_find probes l_offs[m] for m in [ra, rb] inside [0, P - 1] and then reads l_offs[r + 1], r + 1 <= P; it says yes only
         if 0 <= l_offs[r] <= g < l_offs[r + 1] <= slots, and the flag kernel asks it only for g < slots: ev_start[g], ev_len[g],
         kmers[g k ..] are inside.  s_offs[r], s_offs[r + 1] are entries of the array; they are values handed to s2s_chunk_row, which
         says no unless 0 <= lo <= hi <= total and the interval lies in [lo, hi): no sample is read in launch 1 at all.
-      * the compact kernel reads l_offs[p], l_offs[p + 1] for p < P and calls s2s_seg_rank only if 0 <= lo <= hi <= slots: positions up
+      * the compact kernel reads l_offs[p], l_offs[p + 1] for p < P and calls s2s_bitmap_rank only if 0 <= lo <= hi <= slots: positions up
         to slots <= tiles x S2S_SEG_TILE, where trank has tiles + 1 entries and a position that is no multiple of the tile has a word.
         rows[] is written at ranks below the number of flags <= slots.
       * s2s_chunk_load searches c_offs[0 .. P - 1] (the scan of launch 3's counts: written for every read), reads rows[r_offs + i] with

@@ -1,6 +1,6 @@
-"""`segment` on pools of more than 1,024 and more than 2,048 tiles: s2s_segment_scan_kernel (csrc/s2s_segment.h, launch 2) scans the
-tiles' counts 1,024 to a step with a carry, and every smaller pool of tests/test_gpu_segment.py is one step, three of sixteen waves and
-carry 0.  Here: flags in every tile beyond tile 1,024 and beyond tile 2,048; pools of exactly 1,023 .. 2,049 tiles; a silent stretch
+"""`segment` on pools of more than 1,024 and more than 2,048 tiles: launch 2, s2s_scan_kernel<1, S2SScanNext> (csrc/s2s_prims.h), scans
+the tiles' counts 1,024 to a step with a carry, and every smaller pool of tests/test_gpu_segment.py is one step, three of sixteen waves
+and carry 0.  Here: flags in every tile beyond tile 1,024 and beyond tile 2,048; pools of exactly 1,023 .. 2,049 tiles; a silent stretch
 across the border of a step; the events of a record inside a big pool against the device's own answer for it in a small one; the
 command with its batch border on either side of 1,024 tiles.  check() and Buf are those of tests/test_gpu_segment.py: the host twin
 bit for bit, every buffer preset to 0xAB between guard margins, every slot beyond a record's events still preset."""

@@ -60,6 +60,18 @@ def test_host_twin_equals_the_restatement_on_the_edge_cases(te, ts, k):
     assert got["no_rows"]["counters"].tolist() == [0, 0, 0]
 
 
+@pytest.mark.parametrize("P,te,ts,k", CS.MANY_READS)
+def test_host_twin_equals_the_restatement_on_many_short_reads(P, te, ts, k):
+    """The inputs on which tests/test_gpu_preprocess.py takes the device's scans over reads and capacity past one and two steps: the
+    host twin that the device is held to there is held to the numpy restatement here."""
+    case = CS.many_reads(P, te, ts, k)
+    assert len(case["l_offs"]) == P + 1 and set(np.diff(case["l_offs"]).tolist()) == {1, 2}
+    for source in (R.RAW, R.PA):
+        want = CS.ref(case, source, te, ts, reverse=(source == R.PA))
+        CS.same(want, CS.run(case, source, te, ts, reverse=(source == R.PA)), (P, source))
+    assert want["counters"][0] == sum(n // te + 1 for n in want["n_rows"] if n) >= (2 * P if te == 1 else P)
+
+
 def test_pad_rows_and_true_lengths():
     rng = np.random.default_rng(2)
     case = CS.make(rng, 6, [[3, 4, 5, 6, 7], [2]], gaps=False)      # n = te: a whole chunk of pads follows

@@ -171,7 +171,7 @@ def test_one_and_sixteen_threads_agree():
     assert [s.tolist() for s in st] == a[2] and [l.tolist() for l in ln] == a[3]
 
 
-# ------------------------------------------------------------------ pools of more than 1,024 tiles (s2s_segment_scan_kernel's step)
+# ------------------------------------------------------------------ pools of more than 1,024 tiles (the step of the device's scan)
 TILE, SCAN_STEP = 2048, 1024
 
 

@@ -717,7 +717,8 @@ __global__ __launch_bounds__(DEC_WAVES * 64, DEC_WPS) void s2s_eval_kernel(
 // The three per-chunk sums of get_loss (model.py:458-475) from the stage outputs, one wave per chunk, each in a fixed order (lane
 // partials in index order, then the butterfly of gen_wave_sum): a chunk's sums depend on its own rows only.
 //   [0] sum_t (y - target)^2   [1] sum_c -Gamma(conc, rate).log_prob(|d| + (d == 0))   [2] sum_c (stdev - sigma)^2
-// log_prob in torch's form: xlogy(conc, rate) + xlogy(conc - 1, x) - rate * x - lgamma(conc), fp32.  te <= 64: one lane per k-mer.
+// log_prob in torch's form: xlogy(conc, rate) + xlogy(conc - 1, x) - rate * x - lgamma(conc), each k-mer's term formed in double and
+// rounded to fp32, the sums in fp32.  te <= 64: one lane per k-mer.
 __global__ __launch_bounds__(256) void s2s_eval_loss_kernel(const float* __restrict__ y, const float* __restrict__ target,
                                                             const float* __restrict__ sigma, const float* __restrict__ stdev,
                                                             const float* __restrict__ conc, const float* __restrict__ rate,
@@ -735,10 +736,12 @@ __global__ __launch_bounds__(256) void s2s_eval_loss_kernel(const float* __restr
         const long long i = b * te + lane;
         const int dv = dwell[i];
         const float x = dv == 0 ? 1.0f : (float)(dv < 0 ? -dv : dv);
-        const float a = conc[i], r = rate[i];
-        const float am1 = a - 1.0f;
-        const float lp = a * logf(r) + (am1 == 0.0f ? 0.0f : am1 * logf(x)) - r * x - lgammaf(a);
-        nll = -lp;
+        // each k-mer's term in double, rounded once: where the density is near 1 (conc ~ rate ~ 20 at a dwell of 1) the four parts
+        // are of the order of 60 and cancel to a term below 1, and a chunk of such k-mers left float32 parts 1e-5 of its sum apart
+        const double a = conc[i], r = rate[i];
+        const double am1 = a - 1.0;
+        const double lp = a * log(r) + (am1 == 0.0 ? 0.0 : am1 * log((double)x)) - r * (double)x - lgamma(a);
+        nll = (float)-lp;
         const float e = stdev[i] - sigma[i];
         ne = e * e;
     }

@@ -56,14 +56,24 @@ struct HL { h8 hi, lo; };
 __device__ __forceinline__ h8 as_h8(const f32x4 v) { return __builtin_bit_cast(h8, v); }
 
 // x = hi + lo with hi = f16(x) (round to nearest), lo = f16(x - hi): 22 significant bits for |x| >= 2^-3
-// (a subnormal lo below that: absolute error near 2^-25; include/s2s_hip.h states the measured range), in three
-// VALU instructions per pair of values: v_cvt_pk_f16_f32, then v_fma_mix{lo,hi}_f16 computes
-// x * 1.0 - f32(hi) from the fp32 value and the f16 half with a single rounding straight to f16.
+// (a subnormal lo below that: absolute error near 2^-25; include/s2s_hip.h states the measured range), in four
+// full-rate VALU instructions per pair of values: v_cvt_pk_f16_f32, two v_fma_mix_f32 -- x * 1.0 - f32(hi) from
+// the fp32 value and the f16 half that op_sel picks, into an fp32 register -- and a second v_cvt_pk_f16_f32.
+// The residual is EXACT in fp32 (x and hi are multiples of ulp32(x), and they differ by half an f16 ulp at most), so
+// the conversion is the only rounding: the same bits as v_fma_mix{lo,hi}_f16, which rounds x * 1 - hi straight to f16
+// (rounds 1-34 split that way: three instructions per pair, but the f16-destination mix forms issue at the
+// transcendental rate -- 8 cycles each against 4.1: 20.2 cycles per pair against 16.6, and between MFMAs 24 against 20;
+// profiles/r35/valu_cost_probe.txt, issue_probe.txt; tools/probes/split_residual_check.hip runs both over every
+// mantissa of the exponents where they could part).  In the attention loop TWO pairs are split together, stage by stage
+// (split2x2), so that no instruction reads the result of the one in front of it: v_cvt_pk_f16_f32 -> VALU costs a wait
+// state back to back, and pair by pair hipcc left 55 more s_nop per head there than it does now (- 0.9 % cycles per chunk;
+// the GEMM operands stay pair by pair, split2: staged they gain 0.4 % more and the evaluate kernel spills two registers).
 // Written in C so that every instruction stays visible to the compiler's hazard recogniser (MFMA <->
 // VALU wait states, trans forwarding): `one` is an opaque 1.0f (otherwise fma(x, 1, c) folds to an add
-// and the mix form is lost), the empty asm makes the packed hi opaque so its halves are reused through
-// op_sel instead of being converted again, and the file is built with -fno-slp-vectorize (the SLP
-// vectoriser would turn the two fmas into v_pk_fma_f32 plus separate conversions: five instructions).
+// and the mix form is lost), the first empty asm makes the packed hi opaque so its halves are reused through
+// op_sel instead of being converted again, the second keeps the residuals fp32 values (otherwise fma + conversion
+// fold back into v_fma_mixlo_f16), and the file is built with -fno-slp-vectorize (the SLP
+// vectoriser would turn the fmas into v_pk_fma_f32 plus separate conversions).
 // LO = false (the reduced-precision S2S_MODE_F16 decoder): only the f16 rounding of x is kept, lo = 0 -- one
 // v_cvt_pk_f16_f32 per pair; every MFMA that would take a lo operand is skipped at compile time by its caller.
 typedef _Float16 h2v __attribute__((ext_vector_type(2)));
@@ -73,9 +83,25 @@ __device__ __forceinline__ void split2(const float a, const float b, const float
     if (!LO) { hi = hb; lo = 0u; return; }
     asm("" : "+v"(hb));
     const h2v h = __builtin_bit_cast(h2v, hb);
-    const h2v l = {(_Float16)__builtin_fmaf(a, one, -(float)h[0]), (_Float16)__builtin_fmaf(b, one, -(float)h[1])};
+    float ra = __builtin_fmaf(a, one, -(float)h[0]), rb = __builtin_fmaf(b, one, -(float)h[1]);
+    asm("" : "+v"(ra), "+v"(rb));
     hi = hb;
-    lo = __builtin_bit_cast(unsigned, l);
+    lo = __builtin_bit_cast(unsigned, (h2v{(_Float16)ra, (_Float16)rb}));
+}
+// two pairs stage by stage (the attention loop: exp_split4)
+template <bool LO = true>
+__device__ __forceinline__ void split2x2(const float a, const float b, const float c, const float d, const float one, unsigned& h0,
+                                         unsigned& h1, unsigned& l0, unsigned& l1) {
+    unsigned p0 = __builtin_bit_cast(unsigned, (h2v{(_Float16)a, (_Float16)b})), p1 = __builtin_bit_cast(unsigned, (h2v{(_Float16)c, (_Float16)d}));
+    if (!LO) { h0 = p0; h1 = p1; l0 = l1 = 0u; return; }
+    asm("" : "+v"(p0), "+v"(p1));
+    const h2v g0 = __builtin_bit_cast(h2v, p0), g1 = __builtin_bit_cast(h2v, p1);
+    float ra = __builtin_fmaf(a, one, -(float)g0[0]), rb = __builtin_fmaf(b, one, -(float)g0[1]);
+    float rc = __builtin_fmaf(c, one, -(float)g1[0]), rd = __builtin_fmaf(d, one, -(float)g1[1]);
+    asm("" : "+v"(ra), "+v"(rb), "+v"(rc), "+v"(rd));
+    h0 = p0; h1 = p1;
+    l0 = __builtin_bit_cast(unsigned, (h2v{(_Float16)ra, (_Float16)rb}));
+    l1 = __builtin_bit_cast(unsigned, (h2v{(_Float16)rc, (_Float16)rd}));
 }
 // p = exp2(s) for four scores, split.  p itself is not needed afterwards (the row sum comes out of
 // the MFMA with a ones operand).
@@ -88,8 +114,7 @@ __device__ __forceinline__ void exp_split4(const f32x4 s, const float one, unsig
         h0 = __float_as_uint(e0); l0 = __float_as_uint(e1); h1 = __float_as_uint(e2); l1 = __float_as_uint(e3);
         return;
     }
-    split2<LO>(e0, e1, one, h0, l0);
-    split2<LO>(e2, e3, one, h1, l1);
+    split2x2<LO>(e0, e1, e2, e3, one, h0, h1, l0, l1);
 }
 typedef unsigned uv4 __attribute__((ext_vector_type(4)));
 typedef unsigned uv2 __attribute__((ext_vector_type(2)));

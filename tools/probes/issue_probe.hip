@@ -20,6 +20,9 @@ __device__ __forceinline__ float body(float seed, long long* cycles) {
     for (int i = 0; i < 4; ++i) for (int j = 0; j < 16; ++j) d[i][j] = seed;
     float v[16];
     for (int i = 0; i < 16; ++i) v[i] = seed * (i + 1);
+    [[maybe_unused]] float t[16], u[16];                         // second and third registers of the sequences (KIND 6, 7, 8, 11)
+    for (int i = 0; i < 16; ++i) { t[i] = seed + i; u[i] = seed - i; }
+    [[maybe_unused]] const unsigned long long mask = __builtin_amdgcn_ballot_w64(seed > (float)(threadIdx.x & 1));   // KIND 10: an SGPR pair that is not VCC
     const long long t0 = __builtin_readcyclecounter();
 #pragma unroll 1
     for (int it = 0; it < ITERS; ++it) {
@@ -36,7 +39,22 @@ __device__ __forceinline__ float body(float seed, long long* cycles) {
                 else if (KIND == 1) asm volatile("v_exp_f32 %0, %0" : "+v"(v[r]));
                 else if (KIND == 2) asm volatile("v_cvt_pk_f16_f32 %0, %0, %1" : "+v"(v[r]) : "v"(seed));
                 else if (KIND == 3) asm volatile("v_dot2c_f32_f16_e32 %0, -1.0, %1" : "+v"(v[r]) : "v"(seed));
-                else asm volatile("v_fma_mixlo_f16 %0, %0, 1.0, %1 op_sel_hi:[0,0,1]" : "+v"(v[r]) : "v"(seed));
+                else if (KIND == 4) asm volatile("v_fma_mixlo_f16 %0, %0, 1.0, %1 op_sel_hi:[0,0,1]" : "+v"(v[r]) : "v"(seed));
+                // round 35.  KIND 5: the f32-destination mix form; 6 / 7: the hi/lo split of a PAIR of values as it is today (cvt_pk, mixlo,
+                // mixhi) and with f32 residuals (cvt_pk, 2 x mix_f32, cvt_pk) -- NV counts pairs there; 8: v_bfi_b32; 9 / 10: v_cndmask_b32 with
+                // its mask in VCC / in another SGPR pair; 11: v_max3_f32; 12: v_max_f32
+                else if (KIND == 5) asm volatile("v_fma_mix_f32 %0, %0, 1.0, -%1 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(v[r]) : "v"(seed));
+                else if (KIND == 6) asm volatile("v_cvt_pk_f16_f32 %1, %0, %3\n v_fma_mixlo_f16 %2, %0, 1.0, -%1 op_sel_hi:[0,0,1]\n"
+                                                 " v_fma_mixhi_f16 %2, %3, 1.0, -%1 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
+                                                 : "+v"(v[r]), "+v"(t[r]), "+v"(u[r]) : "v"(seed));
+                else if (KIND == 7) asm volatile("v_cvt_pk_f16_f32 %1, %0, %3\n v_fma_mix_f32 %0, %0, 1.0, -%1 op_sel_hi:[0,0,1]\n"
+                                                 " v_fma_mix_f32 %2, %3, 1.0, -%1 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n v_cvt_pk_f16_f32 %2, %0, %2"
+                                                 : "+v"(v[r]), "+v"(t[r]), "+v"(u[r]) : "v"(seed));
+                else if (KIND == 8) asm volatile("v_bfi_b32 %0, %1, %0, %2" : "+v"(v[r]) : "v"(seed), "v"(t[r]));
+                else if (KIND == 9) asm volatile("v_cndmask_b32_e64 %0, %1, %0, vcc" : "+v"(v[r]) : "v"(seed));
+                else if (KIND == 10) asm volatile("v_cndmask_b32_e64 %0, %1, %0, %2" : "+v"(v[r]) : "v"(seed), "s"(mask));
+                else if (KIND == 11) asm volatile("v_max3_f32 %0, %0, %1, %2" : "+v"(v[r]) : "v"(seed), "v"(t[r]));
+                else asm volatile("v_max_f32_e32 %0, %1, %0" : "+v"(v[r]) : "v"(seed));
             }
         }
     }
@@ -46,6 +64,7 @@ __device__ __forceinline__ float body(float seed, long long* cycles) {
     for (int i = 0; i < 8; ++i) acc += c[i][0] + c[i][3];
     for (int i = 0; i < 4; ++i) acc += d[i][0] + d[i][15];
     for (int i = 0; i < 16; ++i) acc += v[i];
+    if (KIND >= 6) for (int i = 0; i < 16; ++i) acc += t[i] + u[i];
     return acc;
 }
 
@@ -117,6 +136,38 @@ int main() {
     run<1, 64, 2, 0, 0>("sweep 8 mfma16 + 64 v_cvt_pk", 256);
     run<0, 64, 4, 0, 0>("sweep 64 mixlo alone", 256);
     run<0, 64, 1, 0, 0>("sweep 64 v_exp alone", 256);
+    // round 35: the candidates of the attention loop's vector diet, alone and between 4 x 32x32x16 MFMAs at the sweep's densities.
+    // (a "pair" is the hi/lo split of two values: 3 instructions today, 4 with f32 residuals)
+    run<0, 32, 5, 1, 0>("r35 32 v_fma_mix_f32 alone", 256);
+    run<1, 8, 5, 1, 0>("r35 4 mfma32 +  8 v_fma_mix_f32", 256);
+    run<1, 24, 5, 1, 0>("r35 4 mfma32 + 24 v_fma_mix_f32", 256);
+    run<1, 32, 5, 1, 0>("r35 4 mfma32 + 32 v_fma_mix_f32", 256);
+    run<1, 64, 5, 1, 0>("r35 4 mfma32 + 64 v_fma_mix_f32", 256);
+    run<0, 16, 6, 1, 0>("r35 16 pairs cvt_pk+mixlo+mixhi alone", 256);
+    run<0, 16, 7, 1, 0>("r35 16 pairs cvt_pk+2 mix_f32+cvt_pk alone", 256);
+    run<1, 8, 6, 1, 0>("r35 4 mfma32 +  8 pairs cvt_pk+mixlo+mixhi", 256);
+    run<1, 8, 7, 1, 0>("r35 4 mfma32 +  8 pairs cvt_pk+2 mix_f32+cvt_pk", 256);
+    run<1, 16, 6, 1, 0>("r35 4 mfma32 + 16 pairs cvt_pk+mixlo+mixhi", 256);
+    run<1, 16, 7, 1, 0>("r35 4 mfma32 + 16 pairs cvt_pk+2 mix_f32+cvt_pk", 256);
+    run<1, 24, 6, 1, 0>("r35 4 mfma32 + 24 pairs cvt_pk+mixlo+mixhi", 256);
+    run<1, 24, 7, 1, 0>("r35 4 mfma32 + 24 pairs cvt_pk+2 mix_f32+cvt_pk", 256);
+    run<0, 32, 8, 1, 0>("r35 32 v_bfi alone", 256);
+    run<0, 32, 9, 1, 0>("r35 32 v_cndmask (vcc) alone", 256);
+    run<0, 32, 10, 1, 0>("r35 32 v_cndmask (sgpr pair) alone", 256);
+    run<0, 32, 11, 1, 0>("r35 32 v_max3 alone", 256);
+    run<0, 32, 12, 1, 0>("r35 32 v_max alone", 256);
+    run<1, 8, 8, 1, 0>("r35 4 mfma32 +  8 v_bfi", 256);
+    run<1, 8, 9, 1, 0>("r35 4 mfma32 +  8 v_cndmask (vcc)", 256);
+    run<1, 8, 10, 1, 0>("r35 4 mfma32 +  8 v_cndmask (sgpr pair)", 256);
+    run<1, 32, 8, 1, 0>("r35 4 mfma32 + 32 v_bfi", 256);
+    run<1, 32, 9, 1, 0>("r35 4 mfma32 + 32 v_cndmask (vcc)", 256);
+    run<1, 32, 10, 1, 0>("r35 4 mfma32 + 32 v_cndmask (sgpr pair)", 256);
+    run<1, 64, 8, 1, 0>("r35 4 mfma32 + 64 v_bfi", 256);
+    run<1, 64, 10, 1, 0>("r35 4 mfma32 + 64 v_cndmask (sgpr pair)", 256);
+    run<1, 16, 11, 1, 0>("r35 4 mfma32 + 16 v_max3", 256);
+    run<1, 32, 12, 1, 0>("r35 4 mfma32 + 32 v_max", 256);
+    run<1, 32, 11, 1, 0>("r35 4 mfma32 + 32 v_max3", 256);
+    run<1, 64, 12, 1, 0>("r35 4 mfma32 + 64 v_max", 256);
     // two waves per SIMD (512 threads)
     run<1, 0, 0, 0, 0>("2 waves/SIMD: 8 mfma16 alone (each)", 512);
     run<0, 32, 0, 0, 0>("2 waves/SIMD: 32 v_fma alone (each)", 512);

@@ -239,13 +239,16 @@ def finish(y_scaled: torch.Tensor, sigma_ext: torch.Tensor, z01: Optional[torch.
 def predict_chunks(sd: Dict[str, torch.Tensor], cfg: dict, codes: np.ndarray, params: PredictParams,
                    inject_g: Optional[torch.Tensor] = None, inject_z01: Optional[torch.Tensor] = None,
                    inject_zdw: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None,
-                   dtype=torch.float32, stages: bool = False, taps: Optional[dict] = None):
+                   dtype=torch.float32, stages: bool = False, taps: Optional[dict] = None, decoder_autocast16: bool = False):
     """predict_step (model.py:195-250) for a batch of chunks given as codes [B,16,k].
 
     Returns dict with at least ``signal`` [B,250] (pA, fp) and ``dur`` [B,16] int32.
     With ``inject_*`` None the oracle draws from torch's own generators (statistical use only).
     ``taps``: a dict that receives, per FFT block of the encoder and the decoder, the largest magnitude of the intermediates
     its Linear layers produce (see ``mha`` and ``ffn``), keyed by the block's state_dict prefix + name.
+    ``decoder_autocast16``: ``decoder()`` alone runs under ``torch.autocast("cpu", dtype=torch.float16)`` (the policy of
+    inference.py:403-404, applied to the one stage S2S_MODE_F16 reduces) and its result is cast back to ``dtype``; encoder, heads,
+    dwell, length regulator and ``finish`` stay as they are.  The bar of the tuned f16 instance (tests/_f16_bar.py).
     """
     if dtype != torch.float32:
         sd = {k: v.to(dtype) for k, v in sd.items()}
@@ -265,7 +268,12 @@ def predict_chunks(sd: Dict[str, torch.Tensor], cfg: dict, codes: np.ndarray, pa
         zdw = torch.randn(B, cfg["max_dna_len"], generator=generator, dtype=dtype)
     dur = durations(params, B, g, zdw, dtype, t_enc=cfg["max_dna_len"])
     h, sigma_ext = length_regulate(enc_out, sigma, dur, cfg["max_signal_len"])
-    y_scaled = decoder(sd, cfg, h, taps)
+    if decoder_autocast16:
+        with torch.autocast("cpu", dtype=torch.float16):
+            y_scaled = decoder(sd, cfg, h, taps)
+        y_scaled = y_scaled.to(dtype)
+    else:
+        y_scaled = decoder(sd, cfg, h, taps)
     z01 = inject_z01
     if params.noise_std > 0 and z01 is None:
         z01 = torch.randn(B, cfg["max_signal_len"], generator=generator, dtype=dtype)

@@ -14,6 +14,7 @@ from seq2squiggle_amd import chunker
 from seq2squiggle_amd.inference import redo_threshold
 from oracle import s2s_oracle as O
 from conftest import load_ckpt, load_npz
+from _f16_bar import QK, variant as _variant     # (the variant checkpoints are shared with the tests of the f16 instance)
 
 pytestmark = pytest.mark.gpu
 MAE_TOL, MAX_TOL = 1e-4, 2e-3
@@ -605,6 +606,9 @@ EDGE_PARAMS = [
     dict(noise_sampling=False, noise_std=50.0),                       # large constant noise: many samples clamp to 0
 ]
 
+EDGE_READS = ["ACGTACGTA", "ACGTACGTAC" * 2 + "ACGT", "ACGTACGTAC" * 2 + "ACGTA", "N" * 60, "acgtacgtacgtacgtacgtacgtacgt",
+              "ACGT_ACGT__ACGTACGTACGTAC", "ACGTNNNNNNNNNACGTACGTRYKMACGTACGTACGATCGATCGATCGATTTTTTTTTTTTTTTTTTTGGGGGGGGGGGGG"]
+
 
 @pytest.mark.parametrize("mode", ["f32", "f16x3"])
 @pytest.mark.parametrize("over", EDGE_PARAMS, ids=lambda d: ",".join(f"{k}={v}" for k, v in d.items()) or "defaults")
@@ -614,8 +618,7 @@ def test_edge_inputs_and_parameters(mode, over):
     sd, cfg = load_ckpt("k9")
     eng = S.Engine(sd, cfg, mode=mode)
     k = 9
-    reads = ["ACGTACGTA", "ACGTACGTAC" * 2 + "ACGT", "ACGTACGTAC" * 2 + "ACGTA", "N" * 60, "acgtacgtacgtacgtacgtacgtacgt",
-             "ACGT_ACGT__ACGTACGTACGTAC", "ACGTNNNNNNNNNACGTACGTRYKMACGTACGTACGATCGATCGATCGATTTTTTTTTTTTTTTTTTTGGGGGGGGGGGGG"]
+    reads = EDGE_READS
     bases, nv, first = S.encode_reads(reads, k)
     codes = np.concatenate([O.encode_read(r, k) for r in reads], 0)
     B = bases.shape[0]
@@ -638,11 +641,9 @@ def test_edge_inputs_and_parameters(mode, over):
     eng.close()
 
 
-@pytest.mark.parametrize("mode", ["f32", "f16x3"])
-@pytest.mark.parametrize("enc_l,dec_l,pre_l", [(1, 3, 0), (3, 1, 2), (4, 4, 4)])
-def test_other_layer_counts(mode, enc_l, dec_l, pre_l):
-    """The C ABI takes 1..4 encoder/decoder layers and 0..4 pre-net layers (s2s_config): checkpoints of those shapes, built
-    from perturbed copies of the synthetic k=9 layers, against the oracle (injected variates, both samplers on)."""
+def layer_count_model(enc_l, dec_l, pre_l):
+    """A checkpoint of enc_l / dec_l FFT blocks and pre_l pre-net layers, built from perturbed copies of the synthetic k=9 layers
+    -> (state_dict, config, the generator the perturbations came from)."""
     sd0, cfg0 = load_ckpt("k9")
     cfg = dict(cfg0, encoder_layers=enc_l, decoder_layers=dec_l, pre_layers=pre_l)
     gen = torch.Generator().manual_seed(100 * enc_l + 10 * dec_l + pre_l)
@@ -661,6 +662,18 @@ def test_other_layer_counts(mode, enc_l, dec_l, pre_l):
         for part in ("weight", "bias"):
             v = sd0[f"encoders.pre_net_stack.0.{part}"]
             sd[f"encoders.pre_net_stack.{i}.{part}"] = v.clone() if i == 0 else perturbed(v)
+    return sd, cfg, gen
+
+
+LAYER_COUNTS = [(1, 3, 0), (3, 1, 2), (4, 4, 4)]
+
+
+@pytest.mark.parametrize("mode", ["f32", "f16x3"])
+@pytest.mark.parametrize("enc_l,dec_l,pre_l", LAYER_COUNTS)
+def test_other_layer_counts(mode, enc_l, dec_l, pre_l):
+    """The C ABI takes 1..4 encoder/decoder layers and 0..4 pre-net layers (s2s_config): checkpoints of those shapes, built
+    from perturbed copies of the synthetic k=9 layers, against the oracle (injected variates, both samplers on)."""
+    sd, cfg, gen = layer_count_model(enc_l, dec_l, pre_l)
     eng = S.Engine(sd, cfg, mode=mode)
     rng = np.random.default_rng(enc_l + dec_l)
     reads = ["".join(rng.choice(list("ACGT"), 700)) for _ in range(2)]
@@ -715,23 +728,6 @@ def test_reduced_precision_f16_mode(tag):
           f"(all chunks: {np.abs(r16 - t).mean():.4f} / {np.abs(r16 - t).max():.1f})")
     assert 1e-4 < d.mean() <= ref_d.mean() and d.max() <= ref_d.max()      # measurably not the parity path; no worse than the reference's GPU path
     eng.close()
-
-
-QK = ("w_qs.weight", "w_ks.weight", "w_qs.bias", "w_ks.bias")
-
-
-def _variant(sd, kind):
-    """Checkpoints that make the fast softmax path redo SOME heads: "x2" = the decoder's w_qs / w_ks doubled; "pos2" / "pos3" =
-    attention on the positional encoding alone (w_qs = w_ks = c I, biases 0: scores follow the sinusoid table, local attention)."""
-    out = {k: v.clone() for k, v in sd.items()}
-    for k in out:
-        if k.startswith("decoders.") and k.endswith(QK):
-            if kind == "x2":
-                out[k] = out[k] * 2.0
-            else:
-                c = float(kind[3:])
-                out[k] = c * torch.eye(64) if k.endswith("weight") else torch.zeros(64)
-    return out
 
 
 def _parity_both_paths(sd, cfg, reads, label, want_mixed=None):

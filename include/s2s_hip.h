@@ -380,6 +380,52 @@ int s2s_kmer_model_accumulate(s2s_handle* h, void* stream, const float* signal /
                               const uint8_t* n_valid /* device [B] */, int32_t B, float digitisation, float range, float offset,
                               int64_t* table /* device [4^k + 1][5] */);
 
+/* The pore model from ALIGNMENTS (`resquiggle --kmer-model-out`, `eventalign --kmer-model-out`): the same table, summed over the
+ * k-mer slots of stored records that an alignment cut, each record with its own calibration.  No handle; the conventions of the
+ * other handle-free entries (device and stream first, stream-ordered, device pointers; the host twin is the definition the kernel
+ * equals bit for bit).  No counterpart in the reference; unvalidated against nanopolish / f5c / uncalled4.
+ *
+ *  l_offs     [P + 1]: record p owns the pooled slots l_offs[p] .. l_offs[p + 1] - 1 -- the layout s2s_event_sums writes;
+ *  codes, ev_len, S, Q   per pooled slot: the row of the slot's k-mer (the `code` above; 4^k is the pooled row of k-mers with a
+ *             letter outside ACGT, which s2s_kmer_model_format never prints), the samples of its event and their sum and sum of
+ *             squares (s2s_event_sums);
+ *  gain, shift   [P], formed by the caller in double from the record's (digitisation, offset, range):
+ *                 gain = rint(range / digitisation * 2^24), 1 .. 2^30       shift = rint(offset * 256), |shift| <= 2^30
+ *             gain == 0: the record contributes nothing, neither to the table nor to `dropped` (what the caller passes for a
+ *             record whose calibration is outside these ranges).
+ * A slot (n = ev_len, S, Q, c = code) of a record with gain != 0, in integers only:
+ *   1. n < 1: no event; nothing is added.
+ *   2. n > 1024: a stalled k-mer, for which s2s_event_fixed is not defined and which a model does not want: OVERLONG, nothing added.
+ *   3. c < 0 or c > 4^k: BAD_CODE, nothing added (no write ever lands outside the table).
+ *   4. (M, D) = s2s_event_fixed(n, (int32)S, Q), in 2^-8 ADC counts, become 2^-8 pA:
+ *        Mp = round-half-even((M + shift) * gain / 2^24): num = (M + shift) * gain; q = floor_div(num, 2^24); r = num - q * 2^24;
+ *             q += 1 if 2r > 2^24, or if 2r == 2^24 and q is odd;
+ *        Dp = floor(D * gain / 2^24).
+ *      |Mp| > 2^23 or Dp > 2^23: OUT_OF_RANGE, nothing added -- the squares stay <= 2^46, the exactness statement above.
+ *   5. Otherwise row c gets  [0] events += 1  [1] sum_m += Mp  [2] sum_m2 += Mp*Mp  [3] sum_d += Dp  [4] sum_d2 += Dp*Dp: COUNTED.
+ *  table      int64 [4^k + 1][S2S_KMER_MODEL_FIELDS], ADDED to: s2s_kmer_model_format(table, k, 1.0f, 1.0f, 0.0f, ...) prints pA.
+ *             With gain = 2^24 and shift = 0, Mp = M and Dp = D: on the same events the table of s2s_kmer_model_accumulate.
+ *  dropped    int64 [4], ADDED to: {overlong, out_of_range, bad_code, counted}.
+ *  workgroups 0: the library's choice; 1 .. S2S_KMER_MODEL_MAX_WORKGROUPS: exactly that many persistent workgroups (a test crosses
+ *             the flush interval and the probe overflow with a few thousand slots this way).  The table does not depend on it.
+ * All adds are 64-bit integer adds: table and dropped depend only on the SET of slots, not on batching, the grid, or which of the
+ * GPU and the host ran.
+ * Persistent workgroups of 256 threads walk the POOLED slots, 64 consecutive ones per wave and round, whatever the reads' lengths; a
+ * lane finds its record by a search in l_offs (a slot that no record holds adds nothing), lanes of a wave with equal codes are
+ * merged, and the first lane of a code adds into the workgroup's write-combining cache -- the cache, constants and rules of
+ * s2s_kmer_model_accumulate, flushed every S2S_KMER_MODEL_FLUSH_ROUNDS rounds and at the end.  The four counts are summed per wave:
+ * one atomic per wave and non-zero count.  Static LDS: the cache's 45,100 B, nothing else.  The slot count l_offs[P] is on the
+ * device: with workgroups == 0 the entry launches S2S_KMER_MODEL_MAX_WORKGROUPS and those without a round leave at once.
+ * S2S_ERR_ARG: k outside 1..10, P < 0, a NULL pointer with P > 0, workgroups outside 0..S2S_KMER_MODEL_MAX_WORKGROUPS; on the host
+ * twin offsets that decrease or begin below 0, or threads < 1.  P == 0 is a successful no-op that launches nothing; so is, on the
+ * host, a call without slots.  The host twin runs on one thread whatever `threads` says. */
+int s2s_kmer_model_events(int device, void* stream, const int32_t* codes, const int32_t* ev_len, const int64_t* S, const int64_t* Q,
+                          const int64_t* l_offs /* [P + 1] */, int32_t P, const int64_t* gain, const int64_t* shift /* [P] */,
+                          int32_t k, int32_t workgroups, int64_t* table /* [4^k + 1][5], ADDED to */, int64_t* dropped /* [4], ADDED to */);
+int s2s_kmer_model_events_host(const int32_t* codes, const int32_t* ev_len, const int64_t* S, const int64_t* Q, const int64_t* l_offs,
+                               int32_t P, const int64_t* gain, const int64_t* shift, int32_t k, int64_t* table, int64_t* dropped,
+                               int32_t threads);
+
 /* Replaces the signal compression that pyslow5.write_record_batch (svb-zd) and pod5.Writer.add_reads (the svb16 stage of
  * VBZ) run on the host (reference signal_io.py:167-171, 268-282): StreamVByte encoding of the zig-zag deltas of the packed
  * int16 samples, one output blob per row, so that only ~1.1 bytes per sample cross PCIe.

@@ -40,7 +40,8 @@ EXPORTS = ("s2s_blob_floats", "s2s_create", "s2s_destroy", "s2s_last_error", "s2
            "s2s_segment_capacity", "s2s_segment_scratch_bytes", "s2s_segment", "s2s_segment_host", "s2s_segment_format_bound",
            "s2s_segment_format",
            "s2s_eventalign_scratch_bytes", "s2s_event_means", "s2s_eventalign", "s2s_event_means_host", "s2s_eventalign_host",
-           "s2s_chunk_scratch_bytes", "s2s_chunk_pack", "s2s_chunk_pack_host")
+           "s2s_chunk_scratch_bytes", "s2s_chunk_pack", "s2s_chunk_pack_host",
+           "s2s_kmer_model_events", "s2s_kmer_model_events_host")
 
 
 def lib():
@@ -144,5 +145,7 @@ def lib():
     chunk = [vp, vp, i64, i32, vp, i64] + [vp] * 7 + [i32] * 6 + [i64]
     bind("s2s_chunk_pack", i32, [i32, vp] + chunk + [vp] + [vp] * 7)
     bind("s2s_chunk_pack_host", i32, chunk + [vp] * 7 + [i32])
+    bind("s2s_kmer_model_events", i32, [i32, vp] + [vp] * 5 + [i32, vp, vp, i32, i32, vp, vp])
+    bind("s2s_kmer_model_events_host", i32, [vp] * 5 + [i32, vp, vp, i32, vp, vp, i32])
     _lib = L
     return L

@@ -691,7 +691,24 @@ def _aligner_options(rows: str, unit: str, trace_memory: str, band, after_skip=(
                      help="With --chunks: YAML configuration file with seq_kmer, max_dna_len and max_signal_len."),
         click.option("--seq-kmer", default=None, type=int, help="k of the chunks' k-mers (default: seq_kmer of the config)."),
         click.option("--max-dna-len", default=None, type=int, help="k-mers per chunk, 1..64 (default: max_dna_len of the config)."),
-        click.option("--max-signal-len", default=None, type=int, help="Samples per chunk, 1..1024 (default: max_signal_len of the config)."))
+        click.option("--max-signal-len", default=None, type=int, help="Samples per chunk, 1..1024 (default: max_signal_len of the config)."),
+        click.option("--kmer-model-out", "model_out", default=None, type=click.Path(dir_okay=False),
+                     help="Also write the pore model re-estimated from this run's alignments: per k-mer the statistics of its events' means "
+                          "in pA, summed on the device from the alignment itself.  A file --kmer-model reads: a second round is the same "
+                          "command with it."),
+        click.option("--kmer-model-min-events", "model_min_events", default=None, type=int,
+                     help="With --kmer-model-out: leave out k-mers with fewer events.  [default: 1, a choice, not a measurement]"))
+
+
+def _model_out(model_out, model_min_events):
+    """(NEW.model, min_events) of --kmer-model-out, or None; --kmer-model-min-events alone is a UsageError."""
+    if model_out is None:
+        if model_min_events is not None:
+            raise click.UsageError("--kmer-model-min-events requires --kmer-model-out")
+        return None
+    if model_min_events is not None:
+        _in_range(model_min_events, 1, None, "--kmer-model-min-events")
+    return str(model_out), 1 if model_min_events is None else int(model_min_events)
 
 
 def _aligner_start(command: str, signals, max_samples, trace_memory, cpu) -> None:
@@ -712,7 +729,7 @@ def _aligner_start(command: str, signals, max_samples, trace_memory, cpu) -> Non
                             help="A table of compare --open-ends: restrict every record to its [b_start, b_end) (an untrimmed real read); "
                                  "rows come out in the record's own coordinates.")])
 def resquiggle(seqs, signals, model, out, with_samples, band, skip_penalty, unknown_cost, rna, intervals, cpu, as_json, summary_out,
-               max_samples, trace_memory, chunks_out, config, seq_kmer, max_dna_len, max_signal_len):
+               max_samples, trace_memory, chunks_out, config, seq_kmer, max_dna_len, max_signal_len, model_out, model_min_events):
     """Align every record of a .blow5 / .slow5 file to the levels a pore model expects for the k-mers of its sequence (SEQS: FASTA or
     FASTQ, record names = read ids) and write the event table predict --events writes: read_name, position, model_kmer, start_idx,
     end_idx, event_level_mean, event_stdv.  Both ends are pinned: the first sample belongs to the first k-mer, the last to the last.
@@ -722,10 +739,11 @@ def resquiggle(seqs, signals, model, out, with_samples, band, skip_penalty, unkn
     _in_range(band, 1, SB.max_band(), "--band")
     _in_range(skip_penalty, 0, R.MAX_SKIP_PENALTY, "--skip-penalty")
     _in_range(unknown_cost, 0, R.MAX_UNKNOWN_COST, "--unknown-cost")
+    new_model = _model_out(model_out, model_min_events)
     chunks = None if chunks_out is None else (chunks_out,) + _chunk_geometry(config, seq_kmer, max_dna_len, max_signal_len)
     s = R.resquiggle_files(seqs, signals, model, out, band=band, skip_penalty=skip_penalty, unknown_cost=unknown_cost, rna=rna,
                            intervals=intervals, with_samples=with_samples, cpu=cpu, summary_out=summary_out, max_samples=max_samples,
-                           trace_memory=trace_memory, chunks=chunks)
+                           trace_memory=trace_memory, chunks=chunks, model_out=new_model)
     per = "nan" if s["mean_cost_per_sample"] is None else f"{s['mean_cost_per_sample']:.4f}"
     _echo_summary(s, as_json,
                   f"{s['events']} events of {s['solved']} reads -> {out}  [k {s['k']}, band {band}, skip penalty {skip_penalty}, unknown "
@@ -772,7 +790,7 @@ def segment(signals, out, window_short, window_long, threshold_short, threshold_
     after_rna=[_detector_options("event detector", " (see segment).", " (see segment).")])
 def eventalign(seqs, signals, model, out, with_samples, band_width, skip_penalty, trim_penalty, unknown_cost, rna, window_short,
                window_long, threshold_short, threshold_long, cpu, as_json, summary_out, max_samples, trace_memory, chunks_out, config,
-               seq_kmer, max_dna_len, max_signal_len):
+               seq_kmer, max_dna_len, max_signal_len, model_out, model_min_events):
     """Align the detected events of every UNTRIMMED record of a .blow5 / .slow5 file to the levels a pore model expects for the k-mers
     of its sequence (SEQS: FASTA or FASTQ, record names = read ids) and write the event table predict --events writes, one row per
     k-mer that got events.  Events come from the detector of `segment`; their means are median / MAD normalised over the whole record;
@@ -786,11 +804,13 @@ def eventalign(seqs, signals, model, out, with_samples, band_width, skip_penalty
     _in_range(trim_penalty, 0, EA.MAX_TRIM_PENALTY, "--trim-penalty")
     _in_range(unknown_cost, 0, EA.MAX_UNKNOWN_COST, "--unknown-cost")
     _check_detector(window_short, window_long, threshold_short, threshold_long)
+    new_model = _model_out(model_out, model_min_events)
     chunks = None if chunks_out is None else (chunks_out,) + _chunk_geometry(config, seq_kmer, max_dna_len, max_signal_len)
     s = EA.eventalign_files(seqs, signals, model, out, band_width=band_width, skip_penalty=skip_penalty, trim_penalty=trim_penalty,
                             unknown_cost=unknown_cost, rna=rna, window_short=window_short, window_long=window_long,
                             threshold_short=threshold_short, threshold_long=threshold_long, with_samples=with_samples, cpu=cpu,
-                            summary_out=summary_out, max_samples=max_samples, trace_memory=trace_memory, chunks=chunks)
+                            summary_out=summary_out, max_samples=max_samples, trace_memory=trace_memory, chunks=chunks,
+                            model_out=new_model)
     per = "nan" if s["mean_cost_per_event"] is None else f"{s['mean_cost_per_event']:.4f}"
     _echo_summary(s, as_json,
                   f"{s['events']} rows of {s['solved']} reads -> {out}  [k {s['k']}, band width {band_width}, skip penalty {skip_penalty}, "

@@ -22,6 +22,7 @@
 #include "s2s_segment.h"
 #include "s2s_eventalign.h"
 #include "s2s_chunk.h"
+#include "s2s_kmer_model_events.h"
 
 #include <cctype>
 #include <cstdio>
@@ -2656,6 +2657,26 @@ int s2s_event_sums(int device, void* stream_, const int16_t* samples, const int6
     GUARD_OR_RETURN(nullptr, device);
     S2S_LAUNCH(nullptr, s2s_event_sums_kernel, dim3(P, S2S_RSQ_SUM_SLICES), dim3(256), 0, static_cast<hipStream_t>(stream_), samples,
                as_ll(s_offs), ev_start, ev_len, as_ll(l_offs), as_ll(S), as_ll(Q));
+    return S2S_OK;
+}
+
+// ---- the pore model from alignments (s2s_kmer_model_events.h); the host twin is in s2s_host.cpp
+int s2s_kmer_model_events(int device, void* stream_, const int32_t* codes, const int32_t* ev_len, const int64_t* S, const int64_t* Q,
+                          const int64_t* l_offs, int32_t P, const int64_t* gain, const int64_t* shift, int32_t k, int32_t workgroups,
+                          int64_t* table, int64_t* dropped) {
+    if (k < 1 || k > S2S_KMER_TABLE_MAX_K || P < 0 || workgroups < 0 || workgroups > S2S_KMER_MODEL_MAX_WORKGROUPS ||
+        (P > 0 && (!codes || !ev_len || !S || !Q || !l_offs || !gain || !shift || !table || !dropped)))
+        return fail(nullptr, S2S_ERR_ARG, "s2s_kmer_model_events: bad argument (k 1..10, P >= 0, workgroups 0..S2S_KMER_MODEL_MAX_WORKGROUPS)");
+    if (P == 0) return S2S_OK;
+    GUARD_OR_RETURN(nullptr, device);
+    S2SKmeIn in;
+    in.codes = codes; in.ev_len = ev_len;
+    in.S = as_ll(S); in.Q = as_ll(Q); in.l_offs = as_ll(l_offs);
+    in.gain = as_ll(gain); in.shift = as_ll(shift);
+    in.P = P; in.k = k;
+    // (the slot count l_offs[P] is on the device: the kernel reads it, and a workgroup without a round leaves at once)
+    S2S_LAUNCH(nullptr, s2s_kmer_model_events_kernel, dim3(workgroups ? workgroups : S2S_KMER_MODEL_MAX_WORKGROUPS), dim3(256), 0,
+               static_cast<hipStream_t>(stream_), in, reinterpret_cast<unsigned long long*>(table), reinterpret_cast<unsigned long long*>(dropped));
     return S2S_OK;
 }
 

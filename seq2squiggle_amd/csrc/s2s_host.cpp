@@ -2276,3 +2276,40 @@ extern "C" int s2s_chunk_pack_host(const void* pool, const int64_t* s_offs, int6
     });
     return S2S_OK;
 }
+
+// ================================================================================ the pore model from alignments on the host
+// The definition of include/s2s_hip.h (next to s2s_kmer_model_events) record by record and slot by slot, with the slot rule and the
+// conversion the kernel calls (s2s_kmer_model_events.h).  What the kernel must equal bit for bit.  One thread: the adds of a run
+// meet in a few rows, and the command calls this once per batch behind an alignment that took far longer.
+#include "s2s_kmer_model_events.h"
+
+extern "C" int s2s_kmer_model_events_host(const int32_t* codes, const int32_t* ev_len, const int64_t* S, const int64_t* Q,
+                                          const int64_t* l_offs, int32_t P, const int64_t* gain, const int64_t* shift, int32_t k,
+                                          int64_t* table, int64_t* dropped, int32_t threads) {
+    if (k < 1 || k > S2S_KMER_TABLE_MAX_K || P < 0 || threads < 1 ||
+        (P > 0 && (!codes || !ev_len || !S || !Q || !l_offs || !gain || !shift || !table || !dropped)))
+        return S2S_ERR_ARG;
+    for (int32_t p = 0; p < P; ++p)
+        if (l_offs[p + 1] < l_offs[p] || l_offs[0] < 0) return S2S_ERR_ARG;
+    const int32_t rows = (1 << (2 * k)) + 1;
+    for (int32_t p = 0; p < P; ++p) {
+        if (gain[p] == 0) continue;
+        for (int64_t g = l_offs[p]; g < l_offs[p + 1]; ++g) {
+            int64_t Mp = 0, Dp = 0;
+            const int what = s2s_kme_slot(ev_len[g], S[g], Q[g], codes[g], rows, gain[p], shift[p], Mp, Dp);
+            if (what == S2S_KME_NONE) continue;
+            if (what != S2S_KME_EVENT) {
+                dropped[what - 1] += 1;             // overlong, out_of_range, bad_code: in the order of `dropped`
+                continue;
+            }
+            int64_t* row = table + (int64_t)codes[g] * S2S_KMER_MODEL_FIELDS;
+            row[0] += 1;
+            row[1] += Mp;
+            row[2] += Mp * Mp;
+            row[3] += Dp;
+            row[4] += Dp * Dp;
+            dropped[3] += 1;
+        }
+    }
+    return S2S_OK;
+}

@@ -78,13 +78,14 @@ def _levels(lev_list, known_list, cpu: bool, device: int, threads, norm: bool, l
 
 
 def _run_batch(sig_list, lev_list, known_list, W: int, skip_penalty: int, trim_penalty: int, unknown_cost: int, seg, cpu: bool,
-               device: int = 0, threads: int = None, chunks=None):
+               device: int = 0, threads: int = None, chunks=None, model_out=None):
     """One batch of reads, the whole chain.  sig_list: the stored int16 samples; lev_list: int16 levels per k-mer (any value where
     known_list is False); seg: (w_short, w_long, T_short, T_long).  -> dict(cost int64 [P], first / end / n_events int32 [P], per read
     ev_start / ev_len / kmer (its events) and k_start / k_len / k_events / S / Q (its k-mers; S, Q over the raw samples), med / mad
     int32 [P] of the event means, lmed / lmad int32 [P] of the known levels).  chunks: (preprocess.Chunker, the records' calibrations,
     the cleaned sequences) -- the training chunks are packed from the device buffers behind the last sums; without it nothing else is
-    uploaded or launched."""
+    uploaded or launched.  model_out: (kmer_model.ModelBuilder, the calibrations, the cleaned sequences) -- the k-mer slots are summed
+    into the builder's table behind the last sums, likewise."""
     from ._lib import lib
     P = len(sig_list)
     w_s = seg[0]
@@ -93,6 +94,7 @@ def _run_batch(sig_list, lev_list, known_list, W: int, skip_penalty: int, trim_p
     def tables(offs):
         cap = capacity(np.diff(offs), w_s)
         extra = chunks[0].tables(chunks[1], chunks[2]) if chunks is not None else []
+        extra += model_out[0].tables(model_out[1], model_out[2]) if model_out is not None else []
         return [slots(cap), device_only(lambda: slots([scratch_bytes(c, k, W) for c, k in zip(cap, K)]))] + extra
     B = Batch(sig_list, tables, cpu, device, threads)
     ev_offs = B.tables[0]
@@ -120,6 +122,9 @@ def _run_batch(sig_list, lev_list, known_list, W: int, skip_penalty: int, trim_p
     B.call("event_sums", B.samples, B.offs(), res.ptr("k_start"), res.ptr("k_len"), l_offs, P, res.ptr("S"), res.ptr("Q"))
     if chunks is not None:
         chunks[0].pack(B, P, l_offs, K, res.ptr("k_start"), res.ptr("k_len"), res.ptr("S"), res.ptr("Q"), B.table(2), B.table(3))
+    if model_out is not None:
+        at = 2 if chunks is None else 4
+        model_out[0].add(B, P, l_offs, res.ptr("k_len"), res.ptr("S"), res.ptr("Q"), B.table(at), B.table(at + 1), B.table(at + 2))
     r = res.fetch()
     lo, mo, ne = BL.tables[0], r["m_offs"], r["n_events"]
     per_k = lambda a: [a[lo[p]:lo[p + 1]] for p in range(P)]                         # noqa: E731
@@ -189,12 +194,14 @@ def eventalign_files(seqs, signals, model, out, band_width: int = DEFAULT_BAND_W
                      window_short: int = DEFAULT_WINDOW_SHORT, window_long: int = DEFAULT_WINDOW_LONG,
                      threshold_short: float = DEFAULT_THRESHOLD_SHORT, threshold_long: float = DEFAULT_THRESHOLD_LONG,
                      with_samples: bool = False, cpu: bool = False, device: int = 0, summary_out=None,
-                     max_samples: int = DEFAULT_MAX_SAMPLES, trace_memory: int = DEFAULT_TRACE_MEMORY, chunks=None) -> dict:
+                     max_samples: int = DEFAULT_MAX_SAMPLES, trace_memory: int = DEFAULT_TRACE_MEMORY, chunks=None,
+                     model_out=None) -> dict:
     """pore_align.align_files with this module's solver (one row per unskipped k-mer) -> the counters: reads solved, unreached (no
     path inside the band), refused (or a walk back that may need more than trace_memory on its own: the bound of a read's decision
     scratch is that of s2s_segment_capacity events), without a sequence, without a known level, events (the rows: k-mers with
     events), aligned events, skipped k-mers, the samples trimmed at head and tail, and the mean cost per aligned event in MADs.
-    summary_out: one row per read (SUMMARY_COLUMNS)."""
+    summary_out: one row per read (SUMMARY_COLUMNS).  model_out: (NEW.model, min_events) -- the pore model re-estimated from these
+    alignments."""
     W, skip_penalty, trim_penalty, unknown_cost = _check_params(band_width, skip_penalty, trim_penalty, unknown_cost)
     seg = _check_segment(window_short, window_long, threshold_int(threshold_short), threshold_int(threshold_long))
     return align_files(Aligner(
@@ -205,7 +212,9 @@ def eventalign_files(seqs, signals, model, out, band_width: int = DEFAULT_BAND_W
         need=lambda n, K: scratch_bound(n, K, W, seg[0]),
         refusal=f"eventalign: read %s refused: %d samples against %d k-mers at band width {W} (limit %d each; up to %d bytes of decision "
                 "scratch against --trace-memory %d)",
-        solve=lambda sig, lev, known, ch: _run_batch(sig, lev, known, W, skip_penalty, trim_penalty, unknown_cost, seg, cpu, device, chunks=ch),
+        solve=lambda sig, lev, known, ch, mo: _run_batch(sig, lev, known, W, skip_penalty, trim_penalty, unknown_cost, seg, cpu, device,
+                                                         chunks=ch, model_out=mo),
         account=_account, mean_key="mean_cost_per_event",
         log_tail="%d event row(s) of %d aligned event(s), %d skipped k-mer(s); %d / %d sample(s) trimmed at head / tail; mean cost per "
-                 "aligned event %s MAD"), seqs, signals, model, out, rna, with_samples, cpu, summary_out, max_samples, trace_memory, chunks)
+                 "aligned event %s MAD"), seqs, signals, model, out, rna, with_samples, cpu, summary_out, max_samples, trace_memory, chunks,
+        model_out)

@@ -143,7 +143,8 @@ class Aligner:
     params: dict                # its keys of the summary dict, between k and the counters
     need: Callable              # (samples, k-mers) -> bytes of decision scratch the read may take, before it runs
     refusal: str                # the warning of a refused read: rid, samples, k-mers, the limit of both, `need`, trace_memory
-    solve: Callable             # (samples, levels, known flags per read; the chunks tuple of _run_batch or None) -> its result dict
+    solve: Callable             # (samples, levels, known flags per read; the chunks tuple of _run_batch or None; its model_out tuple
+                                # or None) -> its result dict
     account: Callable           # (result, p, samples of read p) -> (cost, k-mers, (med, mad, level_med, level_mad), its summary
                                 # fields, and for a cost >= 0: the units the cost is spread over, {counter: increment}, the
                                 # (start, length, S, Q) of format_rows)
@@ -154,13 +155,15 @@ class Aligner:
 
 
 def align_files(cmd: Aligner, seqs, signals, model, out, rna: bool, with_samples: bool, cpu: bool, summary_out, max_samples: int,
-                trace_memory: int, chunks) -> dict:
+                trace_memory: int, chunks, model_out=None) -> dict:
     """Write OUT (EVENT_COLUMNS, plus `samples` with with_samples; records in the order of SIGNALS, rows by position), one summary row
     per read (cmd.columns, in record order) and, with chunks = (OUTDIR, seq_kmer, max_dna_len, max_signal_len), the training chunks of
-    the solved reads (preprocess.Chunker, from the device buffers); -> the summary dict.  A record goes to the solver unless it has no
-    sequence (no record of that name in SEQS, or fewer than k letters), no k-mer with a level, or is refused: more than 2^22 samples
-    or k-mers, or cmd.need beyond trace_memory on its own -- by read id, before the batch computes.  A batch holds reads until their
-    samples pass max_samples or their needs pass trace_memory (at least one read).  rna: the levels are read back to front."""
+    the solved reads (preprocess.Chunker, from the device buffers) and, with model_out = (NEW.model, min_events), the pore model
+    re-estimated from the run's own alignments (kmer_model.ModelBuilder, from the same buffers); -> the summary dict.  A record goes to
+    the solver unless it has no sequence (no record of that name in SEQS, or fewer than k letters), no k-mer with a level, or is
+    refused: more than 2^22 samples or k-mers, or cmd.need beyond trace_memory on its own -- by read id, before the batch computes.  A
+    batch holds reads until their samples pass max_samples or their needs pass trace_memory (at least one read).  rna: the levels are
+    read back to front."""
     if int(max_samples) < 1 or int(trace_memory) < 1:
         raise ValueError("max_samples and trace_memory must be >= 1")
     if not cpu:
@@ -172,6 +175,10 @@ def align_files(cmd: Aligner, seqs, signals, model, out, rna: bool, with_samples
         if int(chunks[1]) != k:
             raise click.ClickException(f"--seq-kmer {int(chunks[1])} is not the model's k = {k}")
         chunker = Chunker(chunks[0], k, chunks[2], chunks[3], rna)
+    builder = None
+    if model_out is not None:
+        from .kmer_model import ModelBuilder
+        builder = ModelBuilder(k, rna)
     table, has = level_ints(levels)
     sequences = read_sequences(str(seqs))
     clip = cmd.clip() if cmd.clip is not None else None
@@ -193,7 +200,8 @@ def align_files(cmd: Aligner, seqs, signals, model, out, rna: bool, with_samples
         def flush(batch):
             t0 = time.perf_counter()
             r = cmd.solve([b[2] for b in batch], [b[3] for b in batch], [b[4] for b in batch],
-                          None if chunker is None else (chunker, [b[5] for b in batch], [b[1] for b in batch]))
+                          None if chunker is None else (chunker, [b[5] for b in batch], [b[1] for b in batch]),
+                          None if builder is None else (builder, [b[5] for b in batch], [b[1] for b in batch]))
             t1 = time.perf_counter()
             for p, (rid, clean, sig, _, _, cal, span, no, _) in enumerate(batch):
                 c, K, mm, fields, *solved = cmd.account(r, p, len(sig))
@@ -254,6 +262,8 @@ def align_files(cmd: Aligner, seqs, signals, model, out, rna: bool, with_samples
         s["summary_out"] = str(summary_out)
     if chunker is not None:
         s["chunks"] = chunker.close(cmd.name)
+    if builder is not None:
+        s["kmer_model"] = builder.close(model_out[0], model_out[1])
     logger.info("%s: %d record(s): %d solved, %d unreached, %d refused, %d without a sequence, %d without a known level; " + cmd.log_tail,
                 cmd.name, *cnt.values(), "nan" if mean is None else "%.4f" % mean)
     return s

@@ -64,13 +64,14 @@ def scratch_bytes(n: int, K: int, band: int) -> int:
 
 
 def _run_batch(sig_list, lev_list, known_list, band: int, skip_penalty: int, unknown_cost: int, norm: bool, cpu: bool, device: int = 0,
-               threads: int = None, sums: bool = True, chunks=None):
+               threads: int = None, sums: bool = True, chunks=None, model_out=None):
     """One batch of reads.  sig_list: the stored int16 samples; lev_list: int16 levels per k-mer (any value where known_list is False).
     norm: samples are normalised by their own median / MAD and the levels by the median / MAD of the read's KNOWN levels, both by
     s2s_signal_median_mad / s2s_signal_normalise at scale 64 (else both enter as they are); k-mers without a level get S2S_RSQ_UNKNOWN.
     -> dict(cost int64 [P], start / len int32 per read, S / Q int64 per read (raw samples), med / mad int32 [2 P]: samples, then levels).
     chunks: (preprocess.Chunker, the records' calibrations, the cleaned sequences) -- the training chunks are packed from the device
-    buffers behind the sums; without it nothing else is uploaded or launched."""
+    buffers behind the sums; without it nothing else is uploaded or launched.  model_out: (kmer_model.ModelBuilder, the calibrations,
+    the cleaned sequences) -- the k-mer slots are summed into the builder's table behind the sums, likewise."""
     P = len(sig_list)
     known_recs, full_recs, unknown = split_levels(lev_list, known_list)
 
@@ -79,6 +80,7 @@ def _run_batch(sig_list, lev_list, known_list, band: int, skip_penalty: int, unk
         of the third part from its start); s_offs int64 [P + 1]: their slots of decision scratch (device only)."""
         lens = np.diff(offs)
         extra = chunks[0].tables(chunks[1], chunks[2]) if chunks is not None else []
+        extra += model_out[0].tables(model_out[1], model_out[2]) if model_out is not None else []
         return [(offs[2 * P:] - offs[2 * P]).astype(np.int64), slots([scratch_bytes(lens[p], lens[2 * P + p], band) for p in range(P)])] + extra
     B = Batch(list(sig_list) + known_recs + full_recs, tables, cpu, device, threads)
     l_offs, s_offs = B.tables[:2]
@@ -93,6 +95,9 @@ def _run_batch(sig_list, lev_list, known_list, band: int, skip_penalty: int, unk
         B.call("event_sums", B.samples, B.offs(), res.ptr("start"), res.ptr("len"), B.table(0), P, res.ptr("S"), res.ptr("Q"))
     if chunks is not None:
         chunks[0].pack(B, P, B.table(0), np.diff(l_offs), res.ptr("start"), res.ptr("len"), res.ptr("S"), res.ptr("Q"), B.table(2), B.table(3))
+    if model_out is not None:
+        at = 2 if chunks is None else 4
+        model_out[0].add(B, P, B.table(0), res.ptr("len"), res.ptr("S"), res.ptr("Q"), B.table(at), B.table(at + 1), B.table(at + 2))
     r = res.fetch()
     cut = lambda a: [a[l_offs[p]:l_offs[p + 1]] for p in range(P)]      # noqa: E731
     return dict(cost=r["cost"], start=cut(r["start"]), len=cut(r["len"]), S=cut(r["S"]), Q=cut(r["Q"]), med=r["med"], mad=r["mad"])
@@ -174,13 +179,13 @@ def _clip(intervals):
 def resquiggle_files(seqs, signals, model, out, band: int = DEFAULT_BAND, skip_penalty: int = DEFAULT_SKIP_PENALTY,
                      unknown_cost: int = DEFAULT_UNKNOWN_COST, rna: bool = False, intervals=None, with_samples: bool = False,
                      cpu: bool = False, device: int = 0, summary_out=None, max_samples: int = DEFAULT_MAX_SAMPLES,
-                     trace_memory: int = DEFAULT_TRACE_MEMORY, chunks=None) -> dict:
+                     trace_memory: int = DEFAULT_TRACE_MEMORY, chunks=None, model_out=None) -> dict:
     """pore_align.align_files with this module's solver -> the counters: reads solved, unreached (no path: more than two k-mers per
     sample, or the band too narrow), refused (or a walk back that needs more than trace_memory on its own), without a sequence,
     without a known level, events, skipped k-mers, and the mean cost per sample in MADs (sum of costs / sum of samples / 64 over the
     solved reads).  rna: `position` stays in read coordinates and start_idx falls as it rises.  intervals: restrict every record
     that has a row to [b_start, b_end) (read_intervals); rows come out in the record's own coordinates.  summary_out: one row per
-    read (SUMMARY_COLUMNS)."""
+    read (SUMMARY_COLUMNS).  model_out: (NEW.model, min_events) -- the pore model re-estimated from these alignments."""
     band, skip_penalty, unknown_cost = _check_params(band, skip_penalty, unknown_cost)
     return align_files(Aligner(
         name="resquiggle", columns=SUMMARY_COLUMNS, counters=("events", "skipped_kmers"),
@@ -188,6 +193,8 @@ def resquiggle_files(seqs, signals, model, out, band: int = DEFAULT_BAND, skip_p
         need=lambda n, K: scratch_bytes(n, K, band),
         refusal=f"resquiggle: read %s refused: %d samples against %d k-mers at band {band} (limit %d each; %d bytes of decision scratch "
                 "against --trace-memory %d)",
-        solve=lambda sig, lev, known, ch: _run_batch(sig, lev, known, band, skip_penalty, unknown_cost, True, cpu, device, chunks=ch),
+        solve=lambda sig, lev, known, ch, mo: _run_batch(sig, lev, known, band, skip_penalty, unknown_cost, True, cpu, device, chunks=ch,
+                                                         model_out=mo),
         account=_account, mean_key="mean_cost_per_sample", log_tail="%d event(s), %d skipped k-mer(s); mean cost per sample %s MAD",
-        clip=lambda: _clip(intervals)), seqs, signals, model, out, rna, with_samples, cpu, summary_out, max_samples, trace_memory, chunks)
+        clip=lambda: _clip(intervals)), seqs, signals, model, out, rna, with_samples, cpu, summary_out, max_samples, trace_memory, chunks,
+        model_out)

@@ -1155,6 +1155,61 @@ int s2s_stats_read(s2s_handle* h, uint64_t* out10);
  * wave count, 32-47 the frontend's own phases; tools/diag_phases.py names them); out384 = [8][48].  S2S_ERR_ARG in a normal build. */
 int s2s_diag_read(s2s_handle* h, uint64_t* out384);
 
+/* ---------------------------------------------------------------------------------------------------------------- train
+ * Replaces seq2squiggle.training_step + get_loss + configure_optimizers (model.py:65-105, 419-480) for the Adam / AdamW case, in
+ * exact fp32 on one device: forward (the kernels of s2s_evaluate_chunks on a S2S_MODE_GENERIC_GEOMETRY handle, each layer writing
+ * into buffers of its own -- the tape), backward (csrc/s2s_train.h), global gradient norm, clipping and the optimizer step.
+ * The function:
+ *   total = mean_{B ts} (y - target)^2 + 0.0005 mean_{B te} -Gamma(conc, rate).log_prob(max(|dwell|, 1)) + mean_{B te} (stdev - sigma)^2
+ * with the means over the batch given (a short last batch divides by its own size).  The three heads read emb_out.detach(): their
+ * losses reach only the heads' own weights; the signal loss flows through the decoder, the length regulator (a sum over each
+ * k-mer's samples; cropped samples and rows behind the last dwell give nothing, a k-mer of dwell 0 gets zero), the encoder, the
+ * pre-net and src_emb.  The two position tables have no gradient and never change.  Dropout is NOT applied and there is no
+ * reduced-precision mode (the reference trains in 16-mixed with dropout).
+ *
+ * cfg->compute_mode must be S2S_MODE_GENERIC_GEOMETRY; every size and geometry that mode accepts runs.  A trainer holds fp32
+ * weights, a gradient, Adam's m and v (each the size of the weights, m = v = 0 at create) and the tape.  Inside it uses the
+ * generic handle's aligned packing; every blob it takes or hands out is in the order of s2s_blob_floats.
+ *
+ *  s2s_trainer_set_memory   bytes of tape + backward scratch a micro-batch may use (default S2S_TRAINER_DEFAULT_MEMORY, 2 GiB -- a choice: it keeps a default
+ *                 batch of 512 chunks of the shipped size in one micro-batch and leaves most of the card free).  A batch whose
+ *                 tape exceeds it runs as micro-batches of s2s_trainer_micro_batch(t, B) chunks, the last one shorter; their
+ *                 gradients add in micro-batch order.  One chunk always runs.
+ *  s2s_trainer_weights      copies the weights out in blob order (out_blob: host or device, [s2s_blob_floats]; a host copy
+ *                 synchronises the stream).
+ *  s2s_trainer_gradients    forward and backward only; changes no weight.  kmers / dwell / target / stdev as for
+ *                 s2s_evaluate_chunks (device; dwell >= 0 is a precondition: a negative dwell reads nothing out of range, but its
+ *                 gradient is not defined); out_loss device [B][3]: the per-chunk loss sums, bit-equal to s2s_evaluate_chunks'
+ *                 on a S2S_MODE_GENERIC_GEOMETRY handle with the same weights; out_grad host or device [s2s_blob_floats]: the
+ *                 gradient of `total` in blob order (the position tables' slots 0).
+ *  s2s_trainer_step         the same, then one optimizer step: clip by global L2 norm as clip_grad_norm_ does (scale by
+ *                 clip / (norm + 1e-6) when norm > clip; clip <= 0: none), then torch.optim.Adam (decoupled == 0: g += wd w) or
+ *                 AdamW (decoupled != 0: w *= 1 - lr wd), bias correction by `step` (counts from 1).  The clip scale stays in
+ *                 device memory: nothing returns to the host inside a step.  out_stats device [5] fp32: the three loss means of
+ *                 this forward (signal, duration x 0.0005, noise), their total, and the gradient norm before clipping.
+ * Deterministic: every sum over rows is per-tile partials in row order and one ordered pass, no float atomics; two calls with
+ * the same inputs, B and memory budget give the same bits.  Stream-ordered; scratch grows on demand (the first call of a larger
+ * batch synchronises the stream).  S2S_ERR_ARG: B < 1, a NULL pointer, inputs on another device than the trainer's, step < 1,
+ * betas outside [0, 1), eps <= 0; message: s2s_trainer_last_error(t) (t == NULL: of the last failed create, thread-local). */
+#define S2S_TRAINER_DEFAULT_MEMORY ((size_t)2 << 30)
+typedef struct s2s_trainer s2s_trainer;
+typedef struct s2s_adam {
+    double lr, beta1, beta2, eps, weight_decay;
+    double clip;               /* gradient_clip_val; <= 0: no clipping */
+    int32_t decoupled;         /* 0: Adam (coupled L2), 1: AdamW */
+    int32_t step;              /* 1, 2, ...: the bias-correction exponent */
+} s2s_adam;
+int s2s_trainer_create(const s2s_config* cfg, const void* weights_blob, size_t blob_bytes, int device, s2s_trainer** out);
+void s2s_trainer_destroy(s2s_trainer* t);
+const char* s2s_trainer_last_error(const s2s_trainer* t);
+int s2s_trainer_set_memory(s2s_trainer* t, size_t bytes);
+int64_t s2s_trainer_micro_batch(const s2s_trainer* t, int32_t B);
+int s2s_trainer_weights(s2s_trainer* t, void* stream, float* out_blob);
+int s2s_trainer_gradients(s2s_trainer* t, void* stream, const uint8_t* kmers, const int32_t* dwell, const float* target,
+                          const float* stdev, int32_t B, float* out_loss, float* out_grad);
+int s2s_trainer_step(s2s_trainer* t, void* stream, const uint8_t* kmers, const int32_t* dwell, const float* target,
+                     const float* stdev, int32_t B, const s2s_adam* hyper, float* out_stats);
+
 #ifdef __cplusplus
 }
 #endif

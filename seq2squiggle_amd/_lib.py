@@ -25,6 +25,11 @@ class S2SDebug(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("emb_out", "enc_out", "sigma", "conc", "rate", "g", "y_scaled", "z01", "emb_in", "dec_in")]
 
 
+class S2SAdam(C.Structure):
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
+                ("clip", C.c_double), ("decoupled", C.c_int32), ("step", C.c_int32)]
+
+
 EXPORTS = ("s2s_blob_floats", "s2s_create", "s2s_destroy", "s2s_last_error", "s2s_predict_chunks", "s2s_predict_packed",
            "s2s_export_reads", "s2s_svb_encode", "s2s_philox_u32", "s2s_set_profiling", "s2s_get_kernel_ms", "s2s_stats_read", "s2s_set_attention_path", "s2s_get_attention_path", "s2s_diag_read",
            "s2s_blow5_pack_bound", "s2s_blow5_pack", "s2s_compress_rows", "s2s_sampler_replay", "s2s_sampler_replay_law", "s2s_length_law",
@@ -41,7 +46,9 @@ EXPORTS = ("s2s_blob_floats", "s2s_create", "s2s_destroy", "s2s_last_error", "s2
            "s2s_segment_format",
            "s2s_eventalign_scratch_bytes", "s2s_event_means", "s2s_eventalign", "s2s_event_means_host", "s2s_eventalign_host",
            "s2s_chunk_scratch_bytes", "s2s_chunk_pack", "s2s_chunk_pack_host",
-           "s2s_kmer_model_events", "s2s_kmer_model_events_host")
+           "s2s_kmer_model_events", "s2s_kmer_model_events_host",
+           "s2s_trainer_create", "s2s_trainer_destroy", "s2s_trainer_last_error", "s2s_trainer_set_memory", "s2s_trainer_micro_batch",
+           "s2s_trainer_weights", "s2s_trainer_gradients", "s2s_trainer_step")
 
 
 def lib():
@@ -147,5 +154,13 @@ def lib():
     bind("s2s_chunk_pack_host", i32, chunk + [vp] * 7 + [i32])
     bind("s2s_kmer_model_events", i32, [i32, vp] + [vp] * 5 + [i32, vp, vp, i32, i32, vp, vp])
     bind("s2s_kmer_model_events_host", i32, [vp] * 5 + [i32, vp, vp, i32, vp, vp, i32])
+    bind("s2s_trainer_create", i32, [C.POINTER(S2SConfig), vp, C.c_size_t, i32, C.POINTER(vp)])
+    bind("s2s_trainer_destroy", None, [vp])
+    bind("s2s_trainer_last_error", C.c_char_p, [vp])
+    bind("s2s_trainer_set_memory", i32, [vp, C.c_size_t])
+    bind("s2s_trainer_micro_batch", i64, [vp, i32])
+    bind("s2s_trainer_weights", i32, [vp, vp, vp])
+    bind("s2s_trainer_gradients", i32, [vp, vp, vp, vp, vp, vp, i32, vp, vp])
+    bind("s2s_trainer_step", i32, [vp, vp, vp, vp, vp, vp, i32, C.POINTER(S2SAdam), vp])
     _lib = L
     return L

@@ -874,5 +874,53 @@ def preprocess(events, outdir, config, seq_kmer, max_dna_len, max_signal_len, rn
                    f"{s['chunks_formed']} chunks formed, {s['chunks_kept']} kept, {s['chunks_too_long']} dropped as too long]")
 
 
+@main.command()
+@click.argument("train_dir", type=click.Path(file_okay=False, path_type=pathlib.Path))
+@click.argument("valid_dir", type=click.Path(file_okay=False, path_type=pathlib.Path))
+@click.option("-o", "--out", required=True, type=click.Path(dir_okay=False), help="MODEL_DIR/MODEL.ckpt, written after every epoch.")
+@click.option("-y", "--config", default=None, type=click.Path(dir_okay=False, exists=True),
+              help="YAML configuration file (default: the packaged config.yaml).")
+@click.option("--init", default=None, type=click.Path(dir_okay=False, exists=True),
+              help="Checkpoint to fine-tune; its geometry and sizes must be the config's (default: torch's default initialisation).")
+@click.option("--seed", default=0, type=int, show_default=True, help="Seed of the initialisation and of the per-epoch permutations.")
+@click.option("--max-steps", default=None, type=int, help="Stop after this many optimizer steps (default: max_epochs epochs).")
+@click.option("--train-memory", default=None, type=int,
+              help="Bytes of tape and backward scratch per micro-batch; a larger batch runs as micro-batches (default 2 GiB: a choice).")
+@click.option("--keep-epochs", is_flag=True, help="Also keep a MODEL-epoch=N.ckpt copy per epoch.")
+@click.option("--json", "as_json", is_flag=True, help="Log one JSON object per step and per epoch instead of the text lines.")
+def train(train_dir, valid_dir, out, config, init, seed, max_steps, train_memory, keep_epochs, as_json):
+    """Fit a checkpoint to a preprocess directory on one GPU: the reference's training_step, get_loss and configure_optimizers for
+    Adam / AdamW in exact fp32 (no dropout, no mixed precision); after every epoch the four valid_* losses of `evaluate` on
+    VALID_DIR and the checkpoint."""
+    if not str(out).endswith(".ckpt"):
+        raise click.BadParameter("must end in .ckpt", param_hint="--out")
+    if not os.path.dirname(str(out)):
+        raise click.BadParameter("needs a directory part: MODEL_DIR/MODEL.ckpt", param_hint="--out")
+    for d, hint in ((train_dir, "TRAIN_DIR"), (valid_dir, "VALID_DIR")):
+        if not d.is_dir():
+            raise click.BadParameter(f"{d} is not a directory", param_hint=hint)
+    if max_steps is not None:
+        _in_range(max_steps, 1, 1 << 31, "--max-steps")
+    if train_memory is not None:
+        _in_range(train_memory, 1, 1 << 46, "--train-memory")
+    cfg = set_config(config)
+    from . import train as TR
+    try:
+        TR.check_config(cfg)
+    except ValueError as e:
+        raise click.BadParameter(str(e), param_hint="--config")
+    for key, lo, hi in (("train_batch_size", 1, 1 << 20), ("max_epochs", 1, 1 << 20)):
+        if not lo <= int(cfg.get(key, 0)) <= hi:
+            raise click.BadParameter(f"{key} must be {lo}..{hi}", param_hint="--config")
+    if not float(cfg.get("lr", 0)) > 0:
+        raise click.BadParameter("lr must be positive", param_hint="--config")
+    import torch  # noqa: F401  (before the library: see engine.py)
+    try:
+        TR.train_run(str(train_dir), str(valid_dir), str(out), cfg, init=init, seed=seed, max_steps=max_steps, train_memory=train_memory,
+                     keep_epochs=keep_epochs, json_log=as_json, log=click.echo)
+    except ValueError as e:
+        raise click.ClickException(str(e))
+
+
 if __name__ == "__main__":
     main()

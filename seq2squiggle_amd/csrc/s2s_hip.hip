@@ -12,6 +12,7 @@
 #include "s2s_device_h.h"
 #include "s2s_generic.h"
 #include "s2s_generic_h.h"
+#include "s2s_train.h"
 #include "../../include/s2s_hip.h"
 #include "s2s_event_fixed.h"
 #define S2S_DTW_KERNELS
@@ -2800,3 +2801,5 @@ int s2s_chunk_pack(int device, void* stream_, const void* pool, const int64_t* s
 }
 
 }  // extern "C"
+
+#include "s2s_train_host.h"

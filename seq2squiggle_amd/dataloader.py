@@ -6,7 +6,7 @@ a DataLoader collate batches of `predict_batch_size` chunks.  Here a batch is th
 n_valid uint8 [B], 25 B per chunk; chunker.encode_read), which `seq2squiggle.predict_step` takes directly; `onehot=True` yields
 the reference's own batch format instead (predict_step accepts both).  The streaming path (inference.run_streaming) does not go
 through batches at all; this class is the drop-in for callers of the reference's Trainer.predict loop.  Training / validation
-loaders are out of scope."""
+batches do not come from this class: `train` reads a preprocess directory itself (train.TrainData, evaluate.EvalData)."""
 import logging
 from typing import Iterable, Iterator, Optional, Tuple
 

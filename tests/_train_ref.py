@@ -59,15 +59,20 @@ def loss_and_grads(sd, cfg, codes, lengths, target, stdev, dtype=torch.float64):
 
 
 def adam_run(sd, cfg, batches, dtype=torch.float64, optimizer="Adam", lr=5e-4, weight_decay=0.0, clip=1.0, eps=1e-7,
-             betas=(0.9, 0.999)):
+             betas=(0.9, 0.999), lrs=None):
     """torch.optim.Adam / AdamW with clip_grad_norm_ over `batches` (an iterable of (codes, lengths, target, stdev)) ->
-    (per-step total losses, per-step gradient norms before clipping, the final state dict as numpy arrays of `dtype`)."""
+    (per-step total losses, per-step gradient norms before clipping, the final state dict as numpy arrays of `dtype`).
+    lrs: the learning rate of every step, written into the param group before that step (what LambdaLR does); default: `lr`
+    throughout."""
     p = leaves(sd, dtype)
     params = [v for v in p.values() if v.requires_grad]
     cls = torch.optim.AdamW if optimizer == "AdamW" else torch.optim.Adam
     opt = cls(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
     losses, norms = [], []
-    for codes, lengths, target, stdev in batches:
+    for s, (codes, lengths, target, stdev) in enumerate(batches):
+        if lrs is not None:
+            for group in opt.param_groups:
+                group["lr"] = float(lrs[s])
         opt.zero_grad(set_to_none=True)
         total, _ = total_loss(p, cfg, codes, lengths, target, stdev, dtype)
         total.backward()

@@ -52,6 +52,22 @@ def on_device(codes, lengths, target, stdev):
             torch.from_numpy(target).cuda().contiguous(), torch.from_numpy(stdev).cuda().contiguous())
 
 
+def budget_for(tr, B, n):
+    """Bisect the trainer's memory budget to n chunks per micro-batch of a batch of B, leave it set and return it."""
+    lo, hi = 1, 1 << 40
+    budget = hi
+    tr.set_memory(budget)
+    while tr.micro_batch(B) != n:
+        assert hi - lo > 1, f"no budget gives {n} chunks per micro-batch"
+        budget = (lo + hi) // 2
+        tr.set_memory(budget)
+        if tr.micro_batch(B) < n:
+            lo = budget
+        elif tr.micro_batch(B) > n:
+            hi = budget
+    return budget
+
+
 def compare(name, dev: dict, g64: dict, g32: dict):
     """-> (r32, the device's worst relative distance, failures) by the module docstring's rule."""
     norm = {k: float(np.linalg.norm(v)) for k, v in g64.items()}
@@ -82,16 +98,9 @@ def test_gradients(tag, B):
     _, _, g64 = R.loss_and_grads(sd, cfg, codes, lengths, target, stdev, torch.float64)
     _, _, g32 = R.loss_and_grads(sd, cfg, codes, lengths, target, stdev, torch.float32)
     tr = T.Trainer(sd, cfg, 0)
-    if B is not None:                                              # bisect the budget to 13 chunks per micro-batch: 37 = 13 + 13 + 11
-        lo, hi = 1, 1 << 40
-        while tr.micro_batch(B) != 13:
-            assert hi - lo > 1, "no budget gives 13 chunks per micro-batch"
-            mid = (lo + hi) // 2
-            tr.set_memory(mid)
-            if tr.micro_batch(B) < 13:
-                lo = mid
-            elif tr.micro_batch(B) > 13:
-                hi = mid
+    if B is not None:                                              # 13 chunks per micro-batch: 37 = 13 + 13 + 11
+        budget_for(tr, B, 13)
+        assert tr.micro_batch(B) == 13
     args = on_device(codes, lengths, target, stdev)
     out = tr.gradients(*args)
     again = tr.gradients(*args)
@@ -115,14 +124,17 @@ def random_inputs(cfg, B, seed):
     rng = np.random.default_rng(seed)
     codes = rng.integers(1, 5, (B, te, k)).astype(np.uint8)
     lengths = rng.integers(0, 2 * ts // te, (B, te)).astype(np.int64)
-    lengths[0, :2] = 0
-    lengths[1, te // 2] = 32767                                       # a stalled k-mer: everything behind it is cropped
+    lengths[0, :min(2, te - 1)] = 0                                   # (below three k-mers the chunk keeps one that has samples)
+    lengths[1 % B, te // 2] = 32767                                   # a stalled k-mer: everything behind it is cropped
     target = rng.random((B, ts), dtype=np.float32)
     stdev = (rng.random((B, te), dtype=np.float32) * 0.02).astype(np.float32)
     return codes, lengths, target, stdev
 
 
-@pytest.mark.parametrize("tag", ["d128", "d512"])
+LARGE = ["d128", "d512"]
+
+
+@pytest.mark.parametrize("tag", LARGE)
 def test_gradients_at_the_large_sizes(tag):
     import _sized_models as SM
     sd, cfg = load_checkpoint(SM.checkpoint_path(tag))

@@ -1735,157 +1735,8 @@ ParamsDev to_dev(const s2s_params* p) {
 
 }  // namespace
 
-// ---- S2S_MODE_GENERIC (s2s_generic.h): the launch in slices of at most gen.slice_max chunks, each slice stage by stage.
-namespace {
-template <int EPI>
-void gen_gemm(hipStream_t st, const float* A, int lda, const float* W, const float* bias, float* C, int ldc, const float* R, int M, int N, int K) {
-    const dim3 grid((M + GEN_BM - 1) / GEN_BM, (N + GEN_BN - 1) / GEN_BN);
-    hipLaunchKernelGGL(gen_gemm_kernel<EPI>, grid, dim3(256), 0, st, A, lda, W, K, bias, C, ldc, R, ldc, M, N, K);
-}
-
-// one FFTBlock (layers.py:116-142) on the rows X [n*T][d]; BIG [n*T][max(3d, dff)] holds QKV (O replaces Q), then the FFN hidden
-void gen_fft_block(hipStream_t st, const float* W, const GenLayer& L, float* X, float* BIG, int n, int T, int d, int dff, int H) {
-    const int M = n * T, hd = d / H;
-    gen_gemm<0>(st, X, d, W + L.wqkv, W + L.bqkv, BIG, 3 * d, nullptr, M, 3 * d, d);
-    const size_t stage = gen_attn_lds_bytes(T, hd, true);
-    if (T > 256) {                            // (S2S_MODE_GENERIC_GEOMETRY's decoder beyond 256 samples)
-        const dim3 grid((unsigned)n * H * ((T + 63) / 64));
-        if (hd <= 16)
-            hipLaunchKernelGGL(gen_attention_long_kernel<1>, grid, dim3(256), 0, st, BIG, d, H, T);
-        else if (hd <= 128)
-            hipLaunchKernelGGL(gen_attention_long_kernel<8>, grid, dim3(256), 0, st, BIG, d, H, T);
-        else
-            hipLaunchKernelGGL(gen_attention_long_kernel<32>, grid, dim3(256), 0, st, BIG, d, H, T);
-    } else if (stage <= GEN_ATTN_STAGE_BYTES)
-        hipLaunchKernelGGL(gen_attention_kernel<true>, dim3(n * H), dim3(256), stage, st, BIG, d, H, T);
-    else
-        hipLaunchKernelGGL(gen_attention_kernel<false>, dim3(n * H), dim3(256), gen_attn_lds_bytes(T, hd, false), st, BIG, d, H, T);
-    gen_gemm<2>(st, BIG, 3 * d, W + L.wfc, W + L.bfc, X, d, X, M, d, d);
-    hipLaunchKernelGGL(gen_layernorm_kernel, dim3((M + 3) / 4), dim3(256), 0, st, X, W + L.ln1g, W + L.ln1b, (long long)M, d);
-    gen_gemm<1>(st, X, d, W + L.w1, W + L.b1, BIG, dff, nullptr, M, dff, d);
-    gen_gemm<2>(st, BIG, dff, W + L.w2, W + L.b2, X, d, X, M, d, dff);
-    hipLaunchKernelGGL(gen_layernorm_kernel, dim3((M + 3) / 4), dim3(256), 0, st, X, W + L.ln2g, W + L.ln2b, (long long)M, d);
-}
-
-// S2S_MODE_GENERIC_F16's and S2S_MODE_GENERIC_GEOMETRY_F16's decoder FFTBlock: gen_fft_block with the matrix products on f16
-// operands (s2s_generic_h.h); the LayerNorms, the biases, ReLU and the residuals stay fp32.  T = ts: 250 for S2S_MODE_GENERIC_F16.
-template <int EPI>
-void gen_gemm_h(hipStream_t st, const float* A, int lda, const float* Wh, int ldw, const float* bias, float* C, int ldc, const float* R, int M, int N,
-                int K) {
-    const dim3 grid((M + GEN_BM - 1) / GEN_BM, (N + GEN_BN - 1) / GEN_BN);
-    hipLaunchKernelGGL(gen_gemm_h_kernel<EPI>, grid, dim3(256), 0, st, A, lda, reinterpret_cast<const _Float16*>(Wh), ldw, bias, C, ldc, R, ldc,
-                       M, N, K);
-}
-
-void gen_fft_block_h(hipStream_t st, const float* W, const GenLayer& L, const GenLayerH& LH, int ld_d, int ld_f, float* X, float* BIG, int n,
-                     int T, int d, int dff, int H) {
-    const int M = n * T, hd = d / H;
-    gen_gemm_h<0>(st, X, d, W + LH.wqkv, ld_d, W + L.bqkv, BIG, 3 * d, nullptr, M, 3 * d, d);
-    if (T > GENH_TP) {                        // (S2S_MODE_GENERIC_GEOMETRY_F16's decoder beyond 256 samples)
-        const dim3 grid((unsigned)n * H * ((T + 63) / 64));
-        if (hd <= 16)
-            hipLaunchKernelGGL(gen_attention_long_h_kernel<1>, grid, dim3(256), 0, st, BIG, d, H, T);
-        else if (hd <= 128)
-            hipLaunchKernelGGL(gen_attention_long_h_kernel<8>, grid, dim3(256), 0, st, BIG, d, H, T);
-        else
-            hipLaunchKernelGGL(gen_attention_long_h_kernel<32>, grid, dim3(256), 0, st, BIG, d, H, T);
-    } else if (T == GEN_T_DEC) {              // (S2S_MODE_GENERIC_F16's instance: mode 7 at 250 samples computes mode 5's numbers)
-        hipLaunchKernelGGL(gen_attention_h_kernel, dim3(n * H), dim3(1024), 0, st, BIG, d, H);
-    } else {
-        hipLaunchKernelGGL(gen_attention_h_any_kernel, dim3(n * H), dim3(1024), 0, st, BIG, d, H, T);
-    }
-    gen_gemm_h<2>(st, BIG, 3 * d, W + LH.wfc, ld_d, W + L.bfc, X, d, X, M, d, d);
-    hipLaunchKernelGGL(gen_layernorm_kernel, dim3((M + 3) / 4), dim3(256), 0, st, X, W + L.ln1g, W + L.ln1b, (long long)M, d);
-    gen_gemm_h<1>(st, X, d, W + LH.w1, ld_d, W + L.b1, BIG, dff, nullptr, M, dff, d);
-    gen_gemm_h<2>(st, BIG, dff, W + LH.w2, ld_f, W + L.b2, X, d, X, M, d, dff);
-    hipLaunchKernelGGL(gen_layernorm_kernel, dim3((M + 3) / 4), dim3(256), 0, st, X, W + L.ln2g, W + L.ln2b, (long long)M, d);
-}
-
-size_t up64(size_t n) { return (n + 63) & ~(size_t)63; }
-}  // namespace
-
-static int predict_generic(s2s_handle* h, hipStream_t st, const uint8_t* bases, const int64_t* chunk_start, const uint8_t* n_valid,
-                           int64_t first_global_chunk, int32_t B, const ParamsDev& P, const float* inject_g, const float* inject_zdw,
-                           const float* inject_z01, float* out_signal, int32_t* out_dur, const DebugDev& D) {
-    s2s_handle::Generic& G = h->gen;
-    const int d = G.d, dff = G.dff, k = h->cfg.seq_kmer, te = G.te, ts = G.ts, nb = te + k - 1;
-    const size_t big_w = (size_t)(3 * d > dff ? 3 * d : dff), tb = te > ts ? te : ts;
-    const int want = B < G.slice_max ? B : G.slice_max;
-    if (want > G.ws_chunks) {                 // grows outside of the steady state only
-        HIP_TRY(h, hipStreamSynchronize(st));
-        if (G.ws) (void)hipFree(G.ws);
-        G.ws = nullptr; G.ws_chunks = 0;
-        const size_t n = want;
-        const size_t floats = up64(n * te * d) + up64(n * te) + up64(n * ts * d) + up64(n * ts) + up64(n * tb * big_w);
-        HIP_TRY(h, hipMalloc(&G.ws, floats * sizeof(float)));
-        G.ws_chunks = want;
-    }
-    const size_t S = G.ws_chunks;
-    float* XE = G.ws;
-    float* SIG = XE + up64(S * te * d);
-    float* XD = SIG + up64(S * te);
-    float* SE = XD + up64(S * ts * d);
-    float* BIG = SE + up64(S * ts);
-    const float* W = h->d_arena;
-    EventPair ev{};
-    if (h->profiling) {
-        HIP_TRY(h, hipEventCreate(&ev.a));
-        HIP_TRY(h, hipEventCreate(&ev.b));
-        HIP_TRY(h, hipEventRecord(ev.a, st));
-    }
-    for (int64_t s = 0; s < B; s += S) {
-        const int n = (int)((B - s < (int64_t)S) ? (B - s) : (int64_t)S);
-        const int Me = n * te, Md = n * ts;
-        const long long fc = (long long)(first_global_chunk + s);
-        DebugDev Ds = D;                      // the caller's arrays, offset to the slice
-        auto off = [&](float* p, size_t per) { return p ? p + (size_t)s * per : nullptr; };
-        Ds.sigma = off(D.sigma, te); Ds.conc = off(D.conc, te); Ds.rate = off(D.rate, te); Ds.g = off(D.g, te);
-        Ds.y_scaled = off(D.y_scaled, ts); Ds.z01 = off(D.z01, ts);
-        // encoder input: src_emb + pre-net (modules.py:70-77), or the caller's rows (s2s_debug.emb_in)
-        if (D.emb_in) {
-            HIP_TRY(h, hipMemcpyAsync(XE, D.emb_in + (size_t)s * te * d, (size_t)Me * d * sizeof(float), hipMemcpyDeviceToDevice, st));
-        } else {
-            const uint8_t* tb = chunk_start ? bases : bases + (size_t)s * nb;
-            const long long* tcs = reinterpret_cast<const long long*>(chunk_start ? chunk_start + s : nullptr);
-            const long long tot = (long long)Me * d;
-            hipLaunchKernelGGL(gen_embed_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, W + G.emb_wt, W + G.emb_b, k, d, tb, tcs,
-                               n_valid + s, n, te, XE);
-            float* cur = XE;
-            for (int i = 0; i < h->cfg.pre_layers; ++i) {
-                float* nxt = cur == XE ? BIG : XE;
-                gen_gemm<1>(st, cur, d, W + G.pre_w[i], W + G.pre_b[i], nxt, d, nullptr, Me, d, d);
-                cur = nxt;
-            }
-            if (cur != XE) HIP_TRY(h, hipMemcpyAsync(XE, cur, (size_t)Me * d * sizeof(float), hipMemcpyDeviceToDevice, st));
-        }
-        if (D.emb_out)
-            HIP_TRY(h, hipMemcpyAsync(D.emb_out + (size_t)s * te * d, XE, (size_t)Me * d * sizeof(float), hipMemcpyDeviceToDevice, st));
-        // heads (modules.py:182-195, 267-278): the three first layers as one GEMM, then the dwell source; + position_enc
-        gen_gemm<1>(st, XE, d, W + G.w0cat, W + G.b0cat, BIG, 3 * d, nullptr, Me, P.duration_sampling ? 3 * d : d, d);
-        hipLaunchKernelGGL(gen_dwell_kernel, dim3((Me + 3) / 4), dim3(256), 0, st, W, G.heads, G.pe_enc, d, n, BIG, XE, SIG, fc, P,
-                           inject_g ? inject_g + s * te : nullptr, inject_zdw ? inject_zdw + s * te : nullptr, out_dur + s * te, Ds, te);
-        for (int l = 0; l < h->cfg.encoder_layers; ++l) gen_fft_block(st, W, G.enc[l], XE, BIG, n, te, d, dff, G.h_enc);
-        if (D.enc_out)
-            HIP_TRY(h, hipMemcpyAsync(D.enc_out + (size_t)s * te * d, XE, (size_t)Me * d * sizeof(float), hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL(gen_lenreg_kernel, dim3((Md + 3) / 4), dim3(256), 0, st, W, G.pe_dec, d, n, XE, SIG, out_dur + s * te, XD, SE,
-                           D.dec_in ? D.dec_in + (size_t)s * ts * d : nullptr, te, ts);
-        for (int l = 0; l < h->cfg.decoder_layers; ++l) {
-            if (G.f16)
-                gen_fft_block_h(st, W, G.dec[l], G.dech[l], G.ld_d, G.ld_f, XD, BIG, n, ts, d, dff, G.h_dec);
-            else
-                gen_fft_block(st, W, G.dec[l], XD, BIG, n, ts, d, dff, G.h_dec);
-        }
-        hipLaunchKernelGGL(gen_emit_kernel, dim3((Md + 3) / 4), dim3(256), 0, st, W, G.out_w, G.out_b, h->cfg.scaling_max_value, d, n, XD, SE,
-                           fc, P, inject_z01 ? inject_z01 + (size_t)s * ts : nullptr, out_signal + (size_t)s * ts, Ds, ts);
-    }
-    if (h->profiling) {
-        HIP_TRY(h, hipEventRecord(ev.b, st));
-        ev.chunks = B;
-        h->events.push_back(ev);
-    }
-    HIP_TRY(h, hipGetLastError());
-    return S2S_OK;
-}
+// ---- S2S_MODE_GENERIC and its three siblings: the launch side of the size-generic pipeline
+#include "s2s_generic_host.h"
 
 extern "C" {
 
@@ -2185,60 +2036,6 @@ static int predict_impl(s2s_handle* h, void* stream_, const uint8_t* bases, cons
     return S2S_OK;
 }
 
-// s2s_evaluate_chunks on the generic pipeline: predict_generic's stages with the teacher-forced embed / heads / emit kernels
-// (s2s_generic.h); gen_lenreg_kernel reads the measured dwell.  y [B][ts], sigma / conc / rate [B][te] (the caller's slice).
-static int evaluate_generic(s2s_handle* h, hipStream_t st, const uint8_t* kmers, const int32_t* dwell, int32_t B, float* y, float* sigma,
-                            float* conc, float* rate) {
-    s2s_handle::Generic& G = h->gen;
-    const int d = G.d, dff = G.dff, k = h->cfg.seq_kmer, te = G.te, ts = G.ts;
-    const size_t big_w = (size_t)(3 * d > dff ? 3 * d : dff), tb = te > ts ? te : ts;
-    const int want = B < G.slice_max ? B : G.slice_max;
-    if (want > G.ws_chunks) {                 // (as predict_generic)
-        HIP_TRY(h, hipStreamSynchronize(st));
-        if (G.ws) (void)hipFree(G.ws);
-        G.ws = nullptr; G.ws_chunks = 0;
-        const size_t n = want;
-        const size_t floats = up64(n * te * d) + up64(n * te) + up64(n * ts * d) + up64(n * ts) + up64(n * tb * big_w);
-        HIP_TRY(h, hipMalloc(&G.ws, floats * sizeof(float)));
-        G.ws_chunks = want;
-    }
-    const size_t S = G.ws_chunks;
-    float* XE = G.ws;
-    float* XD = XE + up64(S * te * d) + up64(S * te);
-    float* SE = XD + up64(S * ts * d);
-    float* BIG = SE + up64(S * ts);
-    const float* W = h->d_arena;
-    for (int64_t s = 0; s < B; s += S) {
-        const int n = (int)((B - s < (int64_t)S) ? (B - s) : (int64_t)S);
-        const int Me = n * te, Md = n * ts;
-        const long long tot = (long long)Me * d;
-        hipLaunchKernelGGL(gen_embed_kmers_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, W + G.emb_wt, W + G.emb_b, k, d,
-                           kmers + (size_t)s * te * k, n, te, XE);
-        float* cur = XE;
-        for (int i = 0; i < h->cfg.pre_layers; ++i) {
-            float* nxt = cur == XE ? BIG : XE;
-            gen_gemm<1>(st, cur, d, W + G.pre_w[i], W + G.pre_b[i], nxt, d, nullptr, Me, d, d);
-            cur = nxt;
-        }
-        if (cur != XE) HIP_TRY(h, hipMemcpyAsync(XE, cur, (size_t)Me * d * sizeof(float), hipMemcpyDeviceToDevice, st));
-        gen_gemm<1>(st, XE, d, W + G.w0cat, W + G.b0cat, BIG, 3 * d, nullptr, Me, 3 * d, d);
-        float* sg = sigma + (size_t)s * te;
-        hipLaunchKernelGGL(gen_dwell_teacher_kernel, dim3((Me + 3) / 4), dim3(256), 0, st, W, G.heads, G.pe_enc, d, n, BIG, XE, sg,
-                           conc + (size_t)s * te, rate + (size_t)s * te, te);
-        for (int l = 0; l < h->cfg.encoder_layers; ++l) gen_fft_block(st, W, G.enc[l], XE, BIG, n, te, d, dff, G.h_enc);
-        hipLaunchKernelGGL(gen_lenreg_kernel, dim3((Md + 3) / 4), dim3(256), 0, st, W, G.pe_dec, d, n, XE, sg, dwell + (size_t)s * te, XD, SE,
-                           nullptr, te, ts);
-        for (int l = 0; l < h->cfg.decoder_layers; ++l) {
-            if (G.f16)
-                gen_fft_block_h(st, W, G.dec[l], G.dech[l], G.ld_d, G.ld_f, XD, BIG, n, ts, d, dff, G.h_dec);
-            else
-                gen_fft_block(st, W, G.dec[l], XD, BIG, n, ts, d, dff, G.h_dec);
-        }
-        hipLaunchKernelGGL(gen_emit_y_kernel, dim3((Md + 3) / 4), dim3(256), 0, st, W, G.out_w, G.out_b, d, n, XD, y + (size_t)s * ts, ts);
-    }
-    return S2S_OK;
-}
-
 #define S2S_EVAL_SLICE 32768                  // chunks per slice of s2s_evaluate_chunks (its y / sigma / conc / rate scratch)
 
 int s2s_evaluate_chunks(s2s_handle* h, void* stream_, const uint8_t* kmers, const int32_t* dwell, const float* target, const float* stdev,
@@ -2257,13 +2054,7 @@ int s2s_evaluate_chunks(s2s_handle* h, void* stream_, const uint8_t* kmers, cons
     const int te = gen ? h->gen.te : S2S_T_ENC, ts = gen ? h->gen.ts : S2S_T_DEC;
     const int want = B < S2S_EVAL_SLICE ? B : S2S_EVAL_SLICE;
     const size_t per = (size_t)ts + 3 * (size_t)te;
-    if (want > h->ev_chunks) {                // grows outside of the steady state only
-        HIP_TRY(h, hipStreamSynchronize(st));
-        if (h->ev_ws) (void)hipFree(h->ev_ws);
-        h->ev_ws = nullptr; h->ev_chunks = 0;
-        HIP_TRY(h, hipMalloc(&h->ev_ws, (size_t)want * per * sizeof(float)));
-        h->ev_chunks = want;
-    }
+    HIP_TRY(h, grow_device(h->ev_ws, h->ev_chunks, want, (size_t)want * per * sizeof(float), st));
     const size_t S = h->ev_chunks;
     ParamsDev P;
     std::memset(&P, 0, sizeof P);

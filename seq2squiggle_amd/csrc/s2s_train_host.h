@@ -1,6 +1,6 @@
 // s2s_train_host.h -- host side of the trainer (s2s_trainer_*, include/s2s_hip.h), included at the end of s2s_hip.hip: the tape,
-// the launch order of the forward (s2s_generic.h's kernels, as evaluate_generic launches them) and backward (s2s_train.h) passes,
-// micro-batching and the optimizer step.
+// the launch order of the forward (evaluate_generic's stages through the launchers it uses, s2s_generic_host.h) and backward
+// (s2s_train.h) passes, micro-batching and the optimizer step.
 //
 // Weights, gradient, m and v live in the generic handle's arena layout (pack_generic: every piece 16-byte aligned for the GEMM's
 // float4 loads, src_emb.weight transposed, q/k/v and the heads' first layers concatenated), not in the blob's: the blob's own
@@ -42,8 +42,8 @@ int tfail(s2s_trainer* t, int code, const std::string& msg) {
             return tfail((t), S2S_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));  \
     } while (0)
 
-// the tape of one FFT block over M rows
-struct TrainBlock { float *qkv, *qc, *p1, *y1, *hf, *p2, *y2; };
+// the tape of one FFT block over M rows: every stage of gen_block_fwd in a buffer of its own
+using TrainBlock = GenBlock;
 
 // Every buffer of a micro-batch of n chunks, carved from one allocation (base == nullptr: sizes only).
 struct TrainTape {
@@ -89,14 +89,6 @@ struct TrainRun {
     const float* W;
     TrainTape T;
 
-    template <int EPI>
-    void gemm(const float* A, int lda, long long w, long long bias, float* C, int ldc, const float* R, int ldr, int M, int N, int K) {
-        const dim3 grid((M + GEN_BM - 1) / GEN_BM, (N + GEN_BN - 1) / GEN_BN);
-        hipLaunchKernelGGL(gen_gemm_kernel<EPI>, grid, dim3(256), 0, st, A, lda, W + w, K, W + bias, C, ldc, R, ldr, M, N, K);
-    }
-    void copy(const float* src, int lds, float* dst, int ldd, long long M, int n) {
-        hipLaunchKernelGGL(train_copy_kernel, dim3((unsigned)((M * n + 255) / 256)), dim3(256), 0, st, src, lds, dst, ldd, M, n);
-    }
     // grad[off .. off + I J) += sum_rows L[row][i] R[row][j]
     void wgrad(const float* L, int ldl, const float* R, int ldr, int I, int J, int M, long long off) {
         const int nz = (M + TR_GRAD_ROWS - 1) / TR_GRAD_ROWS;
@@ -118,37 +110,6 @@ struct TrainRun {
         const dim3 grid((M + TR_TILE - 1) / TR_TILE, (K + TR_TILE - 1) / TR_TILE, 1);
         hipLaunchKernelGGL((train_mm_kernel<true, EPI>), grid, dim3(256), 0, st, dY, N, W + w, K, C, K, E, K, M, K, N, N);
     }
-    void layernorm(float* X, long long g, long long b, int M, int d) {
-        hipLaunchKernelGGL(gen_layernorm_kernel, dim3((M + 3) / 4), dim3(256), 0, st, X, W + g, W + b, (long long)M, d);
-    }
-
-    // gen_fft_block with every stage in a buffer of its own
-    void block_fwd(const GenLayer& L, const float* X, const TrainBlock& B, int n, int Tn, int H) {
-        const int d = t->G.d, dff = t->G.dff, M = n * Tn, hd = d / H;
-        gemm<0>(X, d, L.wqkv, L.bqkv, B.qkv, 3 * d, nullptr, 0, M, 3 * d, d);
-        copy(B.qkv, 3 * d, B.qc, d, M, d);
-        const size_t stage = gen_attn_lds_bytes(Tn, hd, true);
-        if (Tn > 256) {
-            const dim3 grid((unsigned)n * H * ((Tn + 63) / 64));
-            if (hd <= 16)
-                hipLaunchKernelGGL(gen_attention_long_kernel<1>, grid, dim3(256), 0, st, B.qkv, d, H, Tn);
-            else if (hd <= 128)
-                hipLaunchKernelGGL(gen_attention_long_kernel<8>, grid, dim3(256), 0, st, B.qkv, d, H, Tn);
-            else
-                hipLaunchKernelGGL(gen_attention_long_kernel<32>, grid, dim3(256), 0, st, B.qkv, d, H, Tn);
-        } else if (stage <= GEN_ATTN_STAGE_BYTES)
-            hipLaunchKernelGGL(gen_attention_kernel<true>, dim3(n * H), dim3(256), stage, st, B.qkv, d, H, Tn);
-        else
-            hipLaunchKernelGGL(gen_attention_kernel<false>, dim3(n * H), dim3(256), gen_attn_lds_bytes(Tn, hd, false), st, B.qkv, d, H, Tn);
-        gemm<2>(B.qkv, 3 * d, L.wfc, L.bfc, B.p1, d, X, d, M, d, d);
-        copy(B.p1, d, B.y1, d, M, d);
-        layernorm(B.y1, L.ln1g, L.ln1b, M, d);
-        gemm<1>(B.y1, d, L.w1, L.b1, B.hf, dff, nullptr, 0, M, dff, d);
-        gemm<2>(B.hf, dff, L.w2, L.b2, B.p2, d, B.y1, d, M, d, dff);
-        copy(B.p2, d, B.y2, d, M, d);
-        layernorm(B.y2, L.ln2g, L.ln2b, M, d);
-    }
-
     // dio: in the gradient at the block's output, out the gradient at its input X
     void block_bwd(const GenLayer& L, const float* X, const TrainBlock& B, float* dio, int n, int Tn, int H) {
         const int d = t->G.d, dff = t->G.dff, M = n * Tn;
@@ -183,21 +144,17 @@ struct TrainRun {
         const long long tot = (long long)Me * d;
         hipLaunchKernelGGL(gen_embed_kmers_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, W + G.emb_wt, W + G.emb_b, k, d, kmers,
                            n, te, T.e0);
-        const float* emb = T.e0;
-        for (int i = 0; i < c.pre_layers; ++i) {
-            gemm<1>(emb, d, G.pre_w[i], G.pre_b[i], T.pre[i], d, nullptr, 0, Me, d, d);
-            emb = T.pre[i];
-        }
-        gemm<1>(emb, d, G.w0cat, G.b0cat, T.hid, 3 * d, nullptr, 0, Me, 3 * d, d);
-        copy(emb, d, T.xe0, d, Me, d);
+        const float* emb = gen_prenet(st, W, G, c.pre_layers, T.e0, T.pre, Me);
+        gen_gemm<1>(st, emb, d, W + G.w0cat, W + G.b0cat, T.hid, 3 * d, nullptr, Me, 3 * d, d);
+        gen_copy(st, emb, d, T.xe0, d, Me, d);
         hipLaunchKernelGGL(gen_dwell_teacher_kernel, dim3((Me + 3) / 4), dim3(256), 0, st, W, G.heads, G.pe_enc, d, n, T.hid, T.xe0, T.sig, T.conc,
                            T.rate, te);
         const float* x = T.xe0;
-        for (int l = 0; l < c.encoder_layers; ++l) { block_fwd(G.enc[l], x, T.enc[l], n, te, G.h_enc); x = T.enc[l].y2; }
+        for (int l = 0; l < c.encoder_layers; ++l) { gen_block_fwd(st, W, G, G.enc[l], nullptr, x, T.enc[l], n, te, G.h_enc); x = T.enc[l].y2; }
         hipLaunchKernelGGL(gen_lenreg_kernel, dim3((Md + 3) / 4), dim3(256), 0, st, W, G.pe_dec, d, n, x, T.sig, dwell, T.xd0, T.se,
                            (const float*)nullptr, te, ts);
         x = T.xd0;
-        for (int l = 0; l < c.decoder_layers; ++l) { block_fwd(G.dec[l], x, T.dec[l], n, ts, G.h_dec); x = T.dec[l].y2; }
+        for (int l = 0; l < c.decoder_layers; ++l) { gen_block_fwd(st, W, G, G.dec[l], nullptr, x, T.dec[l], n, ts, G.h_dec); x = T.dec[l].y2; }
         hipLaunchKernelGGL(gen_emit_y_kernel, dim3((Md + 3) / 4), dim3(256), 0, st, W, G.out_w, G.out_b, d, n, x, T.y, ts);
         hipLaunchKernelGGL(s2s_eval_loss_kernel, dim3((n + 3) / 4), dim3(256), 0, st, T.y, target, T.sig, stdev, T.conc, T.rate, dwell, n, te, ts,
                            loss);
@@ -211,7 +168,7 @@ struct TrainRun {
         for (int l = c.decoder_layers - 1; l >= 0; --l) block_bwd(G.dec[l], l ? T.dec[l - 1].y2 : T.xd0, T.dec[l], T.da, n, ts, G.h_dec);
         // (T.db is free between blocks: the regulator's sum lands there, then moves to T.da, the blocks' in / out buffer)
         hipLaunchKernelGGL(train_lenreg_bwd_kernel, dim3((Me + 3) / 4), dim3(256), 0, st, T.da, dwell, T.db, (long long)Me, d, te, ts);
-        copy(T.db, d, T.da, d, Me, d);
+        gen_copy(st, T.db, d, T.da, d, Me, d);
         for (int l = c.encoder_layers - 1; l >= 0; --l) block_bwd(G.enc[l], l ? T.enc[l - 1].y2 : T.xe0, T.enc[l], T.da, n, te, G.h_enc);
         float* de = T.da;
         float* other = T.db;
@@ -259,20 +216,8 @@ int train_gradients(s2s_trainer* t, hipStream_t st, const uint8_t* kmers, const 
                     int32_t B) {
     const s2s_config& c = t->cfg;
     const size_t cap = train_micro_batch(t, B);
-    if ((int)cap > t->ws_chunks) {
-        TR_TRY(t, hipStreamSynchronize(st));
-        if (t->ws) (void)hipFree(t->ws);
-        t->ws = nullptr; t->ws_chunks = 0;
-        TR_TRY(t, hipMalloc(&t->ws, train_tape(c, nullptr, cap).floats * sizeof(float)));
-        t->ws_chunks = (int)cap;
-    }
-    if (B > t->losses_cap) {
-        TR_TRY(t, hipStreamSynchronize(st));
-        if (t->losses) (void)hipFree(t->losses);
-        t->losses = nullptr; t->losses_cap = 0;
-        TR_TRY(t, hipMalloc(&t->losses, (size_t)B * 3 * sizeof(float)));
-        t->losses_cap = B;
-    }
+    TR_TRY(t, grow_device(t->ws, t->ws_chunks, (int)cap, train_tape(c, nullptr, cap).floats * sizeof(float), st));
+    TR_TRY(t, grow_device(t->losses, t->losses_cap, B, (size_t)B * 3 * sizeof(float), st));
     TrainRun R{t, st, t->w, train_tape(c, t->ws, cap)};
     TR_TRY(t, hipMemsetAsync(t->g, 0, t->arena_floats * sizeof(float), st));
     const int te = c.max_dna_len, ts = c.max_signal_len, k = c.seq_kmer;

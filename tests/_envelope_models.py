@@ -2,8 +2,8 @@
 
 The cases use the seeded recipe of tests/_geometry_models.py (its functions take this module's CASES).  classes_of(cfg) restates, in
 plain Python, which kernel instance and which remainder class of seq2squiggle_amd/csrc/s2s_generic.h, s2s_generic_h.h and
-gen_fft_block / gen_fft_block_h (s2s_hip.hip) a configuration runs: the encoder's attention at T = max_dna_len with the encoder's
-head_dim, the decoder's at T = max_signal_len with its own; the f16 kernels on the decoder only (the f16 modes keep the encoder
+gen_block_fwd / gen_attention_fwd (s2s_generic_host.h) a configuration runs: the encoder's attention at T = max_dna_len with the
+encoder's head_dim, the decoder's at T = max_signal_len with its own; the f16 kernels on the decoder only (the f16 modes keep the encoder
 side in fp32).  tests/test_envelope_cpu.py asserts that the union over CASES is LABELS, so a class the kernels distinguish cannot
 lose its case unnoticed.  tools/make_envelope_goldens.py records tests/golden/envelope_<tag>.npz from the imported reference."""
 import _geometry_models as GM
@@ -67,7 +67,7 @@ def checkpoint_path(tag):
 
 
 def _attention_fp32(T, hd):
-    """gen_fft_block's attention launch at T keys and head_dim hd."""
+    """gen_attention_fwd's fp32 launch at T keys and head_dim hd."""
     out = set()
     if T > 256:
         nt = 1 if hd <= 16 else 8 if hd <= 128 else 32
@@ -103,7 +103,7 @@ def _attention_fp32(T, hd):
 
 
 def _attention_f16(T, hd):
-    """gen_fft_block_h's attention launch (the decoder of the f16 modes)."""
+    """gen_attention_fwd's f16 launch (the decoder of the f16 modes)."""
     out = set()
     if T > 256:
         nt = 1 if hd <= 16 else 8 if hd <= 128 else 32

@@ -1,7 +1,8 @@
 """Which remainder classes of the backward pass and the optimizer step a trainer call reaches, and the calls the GPU tests make.
 
 train_classes_of(cfg, micro_batches) restates, in plain Python, the case distinctions of seq2squiggle_amd/csrc/s2s_train.h and
-s2s_train_host.h for a call on a checkpoint of config `cfg` whose batch runs as micro-batches of the given sizes, as
+s2s_train_host.h (the forward launches: s2s_generic_host.h) for a call on a checkpoint of config `cfg` whose batch runs as
+micro-batches of the given sizes, as
 tests/_envelope_models.py's classes_of does for the forward kernels:
   train_attention_bwd_kernel, per side (the encoder at T = max_dna_len with its head_dim, the decoder at max_signal_len with its
     own): hp = the power of two >= min(head_dim, 64) that deals lanes to feature slots, ng = 64 / hp row groups per wave; a

@@ -197,7 +197,7 @@ def test_batch_shapes(tag, mode, path):
 
 
 def generic_slice_max(cfg) -> int:
-    """G.slice_max (s2s_hip.hip), as tests/test_gpu_envelope.py restates it."""
+    """G.slice_max (pack_generic, s2s_hip.hip), as tests/test_gpu_envelope.py restates it."""
     te, ts, d, f = (cfg[n] for n in ("max_dna_len", "max_signal_len", "dmodel", "dff"))
     n = (512 << 20) // (4 * (te * d + te + ts * d + ts + max(te, ts) * max(3 * d, f)))
     return max(1, min(n, (2 ** 32 - 1) // (max(cfg["encoder_heads"], cfg["decoder_heads"]) * max(1024, 256 * -(-ts // 64)))))
@@ -243,7 +243,8 @@ def test_slices(tag, mode):
 
 @pytest.mark.parametrize("mode", ["generic", "generic-f16"])
 def test_generic_inner_slice(mode):
-    """slice_max + 13 chunks: evaluate_generic's own slice loop entered twice (its offsets into the caller's y / sigma / conc / rate)."""
+    """slice_max + 13 chunks: evaluate_generic's own slice loop (s2s_generic_host.h) entered twice (its offsets into the caller's y /
+    sigma / conc / rate)."""
     r = reference("k9")
     g = r["g"]
     eng = make_engine("k9", mode)

@@ -1137,6 +1137,30 @@ double s2s_attention_redo_threshold(void);
 int s2s_set_attention_path(s2s_handle* h, int32_t path);
 int s2s_get_attention_path(const s2s_handle* h, int32_t* path, double* calibration_redo_rate);
 
+/* How a launch of the predict kernel (S2S_MODE_F32 / _F16X3 / _F16) is dealt out to its persistent workgroups, one per compute
+ * unit:
+ *   S2S_SCHEDULE_STATIC   workgroup b of G walks the chunks [b n / G, (b + 1) n / G) in groups (16 chunks in the split-f16 modes, 8
+ *                         in f32): the launch lasts as long as its slowest workgroup;
+ *   S2S_SCHEDULE_DYNAMIC  the workgroups take CLAIMS from one counter of the handle, one atomic per group, a group ahead of their
+ *                         need: whole groups first, then the last G x group chunks in shrinking claims (G of group / 2, ... G of
+ *                         2, then singles), so that the last thing any workgroup starts is one chunk.  s2s_schedule_claim is that
+ *                         list: claim c of a launch of n chunks -> [*start, *start + *count), count 0 past the end;
+ *   S2S_SCHEDULE_AUTO     (default) dynamic for a launch of at least S2S_SCHEDULE_AUTO_GROUPS groups per workgroup
+ *                         (s2s_schedule_is_dynamic(n, n_wg, group) != 0), static below, where the taper's extra frontend phases
+ *                         cost more than the tail they remove.
+ * A chunk's output depends on its global index and the seed alone: the schedules give the same bytes.  The environment variable
+ * S2S_SCHEDULE = auto | static | dynamic (any case) sets the handle's schedule at s2s_create; anything else makes s2s_create fail.
+ * RULE: the launches of ONE handle must be stream-ordered -- issued on one stream, or on streams ordered by events.  The
+ * hand-off slots of the workgroups always relied on that; the claim counter does too (a launch leaves it at zero for the next:
+ * its last workgroup to run dry resets it, no host operation per launch).  Two handles share nothing. */
+#define S2S_SCHEDULE_AUTO 0
+#define S2S_SCHEDULE_STATIC 1
+#define S2S_SCHEDULE_DYNAMIC 2
+int s2s_set_schedule(s2s_handle* h, int32_t schedule);
+int s2s_get_schedule(const s2s_handle* h, int32_t* schedule);
+void s2s_schedule_claim(int64_t n, int32_t n_wg, int32_t group, int64_t c, int64_t* start, int32_t* count);
+int32_t s2s_schedule_is_dynamic(int64_t n, int32_t n_wg, int32_t group);
+
 /* Counters of the predict kernel since the last call (every build; synchronises the device, then resets them).  The fast
  * softmax of the split-f16 decoder is data dependent -- a head whose later keys beat the maximum over its pass-0 key sample (the
  * key blocks b = 0 mod 4, see s2s_set_attention_path) by more than the f16 range is redone on a safe path -- and the chip's clock
@@ -1146,8 +1170,11 @@ int s2s_get_attention_path(const s2s_handle* h, int32_t* path, double* calibrati
  *   [2] ... of them redone on the safe path (0 in S2S_MODE_F32, which has no fast path),
  *   [3] shader-clock cycles (s_memtime) and [4] 100 MHz ticks (s_memrealtime) of one thread per workgroup over the whole
  *       kernel, summed over [5] workgroups: [3] / [4] / 10 is the clock in GHz the SIMDs really ran at,
- *   [6] chunks launched on the exact attention path (s2s_set_attention_path), [7..9] reserved (0).
- * A generic handle counts [0] and [1] (with its decoder head count), and has no redo, clock or exact-path counts ([2..6] 0). */
+ *   [6] chunks launched on the exact attention path (s2s_set_attention_path),
+ *   [7] the longest and [8] the shortest of those workgroup spans in 100 MHz ticks ([4] / [5] is their mean; a launch lasts as
+ *       long as the longest; 0 when nothing ran), [9] chunks launched on the dynamic schedule (s2s_set_schedule).
+ * A generic handle counts [0] and [1] (with its decoder head count), and has no redo, clock, span, exact-path or schedule counts
+ * ([2..9] 0). */
 int s2s_stats_read(s2s_handle* h, uint64_t* out10);
 
 /* Diagnostic builds (-DS2S_DIAG, never the shipped library): per wave of a workgroup (8 rows) 48 per-phase shader-cycle sums

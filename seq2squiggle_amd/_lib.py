@@ -32,6 +32,7 @@ class S2SAdam(C.Structure):
 
 EXPORTS = ("s2s_blob_floats", "s2s_create", "s2s_destroy", "s2s_last_error", "s2s_predict_chunks", "s2s_predict_packed",
            "s2s_export_reads", "s2s_svb_encode", "s2s_philox_u32", "s2s_set_profiling", "s2s_get_kernel_ms", "s2s_stats_read", "s2s_set_attention_path", "s2s_get_attention_path", "s2s_diag_read",
+           "s2s_set_schedule", "s2s_get_schedule", "s2s_schedule_claim", "s2s_schedule_is_dynamic",
            "s2s_blow5_pack_bound", "s2s_blow5_pack", "s2s_compress_rows", "s2s_sampler_replay", "s2s_sampler_replay_law", "s2s_length_law",
            "s2s_fasta_count", "s2s_fasta_clean", "s2s_fastq_clean", "s2s_copy_ranges", "s2s_blow5_scan", "s2s_blow5_scan_upto", "s2s_attention_redo_threshold", "s2s_evaluate_chunks",
            "s2s_align_chunks", "s2s_paf_format", "s2s_paf_format_bound", "s2s_event_stats", "s2s_events_format", "s2s_events_format_bound",
@@ -92,6 +93,10 @@ def lib():
     bind("s2s_set_attention_path", i32, [vp, i32])
     bind("s2s_get_attention_path", i32, [vp, C.POINTER(i32), C.POINTER(C.c_double)])
     bind("s2s_diag_read", i32, [vp, C.POINTER(C.c_uint64)])
+    bind("s2s_set_schedule", i32, [vp, i32])
+    bind("s2s_get_schedule", i32, [vp, C.POINTER(i32)])
+    bind("s2s_schedule_claim", None, [i64, i32, i32, i64, C.POINTER(i64), C.POINTER(i32)])
+    bind("s2s_schedule_is_dynamic", i32, [i64, i32, i32])
     bind("s2s_blow5_pack_bound", i64, [i64, i32])
     bind("s2s_blow5_pack", i64, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i64])
     bind("s2s_compress_rows", i64, [vp, vp, i32, i32, i32, i32, vp, i64, vp])

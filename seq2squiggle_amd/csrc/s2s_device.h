@@ -91,11 +91,20 @@ __shared__ unsigned long long s2s_diag_lds[8 * S2S_DIAG_SLOTS];
 #define S2S_STAT_CYCLES 1        // shader-clock cycles (s_memtime) of thread 0, summed over the workgroups
 #define S2S_STAT_TICKS 2         // 100 MHz ticks (s_memrealtime) over the same spans
 #define S2S_STAT_WGS 3           // workgroups summed
+#define S2S_STAT_SPAN_MAX 4      // the longest of those spans in ticks (atomicMax)
+#define S2S_STAT_SPAN_MIN_INV 5  // ~(the shortest): an atomicMax too, so that a slab reset to zeros means "none yet"
+#define S2S_STAT_SCHED 16        // behind the counters, on a 128-byte line of its own: the claim counter and the done counter of
+                                 // the dynamic schedule, two 32-bit words (s2s_schedule.h); zeroed by s2s_create only
 // (256 bytes, not 48: the kernel's dynamic LDS follows this array, and every bank-slot placement in s2s_device_h.h -- V^T row r on
 //  16-byte slot r mod 16, the zeros rows beside them -- assumes that its base is a multiple of 256 bytes, i.e. of the 64 banks;
 //  with a 48-byte array in front SQ_LDS_BANK_CONFLICT went from 4.3 k back to 8.4 k cycles per chunk (profiles/r04/lds_conflicts.txt;
 //  the wall clock was the same: 188.6 k shader cycles at 2.195 GHz against 190.9 k at 2.215 GHz -- the chip is power-limited))
-__shared__ __attribute__((aligned(256))) unsigned s2s_stats_lds[64];      // [0] redo, [4..7] entry stamps
+__shared__ __attribute__((aligned(256))) unsigned s2s_stats_lds[64];      // [0] redo, [4..7] entry stamps, [8..13] the schedule
+#define S2S_LDS_G0 8             // the workgroup's next group: first chunk,
+#define S2S_LDS_N 9              // ... chunks (0: none left)
+#define S2S_LDS_END 10           // static split: the end of the workgroup's range; claims: the launch's chunk count
+#define S2S_LDS_SCHED 11         // [11..12] the claim counter's address (0: static split)
+#define S2S_LDS_GRID 13          // workgroups of the launch
 
 #ifdef S2S_TILEHIST
 // diagnostic build: histogram of the largest shifted score (log2 units below the row's pass-0 maximum) per attention tile,

@@ -10,6 +10,7 @@
 // plus s2s_export_* for the per-read zero-strip / int16 conversion and s2s_svb_* for the containers' signal codecs.
 #include "s2s_device.h"
 #include "s2s_device_h.h"
+#include "s2s_schedule.h"
 #include "s2s_generic.h"
 #include "s2s_generic_h.h"
 #include "s2s_train.h"
@@ -503,7 +504,8 @@ __global__ __launch_bounds__(DEC_WAVES * 64, DEC_WPS) void s2s_fused_kernel(
     const ModelDev M, const float* __restrict__ W, const uint8_t* __restrict__ bases,
     const long long* __restrict__ chunk_start, const uint8_t* __restrict__ n_valid, int n_chunks, long long first_chunk,
     ParamsDev P, const float* __restrict__ inj_g_, const float* __restrict__ inj_zdw_, const float* __restrict__ inj_z01_,
-    float* __restrict__ handoff, int* __restrict__ out_dur, float* __restrict__ out_signal, DebugDev dbg_, long long dbg_base) {
+    float* __restrict__ handoff, int* __restrict__ out_dur, float* __restrict__ out_signal, DebugDev dbg_, long long dbg_base,
+    unsigned* __restrict__ sched) {
     using F = Fused<MODE>;
     const float* const inj_g = TEST ? inj_g_ : nullptr;
     const float* const inj_zdw = TEST ? inj_zdw_ : nullptr;
@@ -534,14 +536,51 @@ __global__ __launch_bounds__(DEC_WAVES * 64, DEC_WPS) void s2s_fused_kernel(
     __syncthreads();
 #endif
     float* const slot0 = handoff + (size_t)blockIdx.x * S2S_MAX_GROUP * S2S_SLOT_FLOATS;
-    const int lo = (int)((long long)blockIdx.x * n_chunks / gridDim.x), hi = (int)((long long)(blockIdx.x + 1) * n_chunks / gridDim.x);
+    // The workgroup's next group of chunks waits in LDS (S2S_LDS_G0 / _N), put there by thread 0 one group ahead and read by every
+    // wave behind the barrier that opens the group loop.  sched == nullptr, the static split: workgroup b walks [b n / G,
+    // (b + 1) n / G) in groups.  Else claims (s2s_schedule.h) from the handle's counter sched[0], one returning atomic per group.
+    // A workgroup's one empty claim counts it into sched[1], which wraps at G by itself; the last one in puts the counter back
+    // to 0 for the handle's next launch (launches of a handle are stream-ordered: include/s2s_hip.h).
+    // (what thread 0 needs for that -- the counter's address, the grid, the end of the range -- waits in LDS too, S2S_LDS_SCHED / _GRID / _END: not
+    //  one register stays live across the group loop for the schedule)
+    auto put_group = [&](const int start, const int count) {
+        s2s_stats_lds[S2S_LDS_G0] = (unsigned)start; s2s_stats_lds[S2S_LDS_N] = (unsigned)count;
+    };
+    auto sched_of = [&]() {
+        return reinterpret_cast<unsigned*>(((unsigned long long)s2s_stats_lds[S2S_LDS_SCHED + 1] << 32) | s2s_stats_lds[S2S_LDS_SCHED]);
+    };
+    auto put_claim = [&](unsigned* const q, const unsigned c) {
+        int start, count;
+        const unsigned G = s2s_stats_lds[S2S_LDS_GRID];
+        s2s_claim_range((int)s2s_stats_lds[S2S_LDS_END], (int)G, F::GROUP, (int)c, &start, &count);
+        put_group(start, count);
+        if (count == 0) {
+            __threadfence();
+            if (atomicInc(q + 1, G - 1) == G - 1) atomicExch(q, 0u);
+        }
+    };
+    if (threadIdx.x == 0) {
+        s2s_stats_lds[S2S_LDS_SCHED] = (unsigned)(unsigned long long)sched;
+        s2s_stats_lds[S2S_LDS_SCHED + 1] = (unsigned)((unsigned long long)sched >> 32);
+        s2s_stats_lds[S2S_LDS_GRID] = gridDim.x;
+        if (sched) {
+            s2s_stats_lds[S2S_LDS_END] = (unsigned)n_chunks;
+            put_claim(sched, atomicAdd(sched, 1u));
+        } else {
+            const int lo = (int)((long long)blockIdx.x * n_chunks / gridDim.x), hi = (int)((long long)(blockIdx.x + 1) * n_chunks / gridDim.x);
+            s2s_stats_lds[S2S_LDS_END] = (unsigned)hi;
+            put_group(lo, hi - lo < F::GROUP ? hi - lo : F::GROUP);
+        }
+    }
 #pragma unroll 1
-    for (int g0 = lo; g0 < hi; g0 += F::GROUP) {
-        const int n_here = hi - g0 < F::GROUP ? hi - g0 : F::GROUP;
+    for (;;) {
         float one = 1.0f;                  // opaque to the optimiser: see split2 in s2s_device_h.h
         asm volatile("" : "+s"(one));
         DIAG_DECL;
         __syncthreads();                   // the previous group's last block is done with the K/V region and with the slots
+        const int g0 = __builtin_amdgcn_readfirstlane((int)s2s_stats_lds[S2S_LDS_G0]);
+        const int n_here = __builtin_amdgcn_readfirstlane((int)s2s_stats_lds[S2S_LDS_N]);
+        if (n_here <= 0) break;
         {
             int lnf = lane;                // (opaque per group, like `ln` below: nothing lane-dependent is hoisted out of the loops and spilled)
             asm volatile("" : "+v"(lnf));
@@ -568,6 +607,15 @@ __global__ __launch_bounds__(DEC_WAVES * 64, DEC_WPS) void s2s_fused_kernel(
         }
         __syncthreads();                   // the group's slots are written (global stores: workgroup-scope release/acquire)
         DIAG_STAMP(7);                     // frontend phase and its two barriers
+        // the next group: every wave has read this one's (g0, n_here) before the barrier above
+        if (threadIdx.x == 0) {
+            if (unsigned* const q = sched_of()) {
+                put_claim(q, atomicAdd(q, 1u));
+            } else {
+                const int hi = (int)s2s_stats_lds[S2S_LDS_END], nx = g0 + F::GROUP;
+                put_group(nx, nx >= hi ? 0 : hi - nx < F::GROUP ? hi - nx : F::GROUP);
+            }
+        }
         f32x4 X[DEC_NQ][4];
         float sig_ext[DEC_NQ];
         {
@@ -628,8 +676,11 @@ __global__ __launch_bounds__(DEC_WAVES * 64, DEC_WPS) void s2s_fused_kernel(
         const unsigned long long r0 = ((unsigned long long)s2s_stats_lds[7] << 32) | s2s_stats_lds[6];
         if (s2s_stats_lds[0]) atomicAdd(dbg.stats + S2S_STAT_REDO, (unsigned long long)s2s_stats_lds[0]);
         atomicAdd(dbg.stats + S2S_STAT_CYCLES, __builtin_readcyclecounter() - c0);
-        atomicAdd(dbg.stats + S2S_STAT_TICKS, __builtin_amdgcn_s_memrealtime() - r0);
+        const unsigned long long span = __builtin_amdgcn_s_memrealtime() - r0;
+        atomicAdd(dbg.stats + S2S_STAT_TICKS, span);
         atomicAdd(dbg.stats + S2S_STAT_WGS, 1ull);
+        atomicMax(dbg.stats + S2S_STAT_SPAN_MAX, span);
+        atomicMax(dbg.stats + S2S_STAT_SPAN_MIN_INV, ~span);          // (the slab is reset to zeros: the minimum rides as its complement)
     }
 }
 
@@ -1312,6 +1363,8 @@ struct s2s_handle {
     long long stat_chunks = 0;              // chunks launched since the last s2s_stats_read
     int attn_exact = 0;                     // decoder attention path of the split-f16 modes (s2s_set_attention_path)
     long long stat_exact_chunks = 0;        // ... chunks launched on the exact path since the last s2s_stats_read
+    int schedule = S2S_SCHEDULE_AUTO;       // how a launch is dealt out to the workgroups (s2s_set_schedule)
+    long long stat_dynamic_chunks = 0;      // ... chunks launched on the dynamic schedule since the last s2s_stats_read
     double calib_redo_rate = -1.0;          // share of the calibration launch's softmax runs that overflowed the fast path (-1: not calibrated)
     std::vector<EventPair> events;
     std::string err;
@@ -1922,6 +1975,19 @@ int s2s_create(const s2s_config* cfg, const void* blob, size_t blob_bytes, int d
     if ((e = hipMalloc(&h->d_diag, 8 * 48 * sizeof(unsigned long long))) != hipSuccess) return bail(e, "hipMalloc(diag)");
     if ((e = hipMemset(h->d_diag, 0, 8 * 48 * sizeof(unsigned long long))) != hipSuccess) return bail(e, "hipMemset(diag)");
 #endif
+    {   // S2S_SCHEDULE = auto | static | dynamic (any case; unset or empty: auto); anything else is refused
+        std::string sch;
+        if (const char* env = getenv("S2S_SCHEDULE"))
+            for (const char* c = env; *c; ++c) sch += (char)std::tolower((unsigned char)*c);
+        if (sch.empty() || sch == "auto") h->schedule = S2S_SCHEDULE_AUTO;
+        else if (sch == "static") h->schedule = S2S_SCHEDULE_STATIC;
+        else if (sch == "dynamic") h->schedule = S2S_SCHEDULE_DYNAMIC;
+        else {
+            g_create_error = "S2S_SCHEDULE must be auto, static or dynamic (got \"" + sch + "\")";
+            s2s_destroy(h);
+            return S2S_ERR_ARG;
+        }
+    }
     // S2S_ATTENTION_PATH = fast | exact (any case): that path, no calibration launch; unset, empty or "auto": calibrate;
     // anything else is refused (a typo must not pin the fast path silently)
     std::string want;
@@ -1955,6 +2021,30 @@ int s2s_get_attention_path(const s2s_handle* h, int32_t* path, double* calibrati
     if (calibration_redo_rate) *calibration_redo_rate = h->calib_redo_rate;
     return S2S_OK;
 }
+
+int s2s_set_schedule(s2s_handle* h, int32_t schedule) {
+    if (!h) return S2S_ERR_ARG;
+    if (schedule != S2S_SCHEDULE_AUTO && schedule != S2S_SCHEDULE_STATIC && schedule != S2S_SCHEDULE_DYNAMIC)
+        return fail(h, S2S_ERR_ARG, "schedule must be 0 (auto), 1 (static) or 2 (dynamic)");
+    h->schedule = schedule;
+    return S2S_OK;
+}
+
+int s2s_get_schedule(const s2s_handle* h, int32_t* schedule) {
+    if (!h || !schedule) return S2S_ERR_ARG;
+    *schedule = h->schedule;
+    return S2S_OK;
+}
+
+void s2s_schedule_claim(int64_t n, int32_t n_wg, int32_t group, int64_t c, int64_t* start, int32_t* count) {
+    int s = 0, k = 0;               // (a launch is at most 2^20 chunks; out of range: an empty claim)
+    if (n >= 0 && n <= (1 << 30) && n_wg > 0 && group > 0 && (int64_t)n_wg * group <= (1 << 30) && c >= 0 && c < (1ll << 31))
+        s2s_claim_range((int)n, n_wg, group, (int)c, &s, &k);
+    if (start) *start = s;
+    if (count) *count = k;
+}
+
+int32_t s2s_schedule_is_dynamic(int64_t n, int32_t n_wg, int32_t group) { return s2s_auto_takes_claims(n, n_wg, group) ? 1 : 0; }
 
 void s2s_destroy(s2s_handle* h) {
     if (!h) return;
@@ -2024,8 +2114,13 @@ static int predict_impl(s2s_handle* h, void* stream_, const uint8_t* bases, cons
                    : test  ? (mode == S2S_MODE_F16 ? s2s_fused_kernel<3, true> : mode == S2S_MODE_F16X3 ? s2s_fused_kernel<1, true> : s2s_fused_kernel<0, true>)
                            : (mode == S2S_MODE_F16 ? s2s_fused_kernel<3, false> : mode == S2S_MODE_F16X3 ? s2s_fused_kernel<1, false> : s2s_fused_kernel<0, false>);
         if (exact) h->stat_exact_chunks += n;
+        // claims from the handle's counter, or the static split (s2s_schedule.h; `auto` decides per launch, on the full grid)
+        const bool dynamic = h->schedule == S2S_SCHEDULE_DYNAMIC ||
+                             (h->schedule == S2S_SCHEDULE_AUTO && s2s_auto_takes_claims(n, h->n_wg, mode == S2S_MODE_F32 ? Fused<0>::GROUP : Fused<1>::GROUP));
+        if (dynamic) h->stat_dynamic_chunks += n;
+        unsigned* const sched = dynamic ? reinterpret_cast<unsigned*>(h->d_stats + S2S_STAT_SCHED) : nullptr;
         hipLaunchKernelGGL(fused, grid, block, mode == S2S_MODE_F16 ? Fused<3>::LDS : mode == S2S_MODE_F16X3 ? Fused<1>::LDS : Fused<0>::LDS, stream, h->model, h->d_arena, tb, tcs,
-                           n_valid + s, n, fc, P, tg, tzdw, tz01, h->handoff, out_dur + s * 16, tsig, D, (long long)s);
+                           n_valid + s, n, fc, P, tg, tzdw, tz01, h->handoff, out_dur + s * 16, tsig, D, (long long)s, sched);
         if (h->profiling) {
             HIP_TRY(h, hipEventRecord(ev.b, stream));
             ev.chunks = n;
@@ -2326,8 +2421,11 @@ int s2s_stats_read(s2s_handle* h, uint64_t* out10) {
                    : (uint64_t)h->stat_chunks * DEC_WAVES * S2S_HEADS * (uint64_t)h->cfg.decoder_layers;
     out10[2] = raw[S2S_STAT_REDO];
     out10[3] = raw[S2S_STAT_CYCLES]; out10[4] = raw[S2S_STAT_TICKS]; out10[5] = raw[S2S_STAT_WGS];
-    out10[6] = (uint64_t)h->stat_exact_chunks; out10[7] = 0; out10[8] = 0; out10[9] = 0;
-    h->stat_chunks = 0; h->stat_exact_chunks = 0;
+    out10[6] = (uint64_t)h->stat_exact_chunks;
+    out10[7] = raw[S2S_STAT_SPAN_MAX];
+    out10[8] = raw[S2S_STAT_SPAN_MIN_INV] ? ~raw[S2S_STAT_SPAN_MIN_INV] : 0;
+    out10[9] = (uint64_t)h->stat_dynamic_chunks;
+    h->stat_chunks = 0; h->stat_exact_chunks = 0; h->stat_dynamic_chunks = 0;
     return S2S_OK;
 }
 

@@ -498,15 +498,37 @@ class Engine:
         self._check(_lib.lib().s2s_get_attention_path(self._h, C.byref(p), C.byref(r)), "s2s_get_attention_path")
         return r.value
 
+    _SCHEDULES = ("auto", "static", "dynamic")
+
+    @property
+    def schedule(self) -> str:
+        """How a launch of the predict kernel is dealt out to its workgroups (s2s_set_schedule): "static" (equal contiguous shares),
+        "dynamic" (claims from a counter, shrinking towards the end of the launch) or "auto" (dynamic for large launches).  The
+        outputs are the same bytes either way.  Starts as the environment's S2S_SCHEDULE, else "auto"."""
+        v = C.c_int32()
+        self._check(_lib.lib().s2s_get_schedule(self._h, C.byref(v)), "s2s_get_schedule")
+        return self._SCHEDULES[v.value]
+
+    @schedule.setter
+    def schedule(self, schedule: str):
+        if schedule not in self._SCHEDULES:
+            raise ValueError("schedule must be 'auto', 'static' or 'dynamic'")
+        self._check(_lib.lib().s2s_set_schedule(self._h, self._SCHEDULES.index(schedule)), "s2s_set_schedule")
+
     def stats(self) -> dict:
         """Counters of the predict kernel since the last call (s2s_stats_read; synchronises the device): how THIS run behaved --
-        the share of softmax runs redone on the safe path and the clock the SIMDs held are data dependent."""
+        the share of softmax runs redone on the safe path and the clock the SIMDs held are data dependent.  wg_span_ms_*: how long
+        the workgroups ran (mean, longest, shortest over every workgroup of every launch counted): a launch lasts as long as its
+        longest."""
         out = (C.c_uint64 * 10)()
         self._check(_lib.lib().s2s_stats_read(self._h, out), "s2s_stats_read")
-        chunks, runs, redo, cyc, ticks, wgs, exact_chunks = (int(x) for x in out[:7])
+        chunks, runs, redo, cyc, ticks, wgs, exact_chunks, span_max, span_min, dynamic_chunks = (int(x) for x in out[:10])
         return {"chunks": chunks, "softmax_runs": runs, "softmax_redone": redo,
                 "redo_rate": (redo / runs) if runs else 0.0,
                 "in_kernel_clock_ghz": (cyc / ticks * 0.1) if ticks else None,
                 "cycles_per_chunk_and_cu": (cyc / chunks) if chunks else None,    # a workgroup owns its CU: sum of their cycles / chunks
                 "shader_cycles": cyc, "ticks_100mhz": ticks, "workgroups": wgs,
-                "chunks_on_exact_path": exact_chunks}
+                "chunks_on_exact_path": exact_chunks,
+                "wg_span_ms_mean": (ticks / wgs * 1e-5) if wgs else 0.0,          # (a tick of the 100 MHz clock is 1e-5 ms)
+                "wg_span_ms_max": span_max * 1e-5, "wg_span_ms_min": span_min * 1e-5,
+                "chunks_on_dynamic_schedule": dynamic_chunks}

@@ -15,7 +15,8 @@ device-only branches run in no other test).  Every integer output is preset to 7
       scratch slot, and the sweep (which never sees path_offs) fills it.  "Nothing is written outside a slot" is what is held:
       every byte outside the scratch slots of pairs with a valid one and outside the right-aligned paths is still 0xAB.
   A3  a and b (q and t) in separate allocations with unrelated offset tables, record starts on odd and even sample indices, a
-      samples pointer that is only 2-byte aligned, everything enqueued on a side stream with one synchronize before the read.
+      samples pointer that is only 2-byte aligned, everything enqueued on a side stream with one synchronize before the read -- and
+      the samples LATE on that stream (tests/_stream_order.py): behind a delay, over decoys, which are put back right after the calls.
   A4  s2s_signal_normalise with med / mad outside what int16 samples can give and with scale 1 and 8192.
 Every comparison is an equality of integers or bytes; the seconds of the limit pairs are printed, not asserted."""
 import time
@@ -25,6 +26,7 @@ import pytest
 
 from seq2squiggle_amd import _lib
 from seq2squiggle_amd import compare as CMP
+import _stream_order as SO
 from _dtw_ref import ref_median_mad, ref_normalise
 from test_compare_cpu import dtw_pair, mixed_pairs, rnd
 from test_compare_open_ends_cpu import KINDS, SHAPES, make
@@ -251,25 +253,48 @@ def test_two_pools_odd_offsets_and_a_side_stream():
     for i in (2, 9, 20, 31, 40):
         qb.append(qb[i] + 1); ql.append(ql[i] + ql[i + 1] - 1); tb.append(tb[i]); tl.append(tl[i] + tl[i + 1] // 2); rv.append(i % 2)
     N = len(qb)
-    side = torch.cuda.Stream()
-    assert side.cuda_stream != torch.cuda.current_stream().cuda_stream
-    with torch.cuda.stream(side):
-        # a: three samples of junk in front, the pointer one sample into the allocation (2-byte aligned only); b: five samples of junk
-        d_a, d_b = up(pool_of(al, junk=3)), up(pool_of(bl, junk=5))
-        d_ao, d_bo, d_so, d_po = up(offsets(al, 2)), up(offsets(bl, 5)), up(so), up(po)
+    # a: three samples of junk in front, the pointer one sample into the allocation (2-byte aligned only); b: five samples of junk.
+    # The four sample pools come LATE on the side stream (tests/_stream_order.py): the tensors hold other samples, a delay holds the
+    # stream, the real samples are copied in behind it.  The offset tables carry addresses: they are in place before the delay.
+    real = dict(a=pool_of(al, junk=3), b=pool_of(bl, junk=5), q=q_pool, t=t_pool)
+    decoy = {k: SO.other_samples([v], 40 + i)[0] for i, (k, v) in enumerate(real.items())}
+    real_d, decoy_d = SO.up(real), SO.up(decoy)
+    d_ao, d_bo, d_so, d_po = up(offsets(al, 2)), up(offsets(bl, 5)), up(so), up(po)
+    d_tab, d_rv = up(np.array(qb + ql + tb + tl, np.int64)), up(np.array(rv, np.uint8))
+    tab = d_tab.data_ptr()
+
+    def three(x):
+        """The three entries on the current stream, on the pools x -> (return codes, cost1, out2, scratch, ops, out3)."""
+        s_ptr = torch.cuda.current_stream().cuda_stream
         cost1, out2 = full(P, I77, torch.int64), full(2 * P, I77, torch.int64)
         scratch, ops = full(so[-1] + 64, B77, torch.uint8), full(po[-1] + 64, B77, torch.uint8)
-        d_q, d_t, d_tab, d_rv = up(q_pool), up(t_pool), up(np.array(qb + ql + tb + tl, np.int64)), up(np.array(rv, np.uint8))
         out3 = full(3 * N, I77, torch.int64)
-        a_ptr, s_ptr, tab = d_a.data_ptr() + 2, side.cuda_stream, d_tab.data_ptr()
+        a_ptr = x["a"].data_ptr() + 2
         assert a_ptr % 4 == 2
-        rcs = [L.s2s_dtw_banded(0, s_ptr, a_ptr, d_ao.data_ptr(), d_b.data_ptr(), d_bo.data_ptr(), P, R, cost1.data_ptr()),
-               L.s2s_dtw_path(0, s_ptr, a_ptr, d_ao.data_ptr(), d_b.data_ptr(), d_bo.data_ptr(), P, R, out2.data_ptr(), scratch.data_ptr(),
+        rcs = [L.s2s_dtw_banded(0, s_ptr, a_ptr, d_ao.data_ptr(), x["b"].data_ptr(), d_bo.data_ptr(), P, R, cost1.data_ptr()),
+               L.s2s_dtw_path(0, s_ptr, a_ptr, d_ao.data_ptr(), x["b"].data_ptr(), d_bo.data_ptr(), P, R, out2.data_ptr(), scratch.data_ptr(),
                               d_so.data_ptr(), ops.data_ptr(), d_po.data_ptr(), out2.data_ptr() + 8 * P),
-               L.s2s_sdtw(0, s_ptr, d_q.data_ptr(), tab, tab + 8 * N, d_t.data_ptr(), tab + 16 * N, tab + 24 * N, d_rv.data_ptr(), N,
+               L.s2s_sdtw(0, s_ptr, x["q"].data_ptr(), tab, tab + 8 * N, x["t"].data_ptr(), tab + 16 * N, tab + 24 * N, d_rv.data_ptr(), N,
                           out3.data_ptr(), out3.data_ptr() + 8 * N, out3.data_ptr() + 16 * N)]
+        return rcs, cost1, out2, scratch, ops, out3
+    three(real_d)                                       # (the kernels' first launch is not what is timed)
+    solo, t_solo = SO.timed(lambda: three(real_d))
+    of_decoy = three(decoy_d)
+    assert not torch.equal(of_decoy[1], solo[1]) and not torch.equal(of_decoy[2], solo[2]) and not torch.equal(of_decoy[5], solo[5])
+    side = SO.side_stream()
+    assert side.cuda_stream != torch.cuda.current_stream().cuda_stream
+    ms = SO.delay_for(t_solo)
+    ins, ev = SO.late(side, real_d, decoy_d, ms)
+    with torch.cuda.stream(side):
+        rcs, cost1, out2, scratch, ops, out3 = three(ins)
+    before = SO.returned_before(side)
+    snaps = SO.early(side, ins, decoy_d, [cost1, out2, ops, out3])
     side.synchronize()
+    SO.lasted("test_gpu_compare_contract: dtw_banded, dtw_path, sdtw", ev, t_solo, ms)
+    assert before, "an entry waited for the stream"
     assert rcs == [0, 0, 0]
+    for (_, snap), now, alone in zip(snaps, (cost1, out2, ops, out3), (solo[1], solo[2], solo[4], solo[5])):
+        assert torch.equal(snap, now) and torch.equal(now, alone)
     hcost, hops = CMP.dtw_path(al, bl, R, cpu=True)
     assert sum(c == -1 for c in hcost.tolist()) == 2
     assert cost1.cpu().numpy().tolist() == hcost.tolist() == CMP.dtw_banded(al, bl, R, cpu=True).tolist()

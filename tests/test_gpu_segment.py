@@ -41,8 +41,11 @@ class Buf:
         return bool((self.t[:GUARD] == FILL).all()) and bool((self.t[GUARD + self.nbytes:] == FILL).all())
 
 
-def device(flat, offs, total, w_s, w_l, T_s, T_l, eo, stream=None, scratch=None):
-    """s2s_segment on guarded buffers -> (rc, n_events [R], start slots, len slots, the scratch buffer)."""
+def device(flat, offs, total, w_s, w_l, T_s, T_l, eo, stream=None, scratch=None, t_solo=0.0):
+    """s2s_segment on guarded buffers -> (rc, n_events [R], start slots, len slots, the scratch buffer).  stream: a side stream, on
+    which the samples come LATE (tests/_stream_order.py): the buffer holds other samples, a delay of ten times t_solo (ms: the same
+    call alone) holds the stream, the real samples are copied in behind it, the call follows, and the other samples are put back
+    right behind it, before anything waits."""
     import torch
     L = _lib.lib()
     R = len(offs) - 1
@@ -53,10 +56,35 @@ def device(flat, offs, total, w_s, w_l, T_s, T_l, eo, stream=None, scratch=None)
     assert need >= 8
     b_sc = scratch if scratch is not None else Buf(need)
     assert b_sc.nbytes >= need
-    torch.cuda.synchronize()
-    rc = L.s2s_segment(0, stream.cuda_stream if stream is not None else None, b_x.ptr, b_offs.ptr, R, int(total), w_s, w_l, T_s, T_l, b_sc.ptr,
-                       b_eo.ptr, b_st.ptr, b_ln.ptr, b_ne.ptr)
-    (stream.synchronize() if stream is not None else torch.cuda.synchronize())
+    args = (b_offs.ptr, R, int(total), w_s, w_l, T_s, T_l, b_sc.ptr, b_eo.ptr)
+    if stream is None:
+        torch.cuda.synchronize()
+        rc = L.s2s_segment(0, None, b_x.ptr, *args, b_st.ptr, b_ln.ptr, b_ne.ptr)
+        torch.cuda.synchronize()
+    else:
+        import _stream_order as SO
+        other = np.ascontiguousarray(SO.other_samples([flat], 99)[0])
+        d_st, d_ln, d_ne = Buf(4 * slots), Buf(4 * slots), Buf(4 * R)                  # what the other samples give, on the default stream
+        b_other = Buf(2 * len(flat), other)
+        torch.cuda.synchronize()
+        assert L.s2s_segment(0, None, b_other.ptr, *args, d_st.ptr, d_ln.ptr, d_ne.ptr) == 0
+        torch.cuda.synchronize()
+        body = {"x": b_x.t[GUARD:GUARD + b_x.nbytes]}
+        real, decoy = {"x": body["x"].clone()}, {"x": b_other.t[GUARD:GUARD + b_x.nbytes].clone()}
+        body["x"].copy_(decoy["x"])
+        torch.cuda.synchronize()
+        ms = SO.delay_for(t_solo)
+        ev = SO.hold(stream, body, real, ms)
+        rc = L.s2s_segment(0, stream.cuda_stream, b_x.ptr, *args, b_st.ptr, b_ln.ptr, b_ne.ptr)
+        before = SO.returned_before(stream)
+        snaps = SO.early(stream, body, decoy, [b_st.t, b_ln.t, b_ne.t])
+        stream.synchronize()
+        SO.lasted("test_gpu_segment: segment", ev, t_solo, ms)
+        assert before, "s2s_segment waited for the stream"
+        assert all(torch.equal(snap, b.t) for (_, snap), b in zip(snaps, (b_st, b_ln, b_ne)))
+        assert not torch.equal(d_st.t, b_st.t), "the other samples give the same events: the late input proves nothing"
+        body["x"].copy_(real["x"])
+        torch.cuda.synchronize()
     for b in (b_x, b_offs, b_eo, b_st, b_ln, b_ne, b_sc):
         assert b.guards_intact()
     assert (b_x.body(np.int16) == flat).all() and (b_offs.body(np.int64) == offs).all() and (b_eo.body(np.int64) == eo).all()
@@ -180,8 +208,11 @@ def test_offsets_that_decrease_or_are_negative_count_as_empty_records():
 def test_side_stream_scratch_reuse_and_argument_errors():
     import torch
     L = _lib.lib()
+    import _stream_order as SO
     recs = [noisy(21, 5000), noisy(22, 100), noisy(23, 9000)]
-    ne, st = check(recs, stream=torch.cuda.Stream())
+    check(recs)
+    _, t_solo = SO.timed(lambda: check(recs))             # (with the host twin's time: a delay of ten times that is long enough)
+    ne, st = check(recs, stream=SO.side_stream(), t_solo=t_solo)
     scratch = Buf(int(L.s2s_segment_scratch_bytes(20000, 3)))
     for rs in (recs, [noisy(31, 9000), noisy(32, 5000), noisy(33, 100)], recs):      # one scratch, three calls: no state is carried over
         got = check(rs, scratch=scratch)

@@ -6,8 +6,9 @@ allocation when they shrink, and takes the gradient, the partials and the statis
   call sequence    one trainer: gradients(B = 7), gradients(B = 2), a budget for 3 chunks per micro-batch and gradients(B = 7) in
                    3 / 3 / 1, a large budget and gradients(B = 9), gradients(B = 1); every loss and gradient bit-equal to a fresh
                    trainer's that was given that budget and that call alone;
-  stream           the same call inside torch.cuda.stream(torch.cuda.Stream()), inputs created on that stream, gives the default
-                   stream's bits: gradients, and three steps (weights and statistics);
+  stream           the same call inside torch.cuda.stream(torch.cuda.Stream()), its inputs copied in on that stream behind a delay
+                   (late inputs, tests/_stream_order.py), gives the default stream's bits: gradients, and three steps (weights and
+                   statistics);
   interleaved      a twelve-step trajectory with a gradients() call of another batch and another B between every two steps ends
                    with the bits of the trajectory without them, weights and every step's statistics: gradients() leaves m, v and
                    the weights alone;
@@ -93,24 +94,47 @@ def test_call_sequence(tag):
 
 @pytest.mark.parametrize("tag", TAGS)
 def test_stream(tag):
+    """The side stream's inputs are LATE (tests/_stream_order.py): the input tensors hold other rows of the golden, a delay of ten times
+    the default stream's run holds the side stream, the real rows are copied in behind it and the calls follow -- a launch, memset or
+    copy that left the stream would read the other rows."""
+    import _stream_order as SO
     sd, cfg = model(tag)[:2]
     tr = T.Trainer(sd, cfg, 0)
-    want = tr.gradients(*batch(tag, 0, STREAM_B))
-    wstats = torch.stack([step(tr, batch(tag, s * STREAM_B, STREAM_B), s) for s in range(3)]).cpu()
-    wweights = tr.weights().cpu()
+
+    def default_stream():
+        want = tr.gradients(*batch(tag, 0, STREAM_B))
+        wstats = torch.stack([step(tr, batch(tag, s * STREAM_B, STREAM_B), s) for s in range(3)]).cpu()
+        return want, wstats, tr.weights().cpu()
+    (want, wstats, wweights), t_solo = SO.timed(default_stream)
     want = {k: v.cpu() for k, v in want.items()}
     tr.close()
     tr = T.Trainer(sd, cfg, 0)
-    side = torch.cuda.Stream()
+    tr.gradients(*batch(tag, 5, STREAM_B))              # (changes no weight: the tape grows here, not behind the delay)
+    real = {(s, i): t for s in range(3) for i, t in enumerate(batch(tag, s * STREAM_B, STREAM_B))}
+    decoy = {(s, i): t for s in range(3) for i, t in enumerate(batch(tag, 3 + s * STREAM_B, STREAM_B))}
+    assert all(not torch.equal(real[k], decoy[k]) for k in real if k[1] in (0, 2))      # other k-mers, other targets
+    side = SO.side_stream()
+    ms = SO.delay_for(t_solo)
+    ins, ev = SO.late(side, real, decoy, ms)
+    rows = lambda s: tuple(ins[s, i] for i in range(4))                                            # noqa: E731
     with torch.cuda.stream(side):
         assert torch.cuda.current_stream() == side and side != torch.cuda.default_stream()
-        got = {k: v.cpu() for k, v in tr.gradients(*batch(tag, 0, STREAM_B)).items()}
-        stats = torch.stack([step(tr, batch(tag, s * STREAM_B, STREAM_B), s) for s in range(3)]).cpu()
-        weights = tr.weights().cpu()
+        got = tr.gradients(*rows(0))
+        stats = torch.stack([step(tr, rows(s), s) for s in range(3)])
+        weights = tr.weights()
+    before = SO.returned_before(side)
+    snaps = SO.early(side, ins, decoy, dict(got, stats=stats, weights=weights))
+    with torch.cuda.stream(side):
+        got, stats, weights = {k: v.cpu() for k, v in got.items()}, stats.cpu(), weights.cpu()
+    SO.lasted(f"test_gpu_train_calls.test_stream {tag}", ev, t_solo, ms)
     tr.close()
+    assert before, "a trainer call waited for the stream"
     assert torch.equal(got["loss"], want["loss"]) and torch.equal(got["grad"], want["grad"])
     assert torch.equal(stats, wstats) and torch.equal(weights, wweights)
     assert not torch.equal(weights, torch.from_numpy(state_dict_to_blob(sd, cfg)))      # the steps did move the weights
+    snaps = dict(snaps)
+    assert torch.equal(snaps[".loss"].cpu(), want["loss"]) and torch.equal(snaps[".grad"].cpu(), want["grad"])
+    assert torch.equal(snaps[".stats"].cpu(), wstats) and torch.equal(snaps[".weights"].cpu(), wweights)
 
 
 @pytest.mark.parametrize("tag", TAGS)

@@ -222,3 +222,27 @@ def test_trained_like_checkpoint_stays_finite():
     for (path, name), m in envelope_rows(sd, inp, "f16x3", ref=ref).items():
         print(f"ENVELOPE f16x3 trained-like x2^-2 {path} {name}: {fmt(m)}")
         assert m["dur_equal"] and m["finite"], (path, name)
+
+
+def test_trained_checkpoint_holds_the_bounds(request):
+    """THIS test, not test_trained_like_checkpoint_stays_finite above, is the evidence about trained weights: that one rescales the
+    synthetic checkpoint (a stand-in from before the project had a trainer) and asserts a finite signal only; this one takes the
+    student "k9" of tests/_trained.py -- 300 Adam steps of the project's trainer from a fresh initialisation -- through the same
+    envelope_rows call, the oracle recomputed on it, and asserts the full parity bounds on both attention paths in both passes."""
+    import _trained as TR
+    inp = inputs()
+    st = TR.student("k9", request)
+    sd = st["sd"]
+    taps = R.intermediates(sd, inp["cfg"], inp["codes"], inp["g"])
+    assert max(taps.values()) < R.RANGE_LIMIT
+    ref = oracle_runs(sd, inp["cfg"], inp)
+    assert not torch.equal(ref["g"][0]["signal"], inp["ref"]["g"][0]["signal"])
+    for name, (r32, r64) in ref.items():              # the caps of within_bounds do not carry it: the reference alone stays inside them
+        r, t = r32["signal"].numpy(), r64["signal"].numpy()
+        agree64 = (r == 0) == (t == 0)
+        assert agree64.mean() > 0.9995 and np.abs(r - t)[agree64].mean() > 0, name
+    rows = envelope_rows(sd, inp, "f16x3", ref=ref)
+    for (path, name), m in rows.items():
+        print(f"TRAINED k9 f16x3 {path} {name}: {fmt(m)}")
+    for (path, name), m in rows.items():
+        assert within_bounds(m, fp64_rule=(name == "g")), (path, name, m)

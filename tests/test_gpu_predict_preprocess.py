@@ -19,11 +19,11 @@ pytestmark = pytest.mark.gpu
 GEOMETRY = (9, 16, 250)
 
 
-@pytest.fixture(scope="module")
-def run(tmp_path_factory):
+def predict_run(d):
+    """The module's one `predict --events --events-samples` run, into the directory d (also the data of tests/_trained.py's k9
+    students)."""
     from seq2squiggle_amd.cli import set_config
     from seq2squiggle_amd.inference import inference_run
-    d = tmp_path_factory.mktemp("predict_preprocess")
     genome = next(iter(U.read_fasta(LAMBDA)))[0].upper()
     (d / "reads.fasta").write_text("".join(f">lambda_{i}\n{genome[3000 * i + 100:3000 * i + 320 + 40 * i]}\n" for i in range(6)))
     U.set_seeds(SEED)
@@ -34,6 +34,11 @@ def run(tmp_path_factory):
                   min_noise=0.0, min_duration=3, min_read_len=30, preserve_read_ids=True, seed=SEED, events=str(d / "truth.tsv"),
                   events_samples=True, kmer_table=None, kmer_model=str(d / "p.model"))
     return d
+
+
+@pytest.fixture(scope="module")
+def run(tmp_path_factory):
+    return predict_run(tmp_path_factory.mktemp("predict_preprocess"))
 
 
 def files_of(d):
